@@ -6,22 +6,32 @@ One process per GPU (torch.distributed over RCCL when N > 1); pairs are independ
 its own pairs with no data-path collective (weak scaling).  Config 5's only exchange -- one all_gather of
 the disparity maps + a checksum all_reduce (shard.py) -- sits at the end of the timed region for the batched
 workload (adcensus_kitti_d256; --gather forces it for any workload, --no-gather removes it); for the other
-workloads it runs after the region.  Either way it is timed by itself (extra.gather_ms) and the rate with / without
-it is reported.
+workloads it runs after the region, with --full only.  Either way it is timed by itself (extra.gather_ms) and the rate
+with / without it is reported.
 A step is one smt_adcensus_compute_batch call over --pairs-per-step (default 8) resident pairs: the steady-state
 throughput configuration (from the second pair of a batch on, the table kernels of the next pair overlap the
-cost kernel of the current one); the latency of a lone pair is reported beside it (ms_single_pair_call).
+cost kernel of the current one); with --full the latency of a lone pair is reported beside it (ms_single_pair_call).
 `python bench.py --gpus N` with N > 1 and no launcher (WORLD_SIZE unset) starts its own N ranks: the parent --
 before anything touches the GPU -- spawns N children of this file with RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_ADDR / MASTER_PORT set (what torch.distributed.run would have set), relays rank 0's JSON line and exits
 non-zero if any child does.  Under a launcher (WORLD_SIZE set) nothing is spawned; a WORLD_SIZE that differs from
---gpus is an error.  For every N the line also carries configs[4] as the strong-scaling case
+--gpus is an error.  With --full, for every N the line also carries configs[4] as the strong-scaling case
 (extra.cfg5_kitti_256pairs_strong: 256 pairs in total, 256/N per rank, the gather inside its timed region).
-Prints ONE JSON line on rank 0.  After the timed region rank 0 also measures, outside `value`:
-  roofline.sclk_mhz / store_ceiling_ms   in-kernel shader clock of the cost kernel and the same-run
-                                         store-only ceiling of its store pattern (smt_adcensus_diag);
-  extra.configs                          BASELINE.json configs 1-5 with per-stage HIP-event times;
-  cpu_baseline                           the CPU oracle on a band of the same pair.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps, writes the outputs of the
+last step when --dump-outputs DIR is given, and prints the headline line (metric, value, unit, ms_per_step,
+ms_per_pair, dtype, config).  Everything else is measured only with --full:
+  roofline                               per-kernel HIP-event times of the timed region (events every few pairs),
+                                         sclk / store-only ceiling of the cost kernel (smt_adcensus_diag), placement
+                                         and store-mode calibration, rocm-smi readings before and after;
+  ms_single_pair_call                    latency of a lone pair;
+  extra.gather_ms / value_with_gather    N > 1 workloads whose exchange is not in the timed region;
+  extra.cfg5_kitti_256pairs_strong       configs[4] as the strong-scaling case, every N (--no-extras skips);
+  extra.configs                          BASELINE.json configs 1-5 with per-stage HIP-event times (--no-extras skips);
+  cpu_baseline                           the CPU oracle on a band of the same pair (--cpu-rows 0 skips).
+--dump-outputs DIR writes the disparity maps the last timed step returned (rank 0's pairs) as DIR/disp_left.npy and
+DIR/disp_right.npy, float32 [pairs][H][W]; above DUMP_BUDGET bytes both are cut to the same seeded sample of rows
+([rows][W], flat row index pair * H + row in DIR/sample_rows.npy).  Inputs are seeded: the same arguments give the
+same inputs on every run.
 """
 import argparse
 import json
@@ -41,6 +51,8 @@ F64_VECTOR_TFLOPS = 78.6   # dense fp64 vector peak
 F32_ADDS_PER_S = 78.6e12   # fp32 vector peak 157.3 TFLOP/s counts an FMA as 2: plain adds issue at half of it
 SAD_U8_PER_S = 4 * 32 * 1024 * 2.4e9   # v_sad_u8: 4 byte differences + add per lane, 32 lanes per clock per SIMD, 1 024 SIMDs, 2.4 GHz
 LDS_B32_TBS = 75.0         # ds_read_b32 aggregate rate with every CU streaming (MI355X_MICROARCH.md, LDS)
+
+DUMP_BUDGET = 56 * 1000 * 1000   # bytes of maps written by --dump-outputs (the whole directory stays under 64 MB)
 
 WORKLOADS = {
     # name: (H, W, D, seed, description)
@@ -309,6 +321,25 @@ def extra_configs(dev, reps=5):
     return out
 
 
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: the [pairs][H][W] maps in `arrays` as <path>/<name>.npy, float32.  Above DUMP_BUDGET every map
+    is cut to the same fixed, seeded sample of rows, so two builds run with the same arguments write the same
+    elements; the flat row indices (pair * H + row, ascending) go to sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    if sum(a.nbytes for a in host.values()) > DUMP_BUDGET:
+        W = next(iter(host.values())).shape[-1]
+        rows = next(iter(host.values())).size // W
+        keep = DUMP_BUDGET // (W * 4 * len(host))
+        pick = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        host = {k: a.reshape(rows, W)[pick] for k, a in host.items()}
+        host["sample_rows"] = pick.astype(np.float64)
+    elif os.path.exists(os.path.join(path, "sample_rows.npy")):
+        os.remove(os.path.join(path, "sample_rows.npy"))     # left by an earlier, sampled run into the same DIR
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_launch(argv, n):
     """`python bench.py --gpus N` without a launcher: be the launcher.  Nothing in this function touches the GPU
     (torch.cuda.device_count() does not initialise it on this image) and nothing is exec'ed: N plain child
@@ -414,10 +445,17 @@ def cfg5_strong(dev, world, rank, on_host, total=256, reps=3):
             "timing": f"best of {reps} repetitions, max over ranks, barrier + synchronize on both sides"}
 
 
+def _positive(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=_positive, default=200, help="timed steps")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="adcensus_1080p_d192", choices=sorted(WORKLOADS))
     ap.add_argument("--pairs-per-step", type=int, default=8,
@@ -428,8 +466,15 @@ def main():
     ap.add_argument("--gather", action="store_true",
                     help="N > 1: put the disparity gather inside the timed region for any workload (default: only for "
                          "adcensus_kitti_d256, the batched configuration whose results are collected)")
-    ap.add_argument("--no-extras", action="store_true", help="skip extra.configs (configs 1-5 after the timed region)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip extra.configs (configs 1-5 after the timed region) "
+                                                               "and the strong-scaling case")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not part of the headline: roofline (kernel events, diag, smi), lone-pair latency, "
+                         "strong scaling, configs 1-5, the CPU baseline, the gather outside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the disparity maps of the last timed step to DIR/*.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(sys.argv[1:], args.gpus)              # never returns; nothing has touched the GPU yet
@@ -469,7 +514,7 @@ def main():
     dl = torch.empty((P, H, W), device=dev)
     dr = torch.empty((P, H, W), device=dev)
     adc = smt.AD_Census().Initialize(Lb[0], Rb[0], D, H, W, 10.0, 30.0)
-    smi_before = smi_snapshot() if rank == 0 else None
+    smi_before = smi_snapshot() if rank == 0 and full else None
 
     def step():
         adc.ComputeBatch(Lb, Rb, dl, dr)
@@ -485,11 +530,12 @@ def main():
 
     # The pair axis shards with no data-path collective.  The batched configuration (configs[4]) ends with one exchange
     # -- all_gather of the disparity maps + a checksum all_reduce (shard.py) -- which belongs to its timed region; for
-    # the other workloads the same exchange is run and timed after the region and reported beside `value`.
+    # the other workloads the same exchange is run and timed after the region and reported beside `value` (--full).
     gather_in_region = dist.is_initialized() and not args.no_gather and (args.gather or args.workload == "adcensus_kitti_d256")
+    gather_after = dist.is_initialized() and not args.no_gather and not gather_in_region and full
     for _ in range(args.warmup):
         step()
-    if dist.is_initialized() and not args.no_gather and args.warmup > 0:
+    if (gather_in_region or gather_after) and args.warmup > 0:
         # part of the warm-up: the first collective of a shape sets up RCCL's channels (64 ms on one GPU)
         shard.gather_disparities(xdl(), world * P)
         shard.checksum(xdl())
@@ -497,7 +543,8 @@ def main():
     # HIP events around the kernels of ~32 pairs spread over the run (each record costs ~3 us of stream time and
     # a timed pair carries four)
     stride = max(1, (args.steps * P) // 32)               # ~32 timed pairs per run
-    adc.timing(stride)
+    if full:
+        adc.timing(stride)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -516,12 +563,16 @@ def main():
         gather_ms = timed_gather()
     barrier()
     dt = time.perf_counter() - t0
-    if dist.is_initialized() and not args.no_gather and not gather_in_region:
+    if gather_after:
         gather_ms = timed_gather()                        # outside the region: reported, not part of `value`
         barrier()
-    prep_ms, cost_ms = adc.kernel_times()
-    adc.timing(False)
+    if full:
+        prep_ms, cost_ms = adc.kernel_times()
+        adc.timing(False)
     adc.status()
+    if rank == 0 and args.dump_outputs:
+        # the maps the last timed step returned (nothing has launched on dl / dr since)
+        dump_outputs(args.dump_outputs, {"disp_left": dl, "disp_right": dr})
 
     tt = torch.tensor([dt, gather_ms or 0.0], dtype=torch.float64, device="cpu" if one_dev else dev)
     if dist.is_initialized():
@@ -535,7 +586,7 @@ def main():
 
     # configs[4] as the strong-scaling case: every rank takes part (256 pairs in total, gather inside)
     strong = None
-    if not args.no_extras:
+    if full and not args.no_extras:
         if world == 1:
             try:
                 strong = cfg5_strong(dev, world, rank, one_dev)
@@ -546,11 +597,11 @@ def main():
 
     # latency of a lone pair (one call, nothing to overlap with), outside the timed region
     single_ms = None
-    if rank == 0:
+    if rank == 0 and full:
         single_ms = ev_timed(lambda: adc.ComputeBatch(Lb[:1], Rb[:1], dl[:1], dr[:1]), 20, warm=2)
     # same-run diagnostics of the dominant kernel, right after the timed region (same DVFS / memory state)
     diag = None
-    if rank == 0 and D % 64 == 0:
+    if rank == 0 and full and D % 64 == 0:
         mhz, stamped_ms, store_ms = adc.diag(20)
         diag = (mhz, stamped_ms, store_ms)
 
@@ -558,36 +609,37 @@ def main():
         hyp_pair = H * W * D
         total_pairs = world * P * args.steps
         value = total_pairs * hyp_pair / dt / 1e6
-        # dominant kernel = k_cost: writes both views' float32 volumes, 8 B per hypothesis
-        alg_bytes = 8.0 * hyp_pair
-        k_ms = float(np.mean(cost_ms)) if cost_ms else float("nan")
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(args.workload)
-        roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": "k_cost_fast2p / k_cost_fast2 (cost volume + fused WTA, both views; every launch of a batch but "
-                          "the last also carries the next pair's table workgroups)",
-                "kernel_ms": round(k_ms, 4), "tables_ms": round(float(np.mean(prep_ms)), 4),
-                "timed_launches": len(cost_ms), "timed_every": stride,
-                "algorithmic_bytes_per_launch": alg_bytes}
-        if diag:
-            mhz, stamped_ms, store_ms = diag
-            roof.update({"sclk_mhz": round(mhz, 1), "store_ceiling_ms": round(store_ms, 4),
-                         "store_ceiling_GBs": round(alg_bytes / (store_ms * 1e-3) / 1e9, 1),
-                         "frac_of_store_ceiling": round(store_ms / k_ms, 4),
-                         "stamped_kernel_ms": round(stamped_ms, 4),
-                         "diag": "smt_adcensus_diag right after the timed region: store-only twin of the kernel "
-                                 "(same grid, chunk order, streaming stores, same buffers) and the kernel with "
-                                 "s_memtime/s_memrealtime stamps, 20 launches each"})
-        tries, place_ms = adc.placement()
-        roof["placement"] = {"candidate_pairs_tried": tries, "kept_pair_store_only_ms": round(place_ms, 4),
-                             "note": "smt_adcensus_create keeps the fastest of up to 6 allocations of the two volumes "
-                                     "(HBM write rate depends on the physical pages, DESIGN.md section 5)"}
-        plain, nt_ms, plain_ms = adc.store_mode()
-        roof["store_mode"] = {"chosen": "plain" if plain else "streaming (nt)", "calibration_nt_ms": round(nt_ms, 4),
-                              "calibration_plain_ms": round(plain_ms, 4)}
-        roof["smi_before"] = smi_before
-        roof["smi_after"] = smi_snapshot()
+        if full:
+            # dominant kernel = k_cost: writes both views' float32 volumes, 8 B per hypothesis
+            alg_bytes = 8.0 * hyp_pair
+            k_ms = float(np.mean(cost_ms)) if cost_ms else float("nan")
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+            traffic, traffic_src = pmc_traffic(args.workload)
+            roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "kernel": "k_cost_fast2p / k_cost_fast2 (cost volume + fused WTA, both views; every launch of a batch but "
+                              "the last also carries the next pair's table workgroups)",
+                    "kernel_ms": round(k_ms, 4), "tables_ms": round(float(np.mean(prep_ms)), 4),
+                    "timed_launches": len(cost_ms), "timed_every": stride,
+                    "algorithmic_bytes_per_launch": alg_bytes}
+            if diag:
+                mhz, stamped_ms, store_ms = diag
+                roof.update({"sclk_mhz": round(mhz, 1), "store_ceiling_ms": round(store_ms, 4),
+                             "store_ceiling_GBs": round(alg_bytes / (store_ms * 1e-3) / 1e9, 1),
+                             "frac_of_store_ceiling": round(store_ms / k_ms, 4),
+                             "stamped_kernel_ms": round(stamped_ms, 4),
+                             "diag": "smt_adcensus_diag right after the timed region: store-only twin of the kernel "
+                                     "(same grid, chunk order, streaming stores, same buffers) and the kernel with "
+                                     "s_memtime/s_memrealtime stamps, 20 launches each"})
+            tries, place_ms = adc.placement()
+            roof["placement"] = {"candidate_pairs_tried": tries, "kept_pair_store_only_ms": round(place_ms, 4),
+                                 "note": "smt_adcensus_create keeps the fastest of up to 6 allocations of the two volumes "
+                                         "(HBM write rate depends on the physical pages, DESIGN.md section 5)"}
+            plain, nt_ms, plain_ms = adc.store_mode()
+            roof["store_mode"] = {"chosen": "plain" if plain else "streaming (nt)", "calibration_nt_ms": round(nt_ms, 4),
+                                  "calibration_plain_ms": round(plain_ms, 4)}
+            roof["smi_before"] = smi_before
+            roof["smi_after"] = smi_snapshot()
         out = {
             "metric": f"Mdisparities/s (HxWxD/s) + ms/pair, {desc}",
             "value": round(value, 2),
@@ -597,7 +649,10 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "ms_per_pair": round(dt / (args.steps * P) * 1e3, 4),
-            "ms_single_pair_call": round(single_ms, 4),
+        }
+        if full:
+            out["ms_single_pair_call"] = round(single_ms, 4)
+        out.update({
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -612,8 +667,9 @@ def main():
                        "world_size": dist.get_world_size() if dist.is_initialized() else 1,
                        "launcher": ("self (bench.py spawned its ranks)" if os.environ.get("SMT_BENCH_SELF_LAUNCHED") == "1"
                                     else ("external (WORLD_SIZE was set)" if launched else "none"))},
-            "roofline": roof,
-        }
+        })
+        if full:
+            out["roofline"] = roof
         extra = {}
         if gather_ms is not None:
             extra["gather_ms"] = round(gather_ms, 3)
@@ -623,14 +679,14 @@ def main():
                 extra["value_with_gather"] = round(total_pairs * hyp_pair / (dt + gather_ms * 1e-3) / 1e6, 2)
         if strong is not None:
             extra["cfg5_kitti_256pairs_strong"] = strong
-        if world == 1 and not args.no_extras:
+        if world == 1 and full and not args.no_extras:
             try:
                 extra["configs"] = extra_configs(dev)
             except Exception as e:                       # never lose the headline line to an extra
                 extra["configs_error"] = repr(e)
         if extra:
             out["extra"] = extra
-        if world == 1 and args.cpu_rows > 0:
+        if world == 1 and full and args.cpu_rows > 0:
             out["cpu_baseline"] = cpu_baseline(H, W, D, seed, args.cpu_rows)
         print(json.dumps(out), flush=True)
     adc.close()

@@ -3,7 +3,7 @@ set -x
 O=gpurun_out/pmc_cost
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-A="python3 bench.py --steps 20 --warmup 5 --no-extras --cpu-rows 0"
+A="python3 bench.py --full --steps 20 --warmup 5 --no-extras --cpu-rows 0"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/a -o a -- $A > $O/a.out 2> $O/a.err
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/b -o b -- $A > $O/b.out 2> $O/b.err
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/c -o c -- $A > $O/c.out 2> $O/c.err
