@@ -163,9 +163,12 @@ int smt_adcensus_set_stream(smt_adcensus *h, void *stream);
 int smt_adcensus_compute(smt_adcensus *h, const float *L, const float *R, int views,
                          float *dispL, float *dispR);
 
-/* Same, for a batch of `pairs` image pairs laid out [pairs][H][W]; the volumes are
- * reused per pair (only the last pair's stay readable), the disparity maps are
- * [pairs][H][W].  This is the sharding unit of the multi-GPU configuration.  The census tables
+/* Same, for a batch of `pairs` image pairs laid out [pairs][H][W]; the disparity maps are
+ * [pairs][H][W].  The volumes are reused per pair and after the call hold the LAST pair's costs:
+ * with both views and D <= 256 the volumes of pairs 0 .. pairs-2 are not written at all (those pairs
+ * take a maps-only kernel; a view whose map is NULL then does no cost work), elsewhere they are
+ * overwritten by the next pair.  SMT_BATCH_VOLUMES=all in the environment (read at every call)
+ * writes every pair's volumes as before, for same-process comparisons.  This is the sharding unit of the multi-GPU configuration.  The census tables
  * are double-buffered inside the handle: with both views and D <= 256 the table workgroups of pair
  * b+1 are spread through the grid of pair b's cost launch (one launch per pair, one stream); single
  * views and D > 256 build them on an internal stream beside pair b's cost kernel.  SMT_OVERLAP =
@@ -185,6 +188,14 @@ int smt_adcensus_force_generic(smt_adcensus *h, int on);
  * workgroups (a multiple of 8) and `nprep` table workgroups every cost group and every table group is reached exactly
  * once.  SMT_OK, or SMT_ERR_STATE if the mapping is not a bijection. */
 int smt_adcensus_selftest_fused_grid(int ncost, int nprep);
+/* Test hook, host only (no GPU): checks the workgroup arithmetic of the maps-only batch launch -- with K chunks per
+ * cost workgroup every 64-pixel chunk of an H x (nbx*64) both-views launch is reached exactly once and on its XCD, and
+ * with `nprep` > 0 table workgroups fused in, every cost and table workgroup too.  SMT_OK or SMT_ERR_STATE. */
+int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep);
+/* Test hook, host only (no GPU): checks the rank table of the maps-only kernel for these sigmas against the float sums
+ * lut[ad] + lut[256+hd] it stands for (order preserved, equal ranks exactly when the bits are equal).  SMT_OK or
+ * SMT_ERR_STATE; SMT_ERR_ARG unless both sigmas are > 0. */
+int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
 
 /* Synchronises the stream and returns SMT_ERR_DOMAIN if any pixel seen since the previous
  * smt_adcensus_status call (or since create) was not an integer in 0..255 (then those pairs' volumes

@@ -131,7 +131,8 @@ class AD_Census:
         self._compute(VIEW_BOTH, leftdisp, rightDisp)
 
     def ComputeBatch(self, L, R, leftdisp, rightDisp, views=VIEW_BOTH):
-        """[pairs][row][col] batches; volumes are reused per pair (smt_adcensus_compute_batch)."""
+        """[pairs][row][col] batches (smt_adcensus_compute_batch).  Afterwards the volumes hold the last pair's costs;
+        with both views and D <= 256 the other pairs' volumes are never written (SMT_BATCH_VOLUMES=all writes them)."""
         pairs = L.shape[0]
         _dev(L, torch.float32, (pairs, self.row, self.col), "L")
         _dev(R, torch.float32, (pairs, self.row, self.col), "R")

@@ -25,6 +25,7 @@
 #include "smt_common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <new>
 #include <type_traits>
@@ -41,6 +42,7 @@ struct Tables {
     uint64_t *mask;      // [H][W]
     uint8_t *u8[2];      // [H][W] left, right as bytes
     float *lut;          // 256 + 64 floats
+    uint16_t *rank;      // [256][64]: dense rank of lut[ad] + lut[256 + hd] (build_rank), maps-only kernel
     int *flag;           // domain flag
     int WX;
     unsigned long long *stamp;   // diagnostics only (smt_adcensus_diag): 4 counters per workgroup, else null
@@ -183,13 +185,14 @@ __device__ __forceinline__ void prep_rows(const uint32_t (*__restrict__ sw)[PSW]
 }
 
 // One workgroup of the table launch: (bx, by) of a (gdx, ...) grid -- a 64 x 32 tile, or past the tile rows a block
-// of border columns.  Called with workgroup-uniform arguments by k_prep and by the table workgroups of k_cost_fast2p.
+// of border columns.  Called with workgroup-uniform arguments by k_prep and by the table workgroups of k_cost_fast2p /
+// k_cost_maps2p, each of which passes its own LDS staging area (PSR rows of PSW dwords per image).
+constexpr int PSR = PTH + 8;                                // staged rows (4-row halo)
 __device__ __forceinline__ void prep_tile(const float *__restrict__ Lf, const float *__restrict__ Rf, int H, int W,
-                                          const Tables &T, int bx, int by, int gdx)
+                                          const Tables &T, int bx, int by, int gdx, uint32_t (*__restrict__ sLw)[PSW],
+                                          uint32_t (*__restrict__ sRw)[PSW])
 {
-    constexpr int SR = PTH + 8;                             // staged rows (4-row halo)
-    __shared__ uint32_t sLw[SR][PSW];
-    __shared__ uint32_t sRw[SR][PSW];
+    constexpr int SR = PSR;
     const int tiles_y = (H + PTH - 1) / PTH;
     if (by >= tiles_y) {                                    // workgroup-uniform, before any barrier
         prep_edges(Lf, Rf, H, W, T, (by - tiles_y) * gdx + bx);
@@ -232,7 +235,9 @@ __device__ __forceinline__ void prep_tile(const float *__restrict__ Lf, const fl
 __global__ void __launch_bounds__(PNT) k_prep(const float *__restrict__ Lf, const float *__restrict__ Rf,
                                               int H, int W, Tables T)
 {
-    prep_tile(Lf, Rf, H, W, T, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
+    __shared__ uint32_t sLw[PSR][PSW];
+    __shared__ uint32_t sRw[PSR][PSW];
+    prep_tile(Lf, Rf, H, W, T, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, sLw, sRw);
 }
 
 template <int C> struct vecf { float v[C]; };          // C = 5..8 (D > 256): plain struct, the kernels there use the per-element paths
@@ -396,33 +401,63 @@ __device__ __forceinline__ void st_stream(__amdgpu_buffer_rsrc_t r, unsigned vof
 
 struct __attribute__((aligned(16))) Anchor { uint64_t cen, mask; };
 
+// LDS of the maps-only kernel (k_cost_maps2p): its table plus the staged operands, one set shared by both views
+// (the volume-writing kernels keep per-instantiation static arrays).  The table workgroups stage their tile in tab.
+constexpr int MODE_VOLUME = 0, MODE_MAPS_FLOAT = 1, MODE_MAPS_RANK = 2;         // cost_fast_body's forms
+constexpr int RANK_N = 256 * 64;
+constexpr int XPAD = 4;
+constexpr int PREP_LDS_U16 = 2 * PSR * PSW * 2;            // prep_tile's staging area in uint16 units
+// NBUF staging sets: with two, chunk t+1 is written while chunk t is read (one barrier per chunk instead of two).
+template <int C, int TABN = RANK_N, int NBUF = 1> struct MapsLds {
+    uint16_t tab[TABN];                   // rank table (MODE_MAPS_RANK) or the 320-float LUT (MODE_MAPS_FLOAT)
+    struct {
+        Anchor anc[FTJ];
+        uint64_t cenx[FTJ + 64 * C + 2 * XPAD];
+        uint16_t valx[FTJ + 64 * C + 2 * XPAD];
+        uint16_t vala[FTJ];
+    } st[NBUF];
+};
+template <int MODE> struct MapsCfg {
+    static constexpr int TABN = MODE == MODE_MAPS_FLOAT ? PREP_LDS_U16 : RANK_N;
+    static constexpr int NBUF = MODE == MODE_MAPS_FLOAT ? 2 : 1;        // the rank form has no LDS to spare
+};
+
 // FULL: D == 64*C (no lane / element predication anywhere).  Otherwise C = ceil(D/64): lanes whose
 // first hypothesis is >= D compute a harmless duplicate of lane 0, elements past D are neither
 // stored nor allowed to win the WTA, and the staged arrays carry XPAD spare entries on both sides for
 // the window slots those elements would touch.
-template <int C, int VIEW, bool FULL, bool NTS = true>
+// MODE 0 writes the volume (and the map when disp != null).  MODE 1 and 2 write the map only (disp != null, vol
+// unused) and use the LDS of k_cost_maps2p (`ml`: staged operands in set `buf`, written by MapsStage, and the table the
+// kernel has filled: MODE 1 the 320-float LUT, MODE 2 the 256 x 64 rank table, Tables::rank).  MODE 2 stages the image values x64, so that v_sad_u16(va, vx, hd) is the rank
+// index 64*AD + hd, and its WTA key is rank << 16 | d: one wave min, no tie-break.
+template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME>
 __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tables &T, float *__restrict__ vol,
-                                               float *__restrict__ disp, int i, int bx)
+                                               float *__restrict__ disp, int i, int bx,
+                                               MapsLds<C, MapsCfg<MODE>::TABN, MapsCfg<MODE>::NBUF> *ml = nullptr, int buf = 0)
 {
+    constexpr bool STORE = MODE == MODE_VOLUME;
+    constexpr unsigned VSCALE = MODE == MODE_MAPS_RANK ? 64u : 4u;
     constexpr int DM = 64 * C;                               // largest D this instantiation serves
-    constexpr int XPAD = 4;
     constexpr int NXM = FTJ + DM + 2 * XPAD;
     const int D = FULL ? DM : Drt;
     const int NX = FTJ + D;
-    __shared__ Anchor s_anc[FTJ];
-    __shared__ uint64_t s_cenx_raw[NXM];
+    __shared__ Anchor s_anc_v[FTJ];
+    __shared__ uint64_t s_cenx_v[NXM];
     __shared__ float s_lut[320];
-    __shared__ uint16_t s_valx_raw[NXM];
-    __shared__ uint16_t s_vala[FTJ];
-    uint64_t *s_cenx = s_cenx_raw + XPAD;                    // entry e in [-XPAD, NX + XPAD)
-    uint16_t *s_valx = s_valx_raw + XPAD;
+    __shared__ uint16_t s_valx_v[NXM];
+    __shared__ uint16_t s_vala_v[FTJ];
+    Anchor *s_anc = STORE ? s_anc_v : ml->st[buf].anc;
+    uint16_t *s_vala = STORE ? s_vala_v : ml->st[buf].vala;
+    uint64_t *s_cenx = (STORE ? s_cenx_v : ml->st[buf].cenx) + XPAD;   // entry e in [-XPAD, NX + XPAD)
+    uint16_t *s_valx = (STORE ? s_valx_v : ml->st[buf].valx) + XPAD;
+    const void *tab = STORE ? nullptr : (const void *)ml->tab;
 
     const int j0 = bx * FTJ;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    {
+    if (STORE) {                                             // the maps-only kernel stages through MapsStage
         const uint64_t *cenX = T.cenX[VIEW] + (size_t)i * T.WX;
         const uint8_t *extv = T.u8[VIEW ^ 1] + (size_t)i * W;
         const uint8_t *ancv = T.u8[VIEW] + (size_t)i * W;
@@ -439,7 +474,7 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                 xv = x > W - 1 ? W - 1 : (x < 0 ? 0 : x);
             }
             s_cenx[e] = cenX[xc];
-            s_valx[e] = (uint16_t)(4u * extv[xv]);
+            s_valx[e] = (uint16_t)(VSCALE * extv[xv]);
         }
         for (int e = tid; e < FTJ; e += NT) {
             int j = j0 + e;
@@ -448,11 +483,11 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
             a.cen = T.cenA[VIEW][(size_t)i * W + j];
             a.mask = T.mask[(size_t)i * W + j];
             s_anc[e] = a;
-            s_vala[e] = (uint16_t)(4u * ancv[j]);
+            s_vala[e] = (uint16_t)(VSCALE * ancv[j]);
         }
         for (int e = tid; e < 320; e += NT) s_lut[e] = T.lut[e];
+        __syncthreads();
     }
-    __syncthreads();
 
     const int p0 = wid * FPW;
     const int dlr = lane * C;                                // first hypothesis of this lane
@@ -476,14 +511,18 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
         rc[slot] = s_cenx[e0 + n];
         rv[slot] = s_valx[e0 + n];
     }
-    const char *lutA = (const char *)s_lut;
-    const float *lutC = s_lut + 256;
+    const float *lut = STORE ? s_lut : (const float *)tab;
+    const char *lutA = (const char *)lut;
+    const float *lutC = lut + 256;
+    const char *rankt = (const char *)tab;
     const unsigned ooff = (unsigned)dlr * 4u;
     unsigned osoff = 0;                                      // scalar byte offset of the current pixel in the wave's run
     int res = 0;
     const int npx = min(FPW, W - (j0 + p0));                 // uniform; may be <= 0
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(vol + ((size_t)i * W + j0 + p0) * D), 0, (npx > 0 ? npx : 0) * D * 4, 0x00020000);
+    __amdgpu_buffer_rsrc_t orsrc;
+    if (STORE)
+        orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(vol + ((size_t)i * W + j0 + p0) * D), 0,
+                                                  (npx > 0 ? npx : 0) * D * 4, 0x00020000);
     // interior run: every pixel of this wave has all 63 taps inside the image, so the tap mask is
     // all ones and the two ANDs per hypothesis can be dropped (bit 63 is 0 in every table entry)
     const bool interior = (i >= 4) && (i < H - 4) && (j0 + p0 >= 3) && (j0 + p0 + npx - 1 <= W - 4);
@@ -498,6 +537,10 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
         uint32_t anc_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) Anchor *)(s_anc + p0);
         uint32_t val_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint16_t *)(s_vala + p0);
         asm volatile("" : "+v"(anc_a), "+v"(val_a));
+        // maps-only forms: the same for the entry that joins the ring; the volume-writing form keeps its measured code
+        uint32_t nx_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint64_t *)(s_cenx + e0);
+        uint32_t nv_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint16_t *)(s_valx + e0);
+        if (!STORE) asm volatile("" : "+v"(nx_a), "+v"(nv_a));
         for (int g = 0; g < npx; g += C) {
 #pragma unroll
             for (int u = 0; u < C; u++) {
@@ -513,8 +556,8 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                     const unsigned va = *(lds_u16_p)(size_t)(val_a + 2u * u);
                     // entry that joins the ring for the next pixel (always inside the staged range)
                     const int nn = (VIEW == 0) ? (q + 1) : (q + C);
-                    const uint64_t nc = s_cenx[e0 + nn];
-                    const unsigned nv = s_valx[e0 + nn];
+                    const uint64_t nc = STORE ? s_cenx[e0 + nn] : *(lds_u64_p)(size_t)(nx_a + 8u * (unsigned)(nn - g));
+                    const unsigned nv = STORE ? s_valx[e0 + nn] : *(lds_u16_p)(size_t)(nv_a + 2u * (unsigned)(nn - g));
                     float c[C];
                     unsigned key[C];
 #pragma unroll
@@ -524,19 +567,35 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                         const int slot = (VIEW == 0) ? (((u - k) % C) + C) % C : (u + k) % C;
                         uint64_t x = a.cen ^ rc[slot];
                         if (MASKED) x &= a.mask;
-                        const int hd = __popcll(x);
-                        const unsigned ad4 = __builtin_amdgcn_sad_u16(va, rv[slot], 0u);   // 4*|va - vx|
-                        c[k] = *(const float *)(lutA + ad4) + lutC[hd];
-                        key[k] = ok[k] ? __float_as_uint(c[k]) : 0xFFFFFFFFu;
+                        if (MODE == MODE_MAPS_RANK) {
+                            // 64*AD + hd, the popcount accumulated into the SAD; rank table entries are 2 bytes
+                            const unsigned hd = __builtin_amdgcn_sad_u16(va, rv[slot], (unsigned)__popcll(x));
+                            const unsigned rk = *(const uint16_t *)(rankt + 2u * hd);
+                            key[k] = ok[k] ? ((rk << 16) | (unsigned)(dl + k)) : 0xFFFFFFFFu;
+                        } else {
+                            const int hd = __popcll(x);
+                            const unsigned ad4 = __builtin_amdgcn_sad_u16(va, rv[slot], 0u);   // 4*|va - vx|
+                            c[k] = *(const float *)(lutA + ad4) + lutC[hd];
+                            key[k] = ok[k] ? __float_as_uint(c[k]) : 0xFFFFFFFFu;
+                        }
                     }
-                    if (FULL) st_stream<C, NTS>(orsrc, ooff, osoff, c);
-                    else {
+                    if (STORE) {
+                        if (FULL) st_stream<C, NTS>(orsrc, ooff, osoff, c);
+                        else {
 #pragma unroll
-                        for (int k = 0; k < C; k++)
-                            if (ok[k]) __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(c[k]), orsrc, ooff + 4u * k, osoff, NTS ? 2 : 0);
+                            for (int k = 0; k < C; k++)
+                                if (ok[k]) __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(c[k]), orsrc, ooff + 4u * k, osoff, NTS ? 2 : 0);
+                        }
+                        osoff += (unsigned)D * 4u;
                     }
-                    osoff += (unsigned)D * 4u;
-                    if (disp) {
+                    if (MODE == MODE_MAPS_RANK) {
+                        // smallest rank, then smallest d: the first strict minimum of the costs
+                        unsigned ml = key[0];
+#pragma unroll
+                        for (int k = 1; k < C; k++) ml = min(ml, key[k]);
+                        const int wd = (int)(wave_min_u32(ml) & 0xFFFFu);     // wave-uniform
+                        res = (lane == q) ? wd : res;
+                    } else if (!STORE || disp) {
                         unsigned ml = key[0];
 #pragma unroll
                         for (int k = 1; k < C; k++) ml = min(ml, key[k]);
@@ -556,6 +615,7 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                 }
             }
             anc_a += 16u * C; val_a += 2u * C;
+            nx_a += 8u * C; nv_a += 2u * C;
         }
     };
     if (interior) run(std::false_type{});
@@ -568,6 +628,29 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
 // that space: every XCD then streams its own region of the volumes instead of every eighth 48 KB piece
 // of the same region.  A store-only kernel with this mapping writes 10 % faster (6.9 vs 6.25 TB/s,
 // same box) than with chunks in dispatch order.  The grid is 1-D, padded to a multiple of 8.
+// chunk_decode is the general form: workgroup b takes the K consecutive chunks (b >> 3) * K + t, t = 0 .. K-1, of its
+// XCD's eighth (the maps-only kernel, which fills a 32 KB table once per workgroup); K = 1 is chunk_of_block.
+// maps_groups() is the number of workgroups that covers a launch.
+__host__ __device__ inline bool chunk_decode(int nbx, int H, int nviews, int K, long b, int t, int &view, int &i, int &bx)
+{
+    const long nb = (long)nbx * H * nviews;
+    const long per = (nb + 7) >> 3;
+    const long cl = (b >> 3) * K + t;
+    if (cl >= per) return false;
+    const long c = (b & 7) * per + cl;
+    if (c >= nb) return false;
+    const long rows = (long)nbx * H;
+    view = (int)(c / rows);
+    const long r = c - (long)view * rows;
+    i = (int)(r / nbx);
+    bx = (int)(r - (long)i * nbx);
+    return true;
+}
+__host__ __device__ inline int maps_groups(int nbx, int H, int nviews, int K)
+{
+    const long per = ((long)nbx * H * nviews + 7) >> 3;
+    return (int)(8 * ((per + K - 1) / K));
+}
 __device__ __forceinline__ bool chunk_of_block(int nbx, int H, int nviews, int &view, int &i, int &bx, long b = -1)
 {
     const long nb = (long)nbx * H * nviews;
@@ -662,13 +745,139 @@ __global__ void __launch_bounds__(NT, 8) k_cost_fast2p(int H, int W, int D, Tabl
     const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
     const int b = idx * 8 + (int)(blockIdx.x & 7);
     if (table) {
-        if (b < nprep) prep_tile(nL, nR, H, W, Tn, b % ptx, b / ptx, ptx);
+        __shared__ uint32_t sLw[PSR][PSW];
+        __shared__ uint32_t sRw[PSR][PSW];
+        if (b < nprep) prep_tile(nL, nR, H, W, Tn, b % ptx, b / ptx, ptx, sLw, sRw);
         return;
     }
     int view, i, bx;
     if (!chunk_of_block(nbx, H, 2, view, i, bx, b)) return;
     if (view == 0) cost_fast_body<C, 0, FULL, NTS>(H, W, D, T, vol0, disp0, i, bx);
     else cost_fast_body<C, 1, FULL, NTS>(H, W, D, T, vol1, disp1, i, bx);
+}
+
+// Maps-only form of k_cost_fast2p / k_cost_fast2 for the pairs of a batch whose volumes no caller can read (every
+// pair but the last, smt_adcensus_compute_batch): no volume stores, so the kernel is bound by its arithmetic and LDS
+// reads, not by HBM.  MODE_MAPS_RANK reads one 2-byte rank per hypothesis from a 32 KB LDS table instead of two LUT
+// entries and a float add, and its WTA is a single wave min; the table is filled once per workgroup, which then walks
+// K consecutive chunks of its XCD's range (chunk_decode).  A view whose map is null does no cost work.  With nprep > 0
+// the table workgroups of the next pair are placed as in k_cost_fast2p (fused_grid over the maps_groups() cost
+// workgroups); they stage their tile in the same LDS array.
+// Operands of one chunk of the maps-only kernel: loaded into registers, so that the loads of the workgroup's next chunk
+// are in flight while the current one is computed (at 4 workgroups per CU nothing else hides them), then written to
+// LDS.  Same entries, clamps and scaling as the staging block of cost_fast_body; the view is a runtime argument.
+template <int C, bool FULL>
+struct MapsStage {
+    static constexpr int NE = (FTJ + 64 * C + 2 * XPAD + NT - 1) / NT;      // staged entries per thread
+    uint64_t cen[NE];
+    unsigned val[NE];
+    Anchor anc;
+    unsigned va;
+    __device__ __forceinline__ void load(int view, int i, int bx, int W, int Drt, const Tables &T)
+    {
+        const int D = FULL ? 64 * C : Drt, NX = FTJ + D, j0 = bx * FTJ, tid = threadIdx.x;
+        const uint64_t *cenX = T.cenX[view] + (size_t)i * T.WX;
+        const uint8_t *extv = T.u8[view ^ 1] + (size_t)i * W;
+        const int xbase = (view == 0) ? (j0 - (D - 1)) : j0;
+#pragma unroll
+        for (int n = 0; n < NE; n++) {
+            const int e = tid - (FULL ? 0 : XPAD) + n * NT;
+            if (e < NX + (FULL ? 0 : XPAD)) {
+                const int x = xbase + e;
+                int xc, xv;
+                if (view == 0) {
+                    xc = x < -3 ? -3 : (x > W - 1 ? W - 1 : x);
+                    xv = xc < 0 ? 0 : xc;
+                    xc += 3;
+                } else {
+                    xc = x > W + 3 ? W + 3 : (x < 0 ? 0 : x);
+                    xv = x > W - 1 ? W - 1 : (x < 0 ? 0 : x);
+                }
+                cen[n] = cenX[xc];
+                val[n] = extv[xv];
+            }
+        }
+        if (tid < FTJ) {
+            const int j = min(j0 + tid, W - 1);
+            anc.cen = T.cenA[view][(size_t)i * W + j];
+            anc.mask = T.mask[(size_t)i * W + j];
+            va = T.u8[view][(size_t)i * W + j];
+        }
+    }
+    template <unsigned VSCALE, int TABN, int NBUF>
+    __device__ __forceinline__ void store(MapsLds<C, TABN, NBUF> &ml, int buf, int Drt) const
+    {
+        const int D = FULL ? 64 * C : Drt, NX = FTJ + D, tid = threadIdx.x;
+#pragma unroll
+        for (int n = 0; n < NE; n++) {
+            const int e = tid - (FULL ? 0 : XPAD) + n * NT;
+            if (e < NX + (FULL ? 0 : XPAD)) {
+                ml.st[buf].cenx[XPAD + e] = cen[n];
+                ml.st[buf].valx[XPAD + e] = (uint16_t)(VSCALE * val[n]);
+            }
+        }
+        if (tid < FTJ) { ml.st[buf].anc[tid] = anc; ml.st[buf].vala[tid] = (uint16_t)(VSCALE * va); }
+    }
+};
+
+template <int C, bool FULL, int MODE>
+__global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables T, float *__restrict__ disp0,
+                                                    float *__restrict__ disp1, int nbx, int K, int ncost, int nprep,
+                                                    const float *__restrict__ nL, const float *__restrict__ nR,
+                                                    Tables Tn, int ptx)
+{
+    static_assert(PNT == NT, "");
+    constexpr int TABN = MapsCfg<MODE>::TABN, NBUF = MapsCfg<MODE>::NBUF;
+    static_assert(2 * PSR * PSW * 4 <= TABN * 2 && 320 * 4 <= TABN * 2, "");
+    __shared__ MapsLds<C, TABN, NBUF> lds;
+    uint16_t *s_tab = lds.tab;
+    long b = blockIdx.x;
+    if (nprep > 0) {
+        const FusedGrid f = fused_grid(ncost, nprep);
+        int idx;
+        const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
+        b = idx * 8 + (int)(blockIdx.x & 7);
+        if (table) {
+            uint32_t (*sw)[PSW] = (uint32_t (*)[PSW])s_tab;
+            if (b < nprep) prep_tile(nL, nR, H, W, Tn, (int)b % ptx, (int)b / ptx, ptx, sw, sw + PSR);
+            return;
+        }
+    }
+    const int tid = threadIdx.x;
+    if (MODE == MODE_MAPS_RANK) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        for (int e = tid; e < RANK_N / 8; e += NT) ((u32x4 *)s_tab)[e] = ((const u32x4 *)T.rank)[e];
+    } else {
+        for (int e = tid; e < 320; e += NT) ((float *)s_tab)[e] = T.lut[e];
+    }
+    // the workgroup's next chunk at or after t whose map is requested (workgroup-uniform), K when there is none
+    auto next = [&](int t, int &view, int &i, int &bx) {
+        for (; t < K; t++) {
+            if (!chunk_decode(nbx, H, 2, K, b, t, view, i, bx)) return K;
+            if (view == 0 ? disp0 : disp1) return t;
+        }
+        return K;
+    };
+    MapsStage<C, FULL> st;
+    int view = 0, i = 0, bx = 0;
+    int t = next(0, view, i, bx);
+    if (t < K) st.load(view, i, bx, W, D, T);
+    // With one staging set a barrier must follow the reads of chunk t before chunk t+1 is written.  With two, the barrier
+    // after the write of chunk t+1 is only passed once every wave has finished chunk t-1, the last reader of that set.
+    bool first = true;
+    int buf = 0;
+    while (t < K) {
+        if (NBUF == 1 && !first) __syncthreads();
+        first = false;
+        st.template store<MODE == MODE_MAPS_RANK ? 64u : 4u>(lds, buf, D);
+        __syncthreads();
+        const int cv = view, ci = i, cbx = bx;
+        t = next(t + 1, view, i, bx);
+        if (t < K) st.load(view, i, bx, W, D, T);                       // in flight during this chunk's arithmetic
+        if (cv == 0) cost_fast_body<C, 0, FULL, true, MODE>(H, W, D, T, nullptr, disp0, ci, cbx, &lds, buf);
+        else cost_fast_body<C, 1, FULL, true, MODE>(H, W, D, T, nullptr, disp1, ci, cbx, &lds, buf);
+        buf = NBUF == 1 ? 0 : buf ^ 1;
+    }
 }
 
 // Store-only twin of k_cost_fast2<C, true>: the same grid, workgroup -> chunk order and streaming stores
@@ -875,7 +1084,8 @@ static int place_volumes(smt_adcensus *h, bool allow_search)
 }
 
 template <int C, bool FULL>
-static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL = nullptr, const float *nR = nullptr);
+static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL = nullptr, const float *nR = nullptr,
+                        bool maps = false);
 
 // Streaming (non-temporal) or ordinary stores for the volumes?  Streaming stores were worth 8-19 % on the
 // devices of round 1; on another device the store-only twin is 5 % FASTER with ordinary stores (DESIGN.md
@@ -952,6 +1162,42 @@ SMT_API int smt_adcensus_placement(smt_adcensus *h, int *tries, float *store_onl
     return SMT_OK;
 }
 
+// fusion tables, the reference's own float expression (AD-Census.h:287-288)
+static void build_lut(float sigmaC, float sigmaS, float *lut)
+{
+    for (int k = 0; k < 256; k++) lut[k] = 1.0f - expf(-((float)k / sigmaC));
+    for (int k = 0; k < 64; k++) lut[256 + k] = 1.0f - expf(-((float)k / sigmaS));
+}
+
+// Rank table of the maps-only kernel: rank[64*ad + hd] = dense rank of the f32 sum lut[ad] + lut[256 + hd] (the one
+// IEEE round-to-nearest add the kernels perform) among all 256 x 64 sums.  sigmaC, sigmaS > 0, so every sum is finite
+// and >= +0 and the order of the bit patterns as uint32 is the order of the costs: equal bits get an equal rank,
+// larger bits a larger one.  At most 16384 ranks, so rank << 16 | d is a WTA key for d < 65536.
+static bool build_rank(const float *lut, uint16_t *rank)
+{
+    static_assert(RANK_N <= 65536, "");
+    uint64_t *kv = new (std::nothrow) uint64_t[RANK_N];
+    if (!kv) return false;
+    for (int a = 0; a < 256; a++)
+        for (int c = 0; c < 64; c++) {
+            const float f = lut[a] + lut[256 + c];
+            uint32_t bits;
+            memcpy(&bits, &f, 4);
+            kv[a * 64 + c] = ((uint64_t)bits << 32) | (uint32_t)(a * 64 + c);
+        }
+    std::sort(kv, kv + RANK_N);
+    int r = -1;
+    uint32_t prev = 0;
+    for (int n = 0; n < RANK_N; n++) {
+        const uint32_t bits = (uint32_t)(kv[n] >> 32);
+        if (n == 0 || bits != prev) r++;
+        prev = bits;
+        rank[(uint32_t)kv[n]] = (uint16_t)r;
+    }
+    delete[] kv;
+    return true;
+}
+
 static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsigned flags, smt_adcensus **out)
 {
     if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || !(sigmaC > 0.0f) || !(sigmaS > 0.0f))
@@ -967,11 +1213,13 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
     int rc = place_volumes(h, !(flags & SMT_ADCENSUS_NO_PLACEMENT_SEARCH));
     auto alloc = [&](void **p, size_t bytes) { if (rc == SMT_OK) rc = smt_malloc(p, bytes); };
     alloc((void **)&h->TS[0].lut, 320 * 4);
+    alloc((void **)&h->TS[0].rank, RANK_N * 2);
     alloc((void **)&h->TS[0].flag, 4);
     for (int t = 0; t < 2; t++) {
         h->TS[t].WX = WX;
         h->TS[t].stamp = nullptr;
         h->TS[t].lut = h->TS[0].lut;                     // shared
+        h->TS[t].rank = h->TS[0].rank;
         h->TS[t].flag = h->TS[0].flag;
         for (int v = 0; v < 2; v++) {
             alloc((void **)&h->TS[t].cenA[v], N * 8);
@@ -993,13 +1241,15 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
             smt_adcensus_destroy(h);
             return SMT_ERR_HIP;
         }
-    // fusion tables, the reference's own float expression (AD-Census.h:287-288)
     float lut[320];
-    for (int k = 0; k < 256; k++) lut[k] = 1.0f - expf(-((float)k / sigmaC));
-    for (int k = 0; k < 64; k++) lut[256 + k] = 1.0f - expf(-((float)k / sigmaS));
+    build_lut(sigmaC, sigmaS, lut);
+    uint16_t *rank = new (std::nothrow) uint16_t[RANK_N];
+    if (!rank || !build_rank(lut, rank)) { delete[] rank; smt_adcensus_destroy(h); return SMT_ERR_ALLOC; }
+    const bool rank_ok = hipMemcpy(h->TS[0].rank, rank, RANK_N * 2, hipMemcpyHostToDevice) == hipSuccess;
+    delete[] rank;
     // the reference's `new float[size*dispRange]()` value-initialises the volumes (AD-Census.h:341-342):
     // GetPtrLeft/Right before the first Compute* reads zeros
-    if (hipMemcpy(h->TS[0].lut, lut, sizeof(lut), hipMemcpyHostToDevice) != hipSuccess ||
+    if (!rank_ok || hipMemcpy(h->TS[0].lut, lut, sizeof(lut), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(h->vol[0], 0, V * 4) != hipSuccess || hipMemset(h->vol[1], 0, V * 4) != hipSuccess ||
         hipMemset(h->TS[0].flag, 0, 4) != hipSuccess) {
         smt_adcensus_destroy(h);
@@ -1050,7 +1300,7 @@ SMT_API int smt_adcensus_destroy(smt_adcensus *h)
         }
         (void)hipFree(h->TS[t].mask);
     }
-    (void)hipFree(h->TS[0].lut); (void)hipFree(h->TS[0].flag);
+    (void)hipFree(h->TS[0].lut); (void)hipFree(h->TS[0].rank); (void)hipFree(h->TS[0].flag);
     if (h->ev) {
         for (int k = 0; k < SMT_TIMING_SLOTS * 4; k++) (void)hipEventDestroy(h->ev[k]);
         delete[] h->ev_merged;
@@ -1080,11 +1330,43 @@ static void launch_cost(smt_adcensus *h, int view0, int nviews, float *d0, float
                        view0, h->vol[0], h->vol[1], d0, d1);
 }
 
+// Chunks per workgroup of the maps-only kernel (k_cost_maps2p).  SMT_MAPS_CHUNKS=<1..64> in the environment is a
+// tuning hook (read at every call); SMT_MAPS_KERNEL=rank selects the rank-key form in place of the float LUT (A/B,
+// at the 4 workgroups per CU its 32 KB table leaves room for, it is the slower one).
+static int maps_chunks()
+{
+    const char *env = getenv("SMT_MAPS_CHUNKS");
+    const int k = env ? atoi(env) : 0;
+    return k >= 1 && k <= 64 ? k : 4;
+}
+
 template <int C, bool FULL>
-static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL, const float *nR)
+static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL, const float *nR, bool maps)
 {
     const int nbx = (h->W + FTJ - 1) / FTJ;
     auto blocks = [&](int nviews) { return dim3((unsigned)(((long)nbx * h->H * nviews + 7) / 8 * 8)); };
+    if (views == SMT_VIEW_BOTH && maps) {
+        // pair of a batch whose volumes nobody can read: maps only, the next pair's table workgroups (if any) fused in
+        const int K = maps_chunks();
+        const int ncost = maps_groups(nbx, h->H, 2, K);
+        int nprep = 0, ptx = 1;
+        unsigned grid = (unsigned)ncost;
+        if (nL) {
+            ptx = (h->W + PTW - 1) / PTW;
+            const int pty = (h->H + PTH - 1) / PTH, eb = (h->H + PNT / 16 - 1) / (PNT / 16);
+            nprep = ptx * (pty + (eb + ptx - 1) / ptx);
+            grid = 8u * (unsigned)fused_grid(ncost, nprep).groups;
+        }
+        const Tables &Tn = h->TS[(h->n_pairs + 1) & 1];
+        const char *env = getenv("SMT_MAPS_KERNEL");
+        if (env && env[0] == 'r')
+            hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_RANK>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
+                               h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx);
+        else
+            hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_FLOAT>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
+                               h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx);
+        return;
+    }
     if (views == SMT_VIEW_BOTH && nL) {
         // this pair's cost workgroups + the next pair's table workgroups (into the other table set) in one launch
         const int ncost = (int)blocks(2).x;
@@ -1136,9 +1418,10 @@ static bool fast_both_views(const smt_adcensus *h, int views)
     return views == SMT_VIEW_BOTH && !h->force_generic && (h->D + 63) / 64 <= 4;
 }
 
+// maps: the pair's volumes are not written (a batch pair before the last; fast_both_views only).
 static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int views, float *dL,
                          float *dR, bool overlap, bool prepped = false, const float *nL = nullptr,
-                         const float *nR = nullptr)
+                         const float *nR = nullptr, bool maps = false)
 {
     const int H = h->H, W = h->W, D = h->D;
     const int set = (int)(h->n_pairs & 1);
@@ -1182,14 +1465,14 @@ static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int vi
         }
     } else {
         switch (C * 2 + (full ? 1 : 0)) {
-        case 3: launch_fast<1, true>(h, views, dL, dR, nL, nR); break;
-        case 5: launch_fast<2, true>(h, views, dL, dR, nL, nR); break;
-        case 7: launch_fast<3, true>(h, views, dL, dR, nL, nR); break;
-        case 9: launch_fast<4, true>(h, views, dL, dR, nL, nR); break;
-        case 2: launch_fast<1, false>(h, views, dL, dR, nL, nR); break;
-        case 4: launch_fast<2, false>(h, views, dL, dR, nL, nR); break;
-        case 6: launch_fast<3, false>(h, views, dL, dR, nL, nR); break;
-        case 8: launch_fast<4, false>(h, views, dL, dR, nL, nR); break;
+        case 3: launch_fast<1, true>(h, views, dL, dR, nL, nR, maps); break;
+        case 5: launch_fast<2, true>(h, views, dL, dR, nL, nR, maps); break;
+        case 7: launch_fast<3, true>(h, views, dL, dR, nL, nR, maps); break;
+        case 9: launch_fast<4, true>(h, views, dL, dR, nL, nR, maps); break;
+        case 2: launch_fast<1, false>(h, views, dL, dR, nL, nR, maps); break;
+        case 4: launch_fast<2, false>(h, views, dL, dR, nL, nR, maps); break;
+        case 6: launch_fast<3, false>(h, views, dL, dR, nL, nR, maps); break;
+        case 8: launch_fast<4, false>(h, views, dL, dR, nL, nR, maps); break;
         default: return SMT_ERR_ARG;
         }
     }
@@ -1231,11 +1514,18 @@ SMT_API int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const fl
         SMT_HIP(hipEventRecord(h->in_ready, h->stream));
         SMT_HIP(hipStreamWaitEvent(h->prep_stream, h->in_ready, 0));
     }
+    // Only the last pair's volumes stay readable (every pair writes the same two), so pairs 0 .. pairs-2 of the
+    // both-views register-window path take the maps-only kernel.  SMT_BATCH_VOLUMES=all in the environment (read at
+    // every call) writes every pair's volumes as before: same-process A/Bs and tests.
+    const char *venv = getenv("SMT_BATCH_VOLUMES");
+    const bool all_volumes = venv && strcmp(venv, "all") == 0;
+    const bool maps_ok = !all_volumes && fast_both_views(h, views);
     for (int b = 0; b < pairs; b++) {
         const bool more = sched == 2 && b + 1 < pairs;
         int rc = adcensus_pair(h, L + b * N, R + b * N, views, dispL ? dispL + b * N : nullptr,
                                dispR ? dispR + b * N : nullptr, sched == 1 && b > 0, sched == 2 && b > 0,
-                               more ? L + (b + 1) * N : nullptr, more ? R + (b + 1) * N : nullptr);
+                               more ? L + (b + 1) * N : nullptr, more ? R + (b + 1) * N : nullptr,
+                               maps_ok && b + 1 < pairs);
         if (rc != SMT_OK) return rc;
     }
     return SMT_OK;
@@ -1284,6 +1574,82 @@ SMT_API int smt_adcensus_selftest_fused_grid(int ncost, int nprep)
     for (int t = 0; t < ntab && rc == SMT_OK; t++) if (!seen[f.groups + t]) rc = SMT_ERR_STATE;         // table groups 0 .. ntab - 1
     if (rc == SMT_OK && ntab < f.pgroups) rc = SMT_ERR_STATE;
     delete[] seen;
+    return rc;
+}
+
+// Host-side check of the maps-only launch's workgroup arithmetic: with K chunks per cost workgroup (chunk_decode,
+// maps_groups) every 64-pixel chunk of an H x (nbx * 64) both-views launch is reached exactly once, and with `nprep`
+// table workgroups fused in (fused_grid over maps_groups() cost workgroups) so is every cost and table workgroup.
+// Needs no GPU.
+SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
+{
+    if (nbx <= 0 || H <= 0 || K < 1 || nprep < 0) return SMT_ERR_ARG;
+    const long nb = (long)nbx * H * 2;
+    const int ncost = maps_groups(nbx, H, 2, K);
+    if (ncost <= 0 || (ncost & 7)) return SMT_ERR_STATE;
+    unsigned char *seen = new (std::nothrow) unsigned char[(size_t)nb]();
+    if (!seen) return SMT_ERR_ALLOC;
+    int rc = SMT_OK;
+    for (long b = 0; b < ncost && rc == SMT_OK; b++)
+        for (int t = 0; t < K; t++) {
+            int view, i, bx;
+            if (!chunk_decode(nbx, H, 2, K, b, t, view, i, bx)) {
+                // workgroup-uniform early exit: no later t of this workgroup may hold a chunk
+                for (int t2 = t + 1; t2 < K && rc == SMT_OK; t2++)
+                    if (chunk_decode(nbx, H, 2, K, b, t2, view, i, bx)) rc = SMT_ERR_STATE;
+                break;
+            }
+            if (view < 0 || view > 1 || i < 0 || i >= H || bx < 0 || bx >= nbx) { rc = SMT_ERR_STATE; break; }
+            unsigned char &cell = seen[((long)view * H + i) * nbx + bx];
+            if (cell) { rc = SMT_ERR_STATE; break; }
+            cell = 1;
+            // the chunk's XCD is the workgroup's (b % 8): chunks of XCD x are the x-th contiguous eighth
+            if ((((long)view * H + i) * nbx + bx) / ((nb + 7) >> 3) != (b & 7)) { rc = SMT_ERR_STATE; break; }
+        }
+    for (long c = 0; c < nb && rc == SMT_OK; c++) if (!seen[c]) rc = SMT_ERR_STATE;
+    delete[] seen;
+    if (rc == SMT_OK && nprep > 0) rc = smt_adcensus_selftest_fused_grid(ncost, nprep);
+    return rc;
+}
+
+// Host-side check of the rank table (build_rank) against the float sums it stands for: for sigmaC, sigmaS > 0, every
+// sum lut[ad] + lut[256 + hd] is finite and >= +0, ranks are dense from 0, and for any two entries rank order equals
+// float order (equal ranks exactly when the bit patterns are equal).  Needs no GPU.
+SMT_API int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS)
+{
+    if (!(sigmaC > 0.0f) || !(sigmaS > 0.0f)) return SMT_ERR_ARG;
+    float lut[320];
+    build_lut(sigmaC, sigmaS, lut);
+    uint16_t *rank = new (std::nothrow) uint16_t[RANK_N];
+    float *sum = new (std::nothrow) float[RANK_N];
+    float *uniq = new (std::nothrow) float[RANK_N];
+    int rc = (rank && sum && uniq && build_rank(lut, rank)) ? SMT_OK : SMT_ERR_ALLOC;
+    int nu = 0;
+    if (rc == SMT_OK) {
+        for (int e = 0; e < RANK_N; e++) {
+            sum[e] = lut[e >> 6] + lut[256 + (e & 63)];
+            uint32_t bits;
+            memcpy(&bits, &sum[e], 4);
+            if (!(sum[e] >= 0.0f && sum[e] < INFINITY) || (bits >> 31)) rc = SMT_ERR_STATE;   // finite, >= +0
+            uniq[e] = sum[e];
+        }
+        // distinct values in float order; the rank of an entry must be the number of distinct values below it
+        std::sort(uniq, uniq + RANK_N);
+        nu = (int)(std::unique(uniq, uniq + RANK_N) - uniq);
+    }
+    for (int e = 0; e < RANK_N && rc == SMT_OK; e++) {
+        const int below = (int)(std::lower_bound(uniq, uniq + nu, sum[e]) - uniq);
+        if (rank[e] != below || uniq[below] != sum[e]) rc = SMT_ERR_STATE;
+    }
+    // pairwise on a sample of entries: rank order == float order == uint32 bit order
+    for (int a = 0; a < RANK_N && rc == SMT_OK; a += 37)
+        for (int b = 0; b < RANK_N && rc == SMT_OK; b += 41) {
+            uint32_t ba, bb;
+            memcpy(&ba, &sum[a], 4); memcpy(&bb, &sum[b], 4);
+            if ((rank[a] < rank[b]) != (sum[a] < sum[b]) || (rank[a] == rank[b]) != (ba == bb) || (ba < bb) != (sum[a] < sum[b]))
+                rc = SMT_ERR_STATE;
+        }
+    delete[] rank; delete[] sum; delete[] uniq;
     return rc;
 }
 
