@@ -400,7 +400,28 @@ int smt_pipeline_run_batch(smt_pipeline *h, const uint8_t *grayL, const uint8_t 
                            float *dispL, float *dispR, uint8_t *cls, int *counts);
 int smt_pipeline_volumes(smt_pipeline *h, float **cost_left, float **cost_right, float **agg_left,
                          float **agg_right, float **scanline_sum);
-int smt_pipeline_status(smt_pipeline *h); /* synchronising: SMT_ERR_DOMAIN / SMT_ERR_REF_UB seen since the last call */
+/* synchronising: SMT_ERR_DOMAIN / SMT_ERR_REF_UB seen since the last call; SMT_ERR_STATE if a speckle kernel of
+ * smt_pipeline_run_batch_post hit its loop cap (never expected; that pair's dispL / lastDisp are then unspecified) */
+int smt_pipeline_status(smt_pipeline *h);
+/* The two post-filters the driver runs after the LR check (main.cpp:93-94, commented out there like :86-89 and :92):
+ *   RemoveSpeckles(leftDisp, col, row, speckle_diff, speckle_min_area, speckle_invalid)   1, 30, INT_MIN
+ *   MedianFilter(leftDisp, lastDisp, col, row, median_wnd)                                 3
+ * speckle_invalid is the x86 value of int(Invalid_Float = +inf). */
+typedef struct smt_post_params {
+    int speckle_diff;
+    unsigned speckle_min_area;
+    int speckle_invalid;
+    int median_wnd;         /* 1..7 */
+} smt_post_params;
+void smt_post_default_params(smt_post_params *p);
+/* smt_pipeline_run_batch plus main.cpp:93-94 for each pair, right after that pair's LR check: dispL holds the map
+ * after the LR check and RemoveSpeckles (in place, as leftDisp in main.cpp), lastDisp float32 [pairs][H][W] (may be
+ * NULL) its median -- the map main.cpp writes out (:115).  dispR, cls and counts as smt_pipeline_run_batch.  Same
+ * asynchrony and the same results under every SMT_PIPE_SCHEDULE.  The first call allocates the handle's tail scratch
+ * (10 bytes per pixel); later calls allocate nothing. */
+int smt_pipeline_run_batch_post(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                float *dispL, float *dispR, uint8_t *cls, int *counts,
+                                const smt_post_params *post, float *lastDisp);
 
 /* =====================================================================================
  * Left-right consistency              replaces LeftRightConsistency
@@ -611,6 +632,23 @@ int smt_median_filter(const float *in, float *out, int W, int H, int wnd_size, v
  * (its call sites pass +inf: undefined conversion, INT_MIN on x86).  Synchronising. */
 int smt_remove_speckles(float *disparity_map, int W, int H, int diff_insame, unsigned min_speckle_area,
                         int invalid_val, void *stream);
+/* Batch forms, asynchronous: `pairs` maps `stride` / `disp_stride` ELEMENTS apart (0 = dense, H*W; otherwise >= H*W),
+ * H*W < 2^31, enqueued on `stream` in a fixed number of launches (one for the median, four for the speckle filter)
+ * whatever the data and the pair count.
+ * smt_median_filter_batch: every map as smt_median_filter (in and out distinct).  Bit-identical to it and to
+ *   MedianFilter on maps without NaN or -0.0, where the reference's std::sort order is defined.
+ * smt_remove_speckles_batch: every map in place as smt_remove_speckles, bit for bit for every float input.  No host
+ *   synchronisation and, once the library's scratch arena holds 10 * pairs * H * W bytes, no allocation.  err_dev
+ *   (device int, may be NULL) is set nonzero if a kernel hits a loop cap (never expected; the maps are then
+ *   unspecified); the caller clears it. */
+int smt_median_filter_batch(const float *in, float *out, int pairs, size_t stride, int W, int H, int wnd_size,
+                            void *stream);
+int smt_remove_speckles_batch(float *disp, int pairs, size_t disp_stride, int W, int H, int diff_insame,
+                              unsigned min_speckle_area, int invalid_val, int *err_dev, void *stream);
+/* Test hook, host only (no GPU): checks that every 8-adjacent pixel pair of an H x W map lying in two different tiles
+ * of smt_remove_speckles_batch is examined by exactly one thread of its border-merge kernel.  SMT_OK or SMT_ERR_STATE
+ * (SMT_ERR_ARG unless 0 < H*W < 2^28). */
+int smt_speckle_selftest_tiles(int H, int W);
 
 #ifdef __cplusplus
 }

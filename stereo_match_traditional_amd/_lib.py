@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMT_HIP_LIB") or os.path.join(_HERE, "lib", "libsmt_hip.so")  # override: A/B kernel builds
 
 SMT_OK = 0
+SMT_ERR_ARG = -1
 SMT_ERR_DOMAIN = -4
 SMT_ERR_REF_UB = -5
 VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH = 1, 2, 3
@@ -30,6 +31,12 @@ class CrossArmParams(C.Structure):
 class PipelineParams(C.Structure):
     _fields_ = [("sigmaC", C.c_float), ("sigmaS", C.c_float), ("tao", C.c_int), ("p1", C.c_int), ("p2", C.c_int),
                 ("gate", C.c_int)]
+
+
+class PostParams(C.Structure):
+    """smt_post_params: main.cpp:93-94's RemoveSpeckles / MedianFilter arguments."""
+    _fields_ = [("speckle_diff", C.c_int), ("speckle_min_area", C.c_uint), ("speckle_invalid", C.c_int),
+                ("median_wnd", C.c_int)]
 
 
 class ADCensusOption(C.Structure):

@@ -15,7 +15,7 @@ __all__ = ["FillTheHole", "chooseArmLengthLeft", "chooseArmLengthRight", "choose
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
-           "to_float", "MedianFilter", "RemoveSpeckles", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info"]
+           "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info"]
 
 
 def current_stream_ptr(device=None):
@@ -823,6 +823,38 @@ def RemoveSpeckles(disparity_map, width, height, diff_insame, min_speckle_aera, 
     return disparity_map
 
 
+def _map_batch(maps, name):
+    """[P][H][W] float32 maps on the GPU, each map dense, consecutive maps stride(0) >= H*W elements apart."""
+    if not isinstance(maps, torch.Tensor) or not maps.is_cuda or maps.dtype != torch.float32 or maps.dim() != 3:
+        raise TypeError(f"{name} must be a float32 [pairs][H][W] tensor on the GPU")
+    P, H, W = maps.shape
+    if maps.stride(2) != 1 or (H > 1 and maps.stride(1) != W) or (P > 1 and maps.stride(0) < H * W):
+        raise TypeError(f"{name}: every map must be dense and the maps must not overlap (strides {maps.stride()})")
+    return P, H, W, (maps.stride(0) if P > 1 else H * W)
+
+
+@_on_tensor_device
+def MedianFilterBatch(maps, wnd_size):
+    """MedianFilter (PostProcessing.h:314-344) on every map of [pairs][H][W], one launch -> new dense [pairs][H][W]."""
+    P, H, W, stride = _map_batch(maps, "maps")
+    src = maps if stride == H * W else maps.contiguous()
+    out = torch.empty((P, H, W), dtype=torch.float32, device=maps.device)
+    check(lib().smt_median_filter_batch(_ptr(src), _ptr(out), P, C.c_size_t(0), W, H, int(wnd_size),
+                                        current_stream_ptr()), "smt_median_filter_batch")
+    return out
+
+
+@_on_tensor_device
+def RemoveSpecklesBatch(maps, diff_insame, min_speckle_aera, invalid_val):
+    """RemoveSpeckles (PostProcessing.h:250-311) on every map of [pairs][H][W], in place, asynchronous (enqueued on
+    the current stream, nothing waits).  Consecutive maps may lie further apart than H*W (stride(0))."""
+    P, H, W, stride = _map_batch(maps, "maps")
+    check(lib().smt_remove_speckles_batch(_ptr(maps), P, C.c_size_t(stride), W, H, int(diff_insame),
+                                          C.c_uint(min_speckle_aera), int(invalid_val), None, current_stream_ptr()),
+          "smt_remove_speckles_batch")
+    return maps
+
+
 # ======================================================================================
 # Image files (host side): imread / imwrite of the reference's drivers
 # ======================================================================================
@@ -930,6 +962,33 @@ class Pipeline:
         check(lib().smt_pipeline_run_batch(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls), _ptr(counts)),
               "smt_pipeline_run_batch")
         return dl, dr, cls, counts
+
+    def run_post(self, grayL, grayR, **post):
+        """run() plus main.cpp:93-94 per pair -> (dispL after the LR check and RemoveSpeckles, dispR, cls, counts,
+        lastDisp = MedianFilter of dispL).  Keywords override smt_post_default_params: speckle_diff,
+        speckle_min_area, speckle_invalid, median_wnd."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"pipeline handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        q = _lib.PostParams()
+        lib().smt_post_default_params(C.byref(q))
+        for k, v in post.items():
+            if not hasattr(q, k):
+                raise AttributeError(k)
+            setattr(q, k, v)
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        last = torch.empty_like(dl)
+        cls = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        counts = torch.zeros((P, 2), dtype=torch.int32, device=grayL.device)
+        check(lib().smt_pipeline_set_stream(self._h, current_stream_ptr(self.device)), "smt_pipeline_set_stream")
+        check(lib().smt_pipeline_run_batch_post(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
+                                                _ptr(counts), C.byref(q), _ptr(last)), "smt_pipeline_run_batch_post")
+        return dl, dr, cls, counts, last
 
     def volumes(self):
         ps = [C.c_void_p() for _ in range(5)]

@@ -25,7 +25,13 @@
 // the right view's aggregation (its own crossarm handle) beside the left view's scanline, nothing else double-buffered; SMT_PIPE_SCHEDULE=0 runs everything on the caller's stream.
 // Measured at 1920x1080 D=192, 8 pairs per call, ms per pair: 10.7 (0), 9.66-9.76 (1), 9.61-9.66 (2) -- the third
 // stream buys 1 % for a second AD-Census handle (3.3 GB) and a second crossarm handle, hence the default.
+// smt_pipeline_run_batch_post adds main.cpp:93-94 (RemoveSpeckles, MedianFilter) per pair, on M right after that
+// pair's LR check in every schedule: the tail is a few launches on one map, M already holds the map, and on S it would
+// sit in front of the right view's aggregation that the next LR check waits for.  Its scratch (one pair's speckle
+// forest and counts, an error word) is the handle's, allocated by the first _post call; tails follow each other on M,
+// so one set serves every pair.
 #include "smt_common.h"
+#include <limits.h>
 #include <new>
 #include <stdlib.h>
 
@@ -43,6 +49,14 @@ struct smt_pipeline {
     smt_scanline *so;
     float *Lf[2], *Rf[2];    // float copies of the pair in flight, per set
     float *agg[2], *sovol;   // aggregated left / right, scanline sum
+    void *tail;              // speckle scratch of one pair (smt_speckle_scratch_bytes), first _post call
+    int *tail_err;           // nonzero when a speckle kernel hit a loop cap; read and cleared by smt_pipeline_status
+};
+
+// main.cpp:93-94 on one pair, or nothing (post == NULL: smt_pipeline_run_batch)
+struct pipe_tail {
+    const smt_post_params *post;
+    float *last;             // lastDisp [pairs][H][W], may be NULL
 };
 
 SMT_API void smt_pipeline_default_params(smt_pipeline_params *p)
@@ -50,6 +64,14 @@ SMT_API void smt_pipeline_default_params(smt_pipeline_params *p)
     if (!p) return;
     p->sigmaC = 10.0f; p->sigmaS = 30.0f;                 // main.cpp:25-26
     p->tao = 30; p->p1 = 10; p->p2 = 150; p->gate = 2;    // main.cpp:27-30
+}
+
+SMT_API void smt_post_default_params(smt_post_params *p)
+{
+    if (!p) return;
+    p->speckle_diff = 1; p->speckle_min_area = 30;         // main.cpp:93
+    p->speckle_invalid = INT_MIN;                          // int(Invalid_Float = +inf): x86's integer indefinite
+    p->median_wnd = 3;                                     // main.cpp:94
 }
 
 SMT_API int smt_pipeline_destroy(smt_pipeline *h)
@@ -73,6 +95,7 @@ SMT_API int smt_pipeline_destroy(smt_pipeline *h)
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->front) (void)hipStreamDestroy(h->front);
     (void)hipFree(h->sovol);
+    (void)hipFree(h->tail); (void)hipFree(h->tail_err);
     delete h;
     return SMT_OK;
 }
@@ -147,9 +170,21 @@ SMT_API int smt_pipeline_set_stream(smt_pipeline *h, void *s)
 
 #define PIPE_HIP(call) do { if (rc == SMT_OK && (call) != hipSuccess) rc = SMT_ERR_HIP; } while (0)
 
+// main.cpp:93-94 for pair b, on M after its LR check
+static int pipeline_tail(smt_pipeline *h, const pipe_tail &t, float *dl, int b)
+{
+    if (!t.post) return SMT_OK;
+    const int H = h->H, W = h->W;
+    const smt_post_params &q = *t.post;
+    int rc = smt_speckle_enqueue(dl, 1, 0, W, H, q.speckle_diff, q.speckle_min_area, q.speckle_invalid, h->tail,
+                                 h->tail_err, h->stream);                                       // :93
+    if (rc == SMT_OK && t.last) rc = smt_median_filter(dl, t.last + (size_t)b * H * W, W, H, q.median_wnd, (void *)h->stream);   // :94
+    return rc;
+}
+
 // schedules 0 and 1: one set of front-end state, the left view's handle does both views
 static int pipeline_run_simple(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
-                               float *dispR, uint8_t *cls, int *counts)
+                               float *dispR, uint8_t *cls, int *counts, const pipe_tail &tail)
 {
     const int H = h->H, W = h->W;
     const size_t N = (size_t)H * W;
@@ -196,18 +231,17 @@ static int pipeline_run_simple(smt_pipeline *h, const uint8_t *grayL, const uint
         if (rc == SMT_OK) rc = smt_scanline_run(h->so, h->agg[0], h->Lf[0], h->sovol, dl);     // :86-89
         if (two) PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_right[0], 0));
         if (rc == SMT_OK) rc = smt_lrcheck(dl, dr, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);   // :92
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl, b);                                   // :93-94
         if (rc != SMT_OK) { (void)hipStreamSynchronize(h->side); return rc; }
     }
     h->last_set = 0;
     return SMT_OK;
 }
 
-SMT_API int smt_pipeline_run_batch(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
-                                   float *dispL, float *dispR, uint8_t *cls, int *counts)
+static int pipeline_run(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
+                        float *dispR, uint8_t *cls, int *counts, const pipe_tail &tail)
 {
-    if (!h || !grayL || !grayR || pairs <= 0 || !dispL || !dispR || !cls) return SMT_ERR_ARG;
-    smt_dev_guard dev_guard(h->device);
-    if (h->sched != 2) return pipeline_run_simple(h, grayL, grayR, pairs, dispL, dispR, cls, counts);
+    if (h->sched != 2) return pipeline_run_simple(h, grayL, grayR, pairs, dispL, dispR, cls, counts, tail);
     const int H = h->H, W = h->W;
     const size_t N = (size_t)H * W;
     hipStream_t M = h->stream, S = h->side, F = h->front;
@@ -239,6 +273,7 @@ SMT_API int smt_pipeline_run_batch(smt_pipeline *h, const uint8_t *grayL, const 
             PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s ^ 1], 0));
             if (rc == SMT_OK)
                 rc = smt_lrcheck(dl - N, dr - N, H, W, h->P.gate, cls + (b - 1) * N, counts ? counts + 2 * (b - 1) : nullptr, (void *)M);
+            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, b - 1);                     // :93-94 of pair b - 1
         }
         if (rc == SMT_OK) rc = smt_scanline_run(h->so, h->agg[0], h->Lf[s], h->sovol, dl);     // :86-89
         PIPE_HIP(hipEventRecord(h->ev_scan[s], M));
@@ -253,10 +288,36 @@ SMT_API int smt_pipeline_run_batch(smt_pipeline *h, const uint8_t *grayL, const 
         PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s], 0));
         if (rc == SMT_OK)
             rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, (void *)M);
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, b);
         h->last_set = s;
     }
     if (rc != SMT_OK) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(F); }
     return rc;
+}
+
+SMT_API int smt_pipeline_run_batch(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                   float *dispL, float *dispR, uint8_t *cls, int *counts)
+{
+    if (!h || !grayL || !grayR || pairs <= 0 || !dispL || !dispR || !cls) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts, pipe_tail{nullptr, nullptr});
+}
+
+SMT_API int smt_pipeline_run_batch_post(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                        float *dispL, float *dispR, uint8_t *cls, int *counts,
+                                        const smt_post_params *post, float *lastDisp)
+{
+    if (!h || !grayL || !grayR || pairs <= 0 || !dispL || !dispR || !cls || !post) return SMT_ERR_ARG;
+    if (post->median_wnd < 1 || post->median_wnd > 7 || lastDisp == dispL) return SMT_ERR_ARG;
+    if ((long long)h->H * h->W >= (1ll << 31)) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    if (!h->tail) {
+        int rc = smt_malloc(&h->tail, smt_speckle_scratch_bytes(1, h->W, h->H));
+        if (rc == SMT_OK) rc = smt_malloc((void **)&h->tail_err, 4);
+        if (rc == SMT_OK && hipMemsetAsync(h->tail_err, 0, 4, h->stream) != hipSuccess) rc = SMT_ERR_HIP;
+        if (rc != SMT_OK) { (void)hipFree(h->tail); (void)hipFree(h->tail_err); h->tail = nullptr; h->tail_err = nullptr; return rc; }
+    }
+    return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts, pipe_tail{post, lastDisp});
 }
 
 SMT_API int smt_pipeline_volumes(smt_pipeline *h, float **cost_left, float **cost_right, float **agg_left, float **agg_right,
@@ -284,5 +345,10 @@ SMT_API int smt_pipeline_status(smt_pipeline *h)
         if (h->adc[k]) { const int a = smt_adcensus_status(h->adc[k]); if (rc == SMT_OK) rc = a; }
     { const int c = smt_crossarm_status(h->caL); if (rc == SMT_OK) rc = c; }
     if (h->caR) { const int c = smt_crossarm_status(h->caR); if (rc == SMT_OK) rc = c; }
+    if (h->tail_err) {                                   // a speckle kernel of a _post call hit a loop cap
+        int e = 0;
+        if (hipMemcpy(&e, h->tail_err, 4, hipMemcpyDeviceToHost) != hipSuccess) e = 1;
+        if (e) { (void)hipMemset(h->tail_err, 0, 4); if (rc == SMT_OK) rc = SMT_ERR_STATE; }
+    }
     return rc;
 }

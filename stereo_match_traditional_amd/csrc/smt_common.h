@@ -49,6 +49,12 @@ static inline int smt_current_device() { int d = -1; return hipGetDevice(&d) == 
 hipError_t smt_scratch_alloc(void **p, size_t bytes, hipStream_t st);
 void smt_scratch_free(void *p, hipStream_t st);
 
+// Batched RemoveSpeckles on caller-owned scratch (csrc/speckle.hip; smt_pipeline_run_batch_post owns one for a pair):
+// smt_speckle_scratch_bytes(pairs, W, H) bytes, arguments already checked.  Enqueues four launches on `st`.
+size_t smt_speckle_scratch_bytes(int pairs, int W, int H);
+int smt_speckle_enqueue(float *disp, int pairs, size_t stride, int W, int H, int diff_insame, unsigned min_speckle_area,
+                        int invalid_val, void *scratch, int *err_dev, hipStream_t st);
+
 #ifdef __HIPCC__
 constexpr int WAVE = 64;
 

@@ -41,27 +41,31 @@ __global__ void __launch_bounds__(NT) k_u8_to_f32(const uint8_t *__restrict__ sr
 }
 
 // one thread per pixel; window <= 7x7.  std::sort's result on floats (with +inf, no NaN) is the
-// ascending order, so element [n/2] is order-independent of the sort algorithm.
+// ascending order, so element [n/2] is order-independent of the sort algorithm.  Pairs along grid.y (maps
+// `stride` elements apart; smt_median_filter: one).
 __global__ void __launch_bounds__(NT) k_median(const float *__restrict__ in, float *__restrict__ out, int W, int H,
-                                               int radius)
+                                               int radius, int pairs, size_t stride)
 {
     const int p = blockIdx.x * NT + threadIdx.x;
     if (p >= W * H) return;
     const int i = p / W, j = p - i * W;
-    float v[49];
-    int n = 0;
-    for (int r = -radius; r <= radius; r++)
-        for (int c = -radius; c <= radius; c++) {
-            const int row = i + r, col = j + c;
-            if (row >= 0 && row < H && col >= 0 && col < W) {
-                // insertion into the sorted prefix
-                const float x = in[(size_t)row * W + col];
-                int k = n++;
-                while (k > 0 && v[k - 1] > x) { v[k] = v[k - 1]; k--; }
-                v[k] = x;
+    for (int b = blockIdx.y; b < pairs; b += gridDim.y) {
+        const float *src = in + (size_t)b * stride;
+        float v[49];
+        int n = 0;
+        for (int r = -radius; r <= radius; r++)
+            for (int c = -radius; c <= radius; c++) {
+                const int row = i + r, col = j + c;
+                if (row >= 0 && row < H && col >= 0 && col < W) {
+                    // insertion into the sorted prefix
+                    const float x = src[(size_t)row * W + col];
+                    int k = n++;
+                    while (k > 0 && v[k - 1] > x) { v[k] = v[k - 1]; k--; }
+                    v[k] = x;
+                }
             }
-        }
-    out[p] = v[n / 2];
+        out[(size_t)b * stride + p] = v[n / 2];
+    }
 }
 
 }  // namespace
@@ -122,7 +126,20 @@ SMT_API int smt_median_filter(const float *in, float *out, int W, int H, int wnd
     if (!in || !out || in == out || H <= 0 || W <= 0 || wnd_size < 1 || wnd_size > 7) return SMT_ERR_ARG;
     const int n = H * W;
     hipLaunchKernelGGL(k_median, dim3((n + NT - 1) / NT), dim3(NT), 0, smt_stream(stream), in, out, W, H,
-                       wnd_size / 2);
+                       wnd_size / 2, 1, (size_t)0);
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+SMT_API int smt_median_filter_batch(const float *in, float *out, int pairs, size_t stride, int W, int H, int wnd_size,
+                                    void *stream)
+{
+    if (!in || !out || in == out || pairs <= 0 || H <= 0 || W <= 0 || wnd_size < 1 || wnd_size > 7) return SMT_ERR_ARG;
+    if ((long long)H * W >= (1ll << 31) || (stride != 0 && stride < (size_t)H * W)) return SMT_ERR_ARG;
+    const int n = H * W;
+    if (stride == 0) stride = (size_t)n;
+    hipLaunchKernelGGL(k_median, dim3((n + NT - 1) / NT, pairs < 65535 ? pairs : 65535), dim3(NT), 0,
+                       smt_stream(stream), in, out, W, H, wnd_size / 2, pairs, stride);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
