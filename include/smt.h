@@ -176,6 +176,44 @@ int smt_adcensus_compute(smt_adcensus *h, const float *L, const float *R, int vi
 int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const float *R, int pairs,
                                int views, float *dispL, float *dispR);
 
+/* ---- host-fed batches: uint8 images in host memory in, both views' maps in host memory out ----------------------
+ * What main.cpp does around the hot path (imread + cvtColor BGR2GRAY, :16-20; the uchar -> float staging, :46-55; the
+ * maps back to the host for imwrite, :115-117) for a whole batch.  The handle owns a smt_adcensus (created with
+ * SMT_ADCENSUS_NO_PLACEMENT_SEARCH | SMT_ADCENSUS_NO_STORE_CALIBRATION; it exposes no volumes), three streams (copies
+ * in, compute, copies out) and two slots of every device buffer for `chunk` pairs: the copies of chunk k+1 in and of
+ * chunk k-1 out run beside the compute of chunk k, and with D <= 256 the tables of a chunk's first pair are built
+ * inside the previous chunk's last launch, as smt_adcensus_compute_batch does between pairs.  The maps equal
+ * smt_adcensus_compute_batch's (both views) bit for bit. */
+typedef struct smt_adcensus_host smt_adcensus_host;
+#define SMT_MAP_F32 0 /* float32 maps, as smt_adcensus_compute_batch writes them (any D <= 512) */
+#define SMT_MAP_U8 1  /* uint8 maps, exact for the WTA indices; D <= 256 only, else SMT_ERR_ARG */
+/* device < 0: the current one.  channels 1 (gray) or 3 (B, G, R as imread gives them; converted with smt_bgr2gray's
+ * rule).  chunk >= 1 pairs per step. */
+int smt_adcensus_host_create(int device, int H, int W, int D, float sigmaC, float sigmaS, int channels, int map_format,
+                             int chunk, smt_adcensus_host **out);
+/* HOST pointers: L, R uint8 [pairs][H][W][channels]; dispL, dispR [pairs][H][W] of map_format.  Synchronising:
+ * returns once both maps of every pair are in host memory.  pairs == 0 is a no-op.  Pinned memory (smt_host_malloc,
+ * hipHostRegister, torch pin_memory) is what makes the copies overlap; pageable pointers give the same results,
+ * slower. */
+int smt_adcensus_host_run(smt_adcensus_host *h, const uint8_t *L, const uint8_t *R, int pairs, void *dispL,
+                          void *dispR);
+typedef struct smt_host_stats {
+    double wall_ms;                    /* first H2D start -> last D2H end (device events) */
+    double h2d_ms, compute_ms, d2h_ms; /* summed per-chunk event durations on each stream */
+    uint64_t h2d_bytes, d2h_bytes;
+    int chunks, pinned_in, pinned_out; /* pinned_*: both buffers reported as pinned host memory by HIP */
+} smt_host_stats;
+int smt_adcensus_host_stats(smt_adcensus_host *h, smt_host_stats *s); /* of the last run */
+int smt_adcensus_host_destroy(smt_adcensus_host *h);
+int smt_host_malloc(void **p, size_t bytes); /* pinned host memory (hipHostMalloc); plumbing for C / C++ callers */
+int smt_host_free(void *p);
+/* Test hook, host only (no GPU): builds the enqueue schedule of a run of `pairs` pairs in chunks of `chunk` (with and
+ * without the fused table builds, with and without the uint8 pack) and simulates it.  SMT_ERR_STATE if a wait is
+ * enqueued before its record, a slot is overwritten before its last reader is ordered before the write, a pair is
+ * copied in or out other than once, or a pair's tables are not built exactly once before its cost launch; SMT_ERR_ARG
+ * for chunk <= 0 or pairs < 0; else SMT_OK. */
+int smt_adcensus_host_selftest_schedule(int pairs, int chunk);
+
 /* GetPtrLeft / GetPtrRight (AD-Census.h:50-72): borrowed device pointer, valid until
  * destroy. view = SMT_VIEW_LEFT or SMT_VIEW_RIGHT. */
 int smt_adcensus_volume(smt_adcensus *h, int view, float **vol);

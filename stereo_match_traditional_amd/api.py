@@ -15,7 +15,8 @@ __all__ = ["FillTheHole", "chooseArmLengthLeft", "chooseArmLengthRight", "choose
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
-           "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info"]
+           "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info",
+           "ADCensusHostBatch"]
 
 
 def current_stream_ptr(device=None):
@@ -1002,6 +1003,89 @@ class Pipeline:
     def close(self):
         if getattr(self, "_h", None) is not None:
             lib().smt_pipeline_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HostStats(C.Structure):
+    """smt_host_stats (include/smt.h)."""
+    _fields_ = [("wall_ms", C.c_double), ("h2d_ms", C.c_double), ("compute_ms", C.c_double), ("d2h_ms", C.c_double),
+                ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("chunks", C.c_int), ("pinned_in", C.c_int),
+                ("pinned_out", C.c_int)]
+
+
+class ADCensusHostBatch:
+    """AD-Census of whole batches fed from host memory (smt_adcensus_host_*): what AD-CensusV1/main.cpp does around the
+    hot path (imread + cvtColor BGR2GRAY, the uchar -> float staging, the maps back to the host) for many pairs, with
+    the copies in and out overlapped with the compute.  Both views; the maps equal AD_Census.ComputeBatch's bit for bit.
+
+    channels: 1 (gray images [P, row, col]) or 3 (B, G, R images [P, row, col, 3]).  out_dtype: torch.float32 or
+    torch.uint8 (exact, dispRange <= 256 only).  chunk: pairs per step; the default 16 is the fastest point of the
+    measured sweep 2 / 4 / 8 / 16 / 32 at config 5 (256 KITTI pairs, D = 256; profiles/hostfeed_cfg5.json, DESIGN.md
+    section 5).  Pinned tensors
+    (pin_memory()) make the copies overlap; pageable ones give the same maps, slower."""
+
+    def __init__(self, row, col, dispRange, sigmaC=10.0, sigmaS=30.0, channels=1, out_dtype=torch.float32, chunk=16,
+                 device=None):
+        if channels not in (1, 3):
+            raise ValueError("channels must be 1 or 3")
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise ValueError("out_dtype must be torch.float32 or torch.uint8")
+        self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
+        self.channels, self.out_dtype, self.chunk = int(channels), out_dtype, int(chunk)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        fmt = 1 if out_dtype == torch.uint8 else 0
+        h = C.c_void_p()
+        check(lib().smt_adcensus_host_create(_dev_index(self.device), self.row, self.col, self.dispRange,
+                                             C.c_float(sigmaC), C.c_float(sigmaS), self.channels, fmt, self.chunk,
+                                             C.byref(h)), "smt_adcensus_host_create")
+        self._h = h
+
+    def _host(self, t, dtype, shape, name):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cpu":
+            raise ValueError(f"{name} must be a CPU torch tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        return t
+
+    def run(self, L, R, dispL=None, dispR=None):
+        """L, R: CPU uint8 [P, row, col] (channels=1) or [P, row, col, 3]; returns CPU (dispL, dispR) [P, row, col] of
+        out_dtype, allocated with pin_memory=True when not given.  Returns once every map is in host memory."""
+        if not isinstance(L, torch.Tensor) or L.dim() < 1:
+            raise ValueError("L must be a CPU torch tensor")
+        P = int(L.shape[0])
+        img = (P, self.row, self.col) + ((3,) if self.channels == 3 else ())
+        self._host(L, torch.uint8, img, "L")
+        self._host(R, torch.uint8, img, "R")
+        shp = (P, self.row, self.col)
+        if dispL is None:
+            dispL = torch.empty(shp, dtype=self.out_dtype, pin_memory=True)
+        if dispR is None:
+            dispR = torch.empty(shp, dtype=self.out_dtype, pin_memory=True)
+        self._host(dispL, self.out_dtype, shp, "dispL")
+        self._host(dispR, self.out_dtype, shp, "dispR")
+        check(lib().smt_adcensus_host_run(self._h, _ptr(L), _ptr(R), P, _ptr(dispL), _ptr(dispR)),
+              "smt_adcensus_host_run")
+        return dispL, dispR
+
+    def stats(self):
+        """Device-event times and byte counts of the last run (smt_host_stats) as a dict."""
+        s = HostStats()
+        check(lib().smt_adcensus_host_stats(self._h, C.byref(s)), "smt_adcensus_host_stats")
+        return {name: getattr(s, name) for name, _ in HostStats._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().smt_adcensus_host_destroy(self._h)
             self._h = None
 
     def __del__(self):

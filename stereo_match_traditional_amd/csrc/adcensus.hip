@@ -23,6 +23,7 @@
 // dword/x2/x3/x4 store (64*C*4 contiguous bytes per wave).  Row operands are staged in
 // LDS once per workgroup; WTA is a wave min + ballot (first strict minimum, :355-373).
 #include "smt_common.h"
+#include "adcensus_internal.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1502,12 +1503,35 @@ static int batch_schedule(const smt_adcensus *h, int views)
     return want;
 }
 
+// The per-pair loop of a batch (adcensus_internal.h).  Pair b >= 1 follows `sched`; pair 0 is in order, with its tables
+// already built when `prepped`; with sched 2 the last pair builds the tables of (nL, nR) inside its launch when they are
+// given.  With `maps_ok` and fast_both_views the pairs take the maps-only kernel, all but the last when `last_volumes`
+// is set (the last one then leaves its volumes in the handle), every pair when it is clear.
+int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n, int views, float *dispL,
+                         float *dispR, int sched, bool prepped, const float *nL, const float *nR, bool maps_ok,
+                         bool last_volumes)
+{
+    const size_t N = (size_t)h->H * h->W;
+    maps_ok = maps_ok && fast_both_views(h, views);
+    for (int b = 0; b < n; b++) {
+        const bool last = b + 1 == n;
+        const float *bl = sched == 2 ? (last ? nL : L + (b + 1) * N) : nullptr;
+        const float *br = sched == 2 ? (last ? nR : R + (b + 1) * N) : nullptr;
+        int rc = adcensus_pair(h, L + b * N, R + b * N, views, dispL ? dispL + b * N : nullptr,
+                               dispR ? dispR + b * N : nullptr, sched == 1 && b > 0, b > 0 ? sched == 2 : prepped,
+                               bl, br, maps_ok && (!last || !last_volumes));
+        if (rc != SMT_OK) return rc;
+    }
+    return SMT_OK;
+}
+
+bool adcensus_fused_both_views(const smt_adcensus *h) { return fast_both_views(h, SMT_VIEW_BOTH); }
+
 SMT_API int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const float *R, int pairs,
                                        int views, float *dispL, float *dispR)
 {
     if (!h || !L || !R || pairs <= 0 || views < 1 || views > 3) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
-    const size_t N = (size_t)h->H * h->W;
     const int sched = pairs > 1 ? batch_schedule(h, views) : 0;
     if (sched == 1) {
         // order the internal stream behind whatever produced the [pairs][H][W] inputs
@@ -1519,16 +1543,7 @@ SMT_API int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const fl
     // every call) writes every pair's volumes as before: same-process A/Bs and tests.
     const char *venv = getenv("SMT_BATCH_VOLUMES");
     const bool all_volumes = venv && strcmp(venv, "all") == 0;
-    const bool maps_ok = !all_volumes && fast_both_views(h, views);
-    for (int b = 0; b < pairs; b++) {
-        const bool more = sched == 2 && b + 1 < pairs;
-        int rc = adcensus_pair(h, L + b * N, R + b * N, views, dispL ? dispL + b * N : nullptr,
-                               dispR ? dispR + b * N : nullptr, sched == 1 && b > 0, sched == 2 && b > 0,
-                               more ? L + (b + 1) * N : nullptr, more ? R + (b + 1) * N : nullptr,
-                               maps_ok && b + 1 < pairs);
-        if (rc != SMT_OK) return rc;
-    }
-    return SMT_OK;
+    return adcensus_batch_pairs(h, L, R, pairs, views, dispL, dispR, sched, false, nullptr, nullptr, !all_volumes, true);
 }
 
 SMT_API int smt_adcensus_volume(smt_adcensus *h, int view, float **vol)
