@@ -4,7 +4,10 @@ formulations), the scanline optimiser and CrossAggregator against the oracle at 
 usage on the GPU box: python tests/fuzz_long.py [seed] [seconds]
 (last runs, round 3: seed 4242, 240 s: 2 538 cases of each of the four families; seed 777, 300 s with the batch entry under
 random schedules and aggregation variant 13: 1 202 cases of each; seed 2024, 400 s on the round's final code with NCC, the
-scanline optimiser and CrossAggregator added: 1 634 cases of each family; all bit-exact)"""
+scanline optimiser and CrossAggregator added: 1 634 cases of each family; all bit-exact.  Seed 9090, 300 s, with the
+batch section drawing SMT_MAPS_CHUNKS, SMT_MAPS_KERNEL, single views, the maps subset, the sigma pairs and the tie-heavy
+pair kinds of test_adcensus_batch_edges_gpu.py: 1 395 cases of each family, 673 of the batches in the rank form and 683
+single-view; all bit-exact)"""
 import sys, time
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,6 +15,7 @@ import numpy as np, torch
 import stereo_match_traditional_amd as smt
 from stereo_match_traditional_amd._lib import QUIRK_FIX_RIGHT_ARM_STRIDE
 from oracle import oracle as O
+from test_adcensus_batch_edges_gpu import BOTH, LEFT, RIGHT, SIGMAS, TIE_KINDS, Ref, check, make_pair, run_batch
 DEV = "cuda:0"
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
@@ -19,7 +23,7 @@ seed = int(sys.argv[1]) if len(sys.argv) > 1 else 12345
 rng = np.random.default_rng(seed)
 t0 = time.time(); n_adc = n_agg = 0
 budget = float(sys.argv[2]) if len(sys.argv) > 2 else 150.0
-n_sad = n_asw = n_more = 0
+n_sad = n_asw = n_more = n_batch = n_batch_rank = n_batch_single = 0
 t_say = t0
 while time.time() - t0 < budget:
     if time.time() - t_say > 60: t_say = time.time(); print("...", int(t_say - t0), "s", n_adc, "cases", flush=True)
@@ -38,21 +42,34 @@ while time.time() - t0 < budget:
     assert np.array_equal(bits(adc.GetPtrLeft().cpu().numpy()), bits(vl)), ("adcL", H, W, D)
     assert np.array_equal(bits(adc.GetPtrRight().cpu().numpy()), bits(vr)), ("adcR", H, W, D)
     assert np.array_equal(dl.cpu().numpy(), O.wta(vl)) and np.array_equal(dr.cpu().numpy(), O.wta(vr)), ("wta", H, W, D)
-    # the same handle through the batch entry, 2..4 pairs (pair 0 = the pair above, the others its row-shifted / swapped
-    # siblings), under a random schedule: in order, tables on the internal stream, tables inside the previous cost launch
-    B = int(rng.integers(2, 5))
-    Ls = [L] + [np.roll(L, b, axis=0) if b % 2 else R for b in range(1, B)]
-    Rs = [R] + [np.roll(R, b, axis=0) if b % 2 else L for b in range(1, B)]
-    os.environ["SMT_OVERLAP"] = str(int(rng.integers(0, 3)))
-    dlb = torch.empty((B, H, W), device=DEV); drb = torch.empty((B, H, W), device=DEV)
-    adc.ComputeBatch(T(np.stack(Ls)), T(np.stack(Rs)), dlb, drb)
-    os.environ.pop("SMT_OVERLAP")
-    for b in range(1, B):
-        wl = O.adcensus_view(Ls[b], Rs[b], D, 10.0, 30.0, 0); wr = O.adcensus_view(Ls[b], Rs[b], D, 10.0, 30.0, 1)
-        assert np.array_equal(dlb[b].cpu().numpy(), O.wta(wl)) and np.array_equal(drb[b].cpu().numpy(), O.wta(wr)), ("batch wta", H, W, D, b)
-    assert np.array_equal(dlb[0].cpu().numpy(), O.wta(vl)) and np.array_equal(drb[0].cpu().numpy(), O.wta(vr)), ("batch wta 0", H, W, D)
-    assert np.array_equal(bits(adc.GetPtrLeft().cpu().numpy()), bits(wl)) and np.array_equal(bits(adc.GetPtrRight().cpu().numpy()), bits(wr)), ("batch vol", H, W, D)
     adc.close(); n_adc += 1
+    # the batch entry, 2..4 pairs: pair 0 = the pair above, the others its row-shifted / swapped siblings or tie-heavy pairs
+    # (flat, two-level noise, stripes of period 3 / 8 / 64, R = L), on a handle with a random sigma pair (the last two of
+    # SIGMAS collapse a LUT), under a random schedule (in order, tables on the internal stream, tables inside the previous
+    # cost launch), maps-only chunking (SMT_MAPS_CHUNKS) and WTA form (SMT_MAPS_KERNEL), views and subset of the maps
+    B = int(rng.integers(2, 5))
+    Ls, Rs = [L], [R]
+    for b in range(1, B):
+        k = int(rng.integers(0, 8))
+        if k == 0: Ls.append(np.roll(L, b, axis=0)); Rs.append(np.roll(R, b, axis=0))
+        elif k == 1: Ls.append(R); Rs.append(L)
+        else:
+            l, r = make_pair(O, TIE_KINDS[k - 2], H, W, D, rng)
+            Ls.append(l.astype(np.float32)); Rs.append(r.astype(np.float32))
+    sc, ss = SIGMAS[int(rng.integers(0, len(SIGMAS)))]
+    ref = Ref(O, Ls, Rs, D, sc, ss)
+    if (sc, ss) == (10.0, 30.0): ref._vol[0, 0], ref._vol[0, 1] = vl, vr
+    views = [BOTH, BOTH, LEFT, RIGHT][int(rng.integers(0, 4))]
+    m = ["both", "left", "right", "none"][int(rng.integers(0, 4))]
+    knobs = {"SMT_OVERLAP": str(int(rng.integers(0, 3))), "SMT_MAPS_CHUNKS": str(int(rng.choice([1, 2, 3, 4, 8, 64]))),
+             "SMT_MAPS_KERNEL": ["float", "rank"][int(rng.integers(0, 2))]}
+    os.environ.update(knobs)
+    adc = smt.AD_Census().Initialize(T(L), T(R), D, H, W, sc, ss, placement_search=False, store_calibration=False)
+    dlb, drb = run_batch(adc, T(np.stack(Ls)), T(np.stack(Rs)), views, bool(views & LEFT) and m in ("both", "left"),
+                         bool(views & RIGHT) and m in ("both", "right"))
+    check(adc, ref, dlb, drb, views, ("batch", H, W, D, B, (sc, ss), views, m, tuple(sorted(knobs.items()))))
+    for k in knobs: os.environ.pop(k)
+    adc.close(); n_batch += 1; n_batch_rank += knobs["SMT_MAPS_KERNEL"] == "rank"; n_batch_single += views != BOTH
     # ---- aggregation, new variants
     H, W = int(rng.integers(2, 50)), int(rng.integers(2, 140))
     D = int(rng.choice([1, 5, 64, 100, 128, 192, 200, 256, 300]))
@@ -146,4 +163,5 @@ while time.time() - t0 < budget:
     assert np.array_equal(bits(agg.get_cost_ptr().cpu().numpy()), bits(c_ref)), ("ca cost", H, W, D, iters)
     agg.close(); n_more += 1
 print("fuzz ok: seed", seed, "adcensus cases", n_adc, "aggregation cases", n_agg, "sad cases", n_sad, "asw cases", n_asw,
-      "ncc + scanline + crossaggregator cases", n_more)
+      "ncc + scanline + crossaggregator cases", n_more, "batch cases", n_batch, "(rank form", n_batch_rank, "single view",
+      n_batch_single, ")", "seconds", int(time.time() - t0))

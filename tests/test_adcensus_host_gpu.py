@@ -1,6 +1,7 @@
 """Host-fed AD-Census batches (ADCensusHostBatch / smt_adcensus_host_*): uint8 images in host memory in, both views'
 maps in host memory out.  The maps must equal smt_adcensus_compute_batch's on the same pairs staged by hand, bit for
-bit, for every chunking, map format and input format, across reuse of the handle's slots."""
+bit, for every chunking, map format and input format, across reuse of the handle's slots; and the oracle's at the edge
+shapes of the staging and packing kernels."""
 import json
 import os
 
@@ -130,6 +131,51 @@ def test_config5_full_size_hashes(smt, O, out_dtype):
         assert "%016x" % O.fnv1a(dl[b]) == r["adcensus_disp_left"], b
         assert "%016x" % O.fnv1a(dr[b]) == r["adcensus_disp_right"], b
     hb.close()
+
+
+# A chunk of c pairs is one flat array of n = 2 * c * H * W pixels for k_stage_pairs and k_pack_maps, whose 16-pixel
+# vector body leaves n % 16 pixels to a one-by-one tail.  Across their chunks these shapes give every residue n can have
+# (n is even), n < 16 (tail only), W = 1, H = 1 and a partial last chunk (chunk does not divide P).
+EDGES = [  # H, W, D, P, chunk            n of the full / the last chunk (n % 16)
+    (1, 1, 1, 1, 1),                    # 2 (2)
+    (1, 3, 63, 7, 3),                   # 18 (2), 6 (6)
+    (5, 1, 255, 4, 3),                  # 30 (14), 10 (10)
+    (1, 77, 256, 7, 2),                 # 308 (4), 154 (10)
+    (3, 6, 320, 7, 3),                  # 108 (12), 36 (4)
+    (9, 31, 255, 1, 2),                 # 558 (14)
+    (8, 33, 256, 4, 3),                 # 1584 (0), 528 (0)
+    (4, 65, 63, 4, 1),                  # 520 (8)
+]
+
+
+@pytest.mark.parametrize("H,W,D,P,chunk", EDGES)
+def test_edges_against_the_oracle(smt, O, H, W, D, P, chunk):
+    """Gray and BGR input, float32 and uint8 maps: every map equals the oracle's (BGR through O.bgr2gray, uint8 maps
+    the oracle's cast).  The BGR images are low-contrast, so a gray value off by one moves census bits."""
+    rng = np.random.default_rng(H * 1000 + W * 10 + P)
+    for channels in (1, 3):
+        if channels == 1:
+            L, R = pairs_u8(H, W, D, P, 500 + D)
+            gL, gR = L, R
+        else:
+            L = rng.integers(96, 112, (P, H, W, 3), dtype=np.uint8)
+            R = rng.integers(96, 112, (P, H, W, 3), dtype=np.uint8)
+            gL, gR = np.stack([O.bgr2gray(x) for x in L]), np.stack([O.bgr2gray(x) for x in R])
+        ref = [(O.wta(O.adcensus_view(gL[b], gR[b], D, SC, SS, 0)), O.wta(O.adcensus_view(gL[b], gR[b], D, SC, SS, 1)))
+               for b in range(P)]
+        Lt, Rt = torch.from_numpy(L).pin_memory(), torch.from_numpy(R).pin_memory()
+        for out_dtype, fill in ((torch.float32, -1.0), (torch.uint8, 255)):
+            if out_dtype == torch.uint8 and D > 256:
+                continue
+            hb = smt.ADCensusHostBatch(H, W, D, SC, SS, channels=channels, out_dtype=out_dtype, chunk=chunk)
+            ol = torch.full((P, H, W), fill, dtype=out_dtype).pin_memory()
+            orr = torch.full((P, H, W), fill, dtype=out_dtype).pin_memory()
+            dl, dr = hb.run(Lt, Rt, ol, orr)
+            hb.close()
+            cast = np.float32 if out_dtype == torch.float32 else np.uint8
+            for b in range(P):
+                assert np.array_equal(dl[b].numpy(), ref[b][0].astype(cast)), (channels, out_dtype, b, "L")
+                assert np.array_equal(dr[b].numpy(), ref[b][1].astype(cast)), (channels, out_dtype, b, "R")
 
 
 def test_slot_reuse_across_runs(smt):
