@@ -70,8 +70,11 @@ int smt_set_device(int device);
  * AD-Census pipeline (smt_adcensus_*, smt_wta, smt_crossarm_*, smt_scanline_*, smt_pipeline_*: one wavefront
  * spans the disparity axis, a lane owns up to 8 consecutive hypotheses; the tuned kernels cover D <= 256, beyond
  * it the first-version kernels run -- the table-lookup cost kernel, the one-pixel-per-wave rectangle walk, the
- * predicated scanline passes -- with the same results, untuned) and D <= 256 on the window matchers, the
- * CrossAggregator and the CBLSM helpers (smt_sad, smt_ncc, smt_asw, smt_crossagg_*, smt_cblsm_*); ASW window side
+ * predicated scanline passes -- with the same results, untuned), and D <= SMT_MAX_DISPARITY on the window matchers and
+ * the CrossAggregator (smt_sad*, smt_ncc*, smt_asw*, smt_crossagg_*, smt_adcensus_option_aggregate: tuned kernels at
+ * every D -- 5..8 hypothesis slots per lane in SAD, NCC and the CrossAggregator, ASW in chunks of 256 hypotheses with
+ * WinTakeAll's state carried between them; the same rules and bits as below 256).  The CBLSM helpers (smt_cblsm_*)
+ * have no cap of their own (one thread per pixel and hypothesis).  ASW window side
  * 2*(winSize+1)+1 <= 64 (winSize <= 30; one window row per wavefront pass); MedianFilter wnd_size <= 7;
  * volumes of 4 GiB or more take the plain one-pixel-per-wave aggregation kernel (32-bit tap offsets in
  * the shared-tap kernels). */
@@ -509,8 +512,8 @@ int smt_fill_the_hole(float *disp, int row, int col, int dispRange, const int *o
  * ===================================================================================== */
 typedef struct smt_crossagg smt_crossagg;
 
-/* Initialize(width,height,min_disparity,max_disparity) (:19-58). D = max-min.
- * Returns SMT_ERR_ARG where the reference returns false. */
+/* Initialize(width,height,min_disparity,max_disparity) (:19-58). D = max-min, 1 <= D <= SMT_MAX_DISPARITY.
+ * Returns SMT_ERR_ARG where the reference returns false (and for D > SMT_MAX_DISPARITY). */
 int smt_crossagg_create(int W, int H, int D, smt_crossagg **out);
 int smt_crossagg_create_on(int device, int W, int H, int D, smt_crossagg **out);
 int smt_crossagg_destroy(smt_crossagg *h);
@@ -556,6 +559,7 @@ int smt_adcensus_option_aggregate(const smt_adcensus_option *o, const uint8_t *b
 
 /* =====================================================================================
  * Window matchers                     replace SAD/Sad.h, NCC/NCC.h, ASW/ASW.h
+ * 1 <= D <= SMT_MAX_DISPARITY on every entry point below (batch variants included); SMT_ERR_ARG beyond.
  * ===================================================================================== */
 /* GetPointDepthLeft (Sad.h:96-139, view SMT_VIEW_LEFT, WTA = OptimalDisparity :40-85) /
  * GetPointDepthRight (:141-182, view SMT_VIEW_RIGHT, WTA = GetMinSadIndex :22-38).

@@ -153,6 +153,25 @@ typedef int cai2 __attribute__((ext_vector_type(2)));
 typedef int cai3 __attribute__((ext_vector_type(3)));
 typedef int cai4 __attribute__((ext_vector_type(4)));
 
+// FULL taps of C = 5..8 hypotheses per lane (D = 320 .. 512): C = 8 as two 16-byte loads (64 C * 4 bytes per pixel and 32
+// bytes per lane keep them aligned), the others element by element
+template <int C, class P>
+__device__ __forceinline__ void ld_wide(P sp, float (&x)[C])
+{
+    if constexpr (C == 8) {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const cai4 v = *reinterpret_cast<const __attribute__((address_space(1))) cai4 *>(
+                (const __attribute__((address_space(1))) float *)(sp) + 4 * h);
+            x[4 * h] = __int_as_float(v.x); x[4 * h + 1] = __int_as_float(v.y);
+            x[4 * h + 2] = __int_as_float(v.z); x[4 * h + 3] = __int_as_float(v.w);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < C; k++) x[k] = sp[k];
+    }
+}
+
 template <int C, bool HORIZ, bool FINAL, bool FULL>
 __global__ void __launch_bounds__(NT) k_ca_pass2(const float *__restrict__ src, float *__restrict__ dst, int W, int H,
                                                  int D, const uint8_t *__restrict__ arms, const uint16_t *__restrict__ cnt,
@@ -215,10 +234,12 @@ __global__ void __launch_bounds__(NT) k_ca_pass2(const float *__restrict__ src, 
             else if (C == 2) { const cai2 v = *reinterpret_cast<const cai2 *>(sp); x[0] = __int_as_float(v.x); x[C > 1 ? 1 : 0] = __int_as_float(v.y); }
             else if (C == 3) {
                 x[0] = sp[0]; x[C > 1 ? 1 : 0] = sp[C > 1 ? 1 : 0]; x[C > 2 ? 2 : 0] = sp[C > 2 ? 2 : 0];
-            } else {
+            } else if (C == 4) {
                 const cai4 v = *reinterpret_cast<const cai4 *>(sp);
                 x[0] = __int_as_float(v.x); x[C > 1 ? 1 : 0] = __int_as_float(v.y);
                 x[C > 2 ? 2 : 0] = __int_as_float(v.z); x[C > 3 ? 3 : 0] = __int_as_float(v.w);
+            } else {
+                ld_wide(sp, x);
             }
         } else {
 #pragma unroll
@@ -277,10 +298,12 @@ __global__ void __launch_bounds__(NT) k_ca_pass2(const float *__restrict__ src, 
             else if (C == 2) { const cai2 v = *(const __attribute__((address_space(1))) cai2 *)(sp); x[0] = __int_as_float(v.x); x[C > 1 ? 1 : 0] = __int_as_float(v.y); }
             else if (C == 3) {
                 x[0] = sp[0]; x[C > 1 ? 1 : 0] = sp[C > 1 ? 1 : 0]; x[C > 2 ? 2 : 0] = sp[C > 2 ? 2 : 0];
-            } else {
+            } else if (C == 4) {
                 const cai4 v = *(const __attribute__((address_space(1))) cai4 *)(sp);
                 x[0] = __int_as_float(v.x); x[C > 1 ? 1 : 0] = __int_as_float(v.y);
                 x[C > 2 ? 2 : 0] = __int_as_float(v.z); x[C > 3 ? 3 : 0] = __int_as_float(v.w);
+            } else {
+                ld_wide(sp, x);
             }
         } else {
 #pragma unroll
@@ -376,7 +399,7 @@ struct smt_crossagg {
 SMT_API int smt_crossagg_create(int W, int H, int D, smt_crossagg **out)
 {
     if (!out) return SMT_ERR_ARG;
-    if ((long)W * H <= 0 || W <= 0 || H <= 0 || D <= 0 || D > 256) return SMT_ERR_ARG;   // Initialize returns false (:28-31)
+    if ((long)W * H <= 0 || W <= 0 || H <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;   // Initialize returns false (:28-31)
     smt_crossagg *h = new (std::nothrow) smt_crossagg();
     if (!h) return SMT_ERR_ALLOC;
     h->device = smt_current_device();
@@ -496,7 +519,11 @@ SMT_API int smt_crossagg_aggregate(smt_crossagg *h, const uint8_t *img, const fl
         case 1: ca_iter<1>(h, hfirst, in); break;
         case 2: ca_iter<2>(h, hfirst, in); break;
         case 3: ca_iter<3>(h, hfirst, in); break;
-        default: ca_iter<4>(h, hfirst, in); break;
+        case 4: ca_iter<4>(h, hfirst, in); break;
+        case 5: ca_iter<5>(h, hfirst, in); break;                    // D > 256: 5..8 hypotheses per lane, same passes
+        case 6: ca_iter<6>(h, hfirst, in); break;
+        case 7: ca_iter<7>(h, hfirst, in); break;
+        default: ca_iter<8>(h, hfirst, in); break;
         }
         hfirst = !hfirst;
     }

@@ -25,13 +25,15 @@ constexpr int KMAX = 4;        // D <= 256
 __device__ __forceinline__ float wave_min_nonneg(float v) { return __uint_as_float(wave_min_u32(__float_as_uint(v))); }
 
 // ---------------------------------------------------------------------------------- SAD
-// OptimalDisparity (Sad.h:40-85) over the wave-distributed vector sad[d], d = lane+64k.
-__device__ int sad_optimal(const float (&sad)[KMAX], int D, int lane)
+// OptimalDisparity (Sad.h:40-85) over the wave-distributed vector sad[d], d = lane+64k.  KS = KMAX for D <= 256,
+// 8 (the hypothesis slots of SMT_MAX_DISPARITY) beyond.
+template <int KS>
+__device__ int sad_optimal(const float (&sad)[KS], int D, int lane)
 {
     // min over d >= 1, first strict (:46-53), starting from 0xffff
     float lm = 65535.0f; int ld = 0x7fffffff;
 #pragma unroll
-    for (int k = 0; k < KMAX; k++) {
+    for (int k = 0; k < KS; k++) {
         const int d = lane + 64 * k;
         if (d >= 1 && d < D && lm > sad[k]) { lm = sad[k]; ld = d; }
     }
@@ -43,7 +45,7 @@ __device__ int sad_optimal(const float (&sad)[KMAX], int D, int lane)
     // second minimum: starts at sad[0]; every entry equal to minv is skipped (:55-64)
     float ls = INFINITY;
 #pragma unroll
-    for (int k = 0; k < KMAX; k++) {
+    for (int k = 0; k < KS; k++) {
         const int d = lane + 64 * k;
         if (d < D && !(minv == sad[k])) ls = fminf(ls, sad[k]);
     }
@@ -54,9 +56,11 @@ __device__ int sad_optimal(const float (&sad)[KMAX], int D, int lane)
     return (int)best;                                                     // :84
 }
 
-// grid: one wave per ORIGINAL pixel (io, jo); Lp/Rp padded by w = winsize+1
-__global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
-                                            int W, int D, int w, int view, int32_t *__restrict__ disp)
+// grid: one wave per ORIGINAL pixel (io, jo); Lp/Rp padded by w = winsize+1.  KS hypothesis slots per lane: KMAX in
+// k_sad (D <= 256), 8 in k_sad8 (D <= SMT_MAX_DISPARITY); the slots past ceil(D / 64) are skipped at run time.
+template <int KS>
+__device__ __forceinline__ void sad_pixel(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
+                                          int D, int w, int view, int32_t *__restrict__ disp)
 {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -69,13 +73,13 @@ __global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, cons
         return;
     }
     const int dmax = (view == 0) ? jo : (W - 1 - jo);                     // last in-range disparity
-    float sad[KMAX];
+    float sad[KS];
     // top-left corners of the two windows in padded coordinates; hypothesis d is evaluated at min(d, dmax)
     const uint8_t *a = (view == 0 ? Lp : Rp) + (size_t)io * Wp + jo;
-    const uint8_t *b[KMAX];
-    unsigned acc[KMAX];
+    const uint8_t *b[KS];
+    unsigned acc[KS];
 #pragma unroll
-    for (int k = 0; k < KMAX; k++) {
+    for (int k = 0; k < KS; k++) {
         const int d = lane + 64 * k;
         const int dd = d < dmax ? d : dmax;
         b[k] = (view == 0) ? Rp + (size_t)io * Wp + jo - dd : Lp + (size_t)io * Wp + jo + dd;
@@ -97,7 +101,7 @@ __global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, cons
                 __builtin_memcpy(&a4, a + r * Wp + c0, 4);
                 a4 &= m;
 #pragma unroll
-                for (int k = 0; k < KMAX; k++)
+                for (int k = 0; k < KS; k++)
                     if (k < nk) {
                         unsigned b4;
                         __builtin_memcpy(&b4, b[k] + r * Wp + c0, 4);
@@ -109,17 +113,17 @@ __global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, cons
         for (int r = 0; r < side; r++)
             for (int c = 0; c < side; c++)
 #pragma unroll
-                for (int k = 0; k < KMAX; k++)
+                for (int k = 0; k < KS; k++)
                     if (k < nk) acc[k] += (unsigned)abs((int)a[r * Wp + c] - (int)b[k][r * Wp + c]);
     }
 #pragma unroll
-    for (int k = 0; k < KMAX; k++) sad[k] = (lane + 64 * k < D) ? (float)acc[k] : 0.0f;   // sadvalue :15-20
+    for (int k = 0; k < KS; k++) sad[k] = (lane + 64 * k < D) ? (float)acc[k] : 0.0f;   // sadvalue :15-20
     int out;
-    if (view == 0) out = sad_optimal(sad, D, lane);
+    if (view == 0) out = sad_optimal<KS>(sad, D, lane);
     else {                                                                // GetMinSadIndex :22-38
         float lm = INFINITY; int ld = 0;
 #pragma unroll
-        for (int k = 0; k < KMAX; k++) {
+        for (int k = 0; k < KS; k++) {
             const int d = lane + 64 * k;
             if (d < D && sad[k] < lm) { lm = sad[k]; ld = d; }
         }
@@ -128,6 +132,18 @@ __global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, cons
         out = (int)wave_min_u32((unsigned)cand);
     }
     if (lane == 0) disp[p] = out;
+}
+
+__global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
+                                            int W, int D, int w, int view, int32_t *__restrict__ disp)
+{
+    sad_pixel<KMAX>(Lp, Rp, H, W, D, w, view, disp);
+}
+
+__global__ void __launch_bounds__(NT) k_sad8(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
+                                             int W, int D, int w, int view, int32_t *__restrict__ disp)
+{
+    sad_pixel<8>(Lp, Rp, H, W, D, w, view, disp);
 }
 
 // Second formulation (default for windows of side >= 4): k_sad above is bound by its own global-load latency (one
@@ -230,11 +246,12 @@ __global__ void __launch_bounds__(NT) k_sad2(const uint8_t *__restrict__ Lp, con
                 for (int k = 0; k < K; k++) acc[k] = __builtin_amdgcn_sad_u8(a4, ro[btail[k]] & tmask, acc[k]);
             }
         }
-        float sad[KMAX];
+        constexpr int KS = K <= KMAX ? KMAX : 8;         // selection slots: KMAX up to D = 256, 8 beyond
+        float sad[KS];
 #pragma unroll
-        for (int k = 0; k < KMAX; k++) sad[k] = (k < K && lane + 64 * k < D) ? (float)acc[k < K ? k : 0] : 0.0f;   // sadvalue :15-20
+        for (int k = 0; k < KS; k++) sad[k] = (k < K && lane + 64 * k < D) ? (float)acc[k < K ? k : 0] : 0.0f;   // sadvalue :15-20
         int out;
-        if (view == 0) out = sad_optimal(sad, D, lane);
+        if (view == 0) out = sad_optimal<KS>(sad, D, lane);
         else {                                                            // GetMinSadIndex :22-38
             float lm = INFINITY; int ld = 0;
 #pragma unroll
@@ -266,10 +283,12 @@ __device__ double ncc_cost(const uint8_t *a, const uint8_t *b, int W, int side) 
     return num / (sqrt(ls) * sqrt(rs));
 }
 
+// DM: the largest D of the instantiation (256: k_ncc<256> for D <= 256, SMT_MAX_DISPARITY beyond)
+template <int DM>
 __global__ void __launch_bounds__(NT) k_ncc(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R, int H, int W,
                                             int D, int win, int32_t *__restrict__ disp, double *__restrict__ cost_out)
 {
-    __shared__ double s_cost[NT / 64][256];
+    __shared__ double s_cost[NT / 64][DM];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = blockIdx.x * (NT / 64) + wv;
@@ -364,10 +383,15 @@ __device__ __forceinline__ uint32_t lds_u32(const uint32_t *p)
 // Offset (in dwords) of byte-shifted copy s of the right rows.  The 32 lanes of a half-wave read 8 groups x 4
 // copies; consecutive groups sit K dwords apart, so the copies are placed on the banks that spacing leaves free
 // (K = 3 keeps one 2-way overlap).  CS is a multiple of 32.
+// D > 256: for odd K the 8 groups sit on 8 distinct banks, K * {0..7} mod 32, and the shifts 8 K s mod 32 carry that
+// set onto three disjoint copies of itself (K * 8 is the set's own period: multiply by K^-1 mod 32 and the set is
+// 0..7, the shifts 0, 8, 16, 24); K = 6 spans the even banks like K = 2 and takes its layout; K = 8 puts groups
+// g and g + 4, 32 words apart, on one bank whatever the shift (2-way).
 template <int K>
 __device__ __forceinline__ int ncc_copy_off(int s, int CS)
 {
-    const int bank = K == 1 ? 8 * s : (K == 2 ? (s & 1) + 16 * (s >> 1) : s);
+    const int bank = K <= 4 ? (K == 1 ? 8 * s : (K == 2 ? (s & 1) + 16 * (s >> 1) : s))
+                            : ((K & 1) ? (8 * K * s) & 31 : (K == 6 ? (s & 1) + 16 * (s >> 1) : s));
     return s * CS + bank;
 }
 
@@ -786,12 +810,15 @@ __device__ __forceinline__ P uniform_ptr(P p)
 // the arithmetic of k_asw_anchor -- then reads them back through the scalar cache: vector stores, s_waitcnt vmcnt(0)
 // (the stores have reached L2), s_dcache_inv (the scalar cache may hold the previous tile's slot contents), scalar loads.
 // No other wave ever touches a wave's part of the slot, so no barrier is involved.
-template <int K, int A3Q, bool SLOAD, bool OWN>
+// WIDE (D > 256, k_asw3w / k_asw4w): the tile evaluates the chunk of hypotheses dc .. dc + 64 K - 1 only, and WinTakeAll
+// continues the sequential scan of the chunks before it through carry[pixel] = (running minimum, its first index):
+// cflags bit 0 = first chunk (the scan starts at +inf, index 0), bit 1 = last chunk (the pixel's disparity is written).
+template <int K, int A3Q, bool SLOAD, bool OWN, bool WIDE = false>
 __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                           int W, int D, int wins, const double *__restrict__ space,
                                           double *w0, const unsigned *__restrict__ a32, int T,
                                           int view, float *__restrict__ disp, float *__restrict__ cost_out, int i0, int io, int jo0,
-                                          unsigned char *smem)
+                                          unsigned char *smem, int dc = 0, float2 *carry = nullptr, int cflags = 0)
 {
     constexpr int NPX = A3P * A3Q;                         // pixels per workgroup
     constexpr int NXP = NPX + 64 * K;                      // window positions of the other image per row (padded)
@@ -819,7 +846,13 @@ __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const 
     // the other image and the first window position the workgroup can touch:
     //   view 0: xs = jo - dd in [jo0 - (D-1), jo0 + NPX-1];   view 1: xs = jo + dd in [jo0, jo0 + NPX-1 + D-1]
     const uint8_t *Bimg = (view == 0 ? Rp : Lp) + (size_t)io * Wp;
-    const int xbase = (view == 0) ? jo0 - (64 * K - 1) : jo0;
+    int xbase = (view == 0) ? jo0 - (64 * K - 1) : jo0;
+    if constexpr (WIDE) {
+        // chunk dc ..: a hypothesis past dmax is evaluated at dmax, so the positions are xs = max(jc - d, 0) (view 0) and
+        // xs = min(jc + d, max(W - wins - 2, jc)) (view 1), both nondecreasing in jc: the lowest is that of (jo0, dc), and
+        // the NXP positions from it hold the highest
+        xbase = (view == 0) ? max(jo0 - dc - (64 * K - 1), 0) : min(jo0 + dc, max(W - wins - 2, jo0));
+    }
 
     // the wave's A3Q pixels: jo0 + wv and jo0 + A3P + wv (pixels past the row end still help to build the tables)
     bool live[A3Q];
@@ -858,7 +891,7 @@ __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const 
         arow[q] = (cunsigned_p)(a32 + (size_t)io * Wp + jc);
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            const int d = lane + 64 * k;
+            const int d = lane + 64 * k + (WIDE ? dc : 0);
             const int dd = d < dmax[q] ? d : (dmax[q] < 0 ? 0 : dmax[q]);   // d >= D lanes compute a harmless duplicate
             const int xs = (view == 0) ? jc - dd : jc + dd;
             tk[q][k] = s_T + (size_t)(xs - xbase) * side;  // row e of T[e][c]: the row stride (side, odd) keeps b64 reads conflict-free
@@ -939,18 +972,33 @@ __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const 
         float lm = INFINITY; int ld = 0;
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            const int d = lane + 64 * k;
+            const int d = lane + 64 * k + (WIDE ? dc : 0);
             if (d < D && lm > cv[k]) { lm = cv[k]; ld = d; }
         }
         const float m = wave_min_f32(lm);
         int cand = (lm == m) ? ld : 0x7fffffff;
         for (int off = 32; off >= 1; off >>= 1) cand = min(cand, __shfl_xor(cand, off, WAVE));
         const size_t p = (size_t)io * W + jo[q];
-        if (lane == 0) disp[p] = (dmax[q] < 0) ? 0.0f : (float)cand;
+        if constexpr (WIDE) {
+            // the chunk's first strict minimum (m, cand) replaces the running one only if it is strictly smaller (a chunk
+            // without a finite cost has m = +inf and never does): the reference's scan over the concatenated chunks
+            float bm = m;
+            int bi = cand;
+            if (!(cflags & 1)) {
+                const float2 c = carry[p];
+                if (!(m < c.x)) { bm = c.x; bi = __float_as_int(c.y); }
+            }
+            if (lane == 0) {
+                if (cflags & 2) disp[p] = (dmax[q] < 0) ? 0.0f : (float)bi;
+                else carry[p] = make_float2(bm, __int_as_float(bi));
+            }
+        } else {
+            if (lane == 0) disp[p] = (dmax[q] < 0) ? 0.0f : (float)cand;
+        }
         if (cost_out) {
 #pragma unroll
             for (int k = 0; k < K; k++) {
-                const int d = lane + 64 * k;
+                const int d = lane + 64 * k + (WIDE ? dc : 0);
                 if (d < D) cost_out[p * D + d] = (dmax[q] < 0) ? NAN : cv[k];
             }
         }
@@ -1000,6 +1048,51 @@ __global__ void __launch_bounds__(A3P * 64, (K * A3Q <= 4 ? 8 : 4)) k_asw4(const
     }
 }
 
+// D > 256: k_asw3 / k_asw4 over one chunk of at most 256 hypotheses, dc .. dc + 64 K - 1, launched once per chunk with the
+// WinTakeAll state carried between the launches in carry[pixel] (asw3_tile, WIDE).  The anchor table (k_asw3w) is built
+// once for all chunks; the slots of k_asw4w are rebuilt by every chunk's launch (the anchor phase is ~1/(64 K) of a tile's
+// work).  The other image's per-row tables cover the chunk's window positions only, so the LDS image is that of K <= 4.
+// Launch bounds: at K * A3Q = 4 the chunk offset and the carry cost a few registers more than k_asw3 / k_asw4 have
+// under a 64-VGPR budget (k_asw3w<4, 1> spilled 8 B/lane, k_asw4w<2, 2> 60 B/lane); these get 128.
+template <int K, int A3Q, bool SLOAD>
+__global__ void __launch_bounds__(A3P * 64, (K * A3Q < 4 ? 8 : 4)) k_asw3w(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
+                                                   int W, int D, int wins, const double *__restrict__ color,
+                                                   const double *__restrict__ w0, const unsigned *__restrict__ a32, int T,
+                                                   int view, float *__restrict__ disp, float *__restrict__ cost_out, int dc,
+                                                   float2 *__restrict__ carry, int cflags)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NPX = A3P * A3Q, NXP = NPX + 64 * K;
+    double *s_color = (double *)smem + (size_t)(2 * wins + 1) * NXP;
+    for (int e = threadIdx.x; e < 256; e += A3P * 64) s_color[e] = color[e];
+    asw3_tile<K, A3Q, SLOAD, false, true>(Lp, Rp, H, W, D, wins, nullptr, const_cast<double *>(w0), a32, T, view, disp, cost_out, 0,
+                                          (int)blockIdx.y, (int)blockIdx.x * NPX, smem, dc, carry, cflags);
+}
+
+template <int K, int A3Q>
+__global__ void __launch_bounds__(A3P * 64, (K * A3Q < 4 ? 8 : 4)) k_asw4w(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
+                                                   int W, int D, int wins, const double *__restrict__ space, const double *__restrict__ color,
+                                                   double *__restrict__ slots, const unsigned *__restrict__ a32, int T,
+                                                   int view, float *__restrict__ disp, float *__restrict__ cost_out, int dc,
+                                                   float2 *__restrict__ carry, int cflags)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NPX = A3P * A3Q, NXP = NPX + 64 * K;
+    const int side = 2 * wins + 1;
+    double *s_color = (double *)smem + (size_t)side * NXP;
+    float *s_P = (float *)(s_color + 256);
+    double *s_sp2 = (double *)(s_P + ((NXP + side + 1) & ~1));
+    for (int e = threadIdx.x; e < 256; e += A3P * 64) s_color[e] = color[e];
+    for (int e = threadIdx.x; e < side * side; e += A3P * 64) { const double sp = space[e]; s_sp2[e] = sp * sp; }
+    const int tpr = (W + NPX - 1) / NPX, ntiles = tpr * H;
+    double *slot = slots + (size_t)blockIdx.x * NPX * side * side;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        asw3_tile<K, A3Q, true, true, true>(Lp, Rp, H, W, D, wins, space, slot, a32, T, view, disp, cost_out, 0, tile / tpr,
+                                            (tile % tpr) * NPX, smem, dc, carry, cflags);
+        __syncthreads();
+    }
+}
+
 
 }  // namespace
 
@@ -1025,7 +1118,7 @@ SMT_API int smt_sad_set_impl(int impl)
 SMT_API int smt_sad(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winsize, int view,
                     int32_t *disp, void *stream)
 {
-    if (!Lp || !Rp || !disp || H <= 0 || W <= 0 || D <= 0 || D > 256 || winsize < 0 ||
+    if (!Lp || !Rp || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0 ||
         (view != SMT_VIEW_LEFT && view != SMT_VIEW_RIGHT))
         return SMT_ERR_ARG;
     const int N = H * W;
@@ -1035,7 +1128,7 @@ SMT_API int smt_sad(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
     auto copy_words = [](int bytes) { int n = (bytes + 3) / 4 + 1; return n + ((8 - n % 32) % 32 + 32) % 32; };
     const int ALW = copy_words(STP + side - 1), OLW = copy_words(STP + side - 1 + 64 * K - 1);
     const size_t shm = (size_t)side * 4 * (ALW + OLW) * 4;
-    if (g_sad_impl == 2 && side >= 4 && shm <= 64 * 1024) {
+    if (g_sad_impl == 2 && side >= 4 && K <= KMAX && shm <= 64 * 1024) {
         const dim3 grid((W + STP - 1) / STP, H);
         switch (K) {
         case 1: hipLaunchKernelGGL(k_sad2<1>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); break;
@@ -1046,7 +1139,27 @@ SMT_API int smt_sad(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
         SMT_LAUNCH_CHECK();
         return SMT_OK;
     }
-    hipLaunchKernelGGL(k_sad, dim3((N + 3) / 4), dim3(NT), 0, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp);
+    // D > 256: 5..8 slots per lane.  Each staged row of the other image is 64 bytes longer per slot, so these take the LDS
+    // beyond the default 64 KiB (up to the 160 KiB of a CU): every window the K <= 4 instantiations stage fits
+    if (g_sad_impl == 2 && side >= 4 && K > 4 && shm <= 160 * 1024) {
+        const dim3 grid((W + STP - 1) / STP, H);
+#define SMT_SAD2W(KK)                                                                                        \
+    do {                                                                                                     \
+        SMT_HIP(hipFuncSetAttribute((const void *)k_sad2<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+        hipLaunchKernelGGL(k_sad2<KK>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); \
+    } while (0)
+        switch (K) {
+        case 5: SMT_SAD2W(5); break;
+        case 6: SMT_SAD2W(6); break;
+        case 7: SMT_SAD2W(7); break;
+        default: SMT_SAD2W(8); break;
+        }
+#undef SMT_SAD2W
+        SMT_LAUNCH_CHECK();
+        return SMT_OK;
+    }
+    if (K > KMAX) hipLaunchKernelGGL(k_sad8, dim3((N + 3) / 4), dim3(NT), 0, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp);
+    else hipLaunchKernelGGL(k_sad, dim3((N + 3) / 4), dim3(NT), 0, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -1080,7 +1193,7 @@ static int launch_ncc2(int G, dim3 grid, size_t shm, hipStream_t st, const uint8
 SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int winSize, int32_t *disp,
                     double *cost, void *stream)
 {
-    if (!L || !R || !disp || H <= 0 || W <= 0 || D <= 0 || D > 256 || winSize < 0) return SMT_ERR_ARG;
+    if (!L || !R || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winSize < 0) return SMT_ERR_ARG;
     const int N = H * W;
     hipStream_t st = smt_stream(stream);
     const int side = 2 * winSize + 1, Hi = H - 2 * winSize, Wi = W - 2 * winSize;
@@ -1105,7 +1218,11 @@ SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int
             case 1: rc = launch_ncc2<1>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
             case 2: rc = launch_ncc2<2>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
             case 3: rc = launch_ncc2<3>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
-            default: rc = launch_ncc2<4>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
+            case 4: rc = launch_ncc2<4>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
+            case 5: rc = launch_ncc2<5>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
+            case 6: rc = launch_ncc2<6>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
+            case 7: rc = launch_ncc2<7>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
+            default: rc = launch_ncc2<8>(G, grid, shm2, st, L, R, H, W, D, winSize, sums, roots, sums + N, roots + N, RW, CS, disp, cost); break;
             }
             smt_scratch_free(sums, st);
             smt_scratch_free(roots, st);
@@ -1115,7 +1232,8 @@ SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int
         }
         // no scratch memory: the first formulation below
     }
-    hipLaunchKernelGGL(k_ncc, dim3((N + 3) / 4), dim3(NT), 0, st, L, R, H, W, D, winSize, disp, cost);
+    if (D <= 256) hipLaunchKernelGGL(k_ncc<256>, dim3((N + 3) / 4), dim3(NT), 0, st, L, R, H, W, D, winSize, disp, cost);
+    else hipLaunchKernelGGL(k_ncc<SMT_MAX_DISPARITY>, dim3((N + 3) / 4), dim3(NT), 0, st, L, R, H, W, D, winSize, disp, cost);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -1138,7 +1256,7 @@ SMT_API int smt_asw_masks(int winSize, double sigma_s, double sigma_c, double *s
 SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize, const double *space,
                     const double *color, int T, int view, float *disp, float *cost, void *stream)
 {
-    if (!Lp || !Rp || !space || !color || !disp || H <= 0 || W <= 0 || D <= 0 || D > 256 || winSize < 0 ||
+    if (!Lp || !Rp || !space || !color || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winSize < 0 ||
         (view != SMT_VIEW_LEFT && view != SMT_VIEW_RIGHT))
         return SMT_ERR_ARG;
     const int wins = winSize + 1, side = 2 * wins + 1;
@@ -1155,7 +1273,8 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
     }
     if (impl >= 3 && side >= 5) {
         const int A3Q = impl == 4 ? 1 : 2;
-        const int K = (D + 63) / 64, NPX = A3P * A3Q, NXP = NPX + 64 * K;
+        // D > 256 runs in chunks of 256 hypotheses (k_asw3w / k_asw4w): KT = slots of the widest launch, which sizes the LDS
+        const int K = (D + 63) / 64, KT = K < 4 ? K : 4, NPX = A3P * A3Q, NXP = NPX + 64 * KT;
         const size_t shm3 = ((size_t)side * NXP + 256) * 8 + (size_t)(NXP + side) * 4;
         const size_t ntap = (size_t)side * side, na = (size_t)(H + 2 * wins) * (W + 2 * wins);
         // k_asw4 adds the squared spatial mask and the tile's anchor window to the LDS image of k_asw3
@@ -1166,18 +1285,24 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
         const bool slots = impl == 6 && !verify;          // the check kernel compares a whole-image table
         // impl 6: one slot of anchor weights per workgroup in flight (k_asw4); impl 3 / 4 / 5: the whole-image table
         const int tpr = (W + NPX - 1) / NPX;
-        int nwg = tpr * H;
+        int nwg = tpr * H, cus = 0;
         if (slots) {
-            int dev = 0, cus = 0;
+            int dev = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            const int per_cu = (K * A3Q <= 4) ? 2 : 1;   // what the kernel's launch bounds and its LDS tables admit
+            const int per_cu = (KT * A3Q <= 4) ? 2 : 1;  // what the kernel's launch bounds and its LDS tables admit
             if (nwg > cus * per_cu) nwg = cus * per_cu;
         }
-        const size_t tab_bytes = slots ? (size_t)nwg * NPX * ntap * 8 : (size_t)N * ntap * 8;
+        // D > 256: a narrower last chunk runs more workgroups per CU, each with its slot
+        const int nwg_tab = (slots && K > 4) ? min(tpr * H, 2 * cus) : nwg;
+        const size_t tab_bytes = slots ? (size_t)nwg_tab * NPX * ntap * 8 : (size_t)N * ntap * 8;
         double *w0 = nullptr;
         unsigned *a32 = nullptr;
+        float2 *carry = nullptr;                          // D > 256: WinTakeAll's (minimum, first index) between the chunks
         bool have = (slots ? shm4 : shm3) <= 160 * 1024 && smt_scratch_alloc((void **)&w0, tab_bytes, st) == hipSuccess;
         if (have && smt_scratch_alloc((void **)&a32, na * 4, st) != hipSuccess) { smt_scratch_free(w0, st); w0 = nullptr; have = false; }
+        if (have && K > 4 && smt_scratch_alloc((void **)&carry, (size_t)N * sizeof(float2), st) != hipSuccess) {
+            smt_scratch_free(w0, st); smt_scratch_free(a32, st); w0 = nullptr; a32 = nullptr; have = false;
+        }
         if (have) {
             int rc = SMT_OK;                              // one exit path: the scratch is freed whatever happens
             const uint8_t *Ap = v == 0 ? Lp : Rp;
@@ -1219,16 +1344,59 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
         else if (A3Q == 2) SMT_ASW3(KK, 2, true);                                                            \
         else SMT_ASW3(KK, 1, true);                                                                          \
     } while (0)
-            switch (K) {
-            case 1: SMT_ASW3K(1); break;
-            case 2: SMT_ASW3K(2); break;
-            case 3: SMT_ASW3K(3); break;
-            default: SMT_ASW3K(4); break;
+#define SMT_ASW3W(KK, QQ, SL)                                                                                \
+    do {                                                                                                     \
+        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw3w<KK, QQ, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm3c); \
+        if (e_ != hipSuccess) { g_smt_last_hip = (int)e_; rc = SMT_ERR_HIP; break; }                         \
+        hipLaunchKernelGGL((k_asw3w<KK, QQ, SL>), grid, dim3(A3P * 64), shm3c, st, Lp, Rp, H, W, D, wins, color, w0, a32, T, v, disp, cost, \
+                           dc, carry, flags);                                                                \
+    } while (0)
+#define SMT_ASW4W(KK)                                                                                        \
+    do {                                                                                                     \
+        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw4w<KK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4c); \
+        if (e_ != hipSuccess) { g_smt_last_hip = (int)e_; rc = SMT_ERR_HIP; break; }                         \
+        hipLaunchKernelGGL((k_asw4w<KK, 2>), dim3((unsigned)nwgc), dim3(A3P * 64), shm4c, st, Lp, Rp, H, W, D, wins, space, color, w0, a32, \
+                           T, v, disp, cost, dc, carry, flags);                                              \
+    } while (0)
+#define SMT_ASWWK(KK)                                                                                        \
+    do {                                                                                                     \
+        if (slots) SMT_ASW4W(KK);                                                                            \
+        else if (impl == 5) SMT_ASW3W(KK, 2, false);                                                         \
+        else if (A3Q == 2) SMT_ASW3W(KK, 2, true);                                                           \
+        else SMT_ASW3W(KK, 1, true);                                                                         \
+    } while (0)
+            if (K <= 4) {
+                switch (K) {
+                case 1: SMT_ASW3K(1); break;
+                case 2: SMT_ASW3K(2); break;
+                case 3: SMT_ASW3K(3); break;
+                default: SMT_ASW3K(4); break;
+                }
+            } else {
+                // chunks dc = 0, 256 (D <= SMT_MAX_DISPARITY = 512): the first of 4 slots, the last of ceil((D - dc) / 64)
+                for (int dc = 0; dc < D && rc == SMT_OK; dc += 256) {
+                    const int Kc = min(4, (D - dc + 63) / 64), NXPc = NPX + 64 * Kc;
+                    const int flags = (dc == 0 ? 1 : 0) | (dc + 256 >= D ? 2 : 0);
+                    const size_t shm3c = ((size_t)side * NXPc + 256) * 8 + (size_t)(NXPc + side) * 4;
+                    const size_t shm4c = ((size_t)side * NXPc + 256) * 8 + (size_t)((NXPc + side + 1) & ~1) * 4 + ntap * 8 +
+                                         (((size_t)side * (NPX + side - 1) + 15) & ~(size_t)15);
+                    const int nwgc = slots ? min(tpr * H, cus * ((Kc * A3Q <= 4) ? 2 : 1)) : 0;
+                    switch (Kc) {
+                    case 1: SMT_ASWWK(1); break;
+                    case 2: SMT_ASWWK(2); break;
+                    case 3: SMT_ASWWK(3); break;
+                    default: SMT_ASWWK(4); break;
+                    }
+                }
             }
+#undef SMT_ASWWK
+#undef SMT_ASW4W
+#undef SMT_ASW3W
 #undef SMT_ASW3K
 #undef SMT_ASW4
 #undef SMT_ASW3
             if (counts) { check_tables("after k_asw3"); (void)hipFree(counts); }
+            if (carry) smt_scratch_free(carry, st);
             smt_scratch_free(w0, st);
             smt_scratch_free(a32, st);
             if (rc != SMT_OK) return rc;
@@ -1248,7 +1416,11 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
     case 1: SMT_ASW(1); break;
     case 2: SMT_ASW(2); break;
     case 3: SMT_ASW(3); break;
-    default: SMT_ASW(4); break;
+    case 4: SMT_ASW(4); break;
+    case 5: SMT_ASW(5); break;
+    case 6: SMT_ASW(6); break;
+    case 7: SMT_ASW(7); break;
+    default: SMT_ASW(8); break;
     }
 #undef SMT_ASW
     SMT_LAUNCH_CHECK();

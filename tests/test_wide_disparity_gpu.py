@@ -1,0 +1,398 @@
+"""Disparity ranges 257 .. 512 (SMT_MAX_DISPARITY) on the window matchers, the CrossAggregator and the CBLSM helpers:
+SAD / NCC / ASW maps and costs, both formulations of each, against the oracle with the comparison rules the D <= 256
+tests use; batch entry points, the C++ mirror, and the limits (512 accepted, 513 rejected)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def T(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def textured_pair(H, W, g, seed):
+    """L[:, j] = R[:, j - g]: every in-range pixel of either view matches at exactly d = g (cost 0, every other
+    hypothesis of a random texture costs more)."""
+    x = np.random.default_rng(seed).integers(0, 256, (H, W + g), dtype=np.uint8)
+    return np.ascontiguousarray(x[:, :W]), np.ascontiguousarray(x[:, g:g + W])
+
+
+# ------------------------------------------------------------------------------------------------------------ SAD
+def check_sad(smt, O, L, R, D, winsize):
+    Lp, Rp = O.pad_replicate(L, winsize + 1), O.pad_replicate(R, winsize + 1)
+    rl, rr = O.sad(Lp, Rp, D, winsize, 0), O.sad(Lp, Rp, D, winsize, 1)
+    ro, rc = O.sad_crosscheck(rl, rr)
+    try:
+        for impl in (2, 1):
+            smt.sad_set_impl(impl)
+            dl = smt.GetPointDepthLeft(T(Lp), T(Rp), D, winsize)
+            dr = smt.GetPointDepthRight(T(Lp), T(Rp), D, winsize)
+            assert np.array_equal(dl.cpu().numpy(), rl), (impl, "left")
+            assert np.array_equal(dr.cpu().numpy(), rr), (impl, "right")
+            out, cls = smt.sad_CrossCheckDiaparity(dl, dr)
+            assert np.array_equal(out.cpu().numpy(), ro) and np.array_equal(cls.cpu().numpy(), rc), impl
+    finally:
+        smt.sad_set_impl(2)
+    return rl, rr
+
+
+@pytest.mark.parametrize("H,W", [(8, 200), (6, 600)])
+@pytest.mark.parametrize("winsize", [0, 1, 3, 4])
+@pytest.mark.parametrize("D", [257, 320, 448, 512])
+def test_sad_wide(smt, O, D, winsize, H, W):
+    """Both formulations (k_sad2<5..8>, LDS-staged, and the one-wave-per-pixel k_sad8; 3x3 only the latter), both views
+    and the cross check; widths below and above D, neither a multiple of the 32-pixel tile."""
+    L, R = O.synth_pair(H, W, 64, D + winsize, (D + winsize) % 2 == 0)
+    check_sad(smt, O, L, R, D, winsize)
+
+
+@pytest.mark.parametrize("g", [255, 256, 500])
+def test_sad_minimum_at_chunk_edges(smt, O, g):
+    """The true disparity just below, at and far above the 256-hypothesis line, both views."""
+    H, W, D = 4, 600, 512
+    L, R = textured_pair(H, W, g, g)
+    rl, rr = check_sad(smt, O, L, R, D, 1)
+    # away from the replicated border columns, which only one image of a matching window pair holds
+    assert (rl[:, g + 4:W - 4] == g).all() and (rr[:H - 1, 4:W - g - 4] == g).all()   # right: last row never written (Sad.h:157)
+
+
+# ------------------------------------------------------------------------------------------------------------ NCC
+def ncc_case(H, W, seed):
+    from oracle import oracle as orc
+    L, R = orc.synth_pair(H, W, 64, seed, seed % 2 == 0)
+    L = L.copy(); R = R.copy()
+    L[:, 100:150] = 90         # flat over every row and wider than the widest window: 0/0 = NaN costs (NCC.h:46)
+    R[:, 40:160] = 90
+    return L, R
+
+
+def check_ncc(smt, O, L, R, D, win):
+    H, W = L.shape
+    rd, rc = O.ncc(L, R, D, win, want_cost=True)
+    inner = np.zeros((H, W), bool)
+    inner[win:H - win, win:W - win] = True
+    outs = []
+    try:
+        for impl in (2, 1):
+            smt.ncc_set_impl(impl)
+            d, c = smt.NCC_algorithem(T(L), T(R), win, D, want_cost=True)
+            a, b = c.cpu().numpy()[inner], rc[inner]
+            assert np.array_equal(np.isnan(a), np.isnan(b)), impl
+            ok = ~np.isnan(a)
+            assert np.max(np.abs(a[ok] - b[ok]), initial=0.0) <= 1e-4, impl
+            assert np.array_equal(d.cpu().numpy(), rd), impl
+            outs.append(a)
+    finally:
+        smt.ncc_set_impl(2)
+    ok = ~np.isnan(outs[0])
+    assert np.max(np.abs(outs[0][ok] - outs[1][ok]), initial=0.0) <= 1e-12
+    return rd, rc
+
+
+@pytest.mark.parametrize("win", [0, 2, 10, 15, 16])
+@pytest.mark.parametrize("D", [257, 320, 509, 510, 512])
+def test_ncc_wide(smt, O, D, win):
+    """k_ncc2<5..8> (side <= 31; D = 509 takes the shifted hypothesis set, 510..512 not) and the loop nest k_ncc<512>
+    (side 33 is its only path): same NaN pattern, 1e-4 to the oracle, 1e-12 between the two, identical maps."""
+    H, W = 2 * win + 3, 600
+    L, R = ncc_case(H, W, D % 7 + win)
+    _, rc = check_ncc(smt, O, L, R, D, win)
+    assert np.isnan(rc[win:H - win, win:W - win]).any()
+
+
+@pytest.mark.parametrize("g", [255, 256, 500])
+def test_ncc_maximum_at_chunk_edges(smt, O, g):
+    H, W, D, win = 7, 600, 512, 2
+    L, R = textured_pair(H, W, g, g + 1)
+    rd, _ = check_ncc(smt, O, L, R, D, win)
+    # where every hypothesis is in range (elsewhere the first `invalid` 255 wins, NCC.h:88)
+    assert (rd[win:H - win, D + win:W - win] == g).all()
+
+
+# ------------------------------------------------------------------------------------------------------------ ASW
+ASW_IMPLS = (0, 1, 3, 4, 5, 6)
+
+
+def asw_views(smt, Lp, Rp, winSize, D, sp, cm):
+    """{view: [(impl, disp, cost), ...]} over every formulation hook; costs bit-identical and maps equal across them."""
+    res = {}
+    try:
+        for view in (smt.VIEW_LEFT, smt.VIEW_RIGHT):
+            runs = []
+            for impl in ASW_IMPLS:
+                smt.asw_set_impl(impl)
+                d, c = smt.AdaptiveSupportWeight(Lp, Rp, winSize, D, sp, cm, 40, view, want_cost=True)
+                runs.append((impl, d.cpu().numpy(), c.cpu().numpy()))
+            a0 = runs[0][2]
+            for impl, d, c in runs[1:]:
+                assert np.array_equal(np.isnan(a0), np.isnan(c)), (view, impl)
+                ok = ~np.isnan(a0)
+                assert np.array_equal(bits(a0[ok]), bits(c[ok])), (view, impl)
+                assert np.array_equal(runs[0][1], d), (view, impl)
+            res[view] = runs
+    finally:
+        smt.asw_set_impl(0)
+    return res
+
+
+def check_asw(smt, O, L, R, D, winSize, rows=None):
+    H, W = L.shape
+    pad = winSize + 1
+    Lp, Rp = O.pad_replicate(L, pad), O.pad_replicate(R, pad)
+    sp_ref, cm_ref = O.asw_masks(winSize, 50.0, 30.0)
+    sp, cm = smt.asw_masks(winSize, 50.0, 30.0, DEV)
+    res = asw_views(smt, T(Lp), T(Rp), winSize, D, sp, cm)
+    i0, i1 = (0, H) if rows is None else rows
+    maps = []
+    for view, v in ((smt.VIEW_LEFT, 0), (smt.VIEW_RIGHT, 1)):
+        rd, rc = O.asw(Lp, Rp, D, winSize, sp_ref, cm_ref, 40, v, i0=i0, i1=i1, want_cost=True)
+        _, disp, cost = res[view][0]
+        a, b = cost[i0:i1], rc[i0:i1]
+        assert np.array_equal(np.isnan(a), np.isnan(b)), v
+        ok = ~np.isnan(b)
+        assert np.max(np.abs(a[ok] - b[ok]), initial=0.0) <= 1e-4, v
+        got, ref = disp[i0:i1], rd[i0:i1]
+        if rows is None:
+            assert np.array_equal(got, ref), v
+        else:
+            # 35x35 windows: the rule of the config-4 test -- a map may differ from the oracle only where the oracle's two
+            # smallest float costs lie within two float ulps (the float64 sums are reassociated, ~1e-13 relative)
+            srt = np.sort(np.where(np.isnan(b), np.float32(np.inf), b), axis=2)
+            with np.errstate(invalid="ignore"):
+                gap = (srt[..., 1] - srt[..., 0]).astype(np.float64)
+                band = 2.0 * np.spacing(srt[..., 0]).astype(np.float64)
+            assert not ((got != ref) & ~(gap <= band)).any(), v
+        maps.append((disp, rd))
+    if rows is None:
+        out = smt.asw_CrossCheckDiaparity(T(maps[0][0]), T(maps[1][0])).cpu().numpy()
+        assert np.array_equal(out, O.asw_crosscheck(maps[0][1], maps[1][1]))
+    return maps
+
+
+@pytest.mark.parametrize("winSize", [1, 3])
+@pytest.mark.parametrize("D", [257, 320, 512])
+@pytest.mark.parametrize("H,W", [(6, 200), (5, 560)])
+def test_asw_wide(smt, O, H, W, D, winSize):
+    """Chunks of 256 hypotheses (k_asw3w / k_asw4w) for the table hooks 0, 3, 4, 5, 6 and k_asw<5..8> for hook 1: costs
+    bit-identical across all six, 1e-4 to the oracle, maps equal to the oracle's, cross check."""
+    L, R = O.synth_pair(H, W, 64, D + W + winSize, winSize == 3)
+    check_asw(smt, O, L, R, D, winSize)
+
+
+@pytest.mark.parametrize("D", [257, 320, 512])
+def test_asw_wide_35x35_band(smt, O, D):
+    """winSize 16 (config 4's 35x35 window), the oracle on a band of two rows."""
+    L, R = O.synth_pair(6, 560, 64, D, True)
+    check_asw(smt, O, L, R, D, 16, rows=(2, 4))
+
+
+@pytest.mark.parametrize("g", [255, 256, 500])
+def test_asw_minimum_at_chunk_edges(smt, O, g):
+    """The minimum in the last slot of the first chunk (255), the first slot of the second (256) and deep in the last
+    chunk (500): WinTakeAll's (minimum, first index) carried from chunk to chunk, both views."""
+    H, W, D = 4, 600, 512
+    L, R = textured_pair(H, W, g, g + 2)
+    (dl, _), (dr, _) = check_asw(smt, O, L, R, D, 1)
+    assert (dl[:, g + 4:W - 4] == g).all() and (dr[:, 4:W - g - 4] == g).all()
+
+
+# --------------------------------------------------------------------------------------------------- CrossAggregator
+@pytest.mark.parametrize("iters", [1, 4])
+@pytest.mark.parametrize("D", [257, 320, 512])
+def test_crossagg_wide(smt, O, D, iters):
+    """ca_iter<5..8> for both pass kernels (D = 512: the FULL form of k_ca_pass2<8>): arms and costs bit for bit."""
+    H, W = 21, 37
+    L, _ = O.synth_pair(H, W, 32, D, D % 2 == 0)
+    bgr = O.synth_bgr(L, D + 1)
+    cost = np.random.default_rng(D * iters).random((H, W, D), dtype=np.float32) * 2
+    a_ref, c_ref = O.crossagg(bgr, cost, iters=iters)
+    for impl in (2, 1):
+        agg = smt.CrossAggregator()
+        assert agg.Initialize(W, H, 0, D, DEV)
+        agg.set_impl(impl)
+        agg.SetData(T(bgr), T(bgr), T(cost))
+        agg.SetParams(34, 17, 20, 6)
+        agg.Aggregate(iters)
+        assert np.array_equal(agg.get_arms_ptr().cpu().numpy(), a_ref), impl
+        assert np.array_equal(bits(agg.get_cost_ptr().cpu().numpy()), bits(c_ref)), impl
+        agg.close()
+
+
+def test_adcensus_option_aggregate_d300(smt, O):
+    H, W, D = 24, 330, 300
+    L, R = O.synth_pair(H, W, 64, 12)
+    bgr = O.synth_bgr(L, 6)
+    opt = smt.ADCensusOption(max_disparity=D)
+    vol = smt.cblsm_ComputeAD(T(L), T(R), D)
+    cost, disp = smt.adcensus_option_aggregate(opt, T(bgr), vol, 4)
+    _, ref = O.crossagg(bgr, O.cblsm_ad(L, R, D, 0), iters=4)
+    assert np.array_equal(bits(cost.cpu().numpy()), bits(ref))
+    assert np.array_equal(disp.cpu().numpy(), O.wta(ref))
+
+
+# ------------------------------------------------------------------------------------------------------ CBLSM helpers
+def test_cblsm_helpers_d300(smt, O):
+    """smt_cblsm_ad (both views), smt_cblsm_choose_arm_length (four directions) and smt_cblsm_cost_aggregation_new at
+    D = 300: one thread per (pixel, hypothesis), no cap of their own."""
+    H, W, D, win = 20, 330, 300, 1
+    Li, Ri = O.synth_pair(H, W, 64, 13)
+    for view, v in ((smt.VIEW_LEFT, 0), (smt.VIEW_RIGHT, 1)):
+        got = smt.cblsm_ComputeAD(T(Li), T(Ri), D, view)
+        assert np.array_equal(bits(got.cpu().numpy()), bits(O.cblsm_ad(Li, Ri, D, v))), v
+    aL = O.arms_all(Li, 25, 6, 17, 34, chain=False, right_row_bug=False)
+    aR = O.arms_all(Ri, 25, 6, 17, 34, chain=False, right_row_bug=False)
+    (LL, LR, LU, LD), (RL, RR, RU, RD) = [T(a) for a in aL], [T(a) for a in aR]
+    got = [smt.chooseArmLengthLeft(LL, LR, RL, RR, D, None, H, W),
+           smt.chooseArmLengthRight(LL, LR, RL, RR, D, None, H, W),
+           smt.chooseArmLengthUp(LU, LD, RU, RD, RL, RR, D, None, H, W),
+           smt.chooseArmLengthDown(LU, LD, RU, RD, RL, RR, D, None, H, W)]
+    vols = [O.choose_arm_length(0, aL[0], None, aR[0], aR[1], D), O.choose_arm_length(1, aL[1], None, aR[0], aR[1], D),
+            O.choose_arm_length(2, aL[2], aR[2], aR[0], aR[1], D), O.choose_arm_length(3, aL[3], aR[3], aR[0], aR[1], D)]
+    for name, g, r in zip(("Left", "Right", "Up", "Down"), got, vols):
+        assert np.array_equal(g.cpu().numpy(), r), name
+    w = win + 1
+    Lp, Rp = np.pad(Li, w, mode="edge"), np.pad(Ri, w, mode="edge")
+    ref = O.cblsm_cost_aggregation_new(Lp, Rp, win, *vols)
+    agg = smt.costAggregationNew(T(Lp), T(Rp), None, *[T(v) for v in vols], D, H, W, win)
+    assert np.array_equal(bits(agg.cpu().numpy()), bits(ref))
+
+
+# ------------------------------------------------------------------------------------------------- batches, C++ mirror
+def test_matcher_batches_d320_equal_single_calls(smt, O):
+    H, W, D, P = 8, 360, 320, 3
+    pairs = [O.synth_pair(H, W, 64, 40 + b, b == 1) for b in range(P)]
+    w = 3
+    Lp = T(np.stack([O.pad_replicate(p[0], w) for p in pairs]))
+    Rp = T(np.stack([O.pad_replicate(p[1], w) for p in pairs]))
+    L = T(np.stack([p[0] for p in pairs]))
+    R = T(np.stack([p[1] for p in pairs]))
+    sp, cm = smt.asw_masks(2, 50.0, 30.0, DEV)
+    for view in (smt.VIEW_LEFT, smt.VIEW_RIGHT):
+        sb = smt.sad_batch(Lp, Rp, D, 2, view)
+        ab = smt.asw_batch(Lp, Rp, 2, D, sp, cm, 40, view)
+        for b in range(P):
+            one = smt.GetPointDepthLeft(Lp[b], Rp[b], D, 2) if view == smt.VIEW_LEFT else smt.GetPointDepthRight(Lp[b], Rp[b], D, 2)
+            assert torch.equal(sb[b], one), (view, b)
+            assert torch.equal(ab[b], smt.AdaptiveSupportWeight(Lp[b], Rp[b], 2, D, sp, cm, 40, view)), (view, b)
+    nb = smt.ncc_batch(L, R, 3, D)
+    for b in range(P):
+        assert torch.equal(nb[b], smt.NCC_algorithem(L[b], R[b], 3, D)), b
+
+
+def test_matchers_main_d320(smt, O):
+    """host/matchers_main.cpp (SAD / NCC / ASW through the C++ mirror) at D = 320, hashes against the oracle."""
+    exe = os.path.join(ROOT, "stereo_match_traditional_amd", "lib", "matchers_main")
+    assert os.path.exists(exe)
+    H, W, D, seed = 12, 400, 320, 7
+    r = subprocess.run([exe, str(H), str(W), str(D), str(seed)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    got = dict(line.split() for line in r.stdout.strip().splitlines())
+    L, R = O.synth_pair(H, W, D, seed)
+    Lp, Rp = O.pad_replicate(L, 4), O.pad_replicate(R, 4)
+    exp = {"sad_left": O.sad(Lp, Rp, D, 3, 0), "sad_right": O.sad(Lp, Rp, D, 3, 1), "ncc": O.ncc(L, R, D, 3)}
+    sp, cm = O.asw_masks(3, 50.0, 30.0)
+    al, ar = O.asw(Lp, Rp, D, 3, sp, cm, 40, 0), O.asw(Lp, Rp, D, 3, sp, cm, 40, 1)
+    exp.update({"asw_left": al, "asw_right": ar, "median": O.median(al, 3),
+                "speckles": O.remove_speckles(al, 1, 30, -(2 ** 31))})
+    for k, v in exp.items():
+        assert got[k] == f"{O.fnv1a(v):016x}", k
+
+
+# ------------------------------------------------------------------------------------------------------------ limits
+def test_limits_512_accepted_513_rejected(smt, O):
+    H, W = 4, 40
+    L, R = O.synth_pair(H, W, 16, 3)
+    Lp, Rp = T(O.pad_replicate(L, 2)), T(O.pad_replicate(R, 2))
+    sp, cm = smt.asw_masks(1, 50.0, 30.0, DEV)
+    bgr = T(O.synth_bgr(L, 1))
+    for D, ok in ((512, True), (513, False)):
+        calls = [lambda: smt.GetPointDepthLeft(Lp, Rp, D, 1), lambda: smt.GetPointDepthRight(Lp, Rp, D, 1),
+                 lambda: smt.NCC_algorithem(T(L), T(R), 1, D),
+                 lambda: smt.AdaptiveSupportWeight(Lp, Rp, 1, D, sp, cm, 40, smt.VIEW_LEFT),
+                 lambda: smt.sad_batch(Lp[None], Rp[None], D, 1), lambda: smt.ncc_batch(T(L)[None], T(R)[None], 1, D),
+                 lambda: smt.asw_batch(Lp[None], Rp[None], 1, D, sp, cm, 40),
+                 lambda: smt.adcensus_option_aggregate(smt.ADCensusOption(max_disparity=D), bgr,
+                                                       torch.zeros((H, W, D), dtype=torch.float32, device=DEV), 1)]
+        for k, call in enumerate(calls):
+            if ok:
+                call()
+            else:
+                with pytest.raises(smt.SmtError):
+                    call()
+        agg = smt.CrossAggregator()
+        assert agg.Initialize(W, H, 0, D, DEV) is ok
+        agg.close()
+    torch.cuda.synchronize()
+
+
+# -------------------------------------------------------------------------------------------------------------- fuzz
+def test_wide_disparity_fuzz(smt, O):
+    """Seeded: D in 257..512, random shapes, windows, views and formulations, every family against the oracle."""
+    rng = np.random.default_rng(20261016)
+    for it in range(10):
+        D = int(rng.integers(257, 513))
+        H = int(rng.integers(3, 9))
+        W = int(rng.integers(D // 2, D + 120))
+        seed = int(rng.integers(0, 1 << 30))
+        L, R = O.synth_pair(H, W, 64, seed, bool(rng.integers(0, 2)))
+        fam = it % 4
+        if fam == 0:
+            ws = int(rng.integers(0, 6))
+            impl = int(rng.choice([1, 2]))
+            view = int(rng.integers(0, 2))
+            Lp, Rp = O.pad_replicate(L, ws + 1), O.pad_replicate(R, ws + 1)
+            try:
+                smt.sad_set_impl(impl)
+                f = smt.GetPointDepthLeft if view == 0 else smt.GetPointDepthRight
+                assert np.array_equal(f(T(Lp), T(Rp), D, ws).cpu().numpy(), O.sad(Lp, Rp, D, ws, view)), (it, D, ws, impl, view)
+            finally:
+                smt.sad_set_impl(2)
+        elif fam == 1:
+            win = int(rng.integers(0, 5))
+            Hn = H + 2 * win
+            L, R = O.synth_pair(Hn, W, 64, seed)
+            impl = int(rng.choice([1, 2]))
+            try:
+                smt.ncc_set_impl(impl)
+                d = smt.NCC_algorithem(T(L), T(R), win, D)
+            finally:
+                smt.ncc_set_impl(2)
+            assert np.array_equal(d.cpu().numpy(), O.ncc(L, R, D, win)), (it, D, win, impl)
+        elif fam == 2:
+            ws = int(rng.integers(0, 4))
+            impl = int(rng.choice(ASW_IMPLS))
+            view = int(rng.integers(0, 2))
+            Lp, Rp = O.pad_replicate(L, ws + 1), O.pad_replicate(R, ws + 1)
+            sp_ref, cm_ref = O.asw_masks(ws, 50.0, 30.0)
+            sp, cm = smt.asw_masks(ws, 50.0, 30.0, DEV)
+            try:
+                smt.asw_set_impl(impl)
+                d = smt.AdaptiveSupportWeight(T(Lp), T(Rp), ws, D, sp, cm, 40, [smt.VIEW_LEFT, smt.VIEW_RIGHT][view])
+            finally:
+                smt.asw_set_impl(0)
+            assert np.array_equal(d.cpu().numpy(), O.asw(Lp, Rp, D, ws, sp_ref, cm_ref, 40, view)), (it, D, ws, impl, view)
+        else:
+            bgr = O.synth_bgr(L, seed % 97)
+            cost = np.random.default_rng(seed).random((H, W, D), dtype=np.float32)
+            iters = int(rng.integers(1, 4))
+            a_ref, c_ref = O.crossagg(bgr, cost, iters=iters)
+            agg = smt.CrossAggregator()
+            assert agg.Initialize(W, H, 0, D, DEV)
+            agg.set_impl(int(rng.choice([1, 2])))
+            agg.SetData(T(bgr), T(bgr), T(cost))
+            agg.SetParams(34, 17, 20, 6)
+            agg.Aggregate(iters)
+            assert np.array_equal(agg.get_arms_ptr().cpu().numpy(), a_ref), (it, D)
+            assert np.array_equal(bits(agg.get_cost_ptr().cpu().numpy()), bits(c_ref)), (it, D)
+            agg.close()
