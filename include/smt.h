@@ -465,6 +465,43 @@ int smt_pipeline_run_batch_post(smt_pipeline *h, const uint8_t *grayL, const uin
                                 const smt_post_params *post, float *lastDisp);
 
 /* =====================================================================================
+ * The active CBLSM/CBLSM.cpp flow, batched      (:64-67, 101-104, 133-134, 146-153)
+ * ===================================================================================== */
+typedef struct smt_cblsm_flow smt_cblsm_flow;
+typedef struct smt_cblsm_params {
+    int tau, sec_length, max_length;   /* 25, 17, 34   CBLSM.cpp:30-32; tau_low is CBLSM.h:719's fixed 6 */
+} smt_cblsm_params;
+void smt_cblsm_default_params(smt_cblsm_params *p);
+/* Owns two crossarm handles (arms of the left and of the right image: by-value threshold, no stride bug, as
+ * smt_crossarm_cblsm_params), the two first-pass volumes and one [H][W][D] scratch: three 4-byte volumes whatever the
+ * batch size.  SMT_ERR_ARG unless 1 <= D <= SMT_MAX_DISPARITY, 0 <= tau <= 255 (CBLSM.cpp:30's uchar),
+ * sec_length >= 0 and 0 <= max_length <= 4096 (smt_crossarm_create's limit). */
+int smt_cblsm_flow_create_on(int device, int H, int W, int D, const smt_cblsm_params *p, smt_cblsm_flow **out);
+int smt_cblsm_flow_destroy(smt_cblsm_flow *h);
+int smt_cblsm_flow_set_stream(smt_cblsm_flow *h, void *stream);
+/* CBLSM.cpp's active lines for `pairs` pairs of uint8 gray images [pairs][H][W] (the images after cvtColor, :21-22),
+ * in the file's order per pair: ArmLength{L,R,Up,Down} of the left and of the right image; the first
+ * costAggregationV5 pass of the left view (ComputeAD volume, left arms) and of the right view (ComputeADRight volume,
+ * right arms); the second pass of the left view on the left arms and of the right view on the LEFT arms (:150); the
+ * WTA of each second pass (ComputeDispOringin, :152-153).
+ *   dispL, dispR   float32 [pairs][H][W], integer-valued
+ * The first pass never materialises the AD volume while max(sec_length, max_length) <= 127: its sums are then exact in
+ * float and come from a summed-area table, bit-identical to the reference's loop (csrc/cblsm.hip); above that bound it
+ * is smt_cblsm_ad + smt_crossarm_aggregate(order 1).  pairs == 0 is a no-op.  Asynchronous like
+ * smt_pipeline_run_batch, on the handle's stream only; one caller thread per handle. */
+int smt_cblsm_flow_run_batch(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                             float *dispL, float *dispR);
+/* the last pair's first-pass volumes, float32 [H][W][D], borrowed (valid until the next run or destroy) */
+int smt_cblsm_flow_volumes(smt_cblsm_flow *h, float **pass1_left, float **pass1_right);
+/* synchronising, read-and-clear: SMT_ERR_REF_UB if a rectangle left the plane since the last call (never expected) */
+int smt_cblsm_flow_status(smt_cblsm_flow *h);
+/* Test hook, host only (no GPU): the first pass's box arithmetic (rectangle corners in a uint32 summed-area table, the
+ * clipping of arms that leave the plane) against direct sums on a random H x W x D volume of bytes (fill 0) or of 255s
+ * (fill 1), arms up to max_arm; and (float)S / (float)n against costAggregationV5's sequential float sum where S < 2^24.
+ * SMT_OK or SMT_ERR_STATE; SMT_ERR_ARG for sizes over 2^26 elements. */
+int smt_cblsm_selftest_box(int H, int W, int D, int max_arm, int fill, unsigned seed);
+
+/* =====================================================================================
  * Left-right consistency              replaces LeftRightConsistency
  *                                     (AD-CensusV1/PostProcessing.h:72-135)
  * ===================================================================================== */

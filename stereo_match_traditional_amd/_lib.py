@@ -33,6 +33,11 @@ class PipelineParams(C.Structure):
                 ("gate", C.c_int)]
 
 
+class CBLSMParams(C.Structure):
+    """smt_cblsm_params: CBLSM.cpp:30-32's tao, secLength, maxLength."""
+    _fields_ = [("tau", C.c_int), ("sec_length", C.c_int), ("max_length", C.c_int)]
+
+
 class PostParams(C.Structure):
     """smt_post_params: main.cpp:93-94's RemoveSpeckles / MedianFilter arguments."""
     _fields_ = [("speckle_diff", C.c_int), ("speckle_min_area", C.c_uint), ("speckle_invalid", C.c_int),

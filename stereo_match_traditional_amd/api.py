@@ -16,7 +16,7 @@ __all__ = ["FillTheHole", "chooseArmLengthLeft", "chooseArmLengthRight", "choose
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
            "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info",
-           "ADCensusHostBatch"]
+           "ADCensusHostBatch", "CBLSMFlow"]
 
 
 def current_stream_ptr(device=None):
@@ -1003,6 +1003,64 @@ class Pipeline:
     def close(self):
         if getattr(self, "_h", None) is not None:
             lib().smt_pipeline_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CBLSMFlow:
+    """CBLSM.cpp's active flow (:64-67, 101-104, 133-134, 146-153) for batches of gray pairs: arms of both images, two
+    costAggregationV5 passes per view (the right view's second on the LEFT arms, :150), ComputeDispOringin of each.
+    Keywords override smt_cblsm_default_params: tau, sec_length, max_length.  The sharding unit of shard.cblsm_batch."""
+
+    def __init__(self, row, col, dispRange, device=None, **params):
+        self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        p = _lib.CBLSMParams()
+        lib().smt_cblsm_default_params(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        h = C.c_void_p()
+        check(lib().smt_cblsm_flow_create_on(_dev_index(self.device), self.row, self.col, self.dispRange, C.byref(p),
+                                             C.byref(h)), "smt_cblsm_flow_create_on")
+        self._h = h
+
+    def run(self, grayL, grayR):
+        """uint8 [pairs][row][col] (or [row][col]) -> (dispL, dispR), float32 [pairs][row][col], on torch's current
+        stream of the handle's device; nothing synchronises."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"CBLSM handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        check(lib().smt_cblsm_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_cblsm_flow_set_stream")
+        check(lib().smt_cblsm_flow_run_batch(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr)),
+              "smt_cblsm_flow_run_batch")
+        return dl, dr
+
+    def volumes(self):
+        """The last pair's first-pass volumes (left view, right view), float32 [row][col][dispRange], borrowed."""
+        ps = [C.c_void_p() for _ in range(2)]
+        check(lib().smt_cblsm_flow_volumes(self._h, *[C.byref(p) for p in ps]), "smt_cblsm_flow_volumes")
+        shp = (self.row, self.col, self.dispRange)
+        return [_view_of(p.value, shp, torch.float32, self.device) for p in ps]
+
+    def status(self):
+        check(lib().smt_cblsm_flow_status(self._h), "smt_cblsm_flow_status")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().smt_cblsm_flow_destroy(self._h)
             self._h = None
 
     def __del__(self):

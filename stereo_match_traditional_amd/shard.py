@@ -86,3 +86,18 @@ def pipeline_batch(L8, R8, D, **params):
     pipe.status()
     pipe.close()
     return dl, dr
+
+
+def cblsm_batch(L8, R8, D, **params):
+    """`compute` for run_sharded on CBLSM.cpp's flow (smt_cblsm_flow_run_batch) for a [count, H, W] uint8 shard on this
+    rank's GPU -> (left maps, right maps).  Keywords as api.CBLSMFlow."""
+    from .api import CBLSMFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = CBLSMFlow(H, W, D, L8.device, **params)
+    dl, dr = flow.run(L8.contiguous(), R8.contiguous())
+    flow.status()
+    flow.close()
+    return dl, dr
