@@ -639,6 +639,34 @@ int smt_asw_masks(int winSize, double sigma_space, double sigma_color, double *s
 int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize,
             const double *space, const double *color, int T, int view, float *disp, float *cost,
             void *stream);
+/* Both views' maps from ONE evaluation of the hypotheses (ASWeight.cpp:60-61 without the second tap loop).  The weight of
+ * a tap is one factor per image and the error min(|a - b|, T) is symmetric, so the right view's cost at column x' and
+ * hypothesis d is the left view's at column x' + d.  Arguments, limits (D <= SMT_MAX_DISPARITY, winSize <= 30), scratch
+ * arena and stream behaviour as smt_asw; costL / costR (float32 [H][W][D]) are optional.  With wins = winSize + 1:
+ *   dispL, costL       exactly what smt_asw(..., SMT_VIEW_LEFT, ...) writes, bit for bit, under every smt_asw_set_impl
+ *                      and for D > 256.
+ *   costR[i][x'][d]    costL[i][x'+d][d] where x' + d <= W - wins - 2 (ASW.h:401 accepts d), otherwise costR[i][x'][d-1]
+ *                      (the chain of :422-425); NaN for every d where x' > W - wins - 2 (the costVolume[-1] columns, where
+ *                      smt_asw writes NaN too).
+ *   dispR              WinTakeAll (ASW.h:193-208, first strict minimum) of that costR; 0 in the costVolume[-1] columns.
+ * This is the reference's right view up to the rounding the library's ASW costs already carry: smt_asw's kernels fold the
+ * weight product as (w0*space^2)*color, so a left cost and smt_asw's right cost of the same hypothesis may differ in the
+ * last bit of the float64 sums.  dispR is therefore NOT promised to equal smt_asw(SMT_VIEW_RIGHT) bit for bit; it follows
+ * from the left costs exactly and meets the oracle under the bar of the other ASW entry points (costs <= 1e-4, maps equal
+ * wherever the two smallest computed costs are more than 2 float ulps apart). */
+int smt_asw_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize,
+                 const double *space, const double *color, int T,
+                 float *dispL, float *dispR, float *costL, float *costR, void *stream);
+/* Test hook (process-wide): how smt_asw_both gets the right view.  2 (default) = rank keys: every hypothesis the left
+ * view computes offers (ordered bits of its float cost) << 32 | d to right pixel x - d, minimum per workgroup in LDS, then
+ * one agent-scope atomic min per touched pixel into an [H][W] key map (8 bytes per pixel of scratch), and a finishing
+ * launch; no volume is written.  1 = the left view with its cost volume (in scratch when costL is NULL) and a
+ * diagonal-gather WinTakeAll kernel.  costR always comes from 1.  Identical maps. */
+int smt_asw_both_set_impl(int impl);
+/* Test hook, host only (no GPU): on pseudo-random float cost rows of a W-column, D-hypothesis left volume (exact ties,
+ * +-0.0, negative values, +inf, NaN at d = 0 and at d > 0) the minimum rank key over a right pixel's diagonal gives the
+ * map of WinTakeAll over the chained right row.  SMT_OK or SMT_ERR_STATE. */
+int smt_asw_selftest_right_keys(int W, int D, int wins, unsigned seed);
 /* Scratch device memory of smt_asw / smt_ncc comes from an arena the library owns (csrc/scratch.hip: hipMalloc'ed
  * blocks cached per device and handed out stream-ordered on the caller's stream).  The arena keeps what it has grown
  * to -- the anchor weights of an smt_asw call (H*W*(2*winSize+3)^2*8 bytes while that is under 6 GiB, beyond it one
@@ -675,6 +703,23 @@ int smt_asw_batch(const uint8_t *Lp, const uint8_t *Rp, int pairs, size_t img_st
 /* CrossCheckDiaparity (ASW.h:108-145): float maps -> uint8 map, 0 = rejected. */
 int smt_asw_crosscheck(const float *dispL, const float *dispR, int H, int W, uint8_t *out,
                        void *stream);
+
+/* The active lines of ASW/ASWeight.cpp for a batch of gray pairs (uint8 [pairs][H][W], unpadded), per pair in the file's
+ * order: copyMakeBorder of both images by winSize + 1 (:54-55), both views (:60-61, through smt_asw_both),
+ * CrossCheckDiaparity (:66) into lastDisp, uint8 [pairs][H][W].  The flow stops at :66 (normalize, filterSpeckles,
+ * medianBlur and FillImageNew are OpenCV / scan-order fillers).  The handle owns the two masks (smt_asw_masks, built and
+ * uploaded once at create), the padded images and one pair of maps: a warm call allocates nothing beyond the scratch
+ * arena.  Asynchronous on the handle's stream; pairs == 0 is a no-op; any of the three outputs may be NULL.
+ * SMT_ERR_ARG for non-positive sizes, NULL inputs, winSize outside 1..30, D outside 1..SMT_MAX_DISPARITY and
+ * non-positive sigmas. */
+typedef struct smt_asw_flow smt_asw_flow;
+typedef struct smt_asw_params { int winSize, T; double sigma_space, sigma_color; } smt_asw_params;  /* 11, 40, 50, 30: ASWeight.cpp:43-47 */
+void smt_asw_default_params(smt_asw_params *p);
+int smt_asw_flow_create_on(int device, int H, int W, int D, const smt_asw_params *p, smt_asw_flow **out);
+int smt_asw_flow_destroy(smt_asw_flow *h);
+int smt_asw_flow_set_stream(smt_asw_flow *h, void *stream);
+int smt_asw_flow_run_batch(smt_asw_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                           float *dispL, float *dispR, uint8_t *lastDisp);
 
 /* =====================================================================================
  * Either side of the path: input staging and the first post-filter

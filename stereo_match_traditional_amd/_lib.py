@@ -38,6 +38,11 @@ class CBLSMParams(C.Structure):
     _fields_ = [("tau", C.c_int), ("sec_length", C.c_int), ("max_length", C.c_int)]
 
 
+class ASWParams(C.Structure):
+    """smt_asw_params: ASWeight.cpp:43-47's winSize, T, sigma_space, sigma_color."""
+    _fields_ = [("winSize", C.c_int), ("T", C.c_int), ("sigma_space", C.c_double), ("sigma_color", C.c_double)]
+
+
 class PostParams(C.Structure):
     """smt_post_params: main.cpp:93-94's RemoveSpeckles / MedianFilter arguments."""
     _fields_ = [("speckle_diff", C.c_int), ("speckle_min_area", C.c_uint), ("speckle_invalid", C.c_int),

@@ -16,7 +16,7 @@ __all__ = ["FillTheHole", "chooseArmLengthLeft", "chooseArmLengthRight", "choose
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
            "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info",
-           "ADCensusHostBatch", "CBLSMFlow"]
+           "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow"]
 
 
 def current_stream_ptr(device=None):
@@ -714,6 +714,31 @@ def AdaptiveSupportWeight(leftGray, rightGray, winSize, dispRange, space, color,
 
 
 @_on_tensor_device
+def AdaptiveSupportWeightBoth(leftGray, rightGray, winSize, dispRange, space, color, T, want_cost=False):
+    """smt_asw_both: ASWeight.cpp:60-61's two views from one evaluation of the hypotheses.  Padded uint8 images.
+    -> (dispL, dispR), or (dispL, dispR, costL, costR) with want_cost."""
+    wins = winSize + 1
+    Hp, Wp = leftGray.shape
+    H, W = Hp - 2 * wins, Wp - 2 * wins
+    _dev(leftGray, torch.uint8, (Hp, Wp), "leftGray")
+    _dev(rightGray, torch.uint8, (Hp, Wp), "rightGray")
+    _dev(space, torch.float64, (2 * winSize + 3, 2 * winSize + 3), "space")
+    _dev(color, torch.float64, (256,), "color")
+    dl = torch.empty((H, W), dtype=torch.float32, device=leftGray.device)
+    dr = torch.empty_like(dl)
+    cl = torch.empty((H, W, dispRange), dtype=torch.float32, device=leftGray.device) if want_cost else None
+    cr = torch.empty_like(cl) if want_cost else None
+    check(lib().smt_asw_both(_ptr(leftGray), _ptr(rightGray), H, W, dispRange, winSize, _ptr(space), _ptr(color), int(T),
+                             _ptr(dl), _ptr(dr), _ptr(cl), _ptr(cr), current_stream_ptr()), "smt_asw_both")
+    return (dl, dr, cl, cr) if want_cost else (dl, dr)
+
+
+def asw_both_set_impl(impl):
+    """2 = rank keys, no volume (default), 1 = left volume + diagonal WinTakeAll (test hook; costR always comes from 1)."""
+    check(lib().smt_asw_both_set_impl(int(impl)), "smt_asw_both_set_impl")
+
+
+@_on_tensor_device
 def sad_batch(leftimgs, rightimgs, MaxDisparity, winsize, view=VIEW_LEFT):
     """smt_sad_batch: [P, H+2w, W+2w] uint8 padded pairs -> int32 [P, H, W] (GetPointDepthLeft / Right per pair)."""
     w = winsize + 1
@@ -1061,6 +1086,55 @@ class CBLSMFlow:
     def close(self):
         if getattr(self, "_h", None) is not None:
             lib().smt_cblsm_flow_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ASWFlow:
+    """ASWeight.cpp's active lines (:54-55, :60-61, :66) for batches of gray pairs: replicate padding by winSize + 1, both
+    views from one pass over the hypotheses (smt_asw_both), CrossCheckDiaparity.  Keywords override
+    smt_asw_default_params: winSize, T, sigma_space, sigma_color.  The sharding unit of shard.asw_batch."""
+
+    def __init__(self, row, col, dispRange, device=None, **params):
+        self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        p = _lib.ASWParams()
+        lib().smt_asw_default_params(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        h = C.c_void_p()
+        check(lib().smt_asw_flow_create_on(_dev_index(self.device), self.row, self.col, self.dispRange, C.byref(p),
+                                           C.byref(h)), "smt_asw_flow_create_on")
+        self._h = h
+
+    def run(self, grayL, grayR):
+        """uint8 [pairs][row][col] (or [row][col]) -> (dispL, dispR, lastDisp): float32, float32, uint8
+        [pairs][row][col], on torch's current stream of the handle's device; nothing synchronises."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"ASW handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        last = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        check(lib().smt_asw_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_asw_flow_set_stream")
+        check(lib().smt_asw_flow_run_batch(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(last)),
+              "smt_asw_flow_run_batch")
+        return dl, dr, last
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().smt_asw_flow_destroy(self._h)
             self._h = None
 
     def __del__(self):

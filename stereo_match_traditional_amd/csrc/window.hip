@@ -568,14 +568,32 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
 // inside the 1e-4 tolerance on the float32 cost the reference itself narrows to (:255-256).
 constexpr int ANT = 1024;      // 16 pixels (waves) per workgroup share one replicated table
 
+// ---- right view from the left view's hypotheses (smt_asw_both) ----
+// The weight of a tap is one factor per image and the error is min(|a - b|, T): both are symmetric in the two images, so
+// the right view's cost at (x', d) is the left view's at (x' + d, d) wherever ASW.h:401 accepts d.  Rank key of such a
+// hypothesis for right pixel x': (order-preserving bits of the float cost) << 32 | d.  The minimum key over d is
+// WinTakeAll's first strict minimum (:193-208): the smaller cost wins, among equal costs the smaller d; -0 ties +0.
+// A NaN never satisfies `min > value`: at d > 0 it gets no key (~0, never a winner), at d = 0 it freezes the scan at 0
+// and gets key 0, below every ordered cost (-inf has 0x007fffff in the upper half).
+constexpr unsigned long long ASW_NOKEY = ~0ull;
+__host__ __device__ inline unsigned long long asw_rkey(float c, unsigned d)
+{
+    if (c != c) return d == 0 ? 0ull : ASW_NOKEY;
+    const unsigned b = __builtin_bit_cast(unsigned, c + 0.0f);           // -0 -> +0
+    return ((unsigned long long)(b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | d;
+}
+
 // K = number of live 64-disparity slots per lane (ceil(D/64)), a template parameter so that the
 // tap loop is branch-free: columns are processed in dwords, the last (partial) dword is taken
 // from columns side-4..side-1 with the weights of already-counted columns zeroed.
-template <int K>
+// BOTH (smt_asw_both, left view only): every hypothesis the pixel really computes also offers its rank key to right
+// pixel jo - d with one agent-scope atomic min into rkeys[H][W]; one wave per pixel has nothing to reduce in LDS first.
+template <int K, bool BOTH = false>
 __global__ void __launch_bounds__(ANT) k_asw(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                              int W, int D, int wins, const double *__restrict__ space,
                                              const double *__restrict__ color, int T, int view,
-                                             float *__restrict__ disp, float *__restrict__ cost_out)
+                                             float *__restrict__ disp, float *__restrict__ cost_out,
+                                             unsigned long long *__restrict__ rkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int side = 2 * wins + 1;
@@ -661,6 +679,19 @@ __global__ void __launch_bounds__(ANT) k_asw(const uint8_t *__restrict__ Lp, con
     float cv[K];
 #pragma unroll
     for (int k = 0; k < K; k++) cv[k] = (float)(sv[k] / sw[k]);
+    if constexpr (BOTH) {
+        if (jo <= W - wins - 2) {
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const int d = lane + 64 * k;
+                if (d < D && d <= dmax) {
+                    const unsigned long long key = asw_rkey(cv[k], (unsigned)d);
+                    if (key != ASW_NOKEY)
+                        __hip_atomic_fetch_min(rkeys + (size_t)io * W + (jo - d), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+    }
 
     // WinTakeAll: first strict minimum (:193-208).  dmax < 0 (right view, last columns): the
     // reference chains every cost to an out-of-bounds read -> all equal -> 0.
@@ -813,12 +844,18 @@ __device__ __forceinline__ P uniform_ptr(P p)
 // WIDE (D > 256, k_asw3w / k_asw4w): the tile evaluates the chunk of hypotheses dc .. dc + 64 K - 1 only, and WinTakeAll
 // continues the sequential scan of the chunks before it through carry[pixel] = (running minimum, its first index):
 // cflags bit 0 = first chunk (the scan starts at +inf, index 0), bit 1 = last chunk (the pixel's disparity is written).
-template <int K, int A3Q, bool SLOAD, bool OWN, bool WIDE = false>
+// BOTH (smt_asw_both, left view only): after the narrowing to float every hypothesis (jo, d) the tile really computes
+// (d <= jo, d < D, jo <= W - wins - 2) offers its rank key to right pixel jo - d.  The tile touches at most NXP - 1 right
+// pixels, jo0 - dc - (64 K - 1) .. jo0 + NPX - 1 - dc: one LDS slot each (the tables' LDS, no longer read), LDS atomic
+// min, then one agent-scope global atomic min per touched pixel into rkeys[H][W] -- the workgroups that reach a right
+// pixel may sit on different XCDs.  Chunks (WIDE) need nothing more: a minimum does not depend on the order.
+template <int K, int A3Q, bool SLOAD, bool OWN, bool WIDE = false, bool BOTH = false>
 __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                           int W, int D, int wins, const double *__restrict__ space,
                                           double *w0, const unsigned *__restrict__ a32, int T,
                                           int view, float *__restrict__ disp, float *__restrict__ cost_out, int i0, int io, int jo0,
-                                          unsigned char *smem, int dc = 0, float2 *carry = nullptr, int cflags = 0)
+                                          unsigned char *smem, int dc = 0, float2 *carry = nullptr, int cflags = 0,
+                                          unsigned long long *__restrict__ rkeys = nullptr)
 {
     constexpr int NPX = A3P * A3Q;                         // pixels per workgroup
     constexpr int NXP = NPX + 64 * K;                      // window positions of the other image per row (padded)
@@ -962,12 +999,32 @@ __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const 
             for (; c < side; c++) tap(c);
         }
     }
+    unsigned long long *s_key = (unsigned long long *)smem;   // BOTH: [NXP] rank keys over s_T
+    const int kx0 = jo0 - (WIDE ? dc : 0) - (64 * K - 1);      // right pixel of slot 0
+    if constexpr (BOTH) {
+        __syncthreads();                                   // the last row's tables are no longer read
+        for (int e = threadIdx.x; e < NXP; e += A3P * 64) s_key[e] = ASW_NOKEY;
+        __syncthreads();
+    }
 #pragma unroll
     for (int q = 0; q < A3Q; q++) {
         if (!live[q]) continue;
         float cv[K];
 #pragma unroll
         for (int k = 0; k < K; k++) cv[k] = (float)(sv[q][k] / sw[q][k]);
+        if constexpr (BOTH) {
+            if (jo[q] <= W - wins - 2) {
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const int d = lane + 64 * k + (WIDE ? dc : 0);
+                    if (d < D && d <= dmax[q]) {
+                        const unsigned long long key = asw_rkey(cv[k], (unsigned)d);
+                        if (key != ASW_NOKEY)
+                            __hip_atomic_fetch_min(s_key + (jo[q] - d - kx0), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+            }
+        }
         // WinTakeAll: first strict minimum (:193-208); dmax < 0: see k_asw
         float lm = INFINITY; int ld = 0;
 #pragma unroll
@@ -1003,32 +1060,42 @@ __device__ __forceinline__ void asw3_tile(const uint8_t *__restrict__ Lp, const 
             }
         }
     }
+    if constexpr (BOTH) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < NXP; e += A3P * 64) {
+            const unsigned long long key = s_key[e];           // a key implies 0 <= kx0 + e = jo - d <= W - wins - 2
+            if (key != ASW_NOKEY)
+                __hip_atomic_fetch_min(rkeys + (size_t)io * W + (kx0 + e), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
-template <int K, int A3Q, bool SLOAD = true>
+template <int K, int A3Q, bool SLOAD = true, bool BOTH = false>
 __global__ void __launch_bounds__(A3P * 64, (K * A3Q <= 4 ? 8 : 4)) k_asw3(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                                    int W, int D, int wins, const double *__restrict__ color,
                                                    const double *__restrict__ w0, const unsigned *__restrict__ a32, int T,
-                                                   int view, float *__restrict__ disp, float *__restrict__ cost_out, int i0)
+                                                   int view, float *__restrict__ disp, float *__restrict__ cost_out, int i0,
+                                                   unsigned long long *__restrict__ rkeys)
 {
     // i0: first image row of this launch's band; w0 holds the anchor weights of the band's rows only
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NPX = A3P * A3Q, NXP = NPX + 64 * K;
     double *s_color = (double *)smem + (size_t)(2 * wins + 1) * NXP;
     for (int e = threadIdx.x; e < 256; e += A3P * 64) s_color[e] = color[e];
-    asw3_tile<K, A3Q, SLOAD, false>(Lp, Rp, H, W, D, wins, nullptr, const_cast<double *>(w0), a32, T, view, disp, cost_out, i0,
-                                    i0 + (int)blockIdx.y, (int)blockIdx.x * NPX, smem);
+    asw3_tile<K, A3Q, SLOAD, false, false, BOTH>(Lp, Rp, H, W, D, wins, nullptr, const_cast<double *>(w0), a32, T, view, disp, cost_out, i0,
+                                                 i0 + (int)blockIdx.y, (int)blockIdx.x * NPX, smem, 0, nullptr, 0, rkeys);
 }
 
 // The same tiles from a fixed number of workgroups that each own one slot of anchor-weight scratch (fourth
 // formulation, default): workgroup b takes tiles b, b + gridDim.x, ... of the row-major tile order and rebuilds its
 // slot for every tile, so the anchor table is O(workgroups in flight) -- 160 MB at 35 x 35 whatever the image size --
 // instead of O(image) (5 GB at 960 x 540), and no separate table kernel runs.  Results are those of k_asw3, bit for bit.
-template <int K, int A3Q>
+template <int K, int A3Q, bool BOTH = false>
 __global__ void __launch_bounds__(A3P * 64, (K * A3Q <= 4 ? 8 : 4)) k_asw4(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                                    int W, int D, int wins, const double *__restrict__ space, const double *__restrict__ color,
                                                    double *__restrict__ slots, const unsigned *__restrict__ a32, int T,
-                                                   int view, float *__restrict__ disp, float *__restrict__ cost_out)
+                                                   int view, float *__restrict__ disp, float *__restrict__ cost_out,
+                                                   unsigned long long *__restrict__ rkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NPX = A3P * A3Q, NXP = NPX + 64 * K;
@@ -1042,8 +1109,8 @@ __global__ void __launch_bounds__(A3P * 64, (K * A3Q <= 4 ? 8 : 4)) k_asw4(const
     const int tpr = (W + NPX - 1) / NPX, ntiles = tpr * H;
     double *slot = slots + (size_t)blockIdx.x * NPX * side * side;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        asw3_tile<K, A3Q, true, true>(Lp, Rp, H, W, D, wins, space, slot, a32, T, view, disp, cost_out, 0, tile / tpr,
-                                      (tile % tpr) * NPX, smem);
+        asw3_tile<K, A3Q, true, true, false, BOTH>(Lp, Rp, H, W, D, wins, space, slot, a32, T, view, disp, cost_out, 0, tile / tpr,
+                                                   (tile % tpr) * NPX, smem, 0, nullptr, 0, rkeys);
         __syncthreads();                                   // the tile's LDS tables are no longer read
     }
 }
@@ -1054,27 +1121,27 @@ __global__ void __launch_bounds__(A3P * 64, (K * A3Q <= 4 ? 8 : 4)) k_asw4(const
 // work).  The other image's per-row tables cover the chunk's window positions only, so the LDS image is that of K <= 4.
 // Launch bounds: at K * A3Q = 4 the chunk offset and the carry cost a few registers more than k_asw3 / k_asw4 have
 // under a 64-VGPR budget (k_asw3w<4, 1> spilled 8 B/lane, k_asw4w<2, 2> 60 B/lane); these get 128.
-template <int K, int A3Q, bool SLOAD>
+template <int K, int A3Q, bool SLOAD, bool BOTH = false>
 __global__ void __launch_bounds__(A3P * 64, (K * A3Q < 4 ? 8 : 4)) k_asw3w(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                                    int W, int D, int wins, const double *__restrict__ color,
                                                    const double *__restrict__ w0, const unsigned *__restrict__ a32, int T,
                                                    int view, float *__restrict__ disp, float *__restrict__ cost_out, int dc,
-                                                   float2 *__restrict__ carry, int cflags)
+                                                   float2 *__restrict__ carry, int cflags, unsigned long long *__restrict__ rkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NPX = A3P * A3Q, NXP = NPX + 64 * K;
     double *s_color = (double *)smem + (size_t)(2 * wins + 1) * NXP;
     for (int e = threadIdx.x; e < 256; e += A3P * 64) s_color[e] = color[e];
-    asw3_tile<K, A3Q, SLOAD, false, true>(Lp, Rp, H, W, D, wins, nullptr, const_cast<double *>(w0), a32, T, view, disp, cost_out, 0,
-                                          (int)blockIdx.y, (int)blockIdx.x * NPX, smem, dc, carry, cflags);
+    asw3_tile<K, A3Q, SLOAD, false, true, BOTH>(Lp, Rp, H, W, D, wins, nullptr, const_cast<double *>(w0), a32, T, view, disp, cost_out, 0,
+                                                (int)blockIdx.y, (int)blockIdx.x * NPX, smem, dc, carry, cflags, rkeys);
 }
 
-template <int K, int A3Q>
+template <int K, int A3Q, bool BOTH = false>
 __global__ void __launch_bounds__(A3P * 64, (K * A3Q < 4 ? 8 : 4)) k_asw4w(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                                    int W, int D, int wins, const double *__restrict__ space, const double *__restrict__ color,
                                                    double *__restrict__ slots, const unsigned *__restrict__ a32, int T,
                                                    int view, float *__restrict__ disp, float *__restrict__ cost_out, int dc,
-                                                   float2 *__restrict__ carry, int cflags)
+                                                   float2 *__restrict__ carry, int cflags, unsigned long long *__restrict__ rkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NPX = A3P * A3Q, NXP = NPX + 64 * K;
@@ -1087,12 +1154,76 @@ __global__ void __launch_bounds__(A3P * 64, (K * A3Q < 4 ? 8 : 4)) k_asw4w(const
     const int tpr = (W + NPX - 1) / NPX, ntiles = tpr * H;
     double *slot = slots + (size_t)blockIdx.x * NPX * side * side;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        asw3_tile<K, A3Q, true, true, true>(Lp, Rp, H, W, D, wins, space, slot, a32, T, view, disp, cost_out, 0, tile / tpr,
-                                            (tile % tpr) * NPX, smem, dc, carry, cflags);
+        asw3_tile<K, A3Q, true, true, true, BOTH>(Lp, Rp, H, W, D, wins, space, slot, a32, T, view, disp, cost_out, 0, tile / tpr,
+                                                  (tile % tpr) * NPX, smem, dc, carry, cflags, rkeys);
         __syncthreads();
     }
 }
 
+
+// ---- smt_asw_both: the right view out of the left view's hypotheses ------------------------------------------------
+// Finish of the rank-key formulation: key map -> dispR.  A separate launch, so that every workgroup's atomics have
+// landed whatever XCD issued them.  x' > W - wins - 2: ASW.h:401 rejects even d = 0, the map is 0 (see k_asw).
+__global__ void __launch_bounds__(256) k_asw_rkeys_finish(const unsigned long long *__restrict__ rkeys, int H, int W, int wins,
+                                                          float *__restrict__ dispR)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (size_t)H * W) return;
+    const int x = (int)(p % W);
+    const unsigned long long key = rkeys[p];
+    dispR[p] = (x > W - wins - 2 || key == ASW_NOKEY) ? 0.0f : (float)(unsigned)key;
+}
+
+// Volume formulation: costR[i][x'][d] = costL[i][x' + d][d] where x' + d <= W - wins - 2, else costR[i][x'][d - 1]
+// (the chain of ASW.h:422-425), NaN for every d where x' > W - wins - 2; dispR = WinTakeAll of it.
+// One workgroup per row and DG_TX right pixels, hypotheses in chunks of DG_DC: the chunk's block of the left volume,
+// columns x0 + dc .. + DG_TX + DG_DC - 1 by hypotheses dc .. dc + DG_DC - 1, goes through LDS with coalesced loads
+// (DG_DC consecutive floats per column).  A wave then owns one right pixel at a time, lane = hypothesis: its diagonal
+// sits at (xl + l) * DG_DC + l = xl * DG_DC + l * (DG_DC + 1) -- the even row pitch makes the lane stride odd, 64 reads on
+// 64 distinct banks -- and the costR stores are DG_DC consecutive floats.  WinTakeAll's state (minimum, its index) and
+// the chain's last accepted cost are carried from chunk to chunk in LDS.  Chain copies never win a strict minimum.
+constexpr int DG_TX = 64, DG_DC = 64, DG_NT = 256;
+__global__ void __launch_bounds__(DG_NT) k_asw_diag(const float *__restrict__ costL, int H, int W, int D, int wins,
+                                                    float *__restrict__ dispR, float *__restrict__ costR)
+{
+    __shared__ float s_blk[(DG_TX + DG_DC) * DG_DC];
+    __shared__ float s_min[DG_TX], s_last[DG_TX];
+    __shared__ int s_idx[DG_TX];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i = blockIdx.y, x0 = blockIdx.x * DG_TX;
+    const int xlim = W - wins - 2;                           // last column with an accepted hypothesis
+    for (int dc = 0; dc < D; dc += DG_DC) {
+        __syncthreads();                                     // the previous chunk's block is no longer read
+        const int d = dc + lane;
+        for (int c = wv; c < DG_TX + DG_DC; c += DG_NT / 64) {
+            const int x = x0 + dc + c;
+            if (x < W && d < D) s_blk[c * DG_DC + lane] = costL[((size_t)i * W + x) * D + d];
+        }
+        __syncthreads();
+        for (int xl = wv; xl < DG_TX; xl += DG_NT / 64) {
+            const int xr = x0 + xl;
+            if (xr >= W) break;
+            const int dlast = xlim - xr;                     // last accepted hypothesis of this pixel (< 0: none)
+            const bool ok = d < D && d <= dlast;
+            const float v = ok ? s_blk[(xl + lane) * DG_DC + lane] : 0.0f;
+            float m = dc == 0 ? __shfl(v, 0, WAVE) : s_min[xl];      // cv[0] starts the scan (:196)
+            int mi = dc == 0 ? 0 : s_idx[xl];
+            const float lv = (ok && d >= 1 && v == v) ? v : INFINITY;
+            const float wm = wave_min_f32(lv);
+            if (wm < m) {                                    // false for a NaN minimum: the scan is frozen at 0
+                m = wm;
+                mi = dc + __builtin_ctzll(__ballot(lv == wm));
+            }
+            float last = s_last[xl];                         // valid once dlast lies in an earlier chunk
+            if (dlast >= dc && dlast < dc + DG_DC) last = __shfl(v, dlast - dc, WAVE);
+            if (lane == 0) {
+                s_min[xl] = m; s_idx[xl] = mi; s_last[xl] = last;
+                if (dc + DG_DC >= D) dispR[(size_t)i * W + xr] = dlast < 0 ? 0.0f : (float)mi;
+            }
+            if (costR && d < D) costR[((size_t)i * W + xr) * D + d] = dlast < 0 ? NAN : (ok ? v : last);
+        }
+    }
+}
 
 }  // namespace
 
@@ -1253,8 +1384,9 @@ SMT_API int smt_asw_masks(int winSize, double sigma_s, double sigma_c, double *s
     return SMT_OK;
 }
 
-SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize, const double *space,
-                    const double *color, int T, int view, float *disp, float *cost, void *stream)
+// smt_asw; rkeys != nullptr (smt_asw_both, left view): the BOTH instantiations, which also fill the right view's key map
+static int asw_run(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize, const double *space,
+                   const double *color, int T, int view, float *disp, float *cost, void *stream, unsigned long long *rkeys)
 {
     if (!Lp || !Rp || !space || !color || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winSize < 0 ||
         (view != SMT_VIEW_LEFT && view != SMT_VIEW_RIGHT))
@@ -1325,45 +1457,55 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
                 if (counts) check_tables("after k_asw_anchor");
             }
             const dim3 grid(tpr, H);
-#define SMT_ASW3(KK, QQ, SL)                                                                                 \
+#define SMT_ASW3(KK, QQ, SL, BB)                                                                               \
     do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw3<KK, QQ, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm3); \
+        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw3<KK, QQ, SL, BB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm3); \
         if (e_ != hipSuccess) { g_smt_last_hip = (int)e_; rc = SMT_ERR_HIP; break; }                         \
-        hipLaunchKernelGGL((k_asw3<KK, QQ, SL>), grid, dim3(A3P * 64), shm3, st, Lp, Rp, H, W, D, wins, color, w0, a32, T, v, disp, cost, 0); \
+        hipLaunchKernelGGL((k_asw3<KK, QQ, SL, BB>), grid, dim3(A3P * 64), shm3, st, Lp, Rp, H, W, D, wins, color, w0, a32, T, v, disp, cost, 0, rkeys); \
     } while (0)
-#define SMT_ASW4(KK)                                                                                         \
+#define SMT_ASW4(KK, BB)                                                                                     \
     do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw4<KK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4); \
+        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw4<KK, 2, BB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4); \
         if (e_ != hipSuccess) { g_smt_last_hip = (int)e_; rc = SMT_ERR_HIP; break; }                         \
-        hipLaunchKernelGGL((k_asw4<KK, 2>), dim3((unsigned)nwg), dim3(A3P * 64), shm4, st, Lp, Rp, H, W, D, wins, space, color, w0, a32, T, v, disp, cost); \
+        hipLaunchKernelGGL((k_asw4<KK, 2, BB>), dim3((unsigned)nwg), dim3(A3P * 64), shm4, st, Lp, Rp, H, W, D, wins, space, color, w0, a32, T, v, disp, cost, rkeys); \
+    } while (0)
+#define SMT_ASW3KB(KK, BB)                                                                                   \
+    do {                                                                                                     \
+        if (slots) SMT_ASW4(KK, BB);                                                                         \
+        else if (impl == 5) SMT_ASW3(KK, 2, false, BB);                                                      \
+        else if (A3Q == 2) SMT_ASW3(KK, 2, true, BB);                                                        \
+        else SMT_ASW3(KK, 1, true, BB);                                                                      \
     } while (0)
 #define SMT_ASW3K(KK)                                                                                        \
     do {                                                                                                     \
-        if (slots) SMT_ASW4(KK);                                                                             \
-        else if (impl == 5) SMT_ASW3(KK, 2, false);                                                          \
-        else if (A3Q == 2) SMT_ASW3(KK, 2, true);                                                            \
-        else SMT_ASW3(KK, 1, true);                                                                          \
+        if (rkeys) SMT_ASW3KB(KK, true);                                                                     \
+        else SMT_ASW3KB(KK, false);                                                                          \
     } while (0)
-#define SMT_ASW3W(KK, QQ, SL)                                                                                \
+#define SMT_ASW3W(KK, QQ, SL, BB)                                                                              \
     do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw3w<KK, QQ, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm3c); \
+        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw3w<KK, QQ, SL, BB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm3c); \
         if (e_ != hipSuccess) { g_smt_last_hip = (int)e_; rc = SMT_ERR_HIP; break; }                         \
-        hipLaunchKernelGGL((k_asw3w<KK, QQ, SL>), grid, dim3(A3P * 64), shm3c, st, Lp, Rp, H, W, D, wins, color, w0, a32, T, v, disp, cost, \
-                           dc, carry, flags);                                                                \
+        hipLaunchKernelGGL((k_asw3w<KK, QQ, SL, BB>), grid, dim3(A3P * 64), shm3c, st, Lp, Rp, H, W, D, wins, color, w0, a32, T, v, disp, cost, \
+                           dc, carry, flags, rkeys);                                                         \
     } while (0)
-#define SMT_ASW4W(KK)                                                                                        \
+#define SMT_ASW4W(KK, BB)                                                                                    \
     do {                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw4w<KK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4c); \
+        hipError_t e_ = hipFuncSetAttribute((const void *)k_asw4w<KK, 2, BB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4c); \
         if (e_ != hipSuccess) { g_smt_last_hip = (int)e_; rc = SMT_ERR_HIP; break; }                         \
-        hipLaunchKernelGGL((k_asw4w<KK, 2>), dim3((unsigned)nwgc), dim3(A3P * 64), shm4c, st, Lp, Rp, H, W, D, wins, space, color, w0, a32, \
-                           T, v, disp, cost, dc, carry, flags);                                              \
+        hipLaunchKernelGGL((k_asw4w<KK, 2, BB>), dim3((unsigned)nwgc), dim3(A3P * 64), shm4c, st, Lp, Rp, H, W, D, wins, space, color, w0, a32, \
+                           T, v, disp, cost, dc, carry, flags, rkeys);                                       \
+    } while (0)
+#define SMT_ASWWKB(KK, BB)                                                                                   \
+    do {                                                                                                     \
+        if (slots) SMT_ASW4W(KK, BB);                                                                        \
+        else if (impl == 5) SMT_ASW3W(KK, 2, false, BB);                                                     \
+        else if (A3Q == 2) SMT_ASW3W(KK, 2, true, BB);                                                       \
+        else SMT_ASW3W(KK, 1, true, BB);                                                                     \
     } while (0)
 #define SMT_ASWWK(KK)                                                                                        \
     do {                                                                                                     \
-        if (slots) SMT_ASW4W(KK);                                                                            \
-        else if (impl == 5) SMT_ASW3W(KK, 2, false);                                                         \
-        else if (A3Q == 2) SMT_ASW3W(KK, 2, true);                                                           \
-        else SMT_ASW3W(KK, 1, true);                                                                         \
+        if (rkeys) SMT_ASWWKB(KK, true);                                                                     \
+        else SMT_ASWWKB(KK, false);                                                                          \
     } while (0)
             if (K <= 4) {
                 switch (K) {
@@ -1390,9 +1532,11 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
                 }
             }
 #undef SMT_ASWWK
+#undef SMT_ASWWKB
 #undef SMT_ASW4W
 #undef SMT_ASW3W
 #undef SMT_ASW3K
+#undef SMT_ASW3KB
 #undef SMT_ASW4
 #undef SMT_ASW3
             if (counts) { check_tables("after k_asw3"); (void)hipFree(counts); }
@@ -1406,11 +1550,16 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
         // table does not fit (LDS or device memory): the first formulation below
     }
     const size_t shm = (size_t)(256 * 32 + side * side) * 8;
+#define SMT_ASWB(KK, BB)                                                                                     \
+    do {                                                                                                     \
+        SMT_HIP(hipFuncSetAttribute((const void *)(k_asw<KK, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+        hipLaunchKernelGGL((k_asw<KK, BB>), dim3((N + 15) / 16), dim3(ANT), shm, smt_stream(stream), Lp, Rp, H, W, D, wins, \
+                           space, color, T, v, disp, cost, rkeys);                                           \
+    } while (0)
 #define SMT_ASW(KK)                                                                                          \
     do {                                                                                                     \
-        SMT_HIP(hipFuncSetAttribute((const void *)k_asw<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
-        hipLaunchKernelGGL(k_asw<KK>, dim3((N + 15) / 16), dim3(ANT), shm, smt_stream(stream), Lp, Rp, H, W, D, wins, \
-                           space, color, T, v, disp, cost);                                                  \
+        if (rkeys) SMT_ASWB(KK, true);                                                                       \
+        else SMT_ASWB(KK, false);                                                                            \
     } while (0)
     switch ((D + 63) / 64) {
     case 1: SMT_ASW(1); break;
@@ -1423,8 +1572,98 @@ SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
     default: SMT_ASW(8); break;
     }
 #undef SMT_ASW
+#undef SMT_ASWB
     SMT_LAUNCH_CHECK();
     return SMT_OK;
+}
+
+SMT_API int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize, const double *space,
+                    const double *color, int T, int view, float *disp, float *cost, void *stream)
+{
+    return asw_run(Lp, Rp, H, W, D, winSize, space, color, T, view, disp, cost, stream, nullptr);
+}
+
+// 2 (default): rank keys, no volume; 1: left volume + k_asw_diag (also whenever costR is asked for)
+static int g_asw_both_impl = 2;
+SMT_API int smt_asw_both_set_impl(int impl)
+{
+    if (impl != 1 && impl != 2) return SMT_ERR_ARG;
+    g_asw_both_impl = impl;
+    return SMT_OK;
+}
+
+SMT_API int smt_asw_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize, const double *space,
+                         const double *color, int T, float *dispL, float *dispR, float *costL, float *costR, void *stream)
+{
+    if (!Lp || !Rp || !space || !color || !dispL || !dispR || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY ||
+        winSize < 0 || winSize > 30)
+        return SMT_ERR_ARG;
+    hipStream_t st = smt_stream(stream);
+    const size_t N = (size_t)H * W;
+    const int wins = winSize + 1;
+    if (g_asw_both_impl == 2 && !costR) {
+        unsigned long long *rkeys = nullptr;
+        if (smt_scratch_alloc((void **)&rkeys, N * 8, st) != hipSuccess) return SMT_ERR_ALLOC;
+        int rc = hipMemsetAsync(rkeys, 0xFF, N * 8, st) == hipSuccess ? SMT_OK : SMT_ERR_HIP;     // ASW_NOKEY everywhere
+        if (rc == SMT_OK) rc = asw_run(Lp, Rp, H, W, D, winSize, space, color, T, SMT_VIEW_LEFT, dispL, costL, stream, rkeys);
+        if (rc == SMT_OK) hipLaunchKernelGGL(k_asw_rkeys_finish, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rkeys, H, W, wins, dispR);
+        smt_scratch_free(rkeys, st);
+        if (rc != SMT_OK) return rc;
+        SMT_LAUNCH_CHECK();
+        return SMT_OK;
+    }
+    float *vol = costL;
+    if (!vol && smt_scratch_alloc((void **)&vol, N * D * 4, st) != hipSuccess) return SMT_ERR_ALLOC;
+    int rc = asw_run(Lp, Rp, H, W, D, winSize, space, color, T, SMT_VIEW_LEFT, dispL, vol, stream, nullptr);
+    if (rc == SMT_OK)
+        hipLaunchKernelGGL(k_asw_diag, dim3((W + DG_TX - 1) / DG_TX, H), dim3(DG_NT), 0, st, (const float *)vol, H, W, D, wins, dispR, costR);
+    if (!costL) smt_scratch_free(vol, st);
+    if (rc != SMT_OK) return rc;
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+// Host only (no GPU): on random float rows -- exact ties, +-0.0, negative values, a NaN at d = 0, a NaN at d > 0 -- the
+// minimum of asw_rkey over a right pixel's diagonal must be WinTakeAll (ASW.h:193-208) of its chained cost row.
+SMT_API int smt_asw_selftest_right_keys(int W, int D, int wins, unsigned seed)
+{
+    if (W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || wins < 0 || W > (1 << 16)) return SMT_ERR_ARG;
+    uint64_t rng = 0x9E3779B97F4A7C15ull ^ ((uint64_t)seed * 0xD1342543DE82EF95ull + 1);
+    auto next = [&rng]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (uint32_t)(rng >> 11); };
+    // left costs [W][D] from a small palette, so that exact ties are the rule
+    static const float pal[] = {0.0f, -0.0f, 1.5f, 1.5f, -2.25f, 3.0f, 0.125f, -0.0f, 7.0f, -2.25f, INFINITY, 1e-30f};
+    float *cl = (float *)malloc((size_t)W * D * sizeof(float)), *row = (float *)malloc((size_t)D * sizeof(float));
+    if (!cl || !row) { free(cl); free(row); return SMT_ERR_ALLOC; }
+    for (size_t k = 0; k < (size_t)W * D; k++) {
+        const uint32_t r = next();
+        cl[k] = (r % 7 == 0) ? (float)(int)(r >> 8 & 1023) / 64.0f - 8.0f : pal[(r >> 3) % (sizeof pal / sizeof pal[0])];
+        if (r % 23 == 0) cl[k] = NAN;                                        // NaNs land at d = 0 and at d > 0
+    }
+    const int xlim = W - wins - 2;
+    int rc = SMT_OK;
+    bool nan0 = false, nanx = false, tie = false, neg = false;
+    for (int x = 0; x < W && rc == SMT_OK; x++) {
+        // the reference's right row: accepted hypotheses, then the chain; nothing accepted -> all equal -> 0
+        int want = 0;
+        if (xlim - x >= 0) {
+            for (int d = 0; d < D; d++) row[d] = (x + d <= xlim) ? cl[(size_t)(x + d) * D + d] : row[d - 1];
+            float mn = row[0];
+            for (int d = 1; d < D; d++) if (mn > row[d]) { mn = row[d]; want = d; }
+            nan0 |= row[0] != row[0];
+            for (int d = 1; d < D; d++) { nanx |= row[d] != row[d]; tie |= row[d] == row[d - 1] && x + d <= xlim; neg |= row[d] < 0; }
+        }
+        unsigned long long best = ASW_NOKEY;
+        for (int d = 0; d < D && x + d <= xlim; d++) {
+            const unsigned long long key = asw_rkey(cl[(size_t)(x + d) * D + d], (unsigned)d);
+            if (key < best) best = key;
+        }
+        const int got = (x > xlim || best == ASW_NOKEY) ? 0 : (int)(unsigned)best;
+        if (got != want) rc = SMT_ERR_STATE;
+    }
+    // the rows must have exercised what the keys encode (a row set too small to hold them is not a failure)
+    if (rc == SMT_OK && (size_t)W * D >= 4096 && D >= 8 && xlim >= 16 && !(nan0 && nanx && tie && neg)) rc = SMT_ERR_STATE;
+    free(cl); free(row);
+    return rc;
 }
 
 // ---- batch variants: the single-pair entry points pair by pair on the caller's stream --------------

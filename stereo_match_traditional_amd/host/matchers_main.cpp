@@ -68,16 +68,17 @@ int main(int argc, char **argv)
             smt::NCC_algorithem(L.data(), R.data(), W, H, d.data(), 3, D);
             printf("ncc %016llx\n", (unsigned long long)fnv(d.data(), n * 4));
         }
-        {   // ASWeight.cpp:43-61
+        {   // ASWeight.cpp:43-66
             const int winSize = 3, w = winSize + 1, T = 40;
             std::vector<double> sp, cm;
             smt::getMasks(sp, cm, winSize, 50, 30);
             auto Lp = pad(L, H, W, w), Rp = pad(R, H, W, w);
             std::vector<float> dl(n), dr(n);
-            smt::AdaptiveSupportWeight(dl.data(), Lp.data(), Rp.data(), H + 2 * w, W + 2 * w, winSize, D, sp, cm, T, true);
-            smt::AdaptiveSupportWeight(dr.data(), Lp.data(), Rp.data(), H + 2 * w, W + 2 * w, winSize, D, sp, cm, T, false);
-            printf("asw_left %016llx\nasw_right %016llx\n", (unsigned long long)fnv(dl.data(), n * 4),
-                   (unsigned long long)fnv(dr.data(), n * 4));
+            std::vector<unsigned char> last(n);
+            smt::AdaptiveSupportWeightBoth(dl.data(), dr.data(), last.data(), Lp.data(), Rp.data(), H + 2 * w, W + 2 * w,
+                                           winSize, D, sp, cm, T);     // ASWeight.cpp:60-61, :66
+            printf("asw_left %016llx\nasw_right %016llx\nasw_cross %016llx\n", (unsigned long long)fnv(dl.data(), n * 4),
+                   (unsigned long long)fnv(dr.data(), n * 4), (unsigned long long)fnv(last.data(), n));
             std::vector<float> med(n);
             smt::MedianFilter(dl.data(), med.data(), W, H, 3);             // main.cpp:94
             printf("median %016llx\n", (unsigned long long)fnv(med.data(), n * 4));

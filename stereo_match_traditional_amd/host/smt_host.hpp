@@ -417,6 +417,26 @@ inline void AdaptiveSupportWeight(float *disp, const unsigned char *leftGray, co
     d.download(disp);
 }
 
+// ASWeight.cpp:60-66 in one call: AdaptiveSupportWeight, AdaptiveSupportWeightRight (both maps from one evaluation of the
+// hypotheses, smt_asw_both) and CrossCheckDiaparity (ASW.h:108-145) into lastDisp, uchar [rows-2w][cols-2w] (may be null)
+inline void AdaptiveSupportWeightBoth(float *dispL, float *dispR, unsigned char *lastDisp, const unsigned char *leftGray,
+                                      const unsigned char *rightGray, int rows, int cols, int winSize, int dispRange,
+                                      const std::vector<double> &space, const std::vector<double> &color, int T)
+{
+    const int w = winSize + 1, H = rows - 2 * w, W = cols - 2 * w;
+    DevBuf<unsigned char> L((size_t)rows * cols), R((size_t)rows * cols), last((size_t)H * W);
+    DevBuf<double> sp(space.size()), cm(color.size());
+    DevBuf<float> dl((size_t)H * W), dr((size_t)H * W);
+    L.upload(leftGray); R.upload(rightGray); sp.upload(space.data()); cm.upload(color.data());
+    check(smt_asw_both(L.get(), R.get(), H, W, dispRange, winSize, sp.get(), cm.get(), T, dl.get(), dr.get(), nullptr,
+                       nullptr, nullptr), "smt_asw_both");
+    dl.download(dispL); dr.download(dispR);
+    if (lastDisp) {
+        check(smt_asw_crosscheck(dl.get(), dr.get(), H, W, last.get(), nullptr), "smt_asw_crosscheck");
+        last.download(lastDisp);
+    }
+}
+
 // MedianFilter / RemoveSpeckles (PostProcessing.h:250-344) on host maps
 inline void MedianFilter(const float *in, float *out, const int &width, const int &height, const int wnd_size)
 {

@@ -101,3 +101,17 @@ def cblsm_batch(L8, R8, D, **params):
     flow.status()
     flow.close()
     return dl, dr
+
+
+def asw_batch(L8, R8, D, **params):
+    """`compute` for run_sharded on ASWeight.cpp's flow (smt_asw_flow_run_batch) for a [count, H, W] uint8 shard on this
+    rank's GPU -> (left maps, right maps).  Keywords as api.ASWFlow."""
+    from .api import ASWFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = ASWFlow(H, W, D, L8.device, **params)
+    dl, dr, _ = flow.run(L8.contiguous(), R8.contiguous())
+    flow.close()
+    return dl, dr

@@ -1,0 +1,275 @@
+"""smt_asw_both (both views' ASW maps from one evaluation of the hypotheses) and smt_asw_flow_* (ASWeight.cpp:54-66 for
+batches).  The exact statement of the feature carries no tolerance: the left outputs are smt_asw's bit for bit, and the
+right outputs are the diagonal gather + chain + first strict minimum of that GPU left volume, bit for bit.  Against the
+oracle's right view the bar is that of the other ASW tests."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from test_asw_both_cpu import right_from_left
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+SMT_ERR_ARG = -1
+
+SHAPES = [(14, 40, 16, 2, 1, False), (10, 36, 64, 4, 2, True), (8, 30, 70, 1, 3, False), (6, 24, 1, 2, 4, False),
+          (5, 20, 130, 3, 5, True), (9, 300, 300, 2, 7, False), (24, 96, 48, 5, 11, True)]
+
+
+def T(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def same_bits(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def padded(O, H, W, winSize, seed, noise):
+    L, R = O.synth_pair(H, W, 32, seed, noise)
+    return O.pad_replicate(L, winSize + 1), O.pad_replicate(R, winSize + 1)
+
+
+@pytest.fixture
+def hooks(smt):
+    yield smt
+    smt.asw_set_impl(0)
+    smt.asw_both_set_impl(2)
+
+
+@pytest.mark.parametrize("H,W,D,winSize,seed,noise", SHAPES)
+def test_left_outputs_are_smt_asw_bit_for_bit(hooks, O, H, W, D, winSize, seed, noise):
+    smt = hooks
+    Lp, Rp = padded(O, H, W, winSize, seed, noise)
+    sp, cm = smt.asw_masks(winSize, 50.0, 30.0, DEV)
+    for impl in (0, 3, 6, 1, 4, 5):
+        smt.asw_set_impl(impl)
+        d0, c0 = smt.AdaptiveSupportWeight(T(Lp), T(Rp), winSize, D, sp, cm, 40, smt.VIEW_LEFT, want_cost=True)
+        for both in (2, 1):
+            smt.asw_both_set_impl(both)
+            dl, dr = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40)
+            assert torch.equal(dl, d0), (impl, both)
+            dl, dr2, cl, cr = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40, want_cost=True)
+            assert torch.equal(dl, d0), (impl, both)
+            assert same_bits(cl.cpu().numpy(), c0.cpu().numpy()), (impl, both)
+            assert torch.equal(dr, dr2), (impl, both)
+
+
+@pytest.mark.parametrize("H,W,D,winSize,seed,noise", SHAPES)
+def test_right_outputs_follow_from_the_gpu_left_volume_exactly(hooks, O, H, W, D, winSize, seed, noise):
+    smt = hooks
+    Lp, Rp = padded(O, H, W, winSize, seed, noise)
+    sp, cm = smt.asw_masks(winSize, 50.0, 30.0, DEV)
+    maps = {}
+    for both in (2, 1):
+        smt.asw_both_set_impl(both)
+        dl, dr, cl, cr = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40, want_cost=True)
+        cr_want, dr_want = right_from_left(cl.cpu().numpy(), winSize + 1)
+        assert np.array_equal(np.isnan(cr.cpu().numpy()), np.isnan(cr_want)), both
+        ok = ~np.isnan(cr_want)
+        assert np.array_equal(bits(cr.cpu().numpy())[ok], bits(cr_want)[ok]), both
+        assert np.array_equal(dr.cpu().numpy(), dr_want), both
+        # maps only: impl 2 runs the rank keys here (with costR it hands over to the volume formulation)
+        _, dr_only = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40)
+        assert np.array_equal(dr_only.cpu().numpy(), dr_want), both
+        # ... and with costL alone the keys run beside the volume store
+        dl2, dr3 = torch.empty_like(dl), torch.empty_like(dr)
+        cl2 = torch.empty_like(cl)
+        from stereo_match_traditional_amd._lib import check, lib
+        tl, tr = T(Lp), T(Rp)
+        check(lib().smt_asw_both(C.c_void_p(tl.data_ptr()), C.c_void_p(tr.data_ptr()), H, W, D, winSize,
+                                 C.c_void_p(sp.data_ptr()), C.c_void_p(cm.data_ptr()), 40, C.c_void_p(dl2.data_ptr()),
+                                 C.c_void_p(dr3.data_ptr()), C.c_void_p(cl2.data_ptr()), None,
+                                 smt.current_stream_ptr()), "smt_asw_both")
+        torch.cuda.synchronize()
+        assert same_bits(cl2.cpu().numpy(), cl.cpu().numpy()) and np.array_equal(dr3.cpu().numpy(), dr_want), both
+        maps[both] = dr_only
+    assert torch.equal(maps[1], maps[2])
+
+
+@pytest.mark.parametrize("H,W,D,winSize,seed,noise", SHAPES)
+def test_right_view_against_the_oracle(hooks, O, H, W, D, winSize, seed, noise, capsys):
+    """costR within 1e-4 with the oracle's NaN pattern.  dispR equal wherever the oracle's two smallest computed right
+    costs (d <= W - wins - 2 - x') are more than 2 float ulps apart; on these shapes the oracle has no pixel inside
+    that band (counted and asserted here), so the maps are compared whole."""
+    smt = hooks
+    Lp, Rp = padded(O, H, W, winSize, seed, noise)
+    sp_ref, cm_ref = O.asw_masks(winSize, 50.0, 30.0)
+    sp, cm = smt.asw_masks(winSize, 50.0, 30.0, DEV)
+    rd, rc = O.asw(Lp, Rp, D, winSize, sp_ref, cm_ref, 40, 1, want_cost=True)
+    wins = winSize + 1
+    comp = np.where(np.arange(D)[None, None, :] <= (W - wins - 2 - np.arange(W))[None, :, None], rc, np.float32(np.inf))
+    comp = np.where(np.isnan(comp), np.float32(np.inf), comp)
+    if D > 1:
+        srt = np.sort(comp, axis=2)
+        with np.errstate(invalid="ignore"):
+            gap = (srt[:, :, 1] - srt[:, :, 0]).astype(np.float64)
+            band = 2.0 * np.spacing(srt[:, :, 0]).astype(np.float64)
+        in_band = int((gap <= band).sum())
+    else:
+        in_band = 0
+    with capsys.disabled():
+        print(f"\nASW both {(H, W, D, winSize)}: oracle right-view pixels inside the 2-ulp band: {in_band}")
+    assert in_band == 0
+    for both in (2, 1):
+        smt.asw_both_set_impl(both)
+        dl, dr, cl, cr = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40, want_cost=True)
+        a = cr.cpu().numpy()
+        assert np.array_equal(np.isnan(a), np.isnan(rc)), both
+        ok = ~np.isnan(rc)
+        err = float(np.max(np.abs(a[ok].astype(np.float64) - rc[ok]), initial=0.0))
+        with capsys.disabled():
+            print(f"  impl {both}: max |costR - oracle| = {err:.3g}")
+        assert err <= 1e-4, both
+        _, dr_only = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40)
+        assert np.array_equal(dr.cpu().numpy(), rd), both
+        assert np.array_equal(dr_only.cpu().numpy(), rd), both
+
+
+def test_flow_batch(hooks, O):
+    """Three pairs of (24, 96, D = 48, winSize 5), pair 2 a copy of pair 0.  The cross-checked map is compared with the
+    oracle's own: valid because on both inputs (seeds 11 and 12, with noise) the oracle has no pixel of either view
+    whose two smallest computed costs lie within 2 float ulps (counted on the CPU; seed 12 without noise has 23)."""
+    smt = hooks
+    H, W, D, ws = 24, 96, 48, 5
+    pairs = [O.synth_pair(H, W, 32, 11, True), O.synth_pair(H, W, 32, 12, True)]
+    pairs.append(pairs[0])
+    L = T(np.stack([p[0] for p in pairs]))
+    R = T(np.stack([p[1] for p in pairs]))
+    f = smt.ASWFlow(H, W, D, winSize=ws)
+    dl, dr, last = f.run(L, R)
+    sp, cm = smt.asw_masks(ws, 50.0, 30.0, DEV)
+    sp_ref, cm_ref = O.asw_masks(ws, 50.0, 30.0)
+    for b, (l, r) in enumerate(pairs):
+        Lp, Rp = O.pad_replicate(l, ws + 1), O.pad_replicate(r, ws + 1)
+        bl, br = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), ws, D, sp, cm, 40)
+        assert torch.equal(dl[b], bl) and torch.equal(dr[b], br), b
+        assert torch.equal(last[b], smt.asw_CrossCheckDiaparity(bl, br)), b
+        ol = O.asw(Lp, Rp, D, ws, sp_ref, cm_ref, 40, 0)
+        orr = O.asw(Lp, Rp, D, ws, sp_ref, cm_ref, 40, 1)
+        assert np.array_equal(last[b].cpu().numpy(), O.asw_crosscheck(ol, orr)), b
+    assert torch.equal(dl[2], dl[0]) and torch.equal(dr[2], dr[0]) and torch.equal(last[2], last[0])
+    # a second and a third run on the same handle: the same bytes, and no growth of the scratch arena
+    out2 = f.run(L, R)
+    torch.cuda.synchronize()
+    r2 = smt.scratch_info()
+    out3 = f.run(L, R)
+    torch.cuda.synchronize()
+    r3 = smt.scratch_info()
+    for a, b, c in zip((dl, dr, last), out2, out3):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    assert r3[0] == r2[0], (r2, r3)
+    # pairs = 0 leaves the outputs untouched; outputs are optional
+    from stereo_match_traditional_amd._lib import lib
+    keep = [t.clone() for t in (dl, dr, last)]
+    p = lambda t: C.c_void_p(t.data_ptr())
+    assert lib().smt_asw_flow_run_batch(f._h, p(L), p(R), 0, p(dl), p(dr), p(last)) == 0
+    assert lib().smt_asw_flow_run_batch(f._h, None, None, 0, None, None, None) == 0
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(keep, (dl, dr, last)))
+    only_last = torch.zeros_like(last)
+    assert lib().smt_asw_flow_run_batch(f._h, p(L), p(R), 3, None, None, p(only_last)) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(only_last, last)
+    assert lib().smt_asw_flow_run_batch(f._h, p(L), p(R), -1, p(dl), p(dr), p(last)) == SMT_ERR_ARG
+    assert lib().smt_asw_flow_run_batch(f._h, None, p(R), 1, p(dl), p(dr), p(last)) == SMT_ERR_ARG
+    assert lib().smt_asw_flow_run_batch(None, p(L), p(R), 1, p(dl), p(dr), p(last)) == SMT_ERR_ARG
+    f.close()
+    # the sharding unit
+    from stereo_match_traditional_amd import shard
+    sl, sr = shard.asw_batch(L, R, D, winSize=ws)
+    assert torch.equal(sl, dl) and torch.equal(sr, dr)
+
+
+def test_bad_arguments_are_rejected_before_any_launch(smt):
+    from stereo_match_traditional_amd import _lib as Lb
+    lib = Lb.lib()
+    H, W, D = 8, 16, 4
+    h = C.c_void_p()
+
+    def params(**kw):
+        p = Lb.ASWParams()
+        lib.smt_asw_default_params(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return C.byref(p)
+
+    bad = [(0, W, D, params()), (H, 0, D, params()), (-1, W, D, params()), (H, W, 0, params()), (H, W, 513, params()),
+           (H, W, D, params(winSize=0)), (H, W, D, params(winSize=31)), (H, W, D, params(sigma_space=0.0)),
+           (H, W, D, params(sigma_color=-1.0)), (H, W, D, params(sigma_color=float("nan")))]
+    for hh, ww, dd, pp in bad:
+        assert lib.smt_asw_flow_create_on(0, hh, ww, dd, pp, C.byref(h)) == SMT_ERR_ARG, (hh, ww, dd)
+    assert lib.smt_asw_flow_create_on(0, H, W, D, params(), None) == SMT_ERR_ARG
+    assert lib.smt_asw_flow_create_on(-1, H, W, D, params(), C.byref(h)) == SMT_ERR_ARG
+    assert lib.smt_asw_flow_create_on(0, H, W, D, None, C.byref(h)) == 0          # NULL params: the defaults
+    assert lib.smt_asw_flow_set_stream(None, None) == SMT_ERR_ARG
+    assert lib.smt_asw_flow_destroy(None) == SMT_ERR_ARG
+    assert lib.smt_asw_flow_destroy(h) == 0
+
+    ws = 2
+    sp, cm = smt.asw_masks(ws, 50.0, 30.0, DEV)
+    Lp = torch.full((H + 2 * ws + 2, W + 2 * ws + 2), 7, dtype=torch.uint8, device=DEV)
+    dl = torch.full((H, W), -5.0, device=DEV)
+    dr = torch.full((H, W), -5.0, device=DEV)
+    p = lambda t: C.c_void_p(t.data_ptr())
+
+    def call(L, R, D_, ws_):
+        return lib.smt_asw_both(L, R, H, W, D_, ws_, p(sp), p(cm), 40, p(dl), p(dr), None, None, smt.current_stream_ptr())
+
+    assert call(p(Lp), p(Lp), 0, ws) == SMT_ERR_ARG
+    assert call(p(Lp), p(Lp), 513, ws) == SMT_ERR_ARG
+    assert call(p(Lp), p(Lp), D, 31) == SMT_ERR_ARG
+    assert call(None, p(Lp), D, ws) == SMT_ERR_ARG
+    assert call(p(Lp), None, D, ws) == SMT_ERR_ARG
+    torch.cuda.synchronize()
+    assert bool((dl == -5.0).all()) and bool((dr == -5.0).all())                  # nothing was launched
+
+
+def test_config4_size(hooks, O, capsys):
+    """540 x 960, D = 128, winSize 16 (the inputs of test_asw_config4_size_band_vs_oracle).  dispL is smt_asw's left map
+    bit for bit; dispR against the oracle on eight rows under that test's rule (zero mismatches outside the 2-ulp band);
+    dispR against smt_asw's right map: the differing pixels are counted, and on the oracle's rows every one of them
+    must lie inside the oracle's band."""
+    from stereo_match_traditional_amd import synth
+    smt = hooks
+    H, W, D, ws, Tt = 540, 960, 128, 16, 40
+    L, R = synth.synth_pair(H, W, D, 4)
+    pad = ws + 1
+    Lp, Rp = np.pad(L, pad, mode="edge"), np.pad(R, pad, mode="edge")
+    sp_ref, cm_ref = O.asw_masks(ws, 50.0, 30.0)
+    sp, cm = smt.asw_masks(ws, 50.0, 30.0, DEV)
+    tl, tr = T(Lp), T(Rp)
+    dl, dr = smt.AdaptiveSupportWeightBoth(tl, tr, ws, D, sp, cm, Tt)
+    assert torch.equal(dl, smt.AdaptiveSupportWeight(tl, tr, ws, D, sp, cm, Tt, smt.VIEW_LEFT))
+    smt.asw_both_set_impl(1)
+    _, dr1 = smt.AdaptiveSupportWeightBoth(tl, tr, ws, D, sp, cm, Tt)
+    assert torch.equal(dr1, dr)
+    single = smt.AdaptiveSupportWeight(tl, tr, ws, D, sp, cm, Tt, smt.VIEW_RIGHT).cpu().numpy()
+    got_all = dr.cpu().numpy()
+    differs = got_all != single
+    rows = [0, 1, 17, 270, 401, 522, 538, 539]
+    n_mis, n_in_band = 0, 0
+    for row in rows:
+        rd, rc = O.asw(Lp, Rp, D, ws, sp_ref, cm_ref, Tt, 1, i0=row, i1=row + 1, want_cost=True)
+        b = rc[row]
+        assert (got_all[row, W - ws - 2:] == 0).all()
+        srt = np.sort(np.where(np.isnan(b), np.float32(np.inf), b), axis=1)
+        with np.errstate(invalid="ignore"):
+            gap = (srt[:, 1] - srt[:, 0]).astype(np.float64)
+            band = 2.0 * np.spacing(srt[:, 0]).astype(np.float64)
+        inside = gap <= band
+        mis = got_all[row] != rd[row]
+        outside = mis & ~inside
+        assert not outside.any(), (row, np.flatnonzero(outside)[:5], gap[outside][:5])
+        n_mis += int(mis.sum())
+        n_in_band += int(inside.sum())
+        assert not (differs[row] & ~inside).any(), (row, np.flatnonzero(differs[row] & ~inside)[:5])
+    with capsys.disabled():
+        print(f"\nASW both, config 4: dispR vs oracle on {len(rows)} rows x {W} px: {n_mis} WTA mismatches, all inside the "
+              f"2-ulp tie band ({n_in_band} pixels in the band); dispR vs smt_asw(RIGHT): {int(differs.sum())} of {H * W} "
+              f"pixels differ ({int(differs[rows].sum())} on the oracle's rows, all inside the band)")
