@@ -721,6 +721,65 @@ int smt_asw_flow_set_stream(smt_asw_flow *h, void *stream);
 int smt_asw_flow_run_batch(smt_asw_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
                            float *dispL, float *dispR, uint8_t *lastDisp);
 
+/* Both SAD maps from ONE evaluation of the hypotheses (SADmain.cpp:66-67).  Lp, Rp, H, W, D, winsize as smt_sad; every
+ * argument smt_sad accepts is accepted, everything it rejects is rejected.
+ *   dispL  int32 [H][W]      exactly smt_sad(..., SMT_VIEW_LEFT, ...)
+ *   dispR  int32 [H][W]      exactly smt_sad(..., SMT_VIEW_RIGHT, ...) (last row / column 0, Sad.h:157,160)
+ *   costL  float32 [H][W][D] optional: the left view's `sad` vector per pixel, chain entries included
+ *                            (sad[d] = sad[d-1] for d > x, Sad.h:125-129); integer-valued
+ * The right view's cost at (i, x', d) (Sad.h:173-174) is the left view's at (i, x' + d, d) -- sadvalue is an exact,
+ * symmetric integer sum -- and every hypothesis the right view accepts (:167) is one the left view evaluates (:125), so
+ * both maps equal smt_sad's bit for bit.  The costs come from a box-sum kernel (running column sums down the rows, a
+ * sliding sum along the row: the work per hypothesis does not grow with the window) for windows up to 181 x 181
+ * (winsize <= 89, where (cost << 9) | d fits 32 bits); larger windows, and the sizes the dispatch rule in
+ * csrc/sad_both.hip names, run smt_sad once per view inside the call.  Needs 4 * H * W bytes of the scratch arena
+ * (4 * H * W * D under smt_sad_both_set_impl(1) without costL). */
+int smt_sad_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winsize,
+                 int32_t *dispL, int32_t *dispR, float *costL, void *stream);
+/* Test hook (process-wide): how the box form gets the right view.  2 (default) = rank keys: every hypothesis offers
+ * (cost << 9) | d to right pixel x - d, minimum per workgroup in LDS, one agent-scope atomic min per touched pixel into
+ * an [H][W] uint32 key map, then a finishing launch.  1 = the left volume (in scratch when costL is NULL) and a
+ * diagonal-gather minimum kernel.  Identical maps. */
+int smt_sad_both_set_impl(int impl);
+/* Test hooks (process-wide; plain unsynchronised globals like smt_sad_both_set_impl's: a test-only contract, not
+ * thread-safe -- set them while no other thread is inside smt_sad_both).  smt_sad_both_set_dispatch: 0 (default) = the
+ * dispatch rule, 1 = the box form wherever it covers the window, 2 = always the composed smt_sad calls.
+ * smt_sad_both_set_band: rows per band of the box kernel's grid, 0 (default) = chosen from the image size (small
+ * images get bands of one row, which never take a row out of the running sums).  smt_sad_both_last_form: what the last
+ * successful smt_sad_both of the process ran, one of SMT_SAD_FORM_* (0 before the first call). */
+#define SMT_SAD_FORM_COMPOSED   1   /* smt_sad per view */
+#define SMT_SAD_FORM_BOX_KEYS   2   /* box kernel + rank keys */
+#define SMT_SAD_FORM_BOX_VOLUME 3   /* box kernel + left volume + diagonal gather */
+int smt_sad_both_set_dispatch(int mode);
+int smt_sad_both_set_band(int band);
+int smt_sad_both_last_form(void);
+/* Test hooks, host only (no GPU).  smt_sad_selftest_box: on four padded pairs of the shape (pseudo-random, 0 against
+ * 255, opposed checkerboards, a shifted copy) the box kernel's recurrence restated on the host -- same strips, bands,
+ * entering and leaving rows, masked dword groups, sliding sum, chain -- equals the direct double loop for every
+ * (i, x, d).  smt_sad_selftest_right_keys: the minimum key over a right pixel's diagonal is GetMinSadIndex
+ * (Sad.h:22-38) of its chained row, with exact ties (seed % 3 == 0), all-equal rows (1) and costs at the window's
+ * largest value (2).  SMT_OK or SMT_ERR_STATE; SMT_ERR_ARG for non-positive sizes, D > SMT_MAX_DISPARITY, windows the
+ * box kernel does not cover, or (box) more than 2^24 hypotheses. */
+int smt_sad_selftest_box(int H, int W, int D, int winsize, unsigned seed);
+int smt_sad_selftest_right_keys(int W, int D, int winsize, unsigned seed);
+
+/* SAD/SADmain.cpp with :67-68 enabled, for `pairs` gray pairs uint8 [pairs][H][W] (the images after imread(..., 0) /
+ * cvtColor, :27-41), per pair in the file's order: copyMakeBorder by winsize + 1 (:47-48), both views (:66-67, through
+ * smt_sad_both), CrossCheckDiaparity (:68).  dispL, dispR, lastdisp int32 [pairs][H][W]; cls uint8 [pairs][H][W] as
+ * smt_sad_crosscheck; any output may be NULL.  The flow stops at :68: RemoveSpeckles at :69 reads an int Mat through
+ * at<float>, and :71-78 are OpenCV calls and scan-order fillers.  The handle owns the padded images and one set of
+ * maps: a warm call allocates nothing beyond the library's scratch arena.  Asynchronous on the handle's stream;
+ * pairs == 0 is a no-op.  SMT_ERR_ARG for non-positive sizes, NULL inputs, winsize < 0 and D outside
+ * 1..SMT_MAX_DISPARITY. */
+typedef struct smt_sad_flow smt_sad_flow;
+typedef struct smt_sad_params { int winsize; } smt_sad_params;                    /* 3: SADmain.cpp:34 */
+void smt_sad_default_params(smt_sad_params *p);
+int smt_sad_flow_create_on(int device, int H, int W, int D, const smt_sad_params *p, smt_sad_flow **out);
+int smt_sad_flow_destroy(smt_sad_flow *h);
+int smt_sad_flow_set_stream(smt_sad_flow *h, void *stream);
+int smt_sad_flow_run_batch(smt_sad_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                           int32_t *dispL, int32_t *dispR, int32_t *lastdisp, uint8_t *cls);
+
 /* =====================================================================================
  * Either side of the path: input staging and the first post-filter
  * ===================================================================================== */

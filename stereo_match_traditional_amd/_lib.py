@@ -15,6 +15,7 @@ SMT_ERR_DOMAIN = -4
 SMT_ERR_REF_UB = -5
 VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH = 1, 2, 3
 QUIRK_FIX_RIGHT_ARM_STRIDE = 0x1
+SAD_FORM_COMPOSED, SAD_FORM_BOX_KEYS, SAD_FORM_BOX_VOLUME = 1, 2, 3
 
 
 class SmtError(RuntimeError):
@@ -41,6 +42,11 @@ class CBLSMParams(C.Structure):
 class ASWParams(C.Structure):
     """smt_asw_params: ASWeight.cpp:43-47's winSize, T, sigma_space, sigma_color."""
     _fields_ = [("winSize", C.c_int), ("T", C.c_int), ("sigma_space", C.c_double), ("sigma_color", C.c_double)]
+
+
+class SADParams(C.Structure):
+    """smt_sad_params: SADmain.cpp:34's winsize."""
+    _fields_ = [("winsize", C.c_int)]
 
 
 class PostParams(C.Structure):

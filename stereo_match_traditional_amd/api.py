@@ -16,7 +16,8 @@ __all__ = ["FillTheHole", "chooseArmLengthLeft", "chooseArmLengthRight", "choose
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
            "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info",
-           "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow"]
+           "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow",
+           "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow"]
 
 
 def current_stream_ptr(device=None):
@@ -650,6 +651,43 @@ def _sad(Lp, Rp, D, winsize, view):
 
 
 @_on_tensor_device
+def GetPointDepthBoth(leftimg, rightimg, MaxDisparity, winsize, want_cost=False):
+    """smt_sad_both: SADmain.cpp:66-67's two views from one evaluation of the hypotheses.  uint8 images replicate-padded by
+    winsize+1 -> (dispL, dispR) int32, or (dispL, dispR, costL) with want_cost (float32 [H][W][D], integer-valued)."""
+    w = winsize + 1
+    Hp, Wp = leftimg.shape
+    H, W = Hp - 2 * w, Wp - 2 * w
+    _dev(leftimg, torch.uint8, (Hp, Wp), "leftimg")
+    _dev(rightimg, torch.uint8, (Hp, Wp), "rightimg")
+    dl = torch.empty((H, W), dtype=torch.int32, device=leftimg.device)
+    dr = torch.empty_like(dl)
+    cl = torch.empty((H, W, MaxDisparity), dtype=torch.float32, device=leftimg.device) if want_cost else None
+    check(lib().smt_sad_both(_ptr(leftimg), _ptr(rightimg), H, W, MaxDisparity, winsize, _ptr(dl), _ptr(dr), _ptr(cl),
+                             current_stream_ptr()), "smt_sad_both")
+    return (dl, dr, cl) if want_cost else (dl, dr)
+
+
+def sad_both_set_impl(impl):
+    """2 = rank keys, no volume (default), 1 = left volume + diagonal-gather minimum (test hook)."""
+    check(lib().smt_sad_both_set_impl(int(impl)), "smt_sad_both_set_impl")
+
+
+def sad_both_set_dispatch(mode):
+    """0 = the dispatch rule (default), 1 = the box kernel wherever it covers the window, 2 = smt_sad per view (test hook)."""
+    check(lib().smt_sad_both_set_dispatch(int(mode)), "smt_sad_both_set_dispatch")
+
+
+def sad_both_set_band(band):
+    """Rows per band of the box kernel's grid, 0 = chosen from the image size (test hook)."""
+    check(lib().smt_sad_both_set_band(int(band)), "smt_sad_both_set_band")
+
+
+def sad_both_last_form():
+    """What the last GetPointDepthBoth ran: _lib.SAD_FORM_COMPOSED / SAD_FORM_BOX_KEYS / SAD_FORM_BOX_VOLUME (test hook)."""
+    return int(lib().smt_sad_both_last_form())
+
+
+@_on_tensor_device
 def sad_CrossCheckDiaparity(leftdisp, rightdisp):
     """Sad.h:184-222 -> (lastdisp int32, cls uint8)."""
     H, W = leftdisp.shape
@@ -1135,6 +1173,56 @@ class ASWFlow:
     def close(self):
         if getattr(self, "_h", None) is not None:
             lib().smt_asw_flow_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SADFlow:
+    """SADmain.cpp with :67-68 enabled (:47-48, :66-68) for batches of gray pairs: replicate padding by winsize + 1, both
+    views from one pass over the hypotheses (smt_sad_both), CrossCheckDiaparity.  Keywords override
+    smt_sad_default_params: winsize.  The sharding unit of shard.sad_batch."""
+
+    def __init__(self, row, col, dispRange, device=None, **params):
+        self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        p = _lib.SADParams()
+        lib().smt_sad_default_params(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        h = C.c_void_p()
+        check(lib().smt_sad_flow_create_on(_dev_index(self.device), self.row, self.col, self.dispRange, C.byref(p),
+                                           C.byref(h)), "smt_sad_flow_create_on")
+        self._h = h
+
+    def run(self, grayL, grayR):
+        """uint8 [pairs][row][col] (or [row][col]) -> (dispL, dispR, lastdisp, cls): int32, int32, int32, uint8
+        [pairs][row][col], on torch's current stream of the handle's device; nothing synchronises."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"SAD handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.int32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        last = torch.empty_like(dl)
+        cls = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        check(lib().smt_sad_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_sad_flow_set_stream")
+        check(lib().smt_sad_flow_run_batch(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(last), _ptr(cls)),
+              "smt_sad_flow_run_batch")
+        return dl, dr, last, cls
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().smt_sad_flow_destroy(self._h)
             self._h = None
 
     def __del__(self):

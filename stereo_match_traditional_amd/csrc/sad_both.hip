@@ -1,0 +1,646 @@
+// smt_sad_both: both SAD maps (SADmain.cpp:66-67) from ONE evaluation of the hypotheses, and smt_sad_flow_*:
+// SADmain.cpp:47-48, :66-68 for a batch of gray pairs.
+//
+// 1. The right view's costs are the left view's.  With w = winsize + 1 and costL[i][x][d] = SAD of the left window at
+//    column x against the right window at x - d, GetPointDepthRight's cost at (i, x', d) (Sad.h:173-174) is
+//    costL[i][x' + d][d]: sadvalue is an exact integer sum of |a - b|.  The right view accepts d iff x' + d <= W - 1
+//    (:167); at x = x' + d the left view accepts d iff x - d >= 0 (:125), always.  So the right map is the first minimum
+//    over the diagonal, taken here through rank keys (cost << 9) | d: LDS atomic min per workgroup, one agent-scope atomic
+//    min per touched right pixel into an [H][W] key map, and a finishing launch (the kernel boundary orders the atomics of
+//    every XCD before it).
+// 2. costL[i][x][d] is the side x side box sum of AD_d[y][c] = |Lp[y][c] - Rp[y][c - d]|.  k_sad_box keeps, per lane
+//    (hypothesis d = lane + 64 k) and per column of its strip, the running box sum C in a register and moves it one image
+//    row down by adding the horizontal window sums of the entering row and subtracting those of the leaving row; a
+//    horizontal window sum slides along the row (add the entering column's |a - b|, subtract the leaving one's).  The work
+//    per hypothesis does not depend on side (the tap loop of k_sad2 needs side^2 / 4 v_sad_u8); all of it is integer, and
+//    every sum is below 2^24 for side <= 256, so the float handed to sad_optimal is the number the reference holds.
+#include "smt_common.h"
+#include "sad_select.h"
+#include <new>
+#include <stdlib.h>
+#include <type_traits>
+#include <vector>
+
+namespace {
+
+constexpr int BNT = 256;                 // four waves per workgroup
+constexpr int BS = 16;                   // columns per wave: C[BS][K] running box sums in VGPRs
+constexpr int BSW = BS * (BNT / 64);     // columns per workgroup
+constexpr unsigned NOKEY = 0xffffffffu;
+constexpr int BOX_MAX_SIDE = 181;        // 255 * side^2 < 2^23: (cost << 9) | d fits 32 bits and never equals NOKEY
+
+// Staged row geometry, shared by the kernel and its host restatement.  A row of either image sits in LDS expanded to one
+// dword per BYTE offset (entry A = bytes A .. A + 3, as k_sad2 stages its rows): the initial window sum of a row reads
+// aligned dwords for v_sad_u8 whatever the hypothesis, the sliding sum reads the low byte of an entry, and lanes with
+// consecutive d touch consecutive dwords.  Left entries start at column x0 - 1, right entries at x0 - 64 KT (one entry of
+// slack each: the masked tail dword of a 3-wide window starts one byte before the window).
+__host__ __device__ inline int box_lwe(int side) { return (BSW + side + 3) & ~3; }
+__host__ __device__ inline int box_rwe(int side, int KT) { return (64 * KT + BSW + side + 3) & ~3; }
+
+// entry A .. A + 3 of a padded image row (columns clamped into the row: the clamped bytes are only read by hypotheses
+// that the chain of Sad.h:125-129 replaces)
+__device__ __forceinline__ void box_load8(const uint8_t *__restrict__ row, int x, int Wp, unsigned &lo, unsigned &hi)
+{
+    if (x >= 0 && x + 7 <= Wp - 1) {
+        __builtin_memcpy(&lo, row + x, 4);
+        __builtin_memcpy(&hi, row + x + 4, 4);
+    } else {
+        lo = hi = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            int xa = x + b, xb = x + 4 + b;
+            xa = xa < 0 ? 0 : (xa > Wp - 1 ? Wp - 1 : xa);
+            xb = xb < 0 ? 0 : (xb > Wp - 1 ? Wp - 1 : xb);
+            lo |= (unsigned)row[xa] << (8 * b);
+            hi |= (unsigned)row[xb] << (8 * b);
+        }
+    }
+}
+
+// grid (strips of BSW columns, bands of `band` rows).  Step t of a band that starts at row i0 brings in padded row
+// i0 + t, takes out padded row i0 + t - side (once there is one) and, from t = side - 1 on, emits output row
+// i0 + t - side + 1.  The two rows of step t + 1 are fetched into registers before step t computes and written to the
+// other half of the LDS row buffer after it; one barrier per step.  rkeys == nullptr: no right view.
+template <int KT>
+__global__ void __launch_bounds__(BNT) k_sad_box(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
+                                                 int D, int w, int band, int32_t *__restrict__ dispL,
+                                                 float *__restrict__ costL, unsigned *__restrict__ rkeys)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned s_box[];
+    const int side = 2 * w + 1, Wp = W + 2 * w;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int x0 = blockIdx.x * BSW, i0 = blockIdx.y * band;
+    const int i1 = i0 + band < H ? i0 + band : H;
+    const int nk = (D + 63) >> 6;                              // live hypothesis slots (uniform)
+    const int LWE = box_lwe(side), RWE = box_rwe(side, KT), ROWE = LWE + RWE;
+    const int xLb = x0 - 1, xRb = x0 - 64 * KT;
+    constexpr int NKEY = 64 * KT + BSW;
+    unsigned *s_rows = s_box;                                  // [2 halves][entering, leaving][LWE left + RWE right entries]
+    unsigned *s_keys = s_box + 4 * ROWE;                       // [2 halves][NKEY]
+    for (int e = threadIdx.x; e < 2 * NKEY; e += BNT) s_keys[e] = NOKEY;
+
+    // staging: one item = four consecutive entries (two unaligned dword loads, three v_alignbyte, one 16-byte store).
+    // Items of a step: entering row left, entering row right, leaving row left, leaving row right; at most 2 per thread.
+    const int nL4 = LWE >> 2, nR4 = RWE >> 2, nrow4 = nL4 + nR4;
+    unsigned slo[2], shi[2];
+    auto fetch = [&](int t) {
+        const int rE = i0 + t, rL = rE - side;
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const int e = threadIdx.x + q * BNT;
+            slo[q] = shi[q] = 0;
+            if (e < 2 * nrow4) {
+                const int which = e >= nrow4, f = e - which * nrow4;
+                const int r = which ? rL : rE;
+                if (!which || rL >= i0) {
+                    const bool right = f >= nL4;
+                    const int x = right ? xRb + 4 * (f - nL4) : xLb + 4 * f;
+                    box_load8((right ? Rp : Lp) + (size_t)r * Wp, x, Wp, slo[q], shi[q]);
+                }
+            }
+        }
+    };
+    auto commit = [&](int half) {
+        typedef unsigned u4v __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const int e = threadIdx.x + q * BNT;
+            if (e < 2 * nrow4)
+                *reinterpret_cast<u4v *>(s_rows + (size_t)half * 2 * ROWE + 4 * e) =
+                    u4v{slo[q], __builtin_amdgcn_alignbyte(shi[q], slo[q], 1), __builtin_amdgcn_alignbyte(shi[q], slo[q], 2),
+                        __builtin_amdgcn_alignbyte(shi[q], slo[q], 3)};
+        }
+    };
+    fetch(0);
+    commit(0);
+    __syncthreads();
+
+    const int xw = x0 + BS * wv;                               // this wave's first column
+    const bool live = xw < W;
+    const int nfull = side >> 2, rem = side & 3;
+    const unsigned tmask = rem ? (0xffffffffu << (8 * (4 - rem))) : 0u;
+    const int la = xw - xLb;                                   // left entry of column xw
+    int ra[KT];                                                // right entry of column xw - d
+    unsigned C[BS][KT];
+#pragma unroll
+    for (int k = 0; k < KT; k++) {
+        ra[k] = xw - xRb - (lane + 64 * k);
+#pragma unroll
+        for (int j = 0; j < BS; j++) C[j][k] = 0;
+    }
+    // horizontal window sums of one staged row over the wave's BS columns, added to (SUB = false) or taken from C
+    auto row_pass = [&](const unsigned *Lrow, const unsigned *Rrow, auto sub) {
+        constexpr bool SUB = decltype(sub)::value;
+        unsigned run[KT];
+#pragma unroll
+        for (int k = 0; k < KT; k++) run[k] = 0;
+        for (int g = 0; g < nfull; g++) {
+            const unsigned a4 = Lrow[la + 4 * g];
+#pragma unroll
+            for (int k = 0; k < KT; k++)
+                if (k < nk) run[k] = __builtin_amdgcn_sad_u8(a4, Rrow[ra[k] + 4 * g], run[k]);
+        }
+        if (rem) {
+            // the last dword ends at the window's last byte; the bytes already counted are masked out of both operands
+            const unsigned a4 = Lrow[la + side - 4] & tmask;
+#pragma unroll
+            for (int k = 0; k < KT; k++)
+                if (k < nk) run[k] = __builtin_amdgcn_sad_u8(a4, Rrow[ra[k] + side - 4] & tmask, run[k]);
+        }
+        const uint8_t *Lb = reinterpret_cast<const uint8_t *>(Lrow), *Rb = reinterpret_cast<const uint8_t *>(Rrow);
+#pragma unroll
+        for (int j = 0; j < BS; j++) {
+            if (j > 0) {
+                const unsigned aN = Lb[4 * (la + j - 1 + side)], aO = Lb[4 * (la + j - 1)];
+#pragma unroll
+                for (int k = 0; k < KT; k++)
+                    if (k < nk) {
+                        const unsigned bN = Rb[4 * (ra[k] + j - 1 + side)], bO = Rb[4 * (ra[k] + j - 1)];
+                        run[k] = __builtin_amdgcn_sad_u8(aN, bN, run[k]) - __builtin_amdgcn_sad_u8(aO, bO, 0u);
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < KT; k++)
+                if (k < nk) C[j][k] = SUB ? C[j][k] - run[k] : C[j][k] + run[k];
+        }
+    };
+
+    const int nsteps = side - 1 + (i1 - i0);
+    for (int t = 0; t < nsteps; t++) {
+        const int half = t & 1;
+        const int io = i0 + t - side + 1;                      // output row of this step (>= i0: there is one)
+        const bool leaving = t >= side;
+        if (t + 1 < nsteps) fetch(t + 1);
+        unsigned *keys = s_keys + half * NKEY;
+        if (live) {
+            const unsigned *rows = s_rows + (size_t)half * 2 * ROWE;
+            row_pass(rows, rows + LWE, std::false_type());
+            if (leaving) row_pass(rows + ROWE, rows + ROWE + LWE, std::true_type());
+            if (io >= i0) {
+#pragma unroll
+                for (int j = 0; j < BS; j++) {
+                    const int x = xw + j;
+                    if (x >= W) break;
+                    unsigned cc[KT];
+#pragma unroll
+                    for (int k = 0; k < KT; k++) cc[k] = C[j][k];
+                    if (x < D - 1) {                           // Sad.h:125-129: d > x repeats the cost at d = x
+                        unsigned bc = 0;
+#pragma unroll
+                        for (int k = 0; k < KT; k++)
+                            if (k == (x >> 6)) bc = (unsigned)__builtin_amdgcn_readlane((int)cc[k], x & 63);
+#pragma unroll
+                        for (int k = 0; k < KT; k++)
+                            if (lane + 64 * k > x) cc[k] = bc;
+                    }
+                    float sad[KT];
+#pragma unroll
+                    for (int k = 0; k < KT; k++) sad[k] = (k < nk && lane + 64 * k < D) ? (float)cc[k] : 0.0f;   // sadvalue :15-20
+                    const int out = sad_optimal<KT>(sad, D, lane);
+                    const size_t pix = (size_t)io * W + x;
+                    if (lane == 0) dispL[pix] = out;
+                    if (costL) {
+#pragma unroll
+                        for (int k = 0; k < KT; k++)
+                            if (k < nk && lane + 64 * k < D) costL[pix * D + lane + 64 * k] = sad[k];
+                    }
+                    if (rkeys && io < H - 1) {                 // the right view never writes its last row (:157)
+#pragma unroll
+                        for (int k = 0; k < KT; k++) {
+                            const int d = lane + 64 * k;
+                            if (k < nk && d < D && d <= x) atomicMin(&keys[x - d - xRb], (cc[k] << 9) | (unsigned)d);
+                        }
+                    }
+                }
+            }
+        }
+        if (t + 1 < nsteps) commit(half ^ 1);
+        __syncthreads();
+        if (rkeys && io >= i0 && io < H - 1) {
+            // this half is offered to again two steps on, after the next barrier
+            for (int e = threadIdx.x; e < NKEY; e += BNT) {
+                const unsigned v = keys[e];
+                if (v != NOKEY) {
+                    atomicMin(&rkeys[(size_t)io * W + xRb + e], v);
+                    keys[e] = NOKEY;
+                }
+            }
+        }
+    }
+}
+
+// key map -> dispR; the last row and column are never written by GetPointDepthRight (Sad.h:157, :160)
+__global__ void __launch_bounds__(256) k_sad_rkeys_finish(const unsigned *__restrict__ rkeys, int H, int W, int32_t *__restrict__ dispR)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (size_t)H * W) return;
+    const int x = (int)(p % W), i = (int)(p / W);
+    dispR[p] = (i >= H - 1 || x >= W - 1) ? 0 : (int32_t)(rkeys[p] & 511u);
+}
+
+// Volume form of the right view: one wave per right pixel, the first minimum of costL[i][x' + d][d] over
+// d <= min(D - 1, W - 1 - x') through the same keys (the volume holds integers below 2^23)
+__global__ void __launch_bounds__(256) k_sad_diag(const float *__restrict__ costL, int H, int W, int D, int32_t *__restrict__ dispR)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t p = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= (size_t)H * W) return;
+    const int x = (int)(p % W), i = (int)(p / W);
+    if (i >= H - 1 || x >= W - 1) {
+        if (lane == 0) dispR[p] = 0;
+        return;
+    }
+    const int dmax = D - 1 < W - 1 - x ? D - 1 : W - 1 - x;
+    unsigned key = NOKEY;
+    for (int d = lane; d <= dmax; d += 64) {
+        const unsigned k = ((unsigned)costL[(p + d) * D + d] << 9) | (unsigned)d;
+        key = k < key ? k : key;
+    }
+    key = wave_min_u32(key);
+    if (lane == 0) dispR[p] = (int32_t)(key & 511u);
+}
+
+// The left view's sad vector, tap by tap, for windows beyond the box kernel: one thread per (pixel, d)
+__global__ void __launch_bounds__(256) k_sad_volume(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
+                                                    int D, int w, float *__restrict__ costL)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)H * W * D) return;
+    const int d = (int)(e % D);
+    const size_t p = e / D;
+    const int x = (int)(p % W), i = (int)(p / W);
+    const int side = 2 * w + 1, Wp = W + 2 * w, dd = d < x ? d : x;
+    const uint8_t *a = Lp + (size_t)i * Wp + x, *b = Rp + (size_t)i * Wp + x - dd;
+    unsigned acc = 0;
+    for (int r = 0; r < side; r++)
+        for (int c = 0; c < side; c++) acc += (unsigned)abs((int)a[(size_t)r * Wp + c] - (int)b[(size_t)r * Wp + c]);
+    costL[e] = (float)acc;
+}
+
+// Rows per band.  The cost model counts row passes per workgroup -- one per step while a band only adds (its first
+// side - 1 steps), two once a row leaves: 2 band + side - 1 -- times the rounds the grid needs if the device holds 1024
+// workgroups at a time.  That 1024 (256 CUs x 4) is an assumption, not a measurement: the KT >= 4 instantiations run one
+// workgroup per CU, so for D > 128 the model over-estimates the residency four times.  g_sad_both_band overrides it.
+int g_sad_both_band = 0;       // test hook: rows per band, 0 = box_band's choice
+int box_band(int H, int W, int side)
+{
+    const long strips = (W + BSW - 1) / BSW;
+    int best = H;
+    long best_cost = -1;
+    for (int band = 1; band <= H; band++) {
+        const long wgs = strips * ((H + band - 1) / band);
+        const long cost = (2L * band + side - 1) * ((wgs + 1023) / 1024);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = band; }
+    }
+    return best;
+}
+
+template <int KT>
+int launch_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int32_t *dispL, float *costL,
+               unsigned *rkeys)
+{
+    const int side = 2 * w + 1, band = g_sad_both_band > 0 ? (g_sad_both_band < H ? g_sad_both_band : H) : box_band(H, W, side);
+    const size_t shm = ((size_t)4 * (box_lwe(side) + box_rwe(side, KT)) + 2 * (64 * KT + BSW)) * 4;   // <= 24 KiB
+    const dim3 grid((W + BSW - 1) / BSW, (H + band - 1) / band);
+    hipLaunchKernelGGL(k_sad_box<KT>, grid, dim3(BNT), shm, st, Lp, Rp, H, W, D, w, band, dispL, costL, rkeys);
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+int run_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int32_t *dispL, float *costL,
+            unsigned *rkeys)
+{
+    const int K = (D + 63) / 64;
+    if (K <= 1) return launch_box<1>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
+    if (K <= 2) return launch_box<2>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
+    if (K <= 4) return launch_box<4>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
+    return launch_box<8>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
+}
+
+// Which path serves (side, D) by default.  Measured on one MI355X (tools/sad_both_time.py, profiles/sad_both_time.json;
+// smt_sad_both with the box kernel over the same-run sum of the two smt_sad calls, medians): 0.53 at 450x375 D=64 5x5
+// (the smallest window any driver uses), 0.39 at 450x375 D=60 9x9, 0.037 at 45x45, 0.42 at 1920x1080 D=128 9x9, 0.0075 at
+// 45x45.  The box kernel wins at every size measured, so it serves every window it covers.  D > 128 is not timed.
+bool sad_both_use_box(int side, int D)
+{
+    (void)D;
+    return side <= BOX_MAX_SIDE;
+}
+
+int g_sad_both_impl = 2;       // 2: rank keys (default); 1: left volume + k_sad_diag
+int g_sad_both_dispatch = 0;   // 0: sad_both_use_box; 1: the box kernel wherever it covers the window; 2: composed smt_sad calls
+int g_sad_both_last = 0;       // what the last call ran: SMT_SAD_FORM_*
+
+}  // namespace
+
+SMT_API int smt_sad_both_set_impl(int impl)
+{
+    if (impl != 1 && impl != 2) return SMT_ERR_ARG;
+    g_sad_both_impl = impl;
+    return SMT_OK;
+}
+
+SMT_API int smt_sad_both_set_dispatch(int mode)
+{
+    if (mode < 0 || mode > 2) return SMT_ERR_ARG;
+    g_sad_both_dispatch = mode;
+    return SMT_OK;
+}
+
+SMT_API int smt_sad_both_set_band(int band)
+{
+    if (band < 0) return SMT_ERR_ARG;
+    g_sad_both_band = band;
+    return SMT_OK;
+}
+
+SMT_API int smt_sad_both_last_form(void) { return g_sad_both_last; }
+
+SMT_API int smt_sad_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winsize, int32_t *dispL, int32_t *dispR,
+                         float *costL, void *stream)
+{
+    if (!Lp || !Rp || !dispL || !dispR || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0)
+        return SMT_ERR_ARG;
+    hipStream_t st = smt_stream(stream);
+    const size_t N = (size_t)H * W;
+    const int w = winsize + 1;
+    const long long side = 2LL * w + 1;
+    const bool covered = side <= BOX_MAX_SIDE;
+    const bool box = covered && (g_sad_both_dispatch == 1 || (g_sad_both_dispatch == 0 && sad_both_use_box((int)side, D)));
+    if (!box) {
+        int rc = smt_sad(Lp, Rp, H, W, D, winsize, SMT_VIEW_LEFT, dispL, stream);
+        if (rc == SMT_OK) rc = smt_sad(Lp, Rp, H, W, D, winsize, SMT_VIEW_RIGHT, dispR, stream);
+        if (rc != SMT_OK) return rc;
+        if (costL) {
+            hipLaunchKernelGGL(k_sad_volume, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, st, Lp, Rp, H, W, D, w, costL);
+            SMT_LAUNCH_CHECK();
+        }
+        g_sad_both_last = SMT_SAD_FORM_COMPOSED;
+        return SMT_OK;
+    }
+    if (g_sad_both_impl == 2) {
+        unsigned *rkeys = nullptr;
+        if (smt_scratch_alloc((void **)&rkeys, N * 4, st) != hipSuccess) return SMT_ERR_ALLOC;
+        int rc = hipMemsetAsync(rkeys, 0xFF, N * 4, st) == hipSuccess ? SMT_OK : SMT_ERR_HIP;
+        if (rc == SMT_OK) rc = run_box(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
+        if (rc == SMT_OK) hipLaunchKernelGGL(k_sad_rkeys_finish, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rkeys, H, W, dispR);
+        smt_scratch_free(rkeys, st);
+        if (rc != SMT_OK) return rc;
+        SMT_LAUNCH_CHECK();
+        g_sad_both_last = SMT_SAD_FORM_BOX_KEYS;
+        return SMT_OK;
+    }
+    float *vol = costL;
+    if (!vol && smt_scratch_alloc((void **)&vol, N * D * 4, st) != hipSuccess) return SMT_ERR_ALLOC;
+    int rc = run_box(st, Lp, Rp, H, W, D, w, dispL, vol, nullptr);
+    if (rc == SMT_OK) hipLaunchKernelGGL(k_sad_diag, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const float *)vol, H, W, D, dispR);
+    if (!costL) smt_scratch_free(vol, st);
+    if (rc != SMT_OK) return rc;
+    SMT_LAUNCH_CHECK();
+    g_sad_both_last = SMT_SAD_FORM_BOX_VOLUME;
+    return SMT_OK;
+}
+
+// ---- host-only checks ----------------------------------------------------------------------------------------------
+namespace {
+
+struct host_rng {
+    uint64_t s;
+    explicit host_rng(unsigned seed) : s(0x9E3779B97F4A7C15ull ^ ((uint64_t)seed * 0xD1342543DE82EF95ull + 1)) {}
+    uint32_t next() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (uint32_t)(s >> 11); }
+};
+
+unsigned host_sad_u8(unsigned a, unsigned b, unsigned acc)
+{
+    for (int q = 0; q < 4; q++) acc += (unsigned)abs((int)((a >> (8 * q)) & 255) - (int)((b >> (8 * q)) & 255));
+    return acc;
+}
+
+// k_sad_box on the host, hypothesis by hypothesis: the same strips, bands, steps, staged entries, masked dword groups,
+// sliding sums, entering and leaving rows and chain.  cost: [H][W][D].
+void box_host(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int band, unsigned *cost)
+{
+    const int side = 2 * w + 1, Wp = W + 2 * w;
+    const int KT = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
+    const int LWE = box_lwe(side), RWE = box_rwe(side, KT);
+    const int nfull = side >> 2, rem = side & 3;
+    const unsigned tmask = rem ? (0xffffffffu << (8 * (4 - rem))) : 0u;
+    std::vector<unsigned> eL(LWE), eR(RWE), lL(LWE), lR(RWE), C((size_t)BS * 64 * KT);
+    auto stage = [&](std::vector<unsigned> &dst, const uint8_t *row, int xb) {
+        for (size_t e = 0; e < dst.size(); e++) {
+            unsigned v = 0;
+            for (int b = 0; b < 4; b++) {
+                int x = xb + (int)e + b;
+                x = x < 0 ? 0 : (x > Wp - 1 ? Wp - 1 : x);
+                v |= (unsigned)row[x] << (8 * b);
+            }
+            dst[e] = v;
+        }
+    };
+    for (int i0 = 0; i0 < H; i0 += band) {
+        const int i1 = i0 + band < H ? i0 + band : H;
+        for (int x0 = 0; x0 < W; x0 += BSW) {
+            const int xLb = x0 - 1, xRb = x0 - 64 * KT;
+            for (int xw = x0; xw < x0 + BSW && xw < W; xw += BS) {
+                std::fill(C.begin(), C.end(), 0u);
+                const int la = xw - xLb;
+                const int nsteps = side - 1 + (i1 - i0);
+                for (int t = 0; t < nsteps; t++) {
+                    const int rE = i0 + t, rL = rE - side, io = rE - side + 1;
+                    stage(eL, Lp + (size_t)rE * Wp, xLb);
+                    stage(eR, Rp + (size_t)rE * Wp, xRb);
+                    if (rL >= i0) { stage(lL, Lp + (size_t)rL * Wp, xLb); stage(lR, Rp + (size_t)rL * Wp, xRb); }
+                    for (int d = 0; d < D; d++) {
+                        const int ra = xw - xRb - d;
+                        for (int pass = 0; pass < (rL >= i0 ? 2 : 1); pass++) {
+                            const unsigned *Lrow = pass ? lL.data() : eL.data(), *Rrow = pass ? lR.data() : eR.data();
+                            unsigned run = 0;
+                            for (int g = 0; g < nfull; g++) run = host_sad_u8(Lrow[la + 4 * g], Rrow[ra + 4 * g], run);
+                            if (rem) run = host_sad_u8(Lrow[la + side - 4] & tmask, Rrow[ra + side - 4] & tmask, run);
+                            for (int j = 0; j < BS; j++) {
+                                if (j > 0)
+                                    run = host_sad_u8(Lrow[la + j - 1 + side] & 255, Rrow[ra + j - 1 + side] & 255, run) -
+                                          host_sad_u8(Lrow[la + j - 1] & 255, Rrow[ra + j - 1] & 255, 0u);
+                                unsigned &c = C[(size_t)j * 64 * KT + d];
+                                c = pass ? c - run : c + run;
+                            }
+                        }
+                    }
+                    if (io < i0) continue;
+                    for (int j = 0; j < BS && xw + j < W; j++) {
+                        const int x = xw + j;
+                        for (int d = 0; d < D; d++)
+                            cost[((size_t)io * W + x) * D + d] = C[(size_t)j * 64 * KT + (d > x ? x : d)];
+                    }
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+// Host only (no GPU).  On four padded pairs of the given shape -- pseudo-random, constant 0 against constant 255,
+// opposed checkerboards, a shifted copy -- the restated recurrence of k_sad_box (box_host, under the band the launch
+// would choose and under a band of 1 and of 3 rows) equals the direct double loop over the window for every (i, x, d).
+SMT_API int smt_sad_selftest_box(int H, int W, int D, int winsize, unsigned seed)
+{
+    if (H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0 || 2 * (winsize + 1) + 1 > BOX_MAX_SIDE ||
+        (long long)H * W * D > (1 << 24))
+        return SMT_ERR_ARG;
+    const int w = winsize + 1, side = 2 * w + 1, Hp = H + 2 * w, Wp = W + 2 * w;
+    std::vector<uint8_t> L((size_t)Hp * Wp), R((size_t)Hp * Wp);
+    std::vector<unsigned> want((size_t)H * W * D), got((size_t)H * W * D);
+    host_rng rng(seed);
+    for (int pat = 0; pat < 4; pat++) {
+        for (int y = 0; y < Hp; y++)
+            for (int x = 0; x < Wp; x++) {
+                const size_t q = (size_t)y * Wp + x;
+                switch (pat) {
+                case 0: L[q] = (uint8_t)rng.next(); R[q] = (uint8_t)rng.next(); break;
+                case 1: L[q] = 0; R[q] = 255; break;
+                case 2: L[q] = ((x ^ y) & 1) ? 255 : 0; R[q] = ((x ^ y) & 1) ? 0 : 255; break;
+                default: L[q] = (uint8_t)((x * 37 + y * 11) ^ (x >> 2)); R[q] = (uint8_t)(((x + 3) * 37 + y * 11) ^ ((x + 3) >> 2)); break;
+                }
+            }
+        for (int i = 0; i < H; i++)
+            for (int x = 0; x < W; x++)
+                for (int d = 0; d < D; d++) {
+                    const int dd = d < x ? d : x;                      // Sad.h:125-129
+                    unsigned acc = 0;
+                    for (int r = 0; r < side; r++)
+                        for (int c = 0; c < side; c++)
+                            acc += (unsigned)abs((int)L[(size_t)(i + r) * Wp + x + c] - (int)R[(size_t)(i + r) * Wp + x + c - dd]);
+                    want[((size_t)i * W + x) * D + d] = acc;
+                }
+        const int bands[3] = {box_band(H, W, side), 1, 3};
+        for (int b = 0; b < 3; b++) {
+            std::fill(got.begin(), got.end(), 0xdeadbeefu);
+            box_host(L.data(), R.data(), H, W, D, w, bands[b], got.data());
+            if (got != want) return SMT_ERR_STATE;
+        }
+    }
+    return SMT_OK;
+}
+
+// Host only (no GPU).  Left costs [W][D] with exact ties, all-equal rows and values at the 2^23 bound: the minimum of
+// (cost << 9) | d over a right pixel's diagonal is GetMinSadIndex (Sad.h:22-38) of its chained row (:167-171).
+SMT_API int smt_sad_selftest_right_keys(int W, int D, int winsize, unsigned seed)
+{
+    if (W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0 || W > (1 << 16)) return SMT_ERR_ARG;
+    host_rng rng(seed);
+    const long long side = 2LL * (winsize + 1) + 1;
+    const unsigned top = (unsigned)(255 * side * side < (1 << 23) - 1 ? 255 * side * side : (1 << 23) - 1);   // largest cost of the window
+    std::vector<unsigned> cl((size_t)W * D);
+    std::vector<float> row(D);
+    const unsigned pal[] = {0u, 0u, 7u, 7u, top, top, top - 1, 1u, 300u, 300u};
+    const int mode = (int)(seed % 3);                          // 0: palette (ties), 1: every cost equal, 2: near the bound
+    for (auto &c : cl) {
+        const uint32_t r = rng.next();
+        c = mode == 1 ? top : mode == 2 ? top - (r % 3) : ((r % 5 == 0) ? (r >> 8) % (top + 1) : pal[(r >> 3) % 10]);
+    }
+    for (int x = 0; x < W; x++) {
+        for (int d = 0; d < D; d++) row[d] = (x + d <= W - 1) ? (float)cl[(size_t)(x + d) * D + d] : row[d - 1];
+        float mn = row[0];
+        int want = 0;
+        for (int d = 1; d < D; d++) if (row[d] < mn) { mn = row[d]; want = d; }
+        unsigned best = NOKEY;
+        for (int d = 0; d < D && x + d <= W - 1; d++) {
+            const unsigned key = (cl[(size_t)(x + d) * D + d] << 9) | (unsigned)d;
+            if (key == NOKEY) return SMT_ERR_STATE;
+            if (key < best) best = key;
+        }
+        if ((int)(best & 511u) != want) return SMT_ERR_STATE;
+    }
+    return SMT_OK;
+}
+
+// ---- smt_sad_flow_*: the lines of SAD/SADmain.cpp with :67-68 enabled, for a batch of gray pairs -------------------
+//   :47-48  copyMakeBorder(img, winsize + 1, BORDER_REPLICATE) of both images      smt_pad_replicate
+//   :66-67  GetPointDepthLeft, GetPointDepthRight                                  smt_sad_both (one pass over the hypotheses)
+//   :68     CrossCheckDiaparity                                                    smt_sad_crosscheck
+// The flow stops there: RemoveSpeckles at :69 reads an int Mat through at<float>, and :71-78 are OpenCV calls and the
+// scan-order fillers.  The handle owns the padded images and one set of maps, so a warm call allocates nothing beyond
+// the scratch arena of smt_sad_both.
+struct smt_sad_flow {
+    int device;
+    int H, W, D;
+    smt_sad_params P;
+    hipStream_t stream;
+    uint8_t *padL, *padR;       // [H + 2 w][W + 2 w]
+    int32_t *mapL, *mapR, *last;   // maps of the current pair where the caller passes no buffer
+    uint8_t *cls;
+};
+
+SMT_API void smt_sad_default_params(smt_sad_params *p)
+{
+    if (!p) return;
+    p->winsize = 3;                                           // SADmain.cpp:34
+}
+
+SMT_API int smt_sad_flow_destroy(smt_sad_flow *h)
+{
+    if (!h) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(h->padL); (void)hipFree(h->padR);
+    (void)hipFree(h->mapL); (void)hipFree(h->mapR); (void)hipFree(h->last); (void)hipFree(h->cls);
+    delete h;
+    return SMT_OK;
+}
+
+SMT_API int smt_sad_flow_create_on(int device, int H, int W, int D, const smt_sad_params *p, smt_sad_flow **out)
+{
+    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;
+    smt_sad_params P;
+    if (p) P = *p; else smt_sad_default_params(&P);
+    if (P.winsize < 0) return SMT_ERR_ARG;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(device);
+    smt_sad_flow *h = new (std::nothrow) smt_sad_flow();
+    if (!h) return SMT_ERR_ALLOC;
+    h->device = smt_current_device();
+    h->H = H; h->W = W; h->D = D; h->P = P;
+    const int w = P.winsize + 1;
+    const size_t np = ((size_t)H + 2 * (size_t)w) * ((size_t)W + 2 * (size_t)w), N = (size_t)H * W;
+    int rc = smt_malloc((void **)&h->padL, np);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->padR, np);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->mapL, N * 4);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->mapR, N * 4);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->last, N * 4);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->cls, N);
+    if (rc != SMT_OK) { smt_sad_flow_destroy(h); return rc; }
+    *out = h;
+    return SMT_OK;
+}
+
+SMT_API int smt_sad_flow_set_stream(smt_sad_flow *h, void *s)
+{
+    if (!h) return SMT_ERR_ARG;
+    h->stream = smt_stream(s);
+    return SMT_OK;
+}
+
+SMT_API int smt_sad_flow_run_batch(smt_sad_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int32_t *dispL,
+                                   int32_t *dispR, int32_t *lastdisp, uint8_t *cls)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!grayL || !grayR) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    const int H = h->H, W = h->W, w = h->P.winsize + 1;
+    const size_t N = (size_t)H * W;
+    void *st = (void *)h->stream;
+    for (int b = 0; b < pairs; b++) {
+        int32_t *dl = dispL ? dispL + b * N : h->mapL, *dr = dispR ? dispR + b * N : h->mapR;
+        int rc = smt_pad_replicate(grayL + b * N, H, W, w, h->padL, st);                              // SADmain.cpp:47
+        if (rc == SMT_OK) rc = smt_pad_replicate(grayR + b * N, H, W, w, h->padR, st);                // :48
+        if (rc == SMT_OK) rc = smt_sad_both(h->padL, h->padR, H, W, h->D, h->P.winsize, dl, dr, nullptr, st);   // :66-67
+        if (rc == SMT_OK && (lastdisp || cls))
+            rc = smt_sad_crosscheck(dl, dr, H, W, lastdisp ? lastdisp + b * N : h->last, cls ? cls + b * N : h->cls, st);   // :68
+        if (rc != SMT_OK) return rc;
+    }
+    return SMT_OK;
+}

@@ -380,6 +380,48 @@ inline void GetPointDepthLeft(int *disparity, const unsigned char *l, const unsi
 inline void GetPointDepthRight(int *disparity, const unsigned char *l, const unsigned char *r, int rows, int cols,
                                int MaxDisparity, int winsize) { GetPointDepth(disparity, l, r, rows, cols, MaxDisparity, winsize, false); }
 
+// SADmain.cpp:66-67 in one call: both maps from one evaluation of the hypotheses (smt_sad_both); padded host images
+inline void GetPointDepthBoth(int *dispLeft, int *dispRight, const unsigned char *leftimg, const unsigned char *rightimg,
+                              int rows, int cols, int MaxDisparity, int winsize)
+{
+    const int w = winsize + 1, H = rows - 2 * w, W = cols - 2 * w;
+    DevBuf<unsigned char> L((size_t)rows * cols), R((size_t)rows * cols);
+    DevBuf<int> dl((size_t)H * W), dr((size_t)H * W);
+    L.upload(leftimg); R.upload(rightimg);
+    check(smt_sad_both(L.get(), R.get(), H, W, MaxDisparity, winsize, dl.get(), dr.get(), nullptr, nullptr), "smt_sad_both");
+    dl.download(dispLeft); dr.download(dispRight);
+}
+
+// SADmain.cpp:47-48, :66-68 for batches of UNPADDED gray pairs (smt_sad_flow_*): host buffers in and out
+class SadFlow {
+public:
+    SadFlow(int rows, int cols, int MaxDisparity, int winsize = 3, int device = 0) : n_((size_t)rows * cols)
+    {
+        smt_sad_params p;
+        smt_sad_default_params(&p);
+        p.winsize = winsize;
+        check(smt_sad_flow_create_on(device, rows, cols, MaxDisparity, &p, &h_), "smt_sad_flow_create_on");
+    }
+    ~SadFlow() { if (h_) smt_sad_flow_destroy(h_); }
+    SadFlow(const SadFlow &) = delete;
+    SadFlow &operator=(const SadFlow &) = delete;
+    // grayL, grayR: uchar [pairs][rows][cols]; depthleft, depthright, lastdisp: int [pairs][rows][cols] (any may be null)
+    void run(const unsigned char *grayL, const unsigned char *grayR, int pairs, int *depthleft, int *depthright, int *lastdisp)
+    {
+        const size_t n = n_ * (size_t)pairs;
+        DevBuf<unsigned char> L(n), R(n), cls(n);
+        DevBuf<int> dl(n), dr(n), last(n);
+        L.upload(grayL); R.upload(grayR);
+        check(smt_sad_flow_run_batch(h_, L.get(), R.get(), pairs, dl.get(), dr.get(), last.get(), cls.get()), "smt_sad_flow_run_batch");
+        if (depthleft) dl.download(depthleft);
+        if (depthright) dr.download(depthright);
+        if (lastdisp) last.download(lastdisp);
+    }
+private:
+    smt_sad_flow *h_ = nullptr;
+    size_t n_;
+};
+
 // NCC_algorithem(leftImage, rigthImage, width, height, disp, winSize, dispRange) (NCC.h:69-95)
 inline void NCC_algorithem(const unsigned char *leftImage, const unsigned char *rigthImage, int width, int height,
                            int *disp, int winSize, int dispRange)

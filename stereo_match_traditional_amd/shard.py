@@ -115,3 +115,17 @@ def asw_batch(L8, R8, D, **params):
     dl, dr, _ = flow.run(L8.contiguous(), R8.contiguous())
     flow.close()
     return dl, dr
+
+
+def sad_batch(L8, R8, D, **params):
+    """`compute` for run_sharded on SADmain.cpp's flow (smt_sad_flow_run_batch) for a [count, H, W] uint8 shard on this
+    rank's GPU -> (left maps, right maps), int32.  Keywords as api.SADFlow."""
+    from .api import SADFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.int32, device=L8.device)
+        return z, z.clone()
+    flow = SADFlow(H, W, D, L8.device, **params)
+    dl, dr, _, _ = flow.run(L8.contiguous(), R8.contiguous())
+    flow.close()
+    return dl, dr
