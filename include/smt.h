@@ -812,7 +812,9 @@ int smt_u8_to_f32(const uint8_t *src, int H, int W, float *dst, void *stream);
 int smt_median_filter(const float *in, float *out, int W, int H, int wnd_size, void *stream);
 /* RemoveSpeckles(disparity_map, width, height, diff_insame, min_speckle_aera, invalid_val)
  * (AD-CensusV1/PostProcessing.h:250-311), in place.  invalid_val is an int as in the reference
- * (its call sites pass +inf: undefined conversion, INT_MIN on x86).  Synchronising. */
+ * (its call sites pass +inf: undefined conversion, INT_MIN on x86 when converted at run time.  A compiler that folds
+ * the constant at the call site need not agree: g++ -O2 does not give INT_MIN for `RemoveSpeckles(..., Invalid_Float)`,
+ * which is why the reference build used by the tests receives invalid_val as an int argument).  Synchronising. */
 int smt_remove_speckles(float *disparity_map, int W, int H, int diff_insame, unsigned min_speckle_area,
                         int invalid_val, void *stream);
 /* Batch forms, asynchronous: `pairs` maps `stride` / `disp_stride` ELEMENTS apart (0 = dense, H*W; otherwise >= H*W),

@@ -13,10 +13,12 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libsmt_oracle.so")
 _REF = os.path.join(_HERE, "_ref", "libcrossagg_ref.so")
+_REF_ADC = os.path.join(_HERE, "_ref", "libadcensus_ref.so")
+_REF_CBLSM = os.path.join(_HERE, "_ref", "libcblsm_ref.so")
 
 
 def build(verbose=False):
-    """Compile the oracle (and oracle/_ref when /root/reference is present)."""
+    """Compile the oracle (and the three reference builds in oracle/_ref when the reference tree is present)."""
     out = subprocess.run(["make", "-C", _HERE], capture_output=True, text=True)
     if out.returncode != 0:
         raise RuntimeError("oracle build failed:\n" + out.stdout + out.stderr)
@@ -232,6 +234,251 @@ def ref_crossagg(bgr, cost_init, L1=34, L2=17, t1=20, t2=6, iters=4):
     rc = r.ref_crossagg(_p(bgr), _p(cost_init), W, H, D, L1, L2, t1, t2, iters, _p(arms), _p(out))
     assert rc == 0
     return arms, out
+
+
+# --------------------------------------------------------------------------- reference builds
+# The REFERENCE's own AD-CensusV1 and CBLSM.h code (oracle/_ref, see oracle/Makefile `ref`).  Each ref_* function
+# has the signature and return shape of the oracle function it shadows, so a test can run either on the same
+# inputs.  The reference leaks its buffers by design; these are for small test cases.
+def have_ref_adcensus():
+    return os.path.exists(_REF_ADC)
+
+
+def have_ref_cblsm():
+    return os.path.exists(_REF_CBLSM)
+
+
+_refs = {}
+
+
+def _ref(path):
+    if path not in _refs:
+        _refs[path] = C.CDLL(path)
+    return _refs[path]
+
+
+def _w(a, dt):
+    """A writable contiguous copy (the reference takes non-const pointers)."""
+    return np.array(a, dt, copy=True, order="C")
+
+
+def ref_adcensus_both(L, R, D, sigmaC, sigmaS):
+    """Initialize + ComputeADcensus + ComputeADcensusRight + WTA -> (volL, volR, dispL, dispR);
+    shadows adcensus_view(view 0), adcensus_view(view 1) and wta of each."""
+    L = _w(L, np.float32)
+    R = _w(R, np.float32)
+    H, W = L.shape
+    vl = np.empty((H, W, D), np.float32)
+    vr = np.empty((H, W, D), np.float32)
+    dl = np.empty((H, W), np.float32)
+    dr = np.empty((H, W), np.float32)
+    rc = _ref(_REF_ADC).ref_adcensus(_p(L), _p(R), H, W, D, C.c_float(sigmaC), C.c_float(sigmaS),
+                                     _p(vl), _p(vr), _p(dl), _p(dr))
+    assert rc == 0
+    return vl, vr, dl, dr
+
+
+def _ref_arms(img, tau, dirs):
+    img = _w(img, np.uint8)
+    if img.ndim == 2:
+        H, W = img.shape
+        ch = 1
+    else:
+        H, W, ch = img.shape
+    if H > W and 1 in dirs:
+        raise ValueError("reference behaviour undefined for this shape (H > W with the _row bug)")
+    maps = np.empty((4, H, W), np.int32)
+    d = np.ascontiguousarray(dirs, np.int32)
+    t = C.c_int()
+    rc = _ref(_REF_ADC).ref_arms(_p(img), H, W, ch, int(tau), _p(d), len(d), _p(maps), C.byref(t))
+    assert rc == 0
+    return maps, t.value
+
+
+def ref_arms_all(img, tau0=30):
+    """The four Compute*ArmLength calls in main.cpp's order; shadows arms_all(chain=True, right_row_bug=True)."""
+    maps, _ = _ref_arms(img, tau0, (0, 1, 2, 3))
+    return [maps[k] for k in range(4)]
+
+
+def ref_arms_dir(img, dirn, tau):
+    """One Compute*ArmLength call after Initialize(tao=tau); shadows arms_dir (zeroed map, right_row_bug=True)."""
+    maps, t = _ref_arms(img, tau, (dirn,))
+    return maps[dirn], t
+
+
+def ref_arms_seq(img, tau0, dirs):
+    """Single calls in the caller's order on one object -> (four maps, threshold afterwards)."""
+    maps, t = _ref_arms(img, tau0, tuple(dirs))
+    return [maps[k] for k in range(4)], t
+
+
+def ref_aggregate_rect(vol, arms, order=0):
+    """AggregationVertical (order 0) / Aggregation (order 2) + CrossArmAggregation::WTA -> (out, disp).  Only for
+    cases where aggregate_rect reports oob == 0: elsewhere the reference reads outside its plane."""
+    assert order in (0, 2)
+    vol = _w(vol, np.float32)
+    H, W, D = vol.shape
+    maps = np.ascontiguousarray(np.stack([_c(a, np.int32).reshape(H, W) for a in arms]))
+    out = np.empty_like(vol)
+    disp = np.empty((H, W), np.float32)
+    rc = _ref(_REF_ADC).ref_aggregate(_p(maps), _p(vol), H, W, D, order, _p(out), _p(disp))
+    assert rc == 0
+    return out, disp
+
+
+def ref_scanline_all(cost, gray, p1=10, p2=150):
+    """ScanLine + WTA -> dict(left, right, up, down, sum, disp); shadows scan_pass x4, scanline and wta."""
+    cost = _w(cost, np.float32)
+    gray = _w(gray, np.float32)
+    H, W, D = cost.shape
+    o = {k: np.empty_like(cost) for k in ("left", "right", "up", "down", "sum")}
+    o["disp"] = np.empty((H, W), np.float32)
+    rc = _ref(_REF_ADC).ref_scanline(_p(cost), _p(gray), H, W, D, int(p1), int(p2), _p(o["left"]), _p(o["right"]),
+                                     _p(o["up"]), _p(o["down"]), _p(o["sum"]), _p(o["disp"]))
+    assert rc == 0
+    return o
+
+
+def _lists_to_cls(H, W, occ, mis):
+    """The reference's two (row, col) lists as the oracle's class map; both must be in row-major order."""
+    cls = np.zeros((H, W), np.uint8)
+    for lst, c in ((occ, 1), (mis, 2)):
+        flat = lst[:, 0].astype(np.int64) * W + lst[:, 1]
+        assert np.all(np.diff(flat) > 0), "reference list not in row-major order"
+        assert np.all(cls.reshape(-1)[flat] == 0)
+        cls.reshape(-1)[flat] = c
+    return cls
+
+
+def ref_lrcheck(dL, dR, gate=2, want_lists=False):
+    """LeftRightConsistency; shadows lrcheck -> (dL afterwards, cls, n_occ, n_mis)."""
+    dL = _w(dL, np.float32)
+    dR = _w(dR, np.float32)
+    H, W = dL.shape
+    occ = np.empty((H * W, 2), np.int32)
+    mis = np.empty((H * W, 2), np.int32)
+    no, nm = C.c_int(), C.c_int()
+    rc = _ref(_REF_ADC).ref_lrcheck(_p(dL), _p(dR), H, W, int(gate), _p(occ), C.byref(no), _p(mis), C.byref(nm))
+    assert rc == 0
+    occ, mis = occ[:no.value].copy(), mis[:nm.value].copy()
+    if want_lists:
+        return dL, occ, mis
+    return dL, _lists_to_cls(H, W, occ, mis), no.value, nm.value
+
+
+def ref_lrcheck_variant(dL, dR, gate):
+    """LeftAndRightConsistency; shadows lrcheck_variant -> (lastDisp, cls, n_occ, n_mis).  lastDisp starts zeroed
+    (main.cpp:37) though every entry is written."""
+    dL = _w(dL, np.float32)
+    dR = _w(dR, np.float32)
+    H, W = dL.shape
+    last = np.zeros((H, W), np.float32)
+    occ = np.empty((H * W, 2), np.int32)
+    mis = np.empty((H * W, 2), np.int32)
+    no, nm = C.c_int(), C.c_int()
+    rc = _ref(_REF_ADC).ref_lrcheck_variant(_p(dL), _p(dR), _p(last), H, W, C.c_float(gate), _p(occ), C.byref(no),
+                                            _p(mis), C.byref(nm))
+    assert rc == 0
+    return last, _lists_to_cls(H, W, occ[:no.value], mis[:nm.value]), no.value, nm.value
+
+
+def ref_fill_the_hole(disp, dispRange, occ, mis):
+    """FillTheHole; shadows fill_the_hole -> (filled map, third-pass list or None).  Only for cases on which
+    fill_the_hole does not raise: elsewhere the reference writes out of bounds."""
+    d = _w(disp, np.float32)
+    row, col = d.shape
+    occ = np.ascontiguousarray(np.asarray(occ, np.int32).reshape(-1, 2))
+    mis = np.ascontiguousarray(np.asarray(mis, np.int32).reshape(-1, 2))
+    after = np.empty((row * col + len(mis), 2), np.int32)
+    na = C.c_int()
+    rc = _ref(_REF_ADC).ref_fill_the_hole(_p(d), row, col, int(dispRange), _p(occ), len(occ), _p(mis), len(mis),
+                                          _p(after), C.byref(na))
+    assert rc == 0
+    # the list is replaced only when the third pass runs, i.e. when the mismatch list was not empty
+    return d, (after[:na.value].copy() if len(mis) else None)
+
+
+def ref_remove_speckles(d, diff, min_area, invalid_val):
+    """RemoveSpeckles with invalid_val as an int argument (never the constant Invalid_Float, see
+    oracle/ref_build/adcensus_ref_wrap.cpp); shadows remove_speckles."""
+    d = _w(d, np.float32)
+    H, W = d.shape
+    rc = _ref(_REF_ADC).ref_remove_speckles(_p(d), W, H, int(diff), C.c_uint(min_area), int(invalid_val))
+    assert rc == 0
+    return d
+
+
+def ref_median(inp, wnd):
+    inp = _c(inp, np.float32)
+    H, W = inp.shape
+    out = np.empty_like(inp)
+    rc = _ref(_REF_ADC).ref_median(_p(inp), _p(out), W, H, int(wnd))
+    assert rc == 0
+    return out
+
+
+def ref_cblsm_arms_dir(img, dirn, tau, sec=17, maxlen=34):
+    """ArmLength{L,R,Up,Down} (dirn 0..3), threshold by value; shadows arms_dir(right_row_bug=False)[0]."""
+    img = _w(img, np.uint8)
+    if img.ndim == 2:
+        H, W = img.shape
+        ch = 1
+    else:
+        H, W, ch = img.shape
+    out = np.zeros((H, W), np.int32)
+    rc = _ref(_REF_CBLSM).ref_cblsm_arm(_p(img), H, W, ch, int(dirn), int(tau), int(maxlen), int(sec), _p(out))
+    assert rc == 0
+    return out
+
+
+def ref_cblsm_ad(L, R, D, view):
+    L = _w(L, np.uint8)
+    R = _w(R, np.uint8)
+    H, W = L.shape
+    out = np.zeros((H, W, D), np.float32)
+    rc = _ref(_REF_CBLSM).ref_cblsm_ad(_p(L), _p(R), H, W, D, int(view), _p(out))
+    assert rc == 0
+    return out
+
+
+def ref_cblsm_aggregate_v5(vol, arms):
+    """costAggregationV5; shadows aggregate_rect(order=1)[0].  Only where that reports oob == 0."""
+    vol = _w(vol, np.float32)
+    H, W, D = vol.shape
+    a = [_w(x, np.int32) for x in arms]
+    out = np.empty_like(vol)
+    rc = _ref(_REF_CBLSM).ref_cblsm_aggregate_v5(_p(vol), _p(out), _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), D, H, W)
+    assert rc == 0
+    return out
+
+
+def ref_cblsm_disp(vol):
+    """ComputeDispOringin; shadows wta."""
+    vol = _w(vol, np.float32)
+    H, W, D = vol.shape
+    disp = np.empty((H, W), np.float32)
+    rc = _ref(_REF_CBLSM).ref_cblsm_disp(_p(vol), _p(disp), D, H, W)
+    assert rc == 0
+    return disp
+
+
+def ref_choose_arm_length(dirn, own, vert, RL, RR, D):
+    """chooseArmLength{Left,Right,Up,Down}; shadows choose_arm_length.  The reference's argument lists carry maps
+    the function never uses for its result (ArmLR in Left, ArmLL in Right, the other vertical pair in Up / Down);
+    `own` / `vert` stand in for those."""
+    own = _w(own, np.int32); RL = _w(RL, np.int32); RR = _w(RR, np.int32)
+    row, col = own.shape
+    vol = np.empty((row, col, D), np.int32)
+    r = _ref(_REF_CBLSM)
+    if dirn in (0, 1):
+        rc = r.ref_cblsm_choose_lr(int(dirn), _p(own), _p(own), _p(RL), _p(RR), int(D), _p(vol), row, col)
+    else:
+        vert = _w(vert, np.int32)
+        rc = r.ref_cblsm_choose_ud(int(dirn), _p(own), _p(own), _p(vert), _p(vert), _p(RL), _p(RR), int(D), _p(vol),
+                                   row, col)
+    assert rc == 0
+    return vol
 
 
 # --------------------------------------------------------------------------- CBLSM

@@ -9,14 +9,22 @@
  * PARITY STATUS
  *   - orc_crossagg_* (CBLSM/cross_aggregator.cpp) is PINNED: it is checked bit-for-bit
  *     against the unmodified reference source compiled into oracle/_ref/ (see
- *     oracle/ref_build/Makefile) and against tests/golden/ fixtures generated from it.
- *   - Everything else here is "PARITY UNPINNED": every other reference header includes
- *     <opencv2/opencv.hpp> (OpenCV 3.1.0, AD-CensusV1/AD-CensusV1.vcxproj:135), which is
- *     not in this image, and the reference ships no tests, golden vectors or sample
- *     outputs.  Those functions are restated loop-for-loop from the reference text
- *     (file:line cited at each function) and cross-checked against an independently
- *     derived closed form (the HIP kernels use precomputed census tables / two-phase
- *     parallel forms, a different formulation of the same semantics).
+ *     oracle/Makefile) and against tests/golden/ fixtures generated from it.
+ *   - The AD-CensusV1 stages (orc_ad_*, orc_census_*, orc_fuse, orc_adcensus_view, orc_wta, orc_arms_*,
+ *     orc_aggregate_rect orders 0 and 2, orc_scan_*, orc_scanline, orc_lrcheck, orc_lrcheck_variant,
+ *     orc_fill_the_hole, orc_remove_speckles, orc_median) and the live CBLSM.h functions (orc_arms_dir without the
+ *     stride bug = ArmLength{L,R,Up,Down}, orc_cblsm_ad, orc_aggregate_rect order 1 = costAggregationV5, orc_wta =
+ *     ComputeDispOringin, orc_choose_arm_length) are PINNED: AD-CensusV1/{AD-Census.h, CrossArm.cpp,
+ *     ScanlineOptimizer.h, PostProcessing.h} and CBLSM/CBLSM.h use cv::Mat only as a pixel container and compile
+ *     unmodified against oracle/ref_build/shim/opencv2/opencv.hpp (container only; every OpenCV operation with
+ *     arithmetic in it aborts) into oracle/_ref/libadcensus_ref.so and libcblsm_ref.so.  tests/test_ref_pin_cpu.py
+ *     checks this file against those builds bit for bit and against tests/golden/ref_pin_hashes.json.
+ *   - Still "PARITY UNPINNED": orc_sad*, orc_ncc, orc_asw*, orc_cblsm_cost_aggregation_new (costAggregationNew /
+ *     ComputeLocalValue) and orc_bgr2gray.  Their results come out of OpenCV's MatExpr, cv::sum, cv::mean and
+ *     cvtColor (OpenCV 3.1.0, AD-CensusV1/AD-CensusV1.vcxproj:135, not in this image), which a container header
+ *     must not imitate, and the reference ships no tests, golden vectors or sample outputs.  Those functions are
+ *     restated loop-for-loop from the reference text (file:line cited at each function) and cross-checked against
+ *     an independently derived closed form (tests/test_cpu_oracle.py).
  *
  * All citations are relative to /root/reference.  Layout conventions follow the
  * reference: images [H][W] row-major, volumes [H][W][D] with d fastest
@@ -937,7 +945,12 @@ ORC_API void orc_median(const float *in, float *out, int W, int H, int wnd)
     free(buf);
 }
 
-/* RemoveSpeckles                                          PostProcessing.h:250-311 */
+/* RemoveSpeckles                                          PostProcessing.h:250-311
+ * PINNED against oracle/_ref (ref_remove_speckles).  invalid_val is an int here as in the reference's signature.
+ * The call site's argument `Invalid_Float` (+inf, main.cpp:93) converts to int at run time on x86 as INT_MIN
+ * (cvttss2si), the value documented in include/smt.h -- but g++ folds `int(+inf)` at COMPILE time when the constant
+ * is written at the call, and does not fold it to INT_MIN.  The reference wrapper therefore takes invalid_val as an
+ * int argument and never passes Invalid_Float. */
 ORC_API void orc_remove_speckles(float *d, int W, int H, int diff, unsigned min_area, int invalid_val)
 {
     size_t n = (size_t)W * H;
@@ -1106,7 +1119,9 @@ ORC_API void orc_choose_arm_length(int dir, const int *own, const int *vert, con
  * L+R pixels (:1021, :1034 -- "a small error", says the author) and R+1 for a left-clipped row (:1011).
  * Rows or columns that would leave the padded image (impossible with arm volumes from
  * chooseArmLength*) are skipped.  The `#pragma omp parallel for` on the row loop (:982) races on
- * count / value; sequential semantics are the specification. */
+ * count / value; sequential semantics are the specification.
+ * PARITY UNPINNED: both functions take their pixels through ROI by Range and cv::sum, which the container-only
+ * header of the reference builds (oracle/ref_build/shim/opencv2/opencv.hpp) declares but does not imitate. */
 static float orc_cblsm_local_value(const uint8_t *img, int Hp, int Wp, int i, int j, int Up, int Down, int w,
                                    const int *LArm, const int *RArm, int H, int W, int D, int d)
 {

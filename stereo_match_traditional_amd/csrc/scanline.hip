@@ -176,10 +176,19 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
         st_row<C, FULL>(op + start * D, dl, D, res);
         if (WTA) wta_store(res, start);
     }
-    // minLastPath = min over the padded vector (:162-166); pads are 65535
+    // minLastPath = min(cost, minLastPath) over the padded vector, in order (:162-166); pads are 65535.
+    // std::min(a, b) is `b < a ? b : a`: a NaN cost becomes the running minimum and the next entry replaces it,
+    // so the result is the minimum of the entries AFTER the last NaN, the trailing pad included.  (The step's own
+    // `min(minCost, cost_s)` has the arguments the other way round and skips NaNs, :182.)
+    float nan_at = -1.0f;                              // this lane's last NaN entry, exact as a float (D <= 512)
+#pragma unroll
+    for (int k = 0; k < C; k++)
+        if ((FULL || dl + k < D) && last[k] != last[k]) nan_at = (float)(dl + k);
+    const float last_nan = -wave_min_f32_dpp(-nan_at);
     float lm = PAD;
 #pragma unroll
-    for (int k = 0; k < C; k++) lm = ref_min(last[k], lm);
+    for (int k = 0; k < C; k++)
+        if ((float)(dl + k) > last_nan) lm = ref_min(last[k], lm);
     float minLast = wave_min_f32_dpp(lm);
     float lastgray = gp[0];
 

@@ -6,8 +6,8 @@ results of the HIP path and compare (tests/test_config_hashes_gpu.py), so that t
 passes, the right-view aggregation and the LR check are compared at 1920x1080x192 and not only
 property-checked.
 
-The oracle is PARITY UNPINNED for these stages (no reference build without OpenCV, no reference
-fixtures); these hashes pin the HIP path to the oracle, not the oracle to the reference.
+These hashes pin the HIP path to the oracle at full size, not the oracle to the reference: that is done at small
+sizes by tests/test_ref_pin_cpu.py against the reference's own compiled AD-CensusV1 code.
 
 Run:  SMT_ORACLE_OMP=1 python tests/golden/make_config_hashes.py [cfg2] [cfg3] [cfg5] [a18] [--pairs N]
 (OpenMP build of the same oracle file: planes / rows / lines are independent, results identical.)

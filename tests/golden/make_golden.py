@@ -10,6 +10,12 @@ crossagg_ref_hashes.json records FNV-1a hashes (orc_fnv1a) of the reference buil
 outputs on the cases of tests/test_cpu_oracle.py::test_crossagg_oracle_vs_reference_build, so that the
 oracle stays pinned to the reference where oracle/_ref cannot be built.
 `python tests/golden/make_golden.py ref-hashes` writes only that file.
+
+ref_pin_hashes.json does the same for the reference's own AD-CensusV1 and CBLSM.h code (oracle/_ref/libadcensus_ref.so,
+libcblsm_ref.so) on the cases of tests/golden/ref_pin_cases.py: per case its parameters, the hashes of its inputs and
+the hashes of every output of the reference builds (NaN canonicalised, see ref_pin_cases.canon).  Hashes only, no
+arrays.  `python tests/golden/make_golden.py ref-pin` writes only that file; `ref-pin-dump DIR` writes the admitted
+cases' inputs for the sanitizer run of the reference builds (`make -C oracle ref-asan`).
 """
 import json
 import os
@@ -70,8 +76,72 @@ def ref_hashes():
     print("crossagg_ref_hashes.json written")
 
 
+def _ref_pin_cases():
+    sys.path.insert(0, HERE)
+    import ref_pin_cases as RP
+    return RP
+
+
+def ref_pin():
+    RP = _ref_pin_cases()
+    O.build()
+    assert O.have_ref_adcensus() and O.have_ref_cblsm(), "oracle/_ref missing: make -C oracle ref REF=<reference tree>"
+    recs = []
+    for case in RP.CASES:
+        inp = RP.inputs(case, O)
+        assert RP.admitted(case, inp, O), "%s: the reference is undefined on this case; take it off the list" % case["name"]
+        out = RP.run(case, inp, O, "ref")
+        recs.append({"case": {k: (list(v) if isinstance(v, tuple) else v) for k, v in case.items()},
+                     "inputs": RP.hashes(inp, O), "outputs": RP.hashes(out, O)})
+    with open(os.path.join(HERE, "ref_pin_hashes.json"), "w") as f:
+        json.dump({"produced_by": "reference builds (oracle/_ref/libadcensus_ref.so, libcblsm_ref.so); orc_fnv1a, "
+                                  "NaN hashed as 0x7fc00000", "cases": recs}, f, indent=1)
+        f.write("\n")
+    print("ref_pin_hashes.json written (%d cases)" % len(recs))
+
+
+def ref_pin_dump(out_dir):
+    """Inputs of every admitted case as raw files + a manifest for oracle/ref_build/ref_asan_main.cpp:
+    one line per case, `kind name p0..p7 file...`; arrays little-endian, C order."""
+    RP = _ref_pin_cases()
+    O.build()
+    os.makedirs(out_dir, exist_ok=True)
+    lines = []
+    for case in RP.CASES:
+        inp = RP.inputs(case, O)
+        if not RP.admitted(case, inp, O):
+            continue
+        k = case["kind"]
+        g = lambda n: int(case.get(n, 0))
+        prm = {"adcensus": [g("H"), g("W"), g("D")],
+               "arms": [g("H"), g("W"), g("ch"), g("tau"), len(case.get("dirs", ()))] + list(case.get("dirs", ())),
+               "agg": [g("H"), g("W"), g("D"), g("order")],
+               "scan": [g("H"), g("W"), g("D"), g("p1"), g("p2")],
+               "lrcheck": [g("H"), g("W"), g("gate")], "lrvariant": [g("H"), g("W"), g("gate")],
+               "fill": [g("row"), g("col"), g("D"), len(inp.get("occ", ())), len(inp.get("mis", ()))],
+               "speckle": [g("H"), g("W"), g("diff"), g("area"), g("inv")],
+               "median": [g("H"), g("W"), g("wnd")],
+               "cblsm_arms": [g("H"), g("W"), g("ch"), g("tau")],
+               "cblsm_ad": [g("H"), g("W"), g("D")], "cblsm_disp": [g("H"), g("W"), g("D")],
+               "choose": [g("H"), g("W"), g("D")]}[k]
+        prm = (prm + [0] * 9)[:9]
+        files = []
+        for name, a in inp.items():
+            fn = "%s.%s.bin" % (case["name"], name)
+            np.ascontiguousarray(a).tofile(os.path.join(out_dir, fn))
+            files.append(fn)
+        lines.append(" ".join([k, case["name"]] + [str(v) for v in prm] + [str(len(files))] + files))
+    with open(os.path.join(out_dir, "manifest.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("%d cases dumped to %s" % (len(lines), out_dir))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["ref-hashes"]:
         ref_hashes()
+    elif sys.argv[1:] == ["ref-pin"]:
+        ref_pin()
+    elif sys.argv[1:2] == ["ref-pin-dump"] and len(sys.argv) == 3:
+        ref_pin_dump(sys.argv[2])
     else:
         main()

@@ -1,7 +1,8 @@
 """AD-Census cost volume + WTA: HIP path (through the C ABI) vs the CPU oracle, bit-exact.
 
-Oracle functions follow AD-CensusV1/AD-Census.h:75-380 loop for loop ("parity unpinned":
-the reference itself needs OpenCV and ships no fixtures -- see oracle/smt_oracle.c header).
+Oracle functions follow AD-CensusV1/AD-Census.h:75-380 loop for loop and are pinned to that header's own compiled
+code by tests/test_ref_pin_cpu.py (see oracle/smt_oracle.c header); tests/test_ref_pin_gpu.py compares the HIP path
+with the same build's hashes directly.
 """
 import numpy as np
 import pytest

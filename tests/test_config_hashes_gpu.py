@@ -5,8 +5,8 @@ SURVEY 8(d) synthetic pairs.  This is where the up/down scanline passes (Scanlin
 their three quirks), the ((left+right)+up)+down sum (:124), the right-view aggregation (stride-bug arms,
 CrossArm.cpp:60-102, :265) and the LR check (PostProcessing.h:72-135) are compared at 1920x1080x192.
 
-Oracle status for these stages: parity unpinned (oracle/smt_oracle.c header) -- the fixtures pin the HIP
-path to the oracle."""
+The fixtures pin the HIP path to the oracle at full size; the oracle is pinned to the reference's own compiled code
+at small sizes (oracle/smt_oracle.c header, tests/test_ref_pin_cpu.py)."""
 import json
 import os
 

@@ -1,6 +1,6 @@
 """FillTheHole (PostProcessing.h:156-248) on the GPU against the oracle: bit-exact maps and the
-replaced mismatch list.  Parity unpinned (no reference build without OpenCV); the oracle itself is
-cross-checked by an independent restatement in tests/test_cpu_oracle.py."""
+replaced mismatch list.  The oracle is pinned to PostProcessing.h's own compiled code by tests/test_ref_pin_cpu.py
+and cross-checked by an independent restatement in tests/test_cpu_oracle.py."""
 import numpy as np
 import pytest
 import torch

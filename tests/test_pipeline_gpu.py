@@ -1,7 +1,8 @@
 """CrossArm arms + aggregation, ScanlineOptimizer, LeftRightConsistency, CBLSM variants:
 HIP path (through the C ABI) vs the CPU oracle, bit-exact.  Oracle = loop-for-loop
 restatement of AD-CensusV1/{CrossArm.cpp,ScanlineOptimizer.h,PostProcessing.h} and
-CBLSM/CBLSM.h ("parity unpinned", see oracle/smt_oracle.c)."""
+CBLSM/CBLSM.h, pinned to those sources' own compiled code by tests/test_ref_pin_cpu.py except for costAggregationNew
+(still "parity unpinned", see oracle/smt_oracle.c)."""
 import numpy as np
 import pytest
 import torch
