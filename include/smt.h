@@ -543,6 +543,33 @@ int smt_fill_the_hole(float *disp, int row, int col, int dispRange, const int *o
                       int n_occ, const int *mismatch_pairs, int n_mis, int *third_pairs,
                       int *n_third, void *stream);
 
+/* FillTheHole for `pairs` maps with the lists LeftRightConsistency would have produced, taken from the
+ * class maps on the device: exactly smt_fill_the_hole(disp_b, row, col, dispRange, occ, n_occ, mis, n_mis)
+ * with (occ, mis) = smt_lrcheck_lists(cls_b).  Asynchronous: one memset and eight kernel launches on `stream`
+ * whatever the data and the pair count, no host synchronisation, scratch (4 * pairs * row * col bytes and a few
+ * words per pair) from the library's arena.
+ *   disp    float32 [pairs][row][col], filled in place;  cls uint8 as smt_lrcheck writes it (values other than 1 and
+ *           2 are not targets);  strides in ELEMENTS between consecutive maps, 0 = dense, otherwise >= row*col
+ *   status  device int32 [pairs][4], may be NULL: {n_occ, n_mis, n_third, flags}.  n_third is the number of entries
+ *           equal to 65535 after pass 1, -1 when pass 2 was not reached (empty mismatch list, :174, or
+ *           SMT_FILL_UB_LIST).  flags: SMT_FILL_UB_LIST -- a class pixel (i, j) with i*row + j >= row*col, an
+ *           out-of-bounds write in the reference (:244; needs row > col): that pair is not modified;
+ *           SMT_FILL_UB_THIRD -- more holes than mismatches (`fill_disps`, :178 against :189): passes 0 and 1 are
+ *           applied, pass 2 is not.  The other pairs of the batch are unaffected.
+ * The third pass's pixel list is not returned, its count is; a caller who needs the list keeps smt_fill_the_hole,
+ * which also takes lists that no class map expresses (duplicates, any order).
+ * SMT_ERR_ARG for NULL disp or cls, non-positive sizes, dispRange < 0, pairs < 0, row*col >= 2^31 and strides below
+ * row*col; pairs == 0 is a no-op. */
+#define SMT_FILL_UB_LIST 1
+#define SMT_FILL_UB_THIRD 2
+int smt_fill_the_hole_batch(float *disp, const uint8_t *cls, int pairs, size_t disp_stride, size_t cls_stride,
+                            int row, int col, int dispRange, int *status, void *stream);
+/* Test hook, host only (no GPU): the same rule on HOST memory through the same inline functions (csrc/fill_rules.h:
+ * target derivation, set choice, winner gather, pass-2 gating, flags), which is what holds the rule to the oracle
+ * where there is no device.  Arguments and return values as smt_fill_the_hole_batch. */
+int smt_fill_the_hole_batch_host(float *disp, const uint8_t *cls, int pairs, size_t disp_stride, size_t cls_stride,
+                                 int row, int col, int dispRange, int *status);
+
 /* =====================================================================================
  * CrossAggregator (vendored ethan-li AD-Census)   replaces class CrossAggregator
  *                                     (CBLSM/cross_aggregator.{h,cpp})

@@ -14,6 +14,7 @@ SMT_ERR_ARG = -1
 SMT_ERR_DOMAIN = -4
 SMT_ERR_REF_UB = -5
 VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH = 1, 2, 3
+SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD = 1, 2          # flags of smt_fill_the_hole_batch's status
 QUIRK_FIX_RIGHT_ARM_STRIDE = 0x1
 SAD_FORM_COMPOSED, SAD_FORM_BOX_KEYS, SAD_FORM_BOX_VOLUME = 1, 2, 3
 

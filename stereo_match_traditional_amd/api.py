@@ -9,9 +9,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import check, lib, VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH
+from ._lib import check, lib, VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH, SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD  # noqa: F401
 
-__all__ = ["FillTheHole", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
+__all__ = ["FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
@@ -559,6 +559,37 @@ def FillTheHole(row, col, dispRange, dispLeft, occlusion, mismatch):
                                   third.ctypes.data_as(C.c_void_p), C.byref(nt), current_stream_ptr()),
           "smt_fill_the_hole")
     return third[:nt.value].copy() if nt.value >= 0 else mis
+
+
+@_on_tensor_device
+def FillTheHoleBatch(maps, cls, dispRange, check=False):
+    """FillTheHole (PostProcessing.h:156-248) on every map of [pairs][row][col] float32, in place, with the lists
+    LeftRightConsistency would have produced taken from cls (uint8, same shape, as smt_lrcheck writes it) on the
+    device: FillTheHole(row, col, dispRange, maps[b], *lists of cls[b]) for every b.  Asynchronous (enqueued on the
+    current stream, nothing waits).  Returns the [pairs, 4] int32 status tensor {n_occ, n_mis, n_third, flags}; pairs
+    on which the reference writes out of bounds are flagged (SMT_FILL_UB_LIST: untouched; SMT_FILL_UB_THIRD: passes 0
+    and 1 only).  check=True synchronises and raises SmtError(SMT_ERR_REF_UB) naming the first flagged pair."""
+    P, row, col, stride = _map_batch(maps, "maps")
+    if not isinstance(cls, torch.Tensor) or not cls.is_cuda or cls.dtype != torch.uint8 or cls.device != maps.device:
+        raise TypeError("cls must be a uint8 [pairs][row][col] tensor on the maps' GPU")
+    if tuple(cls.shape) != (P, row, col):
+        raise ValueError(f"cls has shape {tuple(cls.shape)}, expected {(P, row, col)}")
+    if cls.stride(2) != 1 or (row > 1 and cls.stride(1) != col) or (P > 1 and cls.stride(0) < row * col):
+        raise TypeError(f"cls: every map must be dense and the maps must not overlap (strides {cls.stride()})")
+    cstride = cls.stride(0) if P > 1 else row * col
+    status = torch.empty((P, 4), dtype=torch.int32, device=maps.device)
+    if P == 0:
+        return status
+    _lib.check(lib().smt_fill_the_hole_batch(_ptr(maps), _ptr(cls), P, C.c_size_t(stride), C.c_size_t(cstride), row,
+                                             col, int(dispRange), _ptr(status), current_stream_ptr()),
+               "smt_fill_the_hole_batch")
+    if check:
+        flags = status[:, 3].cpu().tolist()
+        for b, f in enumerate(flags):
+            if f:
+                raise _lib.SmtError(_lib.SMT_ERR_REF_UB, "smt_fill_the_hole_batch: pair %d, %s" % (
+                    b, "list entry outside the buffer" if f & SMT_FILL_UB_LIST else "more holes than mismatches"))
+    return status
 
 
 # ======================================================================================

@@ -20,6 +20,7 @@
 // angles come from the host libm (sinf/cosf: `sin(float)` is the float overload in C++), like the
 // AD-Census LUTs.
 #include "smt_common.h"
+#include "fill_rules.h"
 #include <cmath>
 #include <climits>
 #include <cstring>
@@ -28,60 +29,7 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr float HOLE = 65535.0f;                      // 0xffff, :182, :212
-
-struct FillCfg {
-    int width, height, maxlen;
-    float sn[2][8], cs[2][8];
-};
-
-__device__ __forceinline__ long lround_f(float v)     // lround(float): half away from zero
-{
-    const double d = (double)v;                        // d +- 0.5 is exact in double
-    return (long)(d + (d >= 0.0 ? 0.5 : -0.5));
-}
-
-// first entry != 65535 along ray s of set `set` from (y, x); false if the ray leaves the buffer first
-__device__ __forceinline__ bool ray(const float *__restrict__ disp, const FillCfg &c, int y, int x, int set, int s,
-                                    float &val)
-{
-    const float sina = c.sn[set][s], cosa = c.cs[set][s];
-    for (int m = 1; m < c.maxlen; m++) {
-        const long yy = lround_f((float)y + (float)m * sina);
-        const long xx = lround_f((float)x + (float)m * cosa);
-        if (yy < 0 || yy >= c.height || xx < 0 || xx >= c.width) return false;
-        const float d = disp[yy * c.width + xx];
-        if (d != HOLE) { val = d; return true; }
-    }
-    return false;
-}
-
-// the 8 lanes of a group hold (found, val); returns the reference's pick: element `1 (or 0)` of
-// the sorted finds for kind 0, element ng/2 for kind 1; 0.0f when nothing was found (:177, :218)
-__device__ __forceinline__ float pick(bool found, float val, int s, int kind)
-{
-    int rank = 0, ng = 0;
-    float vals[8];
-    bool fs[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        vals[j] = __shfl(val, j, 8);
-        fs[j] = __shfl((int)found, j, 8) != 0;
-        if (fs[j]) {
-            ng++;
-            if (vals[j] < val || (vals[j] == val && j < s)) rank++;
-        }
-    }
-    const int want = (kind == 0) ? (ng > 1 ? 1 : 0) : ng / 2;
-    // exactly one finding lane has rank == want; everyone learns its value
-    float out = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const int rj = __shfl(rank, j, 8);
-        if (fs[j] && rj == want) out = vals[j];
-    }
-    return ng == 0 ? 0.0f : out;
-}
+using namespace fillrule;                             // lround_f, ray, pick: csrc/fill_rules.h
 
 __global__ void __launch_bounds__(NT) k_fill_collect(const float *__restrict__ disp, FillCfg c,
                                                      const int *__restrict__ pairs, int n, int switch_from, int kind,
@@ -94,7 +42,7 @@ __global__ void __launch_bounds__(NT) k_fill_collect(const float *__restrict__ d
     const int y = pairs[2 * tt], x = pairs[2 * tt + 1];
     float val = 0.0f;
     const bool found = live && ray(disp, c, y, x, t >= switch_from ? 1 : 0, s, val);
-    const float v = pick(found, val, s, kind);
+    const float v = pick_group(found, val, kind);
     if (live && s == 0) {
         fill[t] = v;
         atomicMax(&winner[(long)y * c.width + x], t);
@@ -149,7 +97,7 @@ __global__ void __launch_bounds__(NT) k_fill_holes(const float *__restrict__ dis
     const int set = (switched || (midline && y >= c.height / 2)) ? 1 : 0;
     float val = 0.0f;
     const bool found = hole && ray(disp, c, y, x, set, s, val);
-    const float v = pick(found, val, s, 1);
+    const float v = pick_group(found, val, 1);
     if (live && s == 0) out[p] = hole ? v : d0;
 }
 
@@ -169,15 +117,7 @@ SMT_API int smt_fill_the_hole(float *disp, int row, int col, int dispRange, cons
         return SMT_ERR_ARG;
     hipStream_t st = smt_stream(stream);
     FillCfg c;
-    c.width = row; c.height = col;                                           // :158-159
-    c.maxlen = (int)(1.0 * dispRange);                                       // :168
-    const float pi = 3.1415926f;
-    const float angle1[8] = {pi, 3 * pi / 4, pi / 2, pi / 4, 0, 7 * pi / 4, 3 * pi / 2, 5 * pi / 4};
-    const float angle2[8] = {pi, 5 * pi / 4, 3 * pi / 2, 7 * pi / 4, 0, pi / 4, pi / 2, 3 * pi / 4};
-    for (int s = 0; s < 8; s++) {
-        c.sn[0][s] = sinf(angle1[s]); c.cs[0][s] = cosf(angle1[s]);
-        c.sn[1][s] = sinf(angle2[s]); c.cs[1][s] = cosf(angle2[s]);
-    }
+    cfg_init(c, row, col, dispRange);
     const long n = (long)row * col;
     if (n_third) *n_third = -1;
     // a listed pair outside the buffer is an out-of-bounds write in the reference (:244)

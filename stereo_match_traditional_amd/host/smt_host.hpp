@@ -12,6 +12,7 @@
 //   - Errors: the reference returns void and has UB on bad input; these methods throw
 //     std::runtime_error carrying smt_strerror().
 #pragma once
+#include <array>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -281,6 +282,26 @@ inline void FillTheHole(const int row, const int col, const int dispRange, float
         mismatch.clear();
         for (int k = 0; k < nt; k++) mismatch.emplace_back(third[2 * k], third[2 * k + 1]);
     }
+}
+
+// FillTheHole on `pairs` host maps [pairs][row][col] with the lists LeftRightConsistency would have produced taken
+// from the class maps (uint8, as smt_lrcheck writes them) on the device: one upload, smt_fill_the_hole_batch, one
+// download.  status[b] = {n_occ, n_mis, n_third, flags} (SMT_FILL_UB_LIST / SMT_FILL_UB_THIRD: smt.h).
+inline void FillTheHoleBatch(int pairs, int row, int col, int dispRange, float *disp, const uint8_t *cls,
+                             std::vector<std::array<int, 4>> &status)
+{
+    status.assign(pairs > 0 ? (size_t)pairs : 0, std::array<int, 4>{{0, 0, -1, 0}});
+    if (pairs <= 0) { check(pairs < 0 ? SMT_ERR_ARG : SMT_OK, "smt_fill_the_hole_batch"); return; }
+    const size_t n = (size_t)pairs * row * col;
+    DevBuf<float> d(n);
+    DevBuf<uint8_t> c(n);
+    DevBuf<int> st((size_t)pairs * 4);
+    d.upload(disp);
+    check(smt_memcpy_h2d(c.get(), cls, n, nullptr), "h2d");
+    check(smt_fill_the_hole_batch(d.get(), c.get(), pairs, 0, 0, row, col, dispRange, st.get(), nullptr),
+          "smt_fill_the_hole_batch");
+    d.download(disp);
+    st.download(&status[0][0]);
 }
 
 // ------------------------------------------------------------------ CBLSM.h:65-236
