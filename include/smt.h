@@ -621,8 +621,56 @@ void smt_adcensus_option_default(smt_adcensus_option *o);
 int smt_adcensus_option_aggregate(const smt_adcensus_option *o, const uint8_t *bytes_left, const float *cost_init,
                                   int W, int H, int num_iters, float *cost_out, float *disp, void *stream);
 
+/* ---- the same caller shape (CBLSM.cpp:133-143, 152) as a batched, device-resident flow: images in, maps out ---- */
+typedef struct smt_crossagg_flow smt_crossagg_flow;
+typedef struct smt_crossagg_flow_params {
+    int L1, L2, t1, t2;   /* 34, 17, 20, 6   adcensus_types.h:69-70 */
+    int num_iters;        /* 4               CBLSM.cpp:142 */
+    int gate;             /* 5               CBLSM.cpp:155 */
+} smt_crossagg_flow_params;
+void smt_crossagg_flow_default_params(smt_crossagg_flow_params *p);
+/* Owns one aggregated volume per view and one intermediate both views share: three float32 [H][W][D] volumes whatever
+ * the batch size, plus arms, support counts and a gray pair.  p == NULL: the defaults.  SMT_ERR_ARG for NULL out,
+ * non-positive sizes, D outside 1..SMT_MAX_DISPARITY, L1 outside 0..255 (arms are uint8), num_iters < 0 and a device
+ * that does not exist. */
+int smt_crossagg_flow_create_on(int device, int H, int W, int D, const smt_crossagg_flow_params *p, smt_crossagg_flow **out);
+int smt_crossagg_flow_destroy(smt_crossagg_flow *h);
+int smt_crossagg_flow_set_stream(smt_crossagg_flow *h, void *stream);
+/* Per pair, in CBLSM.cpp's order:
+ *   bgrL, bgrR     uint8 [pairs][H][W][3], the bytes of :72-87
+ *   grayL, grayR   uint8 [pairs][H][W], the images after cvtColor (:21-22); both may be NULL together, the flow then
+ *                  derives them with smt_bgr2gray's rule into buffers the handle owns
+ *   views          SMT_VIEW_LEFT: ComputeAD (CBLSM.h:327-353; the chain for j - d < 0 is the right index max(j - d, 0)),
+ *                  CrossAggregator::Aggregate(num_iters) with arms from bgrL, ComputeDispOringin -> dispL.
+ *                  SMT_VIEW_RIGHT: ComputeADRight (:355-381, left index min(j + d, W - 1)), arms from bgrR, the same WTA
+ *                  -> dispR.  The reference's commented lines run the left view only: the right view is this flow's own
+ *                  composition of separately pinned stages, as CBLSM.cpp:146 is for the CBLSM flow.
+ *   dispL, dispR   float32 [pairs][H][W], integer-valued; the map of a view that was not requested is not touched
+ *   cls            non-NULL (both views only, else SMT_ERR_ARG): LeftRightConsistency(gate) (CBLSM.cpp:160) runs in
+ *                  place on dispL through smt_lrcheck; cls uint8 [pairs][H][W], counts int32 [pairs][2] (may be NULL)
+ * With num_iters >= 1 the first horizontal pass comes straight from the gray rows in integer arithmetic (the AD volume
+ * never exists; exact, csrc/crossagg_first.h), the WTA sits in the last dividing pass, and that pass stores its volume
+ * for the last pair only.  num_iters == 0 runs smt_cblsm_ad + smt_wta (the reference's result is the AD volume).
+ * Asynchronous on the handle's stream only; one caller thread per handle; a warm call allocates nothing; pairs == 0 is a
+ * no-op.  SMT_ERR_ARG for NULL handle or images, pairs < 0, views outside 1..3, a NULL map for a requested view and
+ * exactly one gray pointer NULL. */
+int smt_crossagg_flow_run_batch(smt_crossagg_flow *h, const uint8_t *bgrL, const uint8_t *bgrR,
+                                const uint8_t *grayL, const uint8_t *grayR, int pairs, int views,
+                                float *dispL, float *dispR, uint8_t *cls, int *counts);
+/* the last pair's aggregated volumes (get_cost_ptr of each view), float32 [H][W][D], borrowed; a view that the last
+ * call did not request keeps what it held */
+int smt_crossagg_flow_volumes(smt_crossagg_flow *h, float **aggL, float **aggR);
+/* Test and timing hook, per handle: 0 = fused kernels (default), 1 = the composed path inside the flow (smt_cblsm_ad,
+ * smt_crossagg_aggregate's passes and smt_wta for every pair).  Identical bits. */
+int smt_crossagg_flow_set_impl(smt_crossagg_flow *h, int impl);
+/* Test hook, host only (no GPU): the integer form of the fused first pass, through the inline arithmetic the kernel
+ * runs (csrc/crossagg_first.h), against sequential float sums over the chained ComputeAD / ComputeADRight volumes, both
+ * views, random arms up to max_arm clipped to the row; fill 0 random bytes, 1 left all 255 and right all 0.  SMT_OK or
+ * SMT_ERR_STATE; SMT_ERR_ARG for non-positive sizes, max_arm outside 0..255 and more than 2^24 hypotheses. */
+int smt_crossagg_selftest_first_pass(int H, int W, int D, int max_arm, int fill, unsigned seed);
+
 /* =====================================================================================
- * Window matchers                     replace SAD/Sad.h, NCC/NCC.h, ASW/ASW.h
+ * Window matchers                    replace SAD/Sad.h, NCC/NCC.h, ASW/ASW.h
  * 1 <= D <= SMT_MAX_DISPARITY on every entry point below (batch variants included); SMT_ERR_ARG beyond.
  * ===================================================================================== */
 /* GetPointDepthLeft (Sad.h:96-139, view SMT_VIEW_LEFT, WTA = OptimalDisparity :40-85) /

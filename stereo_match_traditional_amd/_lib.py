@@ -40,6 +40,13 @@ class CBLSMParams(C.Structure):
     _fields_ = [("tau", C.c_int), ("sec_length", C.c_int), ("max_length", C.c_int)]
 
 
+class CrossAggFlowParams(C.Structure):
+    """smt_crossagg_flow_params: adcensus_types.h:69-70's cross_L1, cross_L2, cross_t1, cross_t2, CBLSM.cpp:142's iteration
+    count and :155's gate."""
+    _fields_ = [("L1", C.c_int), ("L2", C.c_int), ("t1", C.c_int), ("t2", C.c_int), ("num_iters", C.c_int),
+                ("gate", C.c_int)]
+
+
 class ASWParams(C.Structure):
     """smt_asw_params: ASWeight.cpp:43-47's winSize, T, sigma_space, sigma_color."""
     _fields_ = [("winSize", C.c_int), ("T", C.c_int), ("sigma_space", C.c_double), ("sigma_color", C.c_double)]

@@ -17,7 +17,8 @@ __all__ = ["FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmL
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
            "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info",
            "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow",
-           "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow"]
+           "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow",
+           "CrossAggFlow"]
 
 
 def current_stream_ptr(device=None):
@@ -1155,6 +1156,87 @@ class CBLSMFlow:
     def close(self):
         if getattr(self, "_h", None) is not None:
             lib().smt_cblsm_flow_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CrossAggFlow:
+    """CBLSM.cpp:133-143, 152 for batches of colour pairs: ComputeAD / ComputeADRight, CrossAggregator::Aggregate on the
+    view's own colour image, ComputeDispOringin, and on request LeftRightConsistency (:160).  Keywords override
+    smt_crossagg_flow_default_params: L1, L2, t1, t2, num_iters, gate.  The sharding unit of shard.crossagg_batch."""
+
+    def __init__(self, row, col, dispRange, device=None, **params):
+        self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        p = _lib.CrossAggFlowParams()
+        lib().smt_crossagg_flow_default_params(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        h = C.c_void_p()
+        check(lib().smt_crossagg_flow_create_on(_dev_index(self.device), self.row, self.col, self.dispRange, C.byref(p),
+                                                C.byref(h)), "smt_crossagg_flow_create_on")
+        self._h = h
+
+    def run(self, bgrL, bgrR, grayL=None, grayR=None, views=VIEW_BOTH, lr_check=False, dispL=None, dispR=None):
+        """uint8 [pairs][row][col][3] (or [row][col][3]) BGR, optionally the gray pair uint8 [pairs][row][col] (derived
+        with cvtColor_BGR2GRAY's rule when omitted) -> (dispL, dispR), float32 [pairs][row][col]; with lr_check (both
+        views) -> (dispL after LeftRightConsistency, dispR, cls, counts[pairs][2]).  The map of a view that `views`
+        leaves out is None, or the caller's dispL / dispR untouched.  On torch's current stream of the handle's device;
+        nothing synchronises."""
+        if bgrL.dim() == 3:
+            bgrL, bgrR = bgrL[None], bgrR[None]
+            if grayL is not None:
+                grayL = grayL[None]
+            if grayR is not None:
+                grayR = grayR[None]
+        P = bgrL.shape[0]
+        if _dev_index(bgrL.device) != _dev_index(self.device) or bgrR.device != bgrL.device:
+            raise ValueError(f"CrossAggFlow handle lives on {self.device}, images on {bgrL.device} / {bgrR.device}")
+        _dev(bgrL, torch.uint8, (P, self.row, self.col, 3), "bgrL")
+        _dev(bgrR, torch.uint8, (P, self.row, self.col, 3), "bgrR")
+        for g, name in ((grayL, "grayL"), (grayR, "grayR")):
+            if g is not None:
+                _dev(g, torch.uint8, (P, self.row, self.col), name)
+        shp = (P, self.row, self.col)
+        if dispL is None and views & VIEW_LEFT:
+            dispL = torch.empty(shp, dtype=torch.float32, device=bgrL.device)
+        if dispR is None and views & VIEW_RIGHT:
+            dispR = torch.empty(shp, dtype=torch.float32, device=bgrL.device)
+        for d, name in ((dispL, "dispL"), (dispR, "dispR")):
+            if d is not None:
+                _dev(d, torch.float32, shp, name)
+        cls = torch.empty(shp, dtype=torch.uint8, device=bgrL.device) if lr_check else None
+        counts = torch.zeros((P, 2), dtype=torch.int32, device=bgrL.device) if lr_check else None
+        check(lib().smt_crossagg_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_crossagg_flow_set_stream")
+        check(lib().smt_crossagg_flow_run_batch(self._h, _ptr(bgrL), _ptr(bgrR), _ptr(grayL), _ptr(grayR), P, int(views),
+                                                _ptr(dispL), _ptr(dispR), _ptr(cls), _ptr(counts)),
+              "smt_crossagg_flow_run_batch")
+        if lr_check:
+            return dispL, dispR, cls, counts
+        return dispL, dispR
+
+    def volumes(self):
+        """The last pair's aggregated volumes (left view, right view), float32 [row][col][dispRange], borrowed."""
+        ps = [C.c_void_p() for _ in range(2)]
+        check(lib().smt_crossagg_flow_volumes(self._h, *[C.byref(p) for p in ps]), "smt_crossagg_flow_volumes")
+        shp = (self.row, self.col, self.dispRange)
+        return [_view_of(p.value, shp, torch.float32, self.device) for p in ps]
+
+    def set_impl(self, impl):
+        """0 = fused kernels (default), 1 = the composed path (smt_cblsm_ad, the aggregation passes, smt_wta)."""
+        check(lib().smt_crossagg_flow_set_impl(self._h, int(impl)), "smt_crossagg_flow_set_impl")
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().smt_crossagg_flow_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -9,6 +9,10 @@
 // (t = -arm .. +arm).  Pass 1 goes cur -> tmp, pass 2 tmp -> cur with the division by the
 // uint16 support count, exactly like vec_cost_tmp_[0/1] and cost_aggr_ per plane.
 #include "smt_common.h"
+#include "crossagg_first.h"
+#include <limits.h>
+#include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 #include <new>
 
@@ -172,11 +176,15 @@ __device__ __forceinline__ void ld_wide(P sp, float (&x)[C])
     }
 }
 
-template <int C, bool HORIZ, bool FINAL, bool FULL>
-__global__ void __launch_bounds__(NT) k_ca_pass2(const float *__restrict__ src, float *__restrict__ dst, int W, int H,
-                                                 int D, const uint8_t *__restrict__ arms, const uint16_t *__restrict__ cnt,
-                                                 const float *__restrict__ member)
+// WTA (dividing pass only): 0 = the pass as it is; 1 = the wave that holds a pixel's D quotients also reduces them to
+// the first strict minimum with smt_wta's rule (wave_wta) and lane 0 writes it to disp; 2 = 1 without the volume store
+// (smt_crossagg_flow_run_batch: nothing can read the volumes of the pairs before the last).
+template <int C, bool HORIZ, bool FINAL, bool FULL, int WTA>
+__device__ __forceinline__ void ca_pass2_body(const float *__restrict__ src, float *__restrict__ dst, int W, int H,
+                                              int D, const uint8_t *__restrict__ arms, const uint16_t *__restrict__ cnt,
+                                              const float *__restrict__ member, float *__restrict__ disp)
 {
+    static_assert(WTA == 0 || FINAL, "the WTA belongs to the dividing pass");
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // HORIZ: workgroups are dealt to the 8 XCDs round-robin, and the tiles of neighbouring workgroups share their
@@ -370,15 +378,97 @@ __global__ void __launch_bounds__(NT) k_ca_pass2(const float *__restrict__ src, 
             // (wave_quotient, smt_common.h; k_ca_pass keeps the IEEE division as the independent formulation)
             float qv[C];
             wave_quotient<C, FULL>(a, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myn), q)), dl, D, qv);
+            if constexpr (WTA != 2) {
 #pragma unroll
-            for (int k = 0; k < C; k++)
-                if (FULL || dl + k < D) o[k] = qv[k];
+                for (int k = 0; k < C; k++)
+                    if (FULL || dl + k < D) o[k] = qv[k];
+            }
+            if constexpr (WTA != 0) {
+                const int wd = wave_wta<C, FULL>(qv, dl, D);             // elements at or past D are ignored
+                if (lane == 0) disp[p] = (float)wd;
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < C; k++)
                 if (FULL || dl + k < D) o[k] = a[k];
         }
     }
+}
+
+template <int C, bool HORIZ, bool FINAL, bool FULL>
+__global__ void __launch_bounds__(NT) k_ca_pass2(const float *__restrict__ src, float *__restrict__ dst, int W, int H,
+                                                 int D, const uint8_t *__restrict__ arms, const uint16_t *__restrict__ cnt,
+                                                 const float *__restrict__ member)
+{
+    ca_pass2_body<C, HORIZ, FINAL, FULL, 0>(src, dst, W, H, D, arms, cnt, member, nullptr);
+}
+
+// the last pass of the last iteration of the batched flow: the dividing pass with the WTA fused (STORE: the last pair)
+template <int C, bool HORIZ, bool FULL, bool STORE>
+__global__ void __launch_bounds__(NT) k_ca_pass2_wta(const float *__restrict__ src, float *__restrict__ dst, int W, int H,
+                                                     int D, const uint8_t *__restrict__ arms, const uint16_t *__restrict__ cnt,
+                                                     const float *__restrict__ member, float *__restrict__ disp)
+{
+    ca_pass2_body<C, HORIZ, true, FULL, STORE ? 1 : 2>(src, dst, W, H, D, arms, cnt, member, disp);
+}
+
+// ---- fused first horizontal pass of the batched flow (crossagg_first.h) -----------------------------------------
+// One wave per (row, CA1_SEG output pixels, 64 hypotheses), lane = hypothesis, d fastest in the output as in
+// k_ca_pass2.  The wave first stages what its walk reads -- its stretch of the own row, of the other row (clamped
+// columns, 63 more for the 64 hypotheses) and the arms of its pixels -- into LDS, then walks the stretch once: per
+// column one v_sad_u32 into the running prefix and one 2-byte LDS store into its ring, and for the pixel whose window
+// has just closed three 2-byte LDS loads, two subtractions, one conversion and one 256-byte store.  No float volume is
+// read and the loop holds no global load.  The LDS is the wave's own (one wave per workgroup):
+// caf_lds_bytes(Lm) = 8960 + 1223 B at L1 = 34, 64 KiB + 2 KiB at L1 = 255.  Lanes at or past D walk the hypothesis
+// D - 1 and store nothing.
+__host__ __device__ inline int caf_span(int Lm) { return CA1_SEG + 2 * Lm; }            // tap columns of one walk at the most
+static inline size_t caf_lds_bytes(int Lm)
+{
+    return (size_t)ca1_ring_depth(Lm) * 64 * sizeof(uint16_t) + (size_t)caf_span(Lm) + (size_t)(caf_span(Lm) + 63) + 2 * CA1_SEG;
+}
+
+template <int VIEW>
+__global__ void __launch_bounds__(64) k_caf_first(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R,
+                                                  const uint8_t *__restrict__ arms, int H, int W, int D, int Lm, int nseg,
+                                                  int nck, float *__restrict__ dst)
+{
+    extern __shared__ uint16_t caf_ring[];
+    const int lane = threadIdx.x;
+    const long per = gridDim.x / 8;                         // a multiple of 8 (host): every XCD takes one contiguous range of rows
+    const long wid = (long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    const int wpr = nseg * nck;                             // waves per row
+    const long yl = wid / wpr;
+    if (yl >= H) return;
+    const int y = (int)yl, rem = (int)(wid - yl * wpr);
+    const int seg = rem / nck, ck = rem - seg * nck;
+    const int d = ck * 64 + lane, dc = d < D ? d : D - 1;
+    const int xs = seg * CA1_SEG, xe = min(xs + CA1_SEG, W);
+    const int ub = max(xs - Lm, 0), ue = min(xe - 1 + Lm, W - 1);              // ca1_walk's tap columns
+    const int nown = ue - ub + 1, noth = nown + 63;
+    const int obase = VIEW == 0 ? ub - (ck * 64 + 63) : ub + ck * 64;          // column of s_oth[0], before the clamp
+    uint8_t *s_own = reinterpret_cast<uint8_t *>(caf_ring + ca1_ring_depth(Lm) * 64);
+    uint8_t *s_oth = s_own + caf_span(Lm), *s_arm = s_oth + caf_span(Lm) + 63;
+    {
+        const uint8_t *own = (VIEW == 0 ? L : R) + (size_t)y * W, *oth = (VIEW == 0 ? R : L) + (size_t)y * W;
+        const uchar4 *arow = reinterpret_cast<const uchar4 *>(arms) + (size_t)y * W;
+        for (int i = lane; i < nown; i += 64) s_own[i] = own[ub + i];
+        for (int i = lane; i < noth; i += 64) s_oth[i] = oth[ca1_clamp(obase + i, W)];
+        for (int i = lane; i < xe - xs; i += 64) {
+            const uchar4 a = arow[xs + i];
+            s_arm[2 * i] = a.x; s_arm[2 * i + 1] = a.y;
+        }
+    }
+    __syncthreads();                                        // one wave: orders the staging before the walk's reads
+    const uint8_t *my_oth = s_oth + (VIEW == 0 ? -dc : dc) - obase;            // column u -/+ dc sits at s_oth[u -/+ dc - obase]
+    float *orow = dst + (size_t)y * W * D + d;
+    uint16_t *ring = caf_ring + lane;
+    ca1_walk<CA1_G>(xs, xe, W, Lm,
+                    [&](int u) { return (uint32_t)s_own[u - ub]; },
+                    [&](int u) { return (uint32_t)my_oth[u]; },
+                    [&](int x, int &l, int &r) { l = s_arm[2 * (x - xs)]; r = s_arm[2 * (x - xs) + 1]; },
+                    [&](int s, uint32_t P) { ring[s * 64] = (uint16_t)P; },
+                    [&](int s) { return (uint32_t)ring[s * 64]; },
+                    [&](int x, float v) { if (d < D) orow[(size_t)x * D] = v; });
 }
 
 }  // namespace
@@ -394,9 +484,14 @@ struct smt_crossagg {
     uint16_t *cnt[2];
     float *member;       // 256 x 8 membership flags (row m: 1.0f where bit q of m is set)
     int impl;            // 2: shared-tap passes (default), 1: one pixel per wave (first formulation)
+    bool own_tmp;        // false: tmp is another handle's (smt_crossagg_flow shares one intermediate between its views)
 };
 
-SMT_API int smt_crossagg_create(int W, int H, int D, smt_crossagg **out)
+static int ca_create(int W, int H, int D, float *shared_tmp, smt_crossagg **out);
+
+SMT_API int smt_crossagg_create(int W, int H, int D, smt_crossagg **out) { return ca_create(W, H, D, nullptr, out); }
+
+static int ca_create(int W, int H, int D, float *shared_tmp, smt_crossagg **out)
 {
     if (!out) return SMT_ERR_ARG;
     if ((long)W * H <= 0 || W <= 0 || H <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;   // Initialize returns false (:28-31)
@@ -407,7 +502,9 @@ SMT_API int smt_crossagg_create(int W, int H, int D, smt_crossagg **out)
     h->L1 = 34; h->L2 = 17; h->t1 = 20; h->t2 = 6;                       // adcensus_types.h:69-70
     const size_t N = (size_t)W * H;
     int rc = smt_malloc((void **)&h->cur, N * D * 4);
-    if (rc == SMT_OK) rc = smt_malloc((void **)&h->tmp, N * D * 4);
+    h->own_tmp = shared_tmp == nullptr;
+    if (!h->own_tmp) h->tmp = shared_tmp;
+    else if (rc == SMT_OK) rc = smt_malloc((void **)&h->tmp, N * D * 4);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->arms, N * 4);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->pix, N * 4);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->cnt[0], N * 2);
@@ -437,7 +534,8 @@ SMT_API int smt_crossagg_destroy(smt_crossagg *h)
 {
     if (!h) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
-    (void)hipFree(h->cur); (void)hipFree(h->tmp); (void)hipFree(h->arms); (void)hipFree(h->pix);
+    (void)hipFree(h->cur); if (h->own_tmp) (void)hipFree(h->tmp);
+    (void)hipFree(h->arms); (void)hipFree(h->pix);
     (void)hipFree(h->cnt[0]); (void)hipFree(h->cnt[1]);
     (void)hipFree(h->member);
     delete h;
@@ -500,16 +598,23 @@ static void ca_iter(smt_crossagg *h, bool hfirst, const float *in)
     }
 }
 
-SMT_API int smt_crossagg_aggregate(smt_crossagg *h, const uint8_t *img, const float *cost_init, int iters)
+// SetData's image -> arms and support counts of the handle
+static void ca_prepare(smt_crossagg *h, const uint8_t *img)
 {
-    if (!h || !img || !cost_init || iters < 0) return SMT_ERR_ARG;
-    smt_dev_guard dev_guard(h->device);
     const int N = h->W * h->H;
     hipLaunchKernelGGL(k_ca_pack, dim3((N + NT - 1) / NT), dim3(NT), 0, h->stream, img, N, h->pix);
     hipLaunchKernelGGL(k_ca_arms, dim3((N + NT - 1) / NT, 4), dim3(NT), 0, h->stream, h->pix, h->W, h->H, h->L1, h->L2,
                        h->t1, h->t2, h->arms);                            // BuildArms :76-86
     hipLaunchKernelGGL(k_ca_counts, dim3((N + NT - 1) / NT), dim3(NT), 0, h->stream, h->arms, h->W, h->H,
                        h->cnt[0], h->cnt[1]);                             // ComputeSupPixelCount
+}
+
+SMT_API int smt_crossagg_aggregate(smt_crossagg *h, const uint8_t *img, const float *cost_init, int iters)
+{
+    if (!h || !img || !cost_init || iters < 0) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    const int N = h->W * h->H;
+    ca_prepare(h, img);
     if (iters == 0 && cost_init != h->cur)
         SMT_HIP(hipMemcpyAsync(h->cur, cost_init, (size_t)N * h->D * 4, hipMemcpyDeviceToDevice, h->stream)); // :108
     bool hfirst = true;
@@ -584,4 +689,287 @@ SMT_API int smt_adcensus_option_aggregate(const smt_adcensus_option *o, const ui
     if (hipStreamSynchronize(smt_stream(stream)) != hipSuccess && rc == SMT_OK) rc = SMT_ERR_HIP;
     smt_crossagg_destroy(h);
     return rc;
+}
+
+// ---- the caller shape of CBLSM.cpp:133-143, 152 as one batched, device-resident flow -----------------------------
+// Per pair and view: ComputeAD / ComputeADRight, CrossAggregator::Aggregate(num_iters) on the view's own colour image,
+// ComputeDispOringin.  The composed form (impl 1) is exactly that as the library's entry points -- smt_cblsm_ad into the
+// view's volume, smt_crossagg_aggregate in place, smt_wta -- and moves (1 + 2 * 2 * num_iters + 1) float passes over the
+// volume.  The fused form (impl 0) drops three of them: the AD volume never exists (k_caf_first gives the first
+// horizontal pass from the gray rows), the WTA sits in the last dividing pass (k_ca_pass2_wta), and that pass stores
+// its volume for the last pair of a call only.  The middle passes are k_ca_pass2 as smt_crossagg_aggregate runs them.
+struct smt_crossagg_flow {
+    int device;
+    int H, W, D;
+    smt_crossagg_flow_params P;
+    hipStream_t stream;
+    smt_crossagg *ca[2];      // left / right view: arms, counts and the aggregated volume (cur); ca[1]->tmp is ca[0]->tmp
+    uint8_t *gray[2];         // [H][W] each: the gray pair of the current pair when the caller passes none
+    int impl;                 // 0 fused (default), 1 composed
+    bool fuse_first;          // k_caf_first's LDS (caf_lds_bytes at this L1 and W) fits a workgroup of this device
+};
+
+SMT_API void smt_crossagg_flow_default_params(smt_crossagg_flow_params *p)
+{
+    if (!p) return;
+    p->L1 = 34; p->L2 = 17; p->t1 = 20; p->t2 = 6;           // adcensus_types.h:69-70
+    p->num_iters = 4;                                        // CBLSM.cpp:142
+    p->gate = 5;                                             // CBLSM.cpp:155
+}
+
+SMT_API int smt_crossagg_flow_destroy(smt_crossagg_flow *h)
+{
+    if (!h) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    (void)hipDeviceSynchronize();
+    if (h->ca[1]) smt_crossagg_destroy(h->ca[1]);            // borrows ca[0]'s intermediate: first
+    if (h->ca[0]) smt_crossagg_destroy(h->ca[0]);
+    (void)hipFree(h->gray[0]); (void)hipFree(h->gray[1]);
+    delete h;
+    return SMT_OK;
+}
+
+SMT_API int smt_crossagg_flow_create_on(int device, int H, int W, int D, const smt_crossagg_flow_params *p,
+                                        smt_crossagg_flow **out)
+{
+    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;
+    if ((long long)H * W * (SMT_MAX_DISPARITY / 64) > INT_MAX) return SMT_ERR_ARG;   // pixel and wave indices are int
+    smt_crossagg_flow_params P;
+    if (p) P = *p; else smt_crossagg_flow_default_params(&P);
+    if (P.L1 < 0 || P.L1 > 255 || P.num_iters < 0) return SMT_ERR_ARG;               // arms are uint8 (MAX_ARM_LENGTH)
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(device);
+    smt_crossagg_flow *h = new (std::nothrow) smt_crossagg_flow();
+    if (!h) return SMT_ERR_ALLOC;
+    h->device = smt_current_device();
+    h->H = H; h->W = W; h->D = D; h->P = P;
+    int rc = ca_create(W, H, D, nullptr, &h->ca[0]);
+    if (rc == SMT_OK) rc = ca_create(W, H, D, h->ca[0]->tmp, &h->ca[1]);
+    for (int v = 0; v < 2 && rc == SMT_OK; v++) {
+        rc = smt_crossagg_set_params(h->ca[v], P.L1, P.L2, P.t1, P.t2);
+        if (rc == SMT_OK) rc = smt_malloc((void **)&h->gray[v], (size_t)H * W);
+    }
+    if (rc == SMT_OK) {
+        // up to 66 KiB of LDS at L1 = 255: past the 64 KiB every kernel may ask for, so the device's limit decides, and
+        // where it says no the first pass is smt_cblsm_ad + the horizontal k_ca_pass2 (the WTA fusion stays)
+        const size_t lds = caf_lds_bytes(ca1_arm_bound(P.L1, W));
+        int lim = 0;
+        h->fuse_first = lds <= 65536;
+        if (!h->fuse_first && hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess &&
+            lds <= (size_t)lim)
+            h->fuse_first =
+                hipFuncSetAttribute((const void *)k_caf_first<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+                hipFuncSetAttribute((const void *)k_caf_first<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+        (void)hipGetLastError();
+    }
+    if (rc != SMT_OK) { smt_crossagg_flow_destroy(h); return rc; }
+    *out = h;
+    return SMT_OK;
+}
+
+SMT_API int smt_crossagg_flow_set_stream(smt_crossagg_flow *h, void *s)
+{
+    if (!h) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    h->stream = smt_stream(s);
+    int rc = smt_crossagg_set_stream(h->ca[0], s);
+    if (rc == SMT_OK) rc = smt_crossagg_set_stream(h->ca[1], s);
+    return rc;
+}
+
+SMT_API int smt_crossagg_flow_set_impl(smt_crossagg_flow *h, int impl)
+{
+    if (!h || (impl != 0 && impl != 1)) return SMT_ERR_ARG;
+    h->impl = impl;
+    return SMT_OK;
+}
+
+SMT_API int smt_crossagg_flow_volumes(smt_crossagg_flow *h, float **aggL, float **aggR)
+{
+    if (!h) return SMT_ERR_ARG;
+    if (aggL) *aggL = h->ca[0]->cur;
+    if (aggR) *aggR = h->ca[1]->cur;
+    return SMT_OK;
+}
+
+// One iteration of the fused form on the shared-tap passes: k_ca_pass2 as ca_iter2 launches it, except that the first
+// pass is skipped when k_caf_first has already written h->tmp, and that the dividing pass is k_ca_pass2_wta when
+// `disp` is given (the last iteration), with or without its volume store.
+template <int C, bool FULL>
+static void caf_iter(smt_crossagg *h, bool hfirst, const float *in, bool skip_first, float *disp, bool store)
+{
+    const long nh = (long)h->H * ((h->W + CAP - 1) / CAP), nv = (long)h->W * ((h->H + CAP - 1) / CAP);
+    dim3 gh((unsigned)(((nh + 3) / 4 + 7) / 8 * 8)), gv((unsigned)((nv + 3) / 4));
+    const uint16_t *cnt = h->cnt[hfirst ? 0 : 1];
+    if (hfirst) {
+        if (!skip_first)
+            hipLaunchKernelGGL((k_ca_pass2<C, true, false, FULL>), gh, dim3(NT), 0, h->stream, in, h->tmp, h->W, h->H, h->D, h->arms, cnt, h->member);
+        if (!disp)
+            hipLaunchKernelGGL((k_ca_pass2<C, false, true, FULL>), gv, dim3(NT), 0, h->stream, h->tmp, h->cur, h->W, h->H, h->D, h->arms, cnt, h->member);
+        else if (store)
+            hipLaunchKernelGGL((k_ca_pass2_wta<C, false, FULL, true>), gv, dim3(NT), 0, h->stream, h->tmp, h->cur, h->W, h->H, h->D, h->arms, cnt, h->member, disp);
+        else
+            hipLaunchKernelGGL((k_ca_pass2_wta<C, false, FULL, false>), gv, dim3(NT), 0, h->stream, h->tmp, h->cur, h->W, h->H, h->D, h->arms, cnt, h->member, disp);
+    } else {
+        hipLaunchKernelGGL((k_ca_pass2<C, false, false, FULL>), gv, dim3(NT), 0, h->stream, in, h->tmp, h->W, h->H, h->D, h->arms, cnt, h->member);
+        if (!disp)
+            hipLaunchKernelGGL((k_ca_pass2<C, true, true, FULL>), gh, dim3(NT), 0, h->stream, h->tmp, h->cur, h->W, h->H, h->D, h->arms, cnt, h->member);
+        else if (store)
+            hipLaunchKernelGGL((k_ca_pass2_wta<C, true, FULL, true>), gh, dim3(NT), 0, h->stream, h->tmp, h->cur, h->W, h->H, h->D, h->arms, cnt, h->member, disp);
+        else
+            hipLaunchKernelGGL((k_ca_pass2_wta<C, true, FULL, false>), gh, dim3(NT), 0, h->stream, h->tmp, h->cur, h->W, h->H, h->D, h->arms, cnt, h->member, disp);
+    }
+}
+
+// the fused form of one view (0 left, 1 right) of one pair; iters >= 1
+static int caf_view(smt_crossagg_flow *f, int view, const uint8_t *bgr, const uint8_t *gL, const uint8_t *gR, float *disp,
+                    bool store)
+{
+    smt_crossagg *h = f->ca[view];
+    const int H = f->H, W = f->W, D = f->D, iters = f->P.num_iters;
+    ca_prepare(h, bgr);                                                       // SetData, CBLSM.cpp:140
+    if (f->fuse_first) {                                                      // ComputeAD + the first horizontal pass
+        const int Lm = ca1_arm_bound(h->L1, W), nseg = (W + CA1_SEG - 1) / CA1_SEG, nck = (D + 63) / 64;
+        const long waves = (long)H * nseg * nck;
+        const dim3 g1((unsigned)((waves + 7) / 8 * 8));                       // whole rounds of the 8 XCDs
+        const size_t lds = caf_lds_bytes(Lm);
+        if (view == 0) hipLaunchKernelGGL(k_caf_first<0>, g1, dim3(64), lds, h->stream, gL, gR, h->arms, H, W, D, Lm, nseg, nck, h->tmp);
+        else hipLaunchKernelGGL(k_caf_first<1>, g1, dim3(64), lds, h->stream, gL, gR, h->arms, H, W, D, Lm, nseg, nck, h->tmp);
+    } else {
+        const int rc = smt_cblsm_ad(gL, gR, H, W, D, view == 0 ? SMT_VIEW_LEFT : SMT_VIEW_RIGHT, h->cur, (void *)h->stream);
+        if (rc != SMT_OK) return rc;
+    }
+    bool hfirst = true;
+    for (int k = 0; k < iters; k++) {                                         // Aggregate, cross_aggregator.cpp:111-117
+        float *dk = k == iters - 1 ? disp : nullptr;
+        const bool full = D % 64 == 0;
+#define SMT_CAF_ITER(CC) do { if (full) caf_iter<CC, true>(h, hfirst, h->cur, k == 0 && f->fuse_first, dk, store); \
+                              else caf_iter<CC, false>(h, hfirst, h->cur, k == 0 && f->fuse_first, dk, store); } while (0)
+        switch ((D + 63) / 64) {
+        case 1: SMT_CAF_ITER(1); break;
+        case 2: SMT_CAF_ITER(2); break;
+        case 3: SMT_CAF_ITER(3); break;
+        case 4: SMT_CAF_ITER(4); break;
+        case 5: SMT_CAF_ITER(5); break;
+        case 6: SMT_CAF_ITER(6); break;
+        case 7: SMT_CAF_ITER(7); break;
+        default: SMT_CAF_ITER(8); break;
+        }
+#undef SMT_CAF_ITER
+        hfirst = !hfirst;
+    }
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+SMT_API int smt_crossagg_flow_run_batch(smt_crossagg_flow *h, const uint8_t *bgrL, const uint8_t *bgrR,
+                                        const uint8_t *grayL, const uint8_t *grayR, int pairs, int views,
+                                        float *dispL, float *dispR, uint8_t *cls, int *counts)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!bgrL || !bgrR || views < 1 || views > 3 || (grayL == nullptr) != (grayR == nullptr)) return SMT_ERR_ARG;
+    if (((views & SMT_VIEW_LEFT) && !dispL) || ((views & SMT_VIEW_RIGHT) && !dispR)) return SMT_ERR_ARG;
+    if (cls && views != SMT_VIEW_BOTH) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    const int H = h->H, W = h->W, D = h->D;
+    const size_t N = (size_t)H * W;
+    void *st = (void *)h->stream;
+    const bool fused = h->impl == 0 && h->P.num_iters > 0;                    // no iteration: the result is the AD volume
+    for (int b = 0; b < pairs; b++) {
+        const uint8_t *cL = bgrL + b * N * 3, *cR = bgrR + b * N * 3;
+        const uint8_t *gL = grayL ? grayL + b * N : h->gray[0], *gR = grayR ? grayR + b * N : h->gray[1];
+        int rc = SMT_OK;
+        if (!grayL) {                                                         // cvtColor, CBLSM.cpp:21-22
+            rc = smt_bgr2gray(cL, H, W, h->gray[0], st);
+            if (rc == SMT_OK) rc = smt_bgr2gray(cR, H, W, h->gray[1], st);
+        }
+        for (int v = 0; v < 2 && rc == SMT_OK; v++) {
+            if (!(views & (v == 0 ? SMT_VIEW_LEFT : SMT_VIEW_RIGHT))) continue;
+            float *disp = (v == 0 ? dispL : dispR) + b * N;
+            smt_crossagg *ca = h->ca[v];
+            if (fused) {
+                rc = caf_view(h, v, v == 0 ? cL : cR, gL, gR, disp, b == pairs - 1);
+            } else {
+                rc = smt_cblsm_ad(gL, gR, H, W, D, v == 0 ? SMT_VIEW_LEFT : SMT_VIEW_RIGHT, ca->cur, st);        // :133-134
+                if (rc == SMT_OK) rc = smt_crossagg_aggregate(ca, v == 0 ? cL : cR, ca->cur, h->P.num_iters);   // :139-142
+                if (rc == SMT_OK) rc = smt_wta(ca->cur, H, W, D, disp, st);                                      // :152
+            }
+        }
+        if (rc == SMT_OK && cls)                                              // LeftRightConsistency(gate), :160
+            rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);
+        if (rc != SMT_OK) return rc;
+    }
+    return SMT_OK;
+}
+
+// Host only (no GPU): ca1_walk -- the arithmetic k_caf_first runs per lane -- against the reference's formulation: the
+// chained ComputeAD / ComputeADRight volume (CBLSM.h:327-381, restated literally) summed along each pixel's arm by
+// sequential float adds (cross_aggregator.cpp:362-364).  Bytes random (fill 0) or left 255 / right 0 (fill 1, the
+// largest sums); arms random up to max_arm and clipped to the row, every fifth pixel's as long as the row allows.  Walks
+// of CA1_SEG pixels as the kernel's and of 7 (segment starts and ends inside small rows); every pixel must be emitted
+// exactly once with the reference's bits.
+SMT_API int smt_crossagg_selftest_first_pass(int H, int W, int D, int max_arm, int fill, unsigned seed)
+{
+    if (H <= 0 || W <= 0 || D <= 0 || max_arm < 0 || max_arm > 255 || (long long)H * W * D > (1ll << 24)) return SMT_ERR_ARG;
+    const size_t N = (size_t)H * W;
+    uint8_t *img = new (std::nothrow) uint8_t[2 * N], *arm = new (std::nothrow) uint8_t[2 * N];
+    float *vol = new (std::nothrow) float[N * D];
+    const int Lm = ca1_arm_bound(max_arm, W), RD = ca1_ring_depth(Lm);
+    uint16_t *ring = new (std::nothrow) uint16_t[RD];
+    uint8_t *seen = new (std::nothrow) uint8_t[W];
+    auto done = [&](int rc) { delete[] img; delete[] arm; delete[] vol; delete[] ring; delete[] seen; return rc; };
+    if (!img || !arm || !vol || !ring || !seen) return done(SMT_ERR_ALLOC);
+    uint8_t *L = img, *R = img + N;
+    uint32_t st = seed;
+    auto rnd = [&st]() { st = st * 1664525u + 1013904223u; return st >> 8; };
+    for (size_t k = 0; k < N; k++) { L[k] = fill ? 255 : (uint8_t)(rnd() & 255); R[k] = fill ? 0 : (uint8_t)(rnd() & 255); }
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const int ml = x < max_arm ? x : max_arm, mr = W - 1 - x < max_arm ? W - 1 - x : max_arm;
+            const bool longest = (rnd() % 5) == 0;
+            arm[2 * ((size_t)y * W + x)] = (uint8_t)(longest ? ml : (int)(rnd() % (uint32_t)(ml + 1)));
+            arm[2 * ((size_t)y * W + x) + 1] = (uint8_t)(longest ? mr : (int)(rnd() % (uint32_t)(mr + 1)));
+        }
+    for (int view = 0; view < 2; view++) {
+        for (int i = 0; i < H; i++)
+            for (int j = 0; j < W; j++)
+                for (int d = 0; d < D; d++) {
+                    float &cost = vol[((size_t)i * W + j) * D + d];
+                    if (view == 0) {
+                        if (j - d < 0) cost = vol[((size_t)i * W + j) * D + d - 1];
+                        else cost = (float)abs((int)L[(size_t)i * W + j] - (int)R[(size_t)i * W + j - d]);
+                    } else {
+                        if (j + d >= W) cost = vol[((size_t)i * W + j) * D + d - 1];
+                        else cost = (float)abs((int)L[(size_t)i * W + j + d] - (int)R[(size_t)i * W + j]);
+                    }
+                }
+        for (int seglen : {CA1_SEG, 7})
+            for (int y = 0; y < H; y++)
+                for (int d = 0; d < D; d++) {
+                    const uint8_t *own = (view == 0 ? L : R) + (size_t)y * W, *oth = (view == 0 ? R : L) + (size_t)y * W;
+                    const uint8_t *arow = arm + 2 * (size_t)y * W;
+                    bool ok = true;
+                    memset(seen, 0, (size_t)W);
+                    for (int xs = 0; xs < W; xs += seglen) {
+                        for (int s = 0; s < RD; s++) ring[s] = (uint16_t)rnd();   // a walk may rely on nothing it has not written
+                        ca1_walk<CA1_G>(xs, xs + seglen < W ? xs + seglen : W, W, Lm,
+                                 [&](int u) { return (uint32_t)own[u]; },
+                                 [&](int u) { return (uint32_t)oth[ca1_other(view, u, d, W)]; },
+                                 [&](int x, int &l, int &r) { l = arow[2 * x]; r = arow[2 * x + 1]; },
+                                 [&](int s, uint32_t P) { if (s < 0 || s >= RD) ok = false; else ring[s] = (uint16_t)P; },
+                                 [&](int s) { if (s < 0 || s >= RD) { ok = false; return 0u; } return (uint32_t)ring[s]; },
+                                 [&](int x, float v) {
+                                     float seq = 0.0f;
+                                     for (int t = -(int)arow[2 * x]; t <= (int)arow[2 * x + 1]; t++)
+                                         seq = seq + vol[((size_t)y * W + x + t) * D + d];
+                                     if (x < xs || x >= xs + seglen || x >= W || seen[x]++ || memcmp(&v, &seq, 4) != 0) ok = false;
+                                 });
+                    }
+                    for (int x = 0; x < W; x++) ok = ok && seen[x] == 1;
+                    if (!ok) return done(SMT_ERR_STATE);
+                }
+    }
+    return done(SMT_OK);
 }

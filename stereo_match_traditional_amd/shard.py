@@ -103,6 +103,20 @@ def cblsm_batch(L8, R8, D, **params):
     return dl, dr
 
 
+def crossagg_batch(L8, R8, D, **params):
+    """`compute` for run_sharded on the CrossAggregator flow of CBLSM.cpp:133-143, 152 (smt_crossagg_flow_run_batch) for
+    a [count, H, W, 3] uint8 BGR shard on this rank's GPU -> (left maps, right maps).  Keywords as api.CrossAggFlow."""
+    from .api import CrossAggFlow
+    c, H, W = L8.shape[:3]
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = CrossAggFlow(H, W, D, L8.device, **params)
+    dl, dr = flow.run(L8.contiguous(), R8.contiguous())
+    flow.close()
+    return dl, dr
+
+
 def asw_batch(L8, R8, D, **params):
     """`compute` for run_sharded on ASWeight.cpp's flow (smt_asw_flow_run_batch) for a [count, H, W] uint8 shard on this
     rank's GPU -> (left maps, right maps).  Keywords as api.ASWFlow."""
