@@ -493,7 +493,8 @@ int smt_cblsm_flow_run_batch(smt_cblsm_flow *h, const uint8_t *grayL, const uint
                              float *dispL, float *dispR);
 /* the last pair's first-pass volumes, float32 [H][W][D], borrowed (valid until the next run or destroy) */
 int smt_cblsm_flow_volumes(smt_cblsm_flow *h, float **pass1_left, float **pass1_right);
-/* synchronising, read-and-clear: SMT_ERR_REF_UB if a rectangle left the plane since the last call (never expected) */
+/* synchronising, read-and-clear: SMT_ERR_REF_UB if a rectangle left the plane since the last call (never expected);
+ * SMT_ERR_STATE if a speckle kernel of smt_cblsm_flow_run_batch_post hit its loop cap (never expected either) */
 int smt_cblsm_flow_status(smt_cblsm_flow *h);
 /* Test hook, host only (no GPU): the first pass's box arithmetic (rectangle corners in a uint32 summed-area table, the
  * clipping of arms that leave the plane) against direct sums on a random H x W x D volume of bytes (fill 0) or of 255s
@@ -905,6 +906,70 @@ int smt_median_filter_batch(const float *in, float *out, int pairs, size_t strid
                             void *stream);
 int smt_remove_speckles_batch(float *disp, int pairs, size_t disp_stride, int W, int H, int diff_insame,
                               unsigned min_speckle_area, int invalid_val, int *err_dev, void *stream);
+/* MedianFilter(d, d, width, height, wnd_size): the reference's filter called with in == out, as CBLSM.cpp:162 calls it
+ * (`MedianFilter(dispLeft, dispLeft, col, row, 3)`).  That is NOT the out-of-place filter: PostProcessing.h:314-344 reads
+ * `in` while it writes `out` in raster order, so the window of pixel (i, j) holds already-filtered values in the rows
+ * above and to the left on its own row and unfiltered values elsewhere -- a recurrence.  These entries compute exactly
+ * that, per map, bit for bit on maps without NaN or -0.0 (where the reference's std::sort order is defined; with them
+ * the result is unspecified, as for smt_median_filter_batch); +inf is an ordinary value.  wnd_size 1..7; even sizes as
+ * the reference: radius wnd_size / 2, window (2 * radius + 1)^2; wnd_size 1 leaves the map as it is.
+ * Pixel (i, j) runs at step i * (radius + 1) + j: everything it reads filtered has a smaller step number, everything it
+ * reads unfiltered is overwritten at a larger one (csrc/median_schedule.h).  One map belongs to
+ * one workgroup (a thread per row, taller maps band after band), the batch is the parallel axis.  Asynchronous on
+ * `stream`, one launch whatever the data and the pair count, no allocation, no scratch beyond LDS.
+ * SMT_ERR_ARG, before any device work, for NULL disp, pairs <= 0, non-positive sizes, H*W >= 2^31, wnd_size outside
+ * 1..7 and strides (in ELEMENTS, 0 = dense) below H*W.  smt_median_filter[_batch] keep rejecting in == out. */
+int smt_median_filter_inplace(float *disp, int W, int H, int wnd_size, void *stream);
+int smt_median_filter_inplace_batch(float *disp, int pairs, size_t stride, int W, int H, int wnd_size, void *stream);
+/* Test hook (process-wide, unsynchronised like smt_sad_set_impl): 0 (default) = a thread keeps its window in registers
+ * and slides it; rows exchange the entering column through rings in LDS, one barrier per step; unfiltered values come
+ * from a register run refilled by 16-byte loads two refills ahead.  1 = the plain formulation: every step reads its
+ * window from global memory, barrier, writes, barrier.  Identical bits. */
+int smt_median_inplace_set_impl(int impl);
+/* Test hooks, host only (no GPU): the same schedule on HOST memory through the inline functions the kernels run
+ * (csrc/median_schedule.h: step -> (row, column), bands, rings, refill points), which is what holds the schedule to the
+ * oracle where there is no device.  Arguments and return values as smt_median_filter_inplace_batch; the formulation is
+ * smt_median_inplace_set_impl's.  _ex names the formulation, the rows per band (0 = the kernel's: 1024 plain; 1022,
+ * 1020, 506 for radius 1, 2, 3 of the ring form, which spends 2 * radius threads on halo rows; larger: SMT_ERR_ARG) and
+ * the order in which the ring form's threads run inside a step (reverse != 0: descending). */
+int smt_median_filter_inplace_host(float *disp, int pairs, size_t stride, int W, int H, int wnd_size);
+int smt_median_filter_inplace_host_ex(float *disp, int pairs, size_t stride, int W, int H, int wnd_size, int impl, int band,
+                                      int reverse);
+
+/* The tail of CBLSM/CBLSM.cpp (:155, :160-162), which follows both flows built from that file:
+ *   LeftRightConsistency(col, row, gate, dispLeft, dispRight, occlusion, mismatches)   5
+ *   RemoveSpeckles(dispLeft, col, row, speckle_diff, speckle_min_area, speckle_invalid)   1, 50, INT_MIN
+ *   MedianFilter(dispLeft, dispLeft, col, row, median_wnd)                              3, in == out
+ * speckle_invalid is the x86 value of int(Invalid_Float = +inf), as in smt_post_params (see smt_remove_speckles). */
+typedef struct smt_cblsm_post_params {
+    int gate;
+    int speckle_diff;
+    unsigned speckle_min_area;
+    int speckle_invalid;
+    int median_wnd;         /* 1..7 */
+} smt_cblsm_post_params;
+void smt_cblsm_post_default_params(smt_cblsm_post_params *p);
+/* :160-162 on `pairs` DEVICE maps, in that order: smt_lrcheck in place on every dispL (rejected -> +inf; cls uint8
+ * [pairs][H][W] dense, required; counts int32 [pairs][2], may be NULL), then smt_remove_speckles_batch and
+ * smt_median_filter_inplace_batch, each once for the whole batch.  dispL and dispR are `stride` ELEMENTS apart (0 =
+ * dense, otherwise >= H*W); dispR is only read.  post == NULL: the defaults.  err_dev as smt_remove_speckles_batch.
+ * Asynchronous on `stream`; scratch as smt_remove_speckles_batch.  pairs == 0 is a no-op.  SMT_ERR_ARG for NULL maps or
+ * cls, pairs < 0, non-positive sizes, H*W >= 2^31, short strides and median_wnd outside 1..7. */
+int smt_cblsm_tail_batch(float *dispL, const float *dispR, int pairs, size_t stride, int H, int W,
+                         const smt_cblsm_post_params *post, uint8_t *cls, int *counts, int *err_dev, void *stream);
+/* smt_cblsm_flow_run_batch / smt_crossagg_flow_run_batch (both views) for all pairs, then smt_cblsm_tail_batch once over
+ * the batch -- after the batch and not after each pair, because the in-place median only fills the machine across
+ * maps.  dispL ends as the finished map of CBLSM.cpp; dispR is what run_batch writes; cls, counts as smt_cblsm_tail_batch
+ * (cls required).  On the handle's stream with run_batch's asynchrony contract; pairs == 0 is a no-op.  The
+ * CrossAggregator flow takes the gate from `post` (the handle's own gate keeps serving run_batch only).  A speckle
+ * kernel that hit its loop cap (never expected) makes the flow's *_status return SMT_ERR_STATE. */
+int smt_cblsm_flow_run_batch_post(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                  float *dispL, float *dispR, uint8_t *cls, int *counts, const smt_cblsm_post_params *post);
+int smt_crossagg_flow_run_batch_post(smt_crossagg_flow *h, const uint8_t *bgrL, const uint8_t *bgrR, const uint8_t *grayL,
+                                     const uint8_t *grayR, int pairs, float *dispL, float *dispR, uint8_t *cls, int *counts,
+                                     const smt_cblsm_post_params *post);
+/* synchronising, read-and-clear: SMT_ERR_STATE if a speckle kernel of smt_crossagg_flow_run_batch_post hit its loop cap */
+int smt_crossagg_flow_status(smt_crossagg_flow *h);
 /* Test hook, host only (no GPU): checks that every 8-adjacent pixel pair of an H x W map lying in two different tiles
  * of smt_remove_speckles_batch is examined by exactly one thread of its border-merge kernel.  SMT_OK or SMT_ERR_STATE
  * (SMT_ERR_ARG unless 0 < H*W < 2^28). */

@@ -63,6 +63,12 @@ class PostParams(C.Structure):
                 ("median_wnd", C.c_int)]
 
 
+class CBLSMPostParams(C.Structure):
+    """smt_cblsm_post_params: CBLSM.cpp:155's gate and :161-162's RemoveSpeckles / MedianFilter arguments."""
+    _fields_ = [("gate", C.c_int), ("speckle_diff", C.c_int), ("speckle_min_area", C.c_uint),
+                ("speckle_invalid", C.c_int), ("median_wnd", C.c_int)]
+
+
 class ADCensusOption(C.Structure):
     """struct ADCensusOption (CBLSM/adcensus_types.h:45-75)."""
     _fields_ = [("min_disparity", C.c_int32), ("max_disparity", C.c_int32), ("lambda_ad", C.c_int32),

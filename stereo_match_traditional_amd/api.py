@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH, SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD  # noqa: F401
 
-__all__ = ["FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
+__all__ = ["MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
@@ -951,6 +951,51 @@ def RemoveSpecklesBatch(maps, diff_insame, min_speckle_aera, invalid_val):
     return maps
 
 
+@_on_tensor_device
+def MedianFilterInPlace(maps, wnd_size):
+    """MedianFilter(d, d, ...) (PostProcessing.h:314-344 with in == out, as CBLSM.cpp:162 calls it): the raster-order
+    recurrence, not the out-of-place filter.  [H][W] or [pairs][H][W] float32 on the GPU, in place, one launch,
+    asynchronous on the current stream.  Returns the same tensor."""
+    m3 = maps[None] if isinstance(maps, torch.Tensor) and maps.dim() == 2 else maps
+    P, H, W, stride = _map_batch(m3, "maps")
+    check(lib().smt_median_filter_inplace_batch(_ptr(m3), P, C.c_size_t(stride), W, H, int(wnd_size),
+                                                current_stream_ptr()), "smt_median_filter_inplace_batch")
+    return maps
+
+
+def median_inplace_set_impl(impl):
+    """0 = rings in LDS and a sliding register window (default), 1 = the plain formulation.  Identical bits."""
+    check(lib().smt_median_inplace_set_impl(int(impl)), "smt_median_inplace_set_impl")
+
+
+def _cblsm_post(post):
+    q = _lib.CBLSMPostParams()
+    lib().smt_cblsm_post_default_params(C.byref(q))
+    for k, v in post.items():
+        if not hasattr(q, k):
+            raise AttributeError(k)
+        setattr(q, k, v)
+    return q
+
+
+@_on_tensor_device
+def CBLSMTail(dispL, dispR, **post):
+    """CBLSM.cpp:160-162 on [pairs][H][W] (or [H][W]) float32 maps on the GPU: LeftRightConsistency in place on dispL,
+    RemoveSpeckles, MedianFilter in place -> (dispL, cls uint8, counts int32 [pairs][2]).  Keywords override
+    smt_cblsm_post_default_params: gate, speckle_diff, speckle_min_area, speckle_invalid, median_wnd.  Asynchronous on
+    the current stream."""
+    l3, r3 = (dispL[None], dispR[None]) if dispL.dim() == 2 else (dispL, dispR)
+    P, H, W, stride = _map_batch(l3, "dispL")
+    if _map_batch(r3, "dispR") != (P, H, W, stride) or r3.device != l3.device:
+        raise TypeError("dispR must have dispL's shape, stride and device")
+    q = _cblsm_post(post)
+    cls = torch.empty((P, H, W), dtype=torch.uint8, device=l3.device)
+    counts = torch.zeros((P, 2), dtype=torch.int32, device=l3.device)
+    check(lib().smt_cblsm_tail_batch(_ptr(l3), _ptr(r3), P, C.c_size_t(stride), H, W, C.byref(q), _ptr(cls), _ptr(counts),
+                                     None, current_stream_ptr()), "smt_cblsm_tail_batch")
+    return dispL, (cls[0] if dispL.dim() == 2 else cls), counts
+
+
 # ======================================================================================
 # Image files (host side): imread / imwrite of the reference's drivers
 # ======================================================================================
@@ -1143,6 +1188,27 @@ class CBLSMFlow:
               "smt_cblsm_flow_run_batch")
         return dl, dr
 
+    def run_post(self, grayL, grayR, **post):
+        """run() for all pairs, then CBLSM.cpp:160-162 once over the batch -> (dispL = the finished map, dispR, cls,
+        counts[pairs][2]).  Keywords override smt_cblsm_post_default_params: gate, speckle_diff, speckle_min_area,
+        speckle_invalid, median_wnd."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"CBLSM handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        q = _cblsm_post(post)
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        cls = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        counts = torch.zeros((P, 2), dtype=torch.int32, device=grayL.device)
+        check(lib().smt_cblsm_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_cblsm_flow_set_stream")
+        check(lib().smt_cblsm_flow_run_batch_post(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
+                                                  _ptr(counts), C.byref(q)), "smt_cblsm_flow_run_batch_post")
+        return dl, dr, cls, counts
+
     def volumes(self):
         """The last pair's first-pass volumes (left view, right view), float32 [row][col][dispRange], borrowed."""
         ps = [C.c_void_p() for _ in range(2)]
@@ -1221,6 +1287,39 @@ class CrossAggFlow:
         if lr_check:
             return dispL, dispR, cls, counts
         return dispL, dispR
+
+    def run_post(self, bgrL, bgrR, grayL=None, grayR=None, **post):
+        """run() with both views for all pairs, then CBLSM.cpp:160-162 once over the batch -> (dispL = the finished map,
+        dispR, cls, counts[pairs][2]).  The gate comes from `post` (default 5), not from the handle.  Keywords override
+        smt_cblsm_post_default_params."""
+        if bgrL.dim() == 3:
+            bgrL, bgrR = bgrL[None], bgrR[None]
+            if grayL is not None:
+                grayL = grayL[None]
+            if grayR is not None:
+                grayR = grayR[None]
+        P = bgrL.shape[0]
+        if _dev_index(bgrL.device) != _dev_index(self.device) or bgrR.device != bgrL.device:
+            raise ValueError(f"CrossAggFlow handle lives on {self.device}, images on {bgrL.device} / {bgrR.device}")
+        _dev(bgrL, torch.uint8, (P, self.row, self.col, 3), "bgrL")
+        _dev(bgrR, torch.uint8, (P, self.row, self.col, 3), "bgrR")
+        for g, name in ((grayL, "grayL"), (grayR, "grayR")):
+            if g is not None:
+                _dev(g, torch.uint8, (P, self.row, self.col), name)
+        q = _cblsm_post(post)
+        shp = (P, self.row, self.col)
+        dl = torch.empty(shp, dtype=torch.float32, device=bgrL.device)
+        dr = torch.empty_like(dl)
+        cls = torch.empty(shp, dtype=torch.uint8, device=bgrL.device)
+        counts = torch.zeros((P, 2), dtype=torch.int32, device=bgrL.device)
+        check(lib().smt_crossagg_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_crossagg_flow_set_stream")
+        check(lib().smt_crossagg_flow_run_batch_post(self._h, _ptr(bgrL), _ptr(bgrR), _ptr(grayL), _ptr(grayR), P, _ptr(dl),
+                                                     _ptr(dr), _ptr(cls), _ptr(counts), C.byref(q)),
+              "smt_crossagg_flow_run_batch_post")
+        return dl, dr, cls, counts
+
+    def status(self):
+        check(lib().smt_crossagg_flow_status(self._h), "smt_crossagg_flow_status")
 
     def volumes(self):
         """The last pair's aggregated volumes (left view, right view), float32 [row][col][dispRange], borrowed."""

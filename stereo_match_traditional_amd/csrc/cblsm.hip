@@ -157,6 +157,7 @@ struct smt_cblsm_flow {
     float *pass1[2];          // first-pass volumes of the left / right view (the last pair's after a call)
     void *scratch;            // [H][W][D] x 4 B: summed-area table (or AD volume), then each second-pass output
     int *err;                 // nonzero when k_sat_box clipped a rectangle to the plane
+    int *post_err;            // nonzero when a speckle kernel of run_batch_post hit its loop cap
 };
 
 SMT_API void smt_cblsm_default_params(smt_cblsm_params *p)
@@ -173,7 +174,7 @@ SMT_API int smt_cblsm_flow_destroy(smt_cblsm_flow *h)
     if (h->caL) smt_crossarm_destroy(h->caL);
     if (h->caR) smt_crossarm_destroy(h->caR);
     (void)hipFree(h->pass1[0]); (void)hipFree(h->pass1[1]);
-    (void)hipFree(h->scratch); (void)hipFree(h->err);
+    (void)hipFree(h->scratch); (void)hipFree(h->err); (void)hipFree(h->post_err);
     delete h;
     return SMT_OK;
 }
@@ -202,7 +203,8 @@ static int cblsm_create(int H, int W, int D, const smt_cblsm_params *p, smt_cbls
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->pass1[1], V);
     if (rc == SMT_OK) rc = smt_malloc(&h->scratch, V);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->err, 4);
-    if (rc == SMT_OK && hipMemset(h->err, 0, 4) != hipSuccess) rc = SMT_ERR_HIP;
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->post_err, 4);
+    if (rc == SMT_OK && (hipMemset(h->err, 0, 4) != hipSuccess || hipMemset(h->post_err, 0, 4) != hipSuccess)) rc = SMT_ERR_HIP;
     if (rc != SMT_OK) { smt_cblsm_flow_destroy(h); return rc; }
     *out = h;
     return SMT_OK;
@@ -273,6 +275,20 @@ SMT_API int smt_cblsm_flow_run_batch(smt_cblsm_flow *h, const uint8_t *grayL, co
     return SMT_OK;
 }
 
+// run_batch for all pairs, then CBLSM.cpp:160-162 once over the batch (the in-place median's parallel axis is the batch)
+SMT_API int smt_cblsm_flow_run_batch_post(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                          float *dispL, float *dispR, uint8_t *cls, int *counts,
+                                          const smt_cblsm_post_params *post)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!cls || (post && (post->median_wnd < 1 || post->median_wnd > 7))) return SMT_ERR_ARG;
+    int rc = smt_cblsm_flow_run_batch(h, grayL, grayR, pairs, dispL, dispR);
+    if (rc != SMT_OK) return rc;
+    smt_dev_guard dev_guard(h->device);
+    return smt_cblsm_tail_batch(dispL, dispR, pairs, 0, h->H, h->W, post, cls, counts, h->post_err, (void *)h->stream);
+}
+
 SMT_API int smt_cblsm_flow_volumes(smt_cblsm_flow *h, float **pass1_left, float **pass1_right)
 {
     if (!h) return SMT_ERR_ARG;
@@ -291,6 +307,9 @@ SMT_API int smt_cblsm_flow_status(smt_cblsm_flow *h)
     int e = 0;
     if (hipMemcpy(&e, h->err, 4, hipMemcpyDeviceToHost) != hipSuccess) e = 1;
     if (e) { (void)hipMemset(h->err, 0, 4); if (rc == SMT_OK) rc = SMT_ERR_REF_UB; }
+    e = 0;
+    if (hipMemcpy(&e, h->post_err, 4, hipMemcpyDeviceToHost) != hipSuccess) e = 1;
+    if (e) { (void)hipMemset(h->post_err, 0, 4); if (rc == SMT_OK) rc = SMT_ERR_STATE; }
     return rc;
 }
 

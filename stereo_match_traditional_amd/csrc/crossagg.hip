@@ -707,6 +707,7 @@ struct smt_crossagg_flow {
     uint8_t *gray[2];         // [H][W] each: the gray pair of the current pair when the caller passes none
     int impl;                 // 0 fused (default), 1 composed
     bool fuse_first;          // k_caf_first's LDS (caf_lds_bytes at this L1 and W) fits a workgroup of this device
+    int *post_err;            // nonzero when a speckle kernel of run_batch_post hit its loop cap
 };
 
 SMT_API void smt_crossagg_flow_default_params(smt_crossagg_flow_params *p)
@@ -724,7 +725,7 @@ SMT_API int smt_crossagg_flow_destroy(smt_crossagg_flow *h)
     (void)hipDeviceSynchronize();
     if (h->ca[1]) smt_crossagg_destroy(h->ca[1]);            // borrows ca[0]'s intermediate: first
     if (h->ca[0]) smt_crossagg_destroy(h->ca[0]);
-    (void)hipFree(h->gray[0]); (void)hipFree(h->gray[1]);
+    (void)hipFree(h->gray[0]); (void)hipFree(h->gray[1]); (void)hipFree(h->post_err);
     delete h;
     return SMT_OK;
 }
@@ -750,6 +751,8 @@ SMT_API int smt_crossagg_flow_create_on(int device, int H, int W, int D, const s
         rc = smt_crossagg_set_params(h->ca[v], P.L1, P.L2, P.t1, P.t2);
         if (rc == SMT_OK) rc = smt_malloc((void **)&h->gray[v], (size_t)H * W);
     }
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->post_err, 4);
+    if (rc == SMT_OK && hipMemset(h->post_err, 0, 4) != hipSuccess) rc = SMT_ERR_HIP;
     if (rc == SMT_OK) {
         // up to 66 KiB of LDS at L1 = 255: past the 64 KiB every kernel may ask for, so the device's limit decides, and
         // where it says no the first pass is smt_cblsm_ad + the horizontal k_ca_pass2 (the WTA fusion stays)
@@ -901,6 +904,31 @@ SMT_API int smt_crossagg_flow_run_batch(smt_crossagg_flow *h, const uint8_t *bgr
             rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);
         if (rc != SMT_OK) return rc;
     }
+    return SMT_OK;
+}
+
+// both views for all pairs without the handle's own LR check, then CBLSM.cpp:160-162 once over the batch with post's gate
+SMT_API int smt_crossagg_flow_run_batch_post(smt_crossagg_flow *h, const uint8_t *bgrL, const uint8_t *bgrR,
+                                             const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
+                                             float *dispR, uint8_t *cls, int *counts, const smt_cblsm_post_params *post)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!cls || !dispL || !dispR || (post && (post->median_wnd < 1 || post->median_wnd > 7))) return SMT_ERR_ARG;
+    int rc = smt_crossagg_flow_run_batch(h, bgrL, bgrR, grayL, grayR, pairs, SMT_VIEW_BOTH, dispL, dispR, nullptr, nullptr);
+    if (rc != SMT_OK) return rc;
+    smt_dev_guard dev_guard(h->device);
+    return smt_cblsm_tail_batch(dispL, dispR, pairs, 0, h->H, h->W, post, cls, counts, h->post_err, (void *)h->stream);
+}
+
+SMT_API int smt_crossagg_flow_status(smt_crossagg_flow *h)
+{
+    if (!h) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return SMT_ERR_HIP;
+    int e = 0;
+    if (hipMemcpy(&e, h->post_err, 4, hipMemcpyDeviceToHost) != hipSuccess) e = 1;
+    if (e) { (void)hipMemset(h->post_err, 0, 4); return SMT_ERR_STATE; }
     return SMT_OK;
 }
 

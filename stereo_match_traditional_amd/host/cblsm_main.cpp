@@ -7,12 +7,17 @@
 //   :149     costAggregationV5(left result again, LEFT arms)
 //   :150     costAggregationV5(right result again, LEFT arms)            <- the left image's arms, as written
 //   :152-153 ComputeDispOringin x 2
-// (medianBlur :24-25 feeds nothing; copyMakeBorder :124-129 feeds only commented-out calls; LeftRightConsistency
-// :160 and the display conversion are commented out / app shell.)  Host buffers in and out, everything computed by
-// libsmt_hip.so through smt_host.hpp.  Prints FNV-1a hashes for tests/test_cpp_host_gpu.py.
-//   usage: cblsm_main H W D seed
+// (medianBlur :24-25 feeds nothing; copyMakeBorder :124-129 feeds only commented-out calls; the display conversion
+// is app shell.)  Host buffers in and out, everything computed by libsmt_hip.so through smt_host.hpp.  Prints FNV-1a
+// hashes for tests/test_cpp_host_gpu.py.  With --post the file's tail runs as well and the finished map is hashed:
+//   :155, :160  LeftRightConsistency(col, row, gate = 5, dispLeft, dispRight, occlusion, mismatches)
+//   :161        RemoveSpeckles(dispLeft, col, row, 1, 50, Invalid_Float)       int(+inf): INT_MIN on x86
+//   :162        MedianFilter(dispLeft, dispLeft, col, row, 3)                  in == out
+//   usage: cblsm_main H W D seed [--post]
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "smt_host.hpp"
 
 static uint64_t fnv(const void *p, size_t n)
@@ -48,6 +53,8 @@ int main(int argc, char **argv)
     const int row = argc > 1 ? atoi(argv[1]) : 375, col = argc > 2 ? atoi(argv[2]) : 450;
     const int dispRange = argc > 3 ? atoi(argv[3]) : 60;                       // CBLSM.cpp:29
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 6;
+    bool post = false;
+    for (int k = 1; k < argc; k++) post = post || strcmp(argv[k], "--post") == 0;
     try {
         using namespace smt;
         Image imageL, imageR;
@@ -88,6 +95,15 @@ int main(int argc, char **argv)
                (unsigned long long)fnv(costVolumRightSec.data(), V * 4));
         printf("disp_left %016llx\ndisp_right %016llx\n", (unsigned long long)fnv(dispLeft.data(), n * 4),
                (unsigned long long)fnv(dispRight.data(), n * 4));
+        if (post) {
+            int gate = 5;                                                       // :155
+            std::vector<std::pair<int, int>> occlusion, mismatches;
+            LeftRightConsistency(col, row, gate, dispLeft.data(), dispRight.data(), occlusion, mismatches);   // :160
+            RemoveSpeckles(dispLeft.data(), col, row, 1, 50, INT_MIN);          // :161
+            MedianFilter(dispLeft.data(), dispLeft.data(), col, row, 3);        // :162
+            printf("occlusion %zu\nmismatches %zu\ndisp_left_post %016llx\n", occlusion.size(), mismatches.size(),
+                   (unsigned long long)fnv(dispLeft.data(), n * 4));
+        }
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

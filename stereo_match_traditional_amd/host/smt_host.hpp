@@ -501,8 +501,18 @@ inline void AdaptiveSupportWeightBoth(float *dispL, float *dispR, unsigned char 
 }
 
 // MedianFilter / RemoveSpeckles (PostProcessing.h:250-344) on host maps
+// MedianFilter(d, d, ...) as CBLSM.cpp:162 calls it: the raster-order recurrence of the aliased call
+inline void MedianFilterInPlace(float *disp, const int &width, const int &height, const int wnd_size)
+{
+    const size_t n = (size_t)width * height;
+    DevBuf<float> a(n);
+    a.upload(disp);
+    check(smt_median_filter_inplace(a.get(), width, height, wnd_size, nullptr), "smt_median_filter_inplace");
+    a.download(disp);
+}
 inline void MedianFilter(const float *in, float *out, const int &width, const int &height, const int wnd_size)
 {
+    if (in == out) { MedianFilterInPlace(out, width, height, wnd_size); return; }
     const size_t n = (size_t)width * height;
     DevBuf<float> a(n), b(n);
     a.upload(in);

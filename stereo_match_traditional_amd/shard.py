@@ -117,6 +117,38 @@ def crossagg_batch(L8, R8, D, **params):
     return dl, dr
 
 
+def cblsm_post_batch(L8, R8, D, post=None, **params):
+    """`compute` for run_sharded on CBLSM.cpp's flow with its tail (:160-162, smt_cblsm_flow_run_batch_post) for a
+    [count, H, W] uint8 shard on this rank's GPU -> (finished left maps, right maps).  `post`: dict of
+    smt_cblsm_post_params overrides; other keywords as api.CBLSMFlow."""
+    from .api import CBLSMFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = CBLSMFlow(H, W, D, L8.device, **params)
+    dl, dr, _, _ = flow.run_post(L8.contiguous(), R8.contiguous(), **(post or {}))
+    flow.status()
+    flow.close()
+    return dl, dr
+
+
+def crossagg_post_batch(L8, R8, D, post=None, **params):
+    """`compute` for run_sharded on the CrossAggregator flow with CBLSM.cpp's tail (smt_crossagg_flow_run_batch_post) for
+    a [count, H, W, 3] uint8 BGR shard on this rank's GPU -> (finished left maps, right maps).  `post`: dict of
+    smt_cblsm_post_params overrides; other keywords as api.CrossAggFlow."""
+    from .api import CrossAggFlow
+    c, H, W = L8.shape[:3]
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = CrossAggFlow(H, W, D, L8.device, **params)
+    dl, dr, _, _ = flow.run_post(L8.contiguous(), R8.contiguous(), **(post or {}))
+    flow.status()
+    flow.close()
+    return dl, dr
+
+
 def asw_batch(L8, R8, D, **params):
     """`compute` for run_sharded on ASWeight.cpp's flow (smt_asw_flow_run_batch) for a [count, H, W] uint8 shard on this
     rank's GPU -> (left maps, right maps).  Keywords as api.ASWFlow."""
