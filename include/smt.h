@@ -384,6 +384,24 @@ int smt_cblsm_cost_aggregation_new(const uint8_t *Lp, const uint8_t *Rp, int H, 
                                    const int *armvolL, const int *armvolR, const int *armvolUp,
                                    const int *armvolDown, float *cost, void *stream);
 
+/* CBLSM.h:1128-1176 costAggregationV4, the consumer of the four smt_cblsm_choose_arm_length volumes (the reference
+ * wrote it and left it uncalled): vol_out[p][d] = mean of vol_in[.][d] over rows [i - Up, i + Down) and columns
+ * [j - L, j + R) with L, R, Up, Down the arm volumes' entries at (p, d) -- half-open on the far side, unlike V5 --
+ * added row by row in float, in the reference's order, and divided by the int tap count.  An empty rectangle gives
+ * 0.0f / 0 = NaN, as the reference does (sign and payload of the NaN are not part of the contract).
+ *   vol_in, vol_out  float32 [H][W][D], distinct
+ *   armvol*          int32 [H][W][D], any values
+ *   disp             NULL, or float32 [H][W]: ComputeDispOringin (:383-407) of vol_out by smt_wta's rule -- the first
+ *                    strict minimum wins, a NaN at d > 0 never wins, a NaN at d = 0 gives 0; needs D <= SMT_MAX_DISPARITY
+ *   ub_flag          NULL, or a device int that is ORed with 1 when a tap lies outside the plane (the reference then
+ *                    reads out of bounds or from a neighbouring row); such rectangles are clipped to the plane and
+ *                    their hypotheses are unspecified
+ * No cap on D without disp (one thread per pixel and hypothesis).  SMT_ERR_ARG for NULL or aliased volumes,
+ * non-positive sizes, H * W >= 2^31 and more than 2^39 hypotheses.  Asynchronous on `stream`. */
+int smt_cblsm_cost_aggregation_v4(const float *vol_in, const int *armvolL, const int *armvolR, const int *armvolUp,
+                                  const int *armvolDown, int H, int W, int D, float *vol_out, float *disp, int *ub_flag,
+                                  void *stream);
+
 /* =====================================================================================
  * Scanline optimiser                  replaces class ScanlineOptimizer
  *                                     (AD-CensusV1/ScanlineOptimizer.h)
@@ -491,6 +509,21 @@ int smt_cblsm_flow_set_stream(smt_cblsm_flow *h, void *stream);
  * smt_pipeline_run_batch, on the handle's stream only; one caller thread per handle. */
 int smt_cblsm_flow_run_batch(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
                              float *dispL, float *dispR);
+/* The per-hypothesis-arm flow the reference's Visual Studio solution is named after, for `pairs` pairs, per pair:
+ * ArmLength{L,R,Up,Down} of the left and of the right image (CBLSM.cpp:64-67, 101-104), chooseArmLength{Left,Right,Up,
+ * Down} (:108-111), ComputeAD (:133), costAggregationV4 of the AD volume (CBLSM.h:1128-1176), ComputeDispOringin (:152).
+ * LEFT VIEW ONLY: the reference has chooseArmLength* anchored on the left image and no right-view counterpart.
+ *   dispL   float32 [pairs][H][W], integer-valued; a pixel whose hypothesis 0 has an empty rectangle (NaN) gets 0
+ * While max(sec_length, max_length) <= 127 neither the four arm volumes nor the AD volume exist: the arms are derived
+ * inside one kernel from the eight arm maps by the reference's rules (csrc/cblsm_v4_rules.h: the right image's arms
+ * read at column j, not j - d; Up reset when LUp > RUp; Down keeping its count past RDown; their different
+ * comparisons) and the rectangle sums come from the handle's summed-area table, exact because
+ * 255 (2 * 127)^2 < 2^24.  Above that bound the handle composes smt_cblsm_ad, four smt_cblsm_choose_arm_length and
+ * smt_cblsm_cost_aggregation_v4 and allocates three more [H][W][D] volumes on the first such call; otherwise the
+ * handle's buffers suffice.  The parameters alone decide which path runs; both give the same bits.
+ * smt_cblsm_flow_volumes then lends the last pair's V4 volume as pass1_left (pass1_right is not meaningful).
+ * pairs == 0 is a no-op.  Asynchronous on the handle's stream; errors through smt_cblsm_flow_status. */
+int smt_cblsm_flow_run_batch_v4(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL);
 /* the last pair's first-pass volumes, float32 [H][W][D], borrowed (valid until the next run or destroy) */
 int smt_cblsm_flow_volumes(smt_cblsm_flow *h, float **pass1_left, float **pass1_right);
 /* synchronising, read-and-clear: SMT_ERR_REF_UB if a rectangle left the plane since the last call (never expected);
@@ -501,6 +534,13 @@ int smt_cblsm_flow_status(smt_cblsm_flow *h);
  * (fill 1), arms up to max_arm; and (float)S / (float)n against costAggregationV5's sequential float sum where S < 2^24.
  * SMT_OK or SMT_ERR_STATE; SMT_ERR_ARG for sizes over 2^26 elements. */
 int smt_cblsm_selftest_box(int H, int W, int D, int max_arm, int fill, unsigned seed);
+/* Test hook, host only (no GPU): the arm rules smt_cblsm_flow_run_batch_v4's kernel runs (csrc/cblsm_v4_rules.h)
+ * against the loops of CBLSM.h:65-236 as written, for every pixel and hypothesis of eight random H x W arm maps (zeros,
+ * arms at max_arm or the border, W < D allowed); and the half-open box arithmetic (tap count, four-corner sums in a
+ * uint32 table, (float)S / (float)n, NaN for an empty rectangle, clipping) against costAggregationV4's walk on random
+ * bytes.  SMT_OK or SMT_ERR_STATE; SMT_ERR_ARG for non-positive sizes, max_arm outside 0..255 and more than 2^22
+ * hypotheses. */
+int smt_cblsm_selftest_v4(int H, int W, int D, int max_arm, unsigned seed);
 
 /* =====================================================================================
  * Left-right consistency              replaces LeftRightConsistency

@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH, SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD  # noqa: F401
 
-__all__ = ["MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
+__all__ = ["MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
@@ -439,6 +439,32 @@ def costAggregationNew(leftImage, rightImage, CostVolume, ArmvolumeL, ArmvolumeR
     check(lib().smt_cblsm_cost_aggregation_new(_ptr(leftImage), _ptr(rightImage), _row_, _col_, int(dispRange), int(winSize),
                                                _ptr(ArmvolumeL), _ptr(ArmvolumeR), _ptr(ArmvolumeUp), _ptr(ArmvolumeDown),
                                                _ptr(CostVolume), current_stream_ptr()), "smt_cblsm_cost_aggregation_new")
+    return CostVolume
+
+
+@_on_tensor_device
+def costAggregationV4(dispvolume, CostVolume, ArmvolumeL, ArmvolumeR, ArmvolumeUp, ArmvolumeDown, dispRange, _row_, _col_,
+                      winSize=0, disp=None, ub_flag=None):
+    """CBLSM.h:1128-1176 (argument order of the reference; winSize is unused there too).  float32 [row][col][D] volume
+    in, int32 [row][col][D] arm volumes, float32 CostVolume out (allocated when None); rectangles are half-open, an
+    empty one gives NaN.  `disp`: optional float32 [row][col] that receives ComputeDispOringin of the result; `ub_flag`:
+    optional int32 tensor of one element, ORed with 1 when a tap lies outside the plane."""
+    shp = (_row_, _col_, int(dispRange))
+    _dev(dispvolume, torch.float32, shp, "dispvolume")
+    for a in (ArmvolumeL, ArmvolumeR, ArmvolumeUp, ArmvolumeDown):
+        _dev(a, torch.int32, shp, "arm volume")
+    if CostVolume is None:
+        CostVolume = torch.empty(shp, dtype=torch.float32, device=dispvolume.device)
+    _dev(CostVolume, torch.float32, shp, "CostVolume")
+    if disp is not None:
+        _dev(disp, torch.float32, (_row_, _col_), "disp")
+    if ub_flag is not None:
+        _dev(ub_flag, torch.int32, (1,), "ub_flag")
+    check(lib().smt_cblsm_cost_aggregation_v4(_ptr(dispvolume), _ptr(ArmvolumeL), _ptr(ArmvolumeR), _ptr(ArmvolumeUp),
+                                              _ptr(ArmvolumeDown), _row_, _col_, int(dispRange), _ptr(CostVolume),
+                                              _ptr(disp) if disp is not None else None,
+                                              _ptr(ub_flag) if ub_flag is not None else None, current_stream_ptr()),
+          "smt_cblsm_cost_aggregation_v4")
     return CostVolume
 
 
@@ -1208,6 +1234,23 @@ class CBLSMFlow:
         check(lib().smt_cblsm_flow_run_batch_post(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
                                                   _ptr(counts), C.byref(q)), "smt_cblsm_flow_run_batch_post")
         return dl, dr, cls, counts
+
+    def run_v4(self, grayL, grayR):
+        """The per-hypothesis-arm flow (chooseArmLength*, ComputeAD, costAggregationV4, ComputeDispOringin;
+        smt_cblsm_flow_run_batch_v4): uint8 [pairs][row][col] (or [row][col]) -> dispL, float32 [pairs][row][col].  Left
+        view only, as the reference's arm rules are.  volumes()[0] is then the last pair's V4 volume."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"CBLSM handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        check(lib().smt_cblsm_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_cblsm_flow_set_stream")
+        check(lib().smt_cblsm_flow_run_batch_v4(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl)),
+              "smt_cblsm_flow_run_batch_v4")
+        return dl
 
     def volumes(self):
         """The last pair's first-pass volumes (left view, right view), float32 [row][col][dispRange], borrowed."""

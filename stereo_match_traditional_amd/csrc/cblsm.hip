@@ -156,8 +156,9 @@ struct smt_cblsm_flow {
     smt_crossarm *caL, *caR;  // arms of the left / the right image
     float *pass1[2];          // first-pass volumes of the left / right view (the last pair's after a call)
     void *scratch;            // [H][W][D] x 4 B: summed-area table (or AD volume), then each second-pass output
-    int *err;                 // nonzero when k_sat_box clipped a rectangle to the plane
+    int *err;                 // nonzero when k_sat_box (or the costAggregationV4 kernels) clipped a rectangle to the plane
     int *post_err;            // nonzero when a speckle kernel of run_batch_post hit its loop cap
+    int *v4_arms;             // run_batch_v4 past the summed-area bound only: three [H][W][D] arm volumes, allocated on first use
 };
 
 SMT_API void smt_cblsm_default_params(smt_cblsm_params *p)
@@ -174,7 +175,7 @@ SMT_API int smt_cblsm_flow_destroy(smt_cblsm_flow *h)
     if (h->caL) smt_crossarm_destroy(h->caL);
     if (h->caR) smt_crossarm_destroy(h->caR);
     (void)hipFree(h->pass1[0]); (void)hipFree(h->pass1[1]);
-    (void)hipFree(h->scratch); (void)hipFree(h->err); (void)hipFree(h->post_err);
+    (void)hipFree(h->scratch); (void)hipFree(h->err); (void)hipFree(h->post_err); (void)hipFree(h->v4_arms);
     delete h;
     return SMT_OK;
 }
@@ -228,6 +229,19 @@ SMT_API int smt_cblsm_flow_set_stream(smt_cblsm_flow *h, void *s)
     return rc;
 }
 
+// summed-area table of one view's AD volume (0 left, 1 right) -> h->scratch
+static void cblsm_sat_table(smt_cblsm_flow *h, const uint8_t *L8, const uint8_t *R8, int view)
+{
+    const int H = h->H, W = h->W, D = h->D;
+    const int nck = (D + 63) / 64;
+    uint32_t *S = (uint32_t *)h->scratch;
+    const dim3 blk(NT);
+    const unsigned gc = (unsigned)(((long long)W * nck + 3) / 4), gr = (unsigned)(((long long)H * nck + 3) / 4);
+    if (view == 0) hipLaunchKernelGGL(k_sat_cols<0>, dim3(gc), blk, 0, h->stream, L8, R8, H, W, D, nck, S);
+    else hipLaunchKernelGGL(k_sat_cols<1>, dim3(gc), blk, 0, h->stream, L8, R8, H, W, D, nck, S);
+    hipLaunchKernelGGL(k_sat_rows, dim3(gr), blk, 0, h->stream, H, W, D, nck, S);
+}
+
 // first pass of one view (0 left, 1 right) on the arms of `ca` -> h->pass1[view]
 static int cblsm_first_pass(smt_cblsm_flow *h, smt_crossarm *ca, const uint8_t *L8, const uint8_t *R8, int view)
 {
@@ -240,15 +254,9 @@ static int cblsm_first_pass(smt_cblsm_flow *h, smt_crossarm *ca, const uint8_t *
     int *arm[4];
     int rc = smt_crossarm_arm_maps(ca, &arm[0], &arm[1], &arm[2], &arm[3]);
     if (rc != SMT_OK) return rc;
-    const int nck = (D + 63) / 64;
-    uint32_t *S = (uint32_t *)h->scratch;
-    const dim3 blk(NT);
-    const unsigned gc = (unsigned)(((long long)W * nck + 3) / 4), gr = (unsigned)(((long long)H * nck + 3) / 4);
-    if (view == 0) hipLaunchKernelGGL(k_sat_cols<0>, dim3(gc), blk, 0, h->stream, L8, R8, H, W, D, nck, S);
-    else hipLaunchKernelGGL(k_sat_cols<1>, dim3(gc), blk, 0, h->stream, L8, R8, H, W, D, nck, S);
-    hipLaunchKernelGGL(k_sat_rows, dim3(gr), blk, 0, h->stream, H, W, D, nck, S);
-    hipLaunchKernelGGL(k_sat_box, dim3((unsigned)(((long long)H * W + 3) / 4)), blk, 0, h->stream, (const uint32_t *)S,
-                       arm[0], arm[1], arm[2], arm[3], H, W, D, h->pass1[view], h->err);
+    cblsm_sat_table(h, L8, R8, view);
+    hipLaunchKernelGGL(k_sat_box, dim3((unsigned)(((long long)H * W + 3) / 4)), dim3(NT), 0, h->stream,
+                       (const uint32_t *)h->scratch, arm[0], arm[1], arm[2], arm[3], H, W, D, h->pass1[view], h->err);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -270,6 +278,52 @@ SMT_API int smt_cblsm_flow_run_batch(smt_cblsm_flow *h, const uint8_t *grayL, co
         if (rc == SMT_OK) rc = cblsm_first_pass(h, h->caR, L8, R8, 1);               // :134, :146
         if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, h->pass1[0], vol2, 1, dispL + b * N);   // :149, :152
         if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, h->pass1[1], vol2, 1, dispR + b * N);   // :150 (LEFT arms), :153
+        if (rc != SMT_OK) return rc;
+    }
+    return SMT_OK;
+}
+
+// The per-hypothesis-arm flow (CBLSM.cpp:64-67, 101-104, 108-111, 133, costAggregationV4, 152), left view only.  Within
+// the summed-area bound the four arm volumes and the AD volume never exist: the table of the left view's AD and the
+// eight arm maps feed one kernel (cblsm_v4.hip).  Past it the handle composes the library's own entry points on six
+// volumes: AD in the scratch, the arm volumes in pass1[1] and three more allocated on first use, the result in pass1[0].
+SMT_API int smt_cblsm_flow_run_batch_v4(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                        float *dispL)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!grayL || !grayR || !dispL) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    const int H = h->H, W = h->W, D = h->D;
+    const size_t N = (size_t)H * W, V = N * D;
+    if (!h->sat && !h->v4_arms) {
+        const int rc = smt_malloc((void **)&h->v4_arms, 3 * V * sizeof(int));
+        if (rc != SMT_OK) return rc;
+    }
+    void *st = (void *)h->stream;
+    for (int b = 0; b < pairs; b++) {
+        const uint8_t *L8 = grayL + b * N, *R8 = grayR + b * N;
+        int *aL[4], *aR[4];
+        int rc = smt_crossarm_arms(h->caL, L8, 1);                                   // CBLSM.cpp:64-67
+        if (rc == SMT_OK) rc = smt_crossarm_arms(h->caR, R8, 1);                     // :101-104
+        if (rc == SMT_OK) rc = smt_crossarm_arm_maps(h->caL, &aL[0], &aL[1], &aL[2], &aL[3]);
+        if (rc == SMT_OK) rc = smt_crossarm_arm_maps(h->caR, &aR[0], &aR[1], &aR[2], &aR[3]);
+        if (rc != SMT_OK) return rc;
+        if (h->sat) {
+            cblsm_sat_table(h, L8, R8, 0);                                           // :133 as a table
+            // :108-111, costAggregationV4, :152; only the last pair's volume is ever lent
+            rc = smt_cblsm_v4_box_enqueue((const uint32_t *)h->scratch, aL, aR, H, W, D, b == pairs - 1 ? h->pass1[0] : nullptr,
+                                          dispL + b * N, h->err, h->stream);
+        } else {
+            int *vL = (int *)h->pass1[1], *vR = h->v4_arms, *vU = h->v4_arms + V, *vD = h->v4_arms + 2 * V;
+            rc = smt_cblsm_choose_arm_length(0, aL[0], nullptr, aR[0], aR[1], H, W, D, vL, st);                  // :108
+            if (rc == SMT_OK) rc = smt_cblsm_choose_arm_length(1, aL[1], nullptr, aR[0], aR[1], H, W, D, vR, st);  // :109
+            if (rc == SMT_OK) rc = smt_cblsm_choose_arm_length(2, aL[2], aR[2], aR[0], aR[1], H, W, D, vU, st);    // :110
+            if (rc == SMT_OK) rc = smt_cblsm_choose_arm_length(3, aL[3], aR[3], aR[0], aR[1], H, W, D, vD, st);    // :111
+            if (rc == SMT_OK) rc = smt_cblsm_ad(L8, R8, H, W, D, SMT_VIEW_LEFT, (float *)h->scratch, st);          // :133
+            if (rc == SMT_OK) rc = smt_cblsm_cost_aggregation_v4((const float *)h->scratch, vL, vR, vU, vD, H, W, D, h->pass1[0],
+                                                                 dispL + b * N, h->err, st);                    // :152
+        }
         if (rc != SMT_OK) return rc;
     }
     return SMT_OK;

@@ -55,6 +55,13 @@ size_t smt_speckle_scratch_bytes(int pairs, int W, int H);
 int smt_speckle_enqueue(float *disp, int pairs, size_t stride, int W, int H, int diff_insame, unsigned min_speckle_area,
                         int invalid_val, void *scratch, int *err_dev, hipStream_t st);
 
+// The fused costAggregationV4 of smt_cblsm_flow_run_batch_v4 (csrc/cblsm_v4.hip): S = the uint32 summed-area table of
+// the left view's AD volume, armL / armR = the four [H][W] arm maps (left, right, up, down) of the left / right image.
+// Writes the WTA map to `disp` and, unless NULL, the aggregated volume to `vol`; ORs 1 into *err_dev when a rectangle
+// had to be clipped to the plane.  Arguments already checked (D <= SMT_MAX_DISPARITY).  One launch on `st`.
+int smt_cblsm_v4_box_enqueue(const uint32_t *S, int *const armL[4], int *const armR[4], int H, int W, int D, float *vol,
+                             float *disp, int *err_dev, hipStream_t st);
+
 #ifdef __HIPCC__
 constexpr int WAVE = 64;
 

@@ -630,6 +630,27 @@ inline void costAggregationV5(float *dispvolume, float *CostVolume, int *Armvolu
     smt_crossarm_destroy(h);
 }
 
+// costAggregationV4 (CBLSM.h:1128-1176): the mean over the half-open rectangle rows [-up, down) x columns [-L, R) that
+// the four [row][col][dispRange] arm volumes of chooseArmLength* give for each (pixel, d); an empty rectangle is NaN.
+// Throws where a tap lies outside the plane (the reference reads out of bounds there).  winSize is unused by the
+// reference too.
+inline void costAggregationV4(float *dispvolume, float *CostVolume, int *ArmvolumeL, int *ArmvolumeR, int *ArmvolumeUp,
+                              int *ArmvolumeDown, int dispRange, int row, int col, int /*winSize*/)
+{
+    const size_t n = (size_t)row * col * dispRange;
+    DevBuf<float> in(n), out(n);
+    DevBuf<int> aL(n), aR(n), aU(n), aD(n), ub(1);
+    const int zero = 0;
+    int flag = 0;
+    in.upload(dispvolume);
+    aL.upload(ArmvolumeL); aR.upload(ArmvolumeR); aU.upload(ArmvolumeUp); aD.upload(ArmvolumeDown); ub.upload(&zero);
+    check(smt_cblsm_cost_aggregation_v4(in.get(), aL.get(), aR.get(), aU.get(), aD.get(), row, col, dispRange, out.get(),
+                                        nullptr, ub.get(), nullptr), "smt_cblsm_cost_aggregation_v4");
+    out.download(CostVolume);
+    ub.download(&flag);
+    if (flag) check(SMT_ERR_REF_UB, "costAggregationV4");
+}
+
 // ComputeDispOringin (CBLSM.h:383-407): first strict minimum over d
 inline void ComputeDispOringin(float *costVolume, float *disp, int dispRange, int row, int col)
 {

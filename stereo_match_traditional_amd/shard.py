@@ -103,6 +103,22 @@ def cblsm_batch(L8, R8, D, **params):
     return dl, dr
 
 
+def cblsm_v4_batch(L8, R8, D, **params):
+    """`compute` for run_sharded on the per-hypothesis-arm flow (smt_cblsm_flow_run_batch_v4) for a [count, H, W] uint8
+    shard on this rank's GPU -> (left maps, left maps again: the flow has no right view and run_sharded gathers two
+    map sets).  Keywords as api.CBLSMFlow."""
+    from .api import CBLSMFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = CBLSMFlow(H, W, D, L8.device, **params)
+    dl = flow.run_v4(L8.contiguous(), R8.contiguous())
+    flow.status()
+    flow.close()
+    return dl, dl
+
+
 def crossagg_batch(L8, R8, D, **params):
     """`compute` for run_sharded on the CrossAggregator flow of CBLSM.cpp:133-143, 152 (smt_crossagg_flow_run_batch) for
     a [count, H, W, 3] uint8 BGR shard on this rank's GPU -> (left maps, right maps).  Keywords as api.CrossAggFlow."""
