@@ -738,8 +738,10 @@ int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int winSize
             double *cost, void *stream);
 /* Test hook (process-wide): 2 = window statistics once per image + the cross term by v_dot4_u32_u8 (default for
  * windows up to 31x31; needs 24*H*W bytes of stream-ordered scratch for the duration of the call), 1 = the
- * reference's loop nest, one lane per hypothesis (also the fallback).  The two agree to ~1e-14 relative on the
- * costs (both within the 1e-4 tolerance of the reference's own rounding) and give the same NaN pattern. */
+ * reference's loop nest, one lane per hypothesis (also the fallback).  With n = side^2, each is held to the exact value
+ * of the rational function of the bytes: 2 within 2^-50 relative (integers below 2^53, then four roundings), 1 within
+ * 4 n 2^-53 absolute (three length-n float64 sums) -- tests/exact_matchers.py -- and they give the same NaN pattern,
+ * the integer statement A B == 0. */
 int smt_ncc_set_impl(int impl);
 
 /* getGausssianMask (ASW.h:16-35) and getColorMask (:41-47), computed on the HOST in
@@ -768,8 +770,9 @@ int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSi
  * This is the reference's right view up to the rounding the library's ASW costs already carry: smt_asw's kernels fold the
  * weight product as (w0*space^2)*color, so a left cost and smt_asw's right cost of the same hypothesis may differ in the
  * last bit of the float64 sums.  dispR is therefore NOT promised to equal smt_asw(SMT_VIEW_RIGHT) bit for bit; it follows
- * from the left costs exactly and meets the oracle under the bar of the other ASW entry points (costs <= 1e-4, maps equal
- * wherever the two smallest computed costs are more than 2 float ulps apart). */
+ * from the left costs exactly and meets the bar of the other ASW entry points: every cost within ulp_f32 / 2 +
+ * 4 n 2^-53 relative of the exact value (n = (2 winSize + 3)^2; tests/exact_matchers.py), hence equal or adjacent to the
+ * oracle's float, and maps equal to the oracle's wherever its two smallest costs are more than 2 float ulps apart. */
 int smt_asw_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize,
                  const double *space, const double *color, int T,
                  float *dispL, float *dispR, float *costL, float *costR, void *stream);

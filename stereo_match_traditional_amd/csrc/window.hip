@@ -295,8 +295,9 @@ __global__ void __launch_bounds__(NT) k_ncc(const uint8_t *__restrict__ L, const
 // every integer exact in float64 (< 2^53).  Sa, Saa depend on the left position only and Sb, Sbb on the right
 // position only (k_ncc_stats, separable window sums, once per image); what is left per hypothesis is Sab, taken
 // four taps per v_dot4_u32_u8.  The reference accumulates the same quantities in float64 with a rounding per
-// tap; the two agree to ~1e-14 relative, the test tolerance is 1e-4 (north_star), and the cases the reference
-// turns into NaN (a flat window: 0/0) are exact zeros here too.  WinTakeAll's float-narrowed running maximum
+// tap.  The tests hold both to the exact value (tests/exact_matchers.py): this form within 2^-50 relative (exact
+// integers, then two roots, a product and a quotient), the loop nest within 4 n 2^-53 absolute; the cases the
+// reference turns into NaN (a flat window: 0/0) are exact zeros here too.  WinTakeAll's float-narrowed running maximum
 // (NCC.h:53-67) is evaluated in parallel: m before step d equals the maximum of (float)c[e] over e < d (NaN
 // entries skipped, a NaN at d = 0 poisons everything), so d wins iff c[d] > that prefix maximum, and the answer
 // is the last winner.
@@ -529,11 +530,12 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
 // lanes compute them 64 taps at a time (one tap per lane) and the tap loop broadcasts
 // {w0*space, anchor byte} with v_readlane -- no per-tap uniform LDS traffic.  The only per-lane
 // table read is color[|B(q)-B(c)|]; the table is replicated [256][32] in LDS so that lane l
-// always hits bank l%32 (conflict-free random access; float32 copy, relative error 6e-8).  Bytes of the other image are
+// always hits bank l%32 (conflict-free random access; float64 entries, as given).  Bytes of the other image are
 // fetched as (unaligned) dwords, 4 taps per load.
 // Arithmetic: m2 = (w0*space)*w1' with w1' = color*space folded as (w0*space*space)*color -- a
-// re-association of the reference's (color*space)*(color*space); float64 throughout, well
-// inside the 1e-4 tolerance on the float32 cost the reference itself narrows to (:255-256).
+// re-association of the reference's (color*space)*(color*space); float64 throughout, a few
+// 2^-53 per tap against the bound the tests hold the float32 cost to: half a float ulp plus
+// 4 n 2^-53 relative of the exact value (tests/exact_matchers.py; the reference narrows at :255-256).
 constexpr int ANT = 1024;      // 16 pixels (waves) per workgroup share one replicated table
 
 // ---- right view from the left view's hypotheses (smt_asw_both) ----

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import exact_matchers as X
+
 from test_asw_both_cpu import right_from_left
 
 pytestmark = pytest.mark.gpu
@@ -94,7 +96,7 @@ def test_right_outputs_follow_from_the_gpu_left_volume_exactly(hooks, O, H, W, D
 
 @pytest.mark.parametrize("H,W,D,winSize,seed,noise", SHAPES)
 def test_right_view_against_the_oracle(hooks, O, H, W, D, winSize, seed, noise, capsys):
-    """costR within 1e-4 with the oracle's NaN pattern.  dispR equal wherever the oracle's two smallest computed right
+    """costR within 1e-4 and one float ulp of the oracle's value (equal or adjacent floats), with the oracle's NaN pattern.  dispR equal wherever the oracle's two smallest computed right
     costs (d <= W - wins - 2 - x') are more than 2 float ulps apart; on these shapes the oracle has no pixel inside
     that band (counted and asserted here), so the maps are compared whole."""
     smt = hooks
@@ -126,6 +128,7 @@ def test_right_view_against_the_oracle(hooks, O, H, W, D, winSize, seed, noise, 
         with capsys.disabled():
             print(f"  impl {both}: max |costR - oracle| = {err:.3g}")
         assert err <= 1e-4, both
+        assert X.one_f32_ulp_apart(a, rc) <= 1.0, both       # equal or adjacent floats
         _, dr_only = smt.AdaptiveSupportWeightBoth(T(Lp), T(Rp), winSize, D, sp, cm, 40)
         assert np.array_equal(dr.cpu().numpy(), rd), both
         assert np.array_equal(dr_only.cpu().numpy(), rd), both

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import exact_matchers as X
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -91,12 +93,14 @@ def check_ncc(smt, O, L, R, D, win):
             assert np.array_equal(np.isnan(a), np.isnan(b)), impl
             ok = ~np.isnan(a)
             assert np.max(np.abs(a[ok] - b[ok]), initial=0.0) <= 1e-4, impl
+            assert np.max(np.abs(a[ok] - b[ok]), initial=0.0) <= X.ncc_pair_bound(win), impl       # 8 n 2^-53
             assert np.array_equal(d.cpu().numpy(), rd), impl
             outs.append(a)
     finally:
         smt.ncc_set_impl(2)
     ok = ~np.isnan(outs[0])
     assert np.max(np.abs(outs[0][ok] - outs[1][ok]), initial=0.0) <= 1e-12
+    assert np.max(np.abs(outs[0][ok] - outs[1][ok]), initial=0.0) <= X.ncc_forms_bound(win)         # 4 n 2^-53 + 2^-50
     return rd, rc
 
 
@@ -104,7 +108,8 @@ def check_ncc(smt, O, L, R, D, win):
 @pytest.mark.parametrize("D", [257, 320, 509, 510, 512])
 def test_ncc_wide(smt, O, D, win):
     """k_ncc2<5..8> (side <= 31; D = 509 takes the shifted hypothesis set, 510..512 not) and the loop nest k_ncc<512>
-    (side 33 is its only path): same NaN pattern, 1e-4 to the oracle, 1e-12 between the two, identical maps."""
+    (side 33 is its only path): same NaN pattern, 1e-4 and 8 n 2^-53 to the oracle, 1e-12 and 4 n 2^-53 + 2^-50 between the
+    two (exact_matchers.py derives the bounds), identical maps."""
     H, W = 2 * win + 3, 600
     L, R = ncc_case(H, W, D % 7 + win)
     _, rc = check_ncc(smt, O, L, R, D, win)
@@ -162,6 +167,7 @@ def check_asw(smt, O, L, R, D, winSize, rows=None):
         assert np.array_equal(np.isnan(a), np.isnan(b)), v
         ok = ~np.isnan(b)
         assert np.max(np.abs(a[ok] - b[ok]), initial=0.0) <= 1e-4, v
+        assert X.one_f32_ulp_apart(a, b) <= 1.0, v         # equal or adjacent floats
         got, ref = disp[i0:i1], rd[i0:i1]
         if rows is None:
             assert np.array_equal(got, ref), v
@@ -185,7 +191,7 @@ def check_asw(smt, O, L, R, D, winSize, rows=None):
 @pytest.mark.parametrize("H,W", [(6, 200), (5, 560)])
 def test_asw_wide(smt, O, H, W, D, winSize):
     """Chunks of 256 hypotheses (k_asw3w / k_asw4w) for the table hooks 0, 3, 4, 5, 6 and k_asw<5..8> for hook 1: costs
-    bit-identical across all six, 1e-4 to the oracle, maps equal to the oracle's, cross check."""
+    bit-identical across all six, 1e-4 and one float ulp to the oracle, maps equal to the oracle's, cross check."""
     L, R = O.synth_pair(H, W, 64, D + W + winSize, winSize == 3)
     check_asw(smt, O, L, R, D, winSize)
 
