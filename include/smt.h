@@ -48,6 +48,19 @@ typedef enum smt_status {
 
 /* Reference-defect switches.  Default (0) = reference-faithful. */
 #define SMT_QUIRK_FIX_RIGHT_ARM_STRIDE 0x1u /* undo `col = _row` in ComputeRightArmLength (CrossArm.cpp:265) */
+/* the arm threshold is local to one arm walk: every walk starts at tau and uses tau_low from iteration
+ * sec_length + 1 on, instead of one `_tao` that stays lowered for every later pixel and direction (CrossArm.cpp:223-225) */
+#define SMT_QUIRK_FIX_STICKY_TAU 0x2u
+/* the up / down scanline passes run the recurrence of the left / right ones along a column: last[d-1] for the "d-1"
+ * term, the guide read at the pixel itself, grayLast updated every step (ScanlineOptimizer.h:210, :221/:250, :238) */
+#define SMT_QUIRK_FIX_SCAN_VERTICAL 0x4u
+/* the right view's census replicates column W-1 for neighbours past the right edge, as the left view replicates
+ * column 0, instead of reading column 0 (AD-Census.h:242-243) */
+#define SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE 0x8u
+#define SMT_QUIRK_FIX_ALL (SMT_QUIRK_FIX_RIGHT_ARM_STRIDE | SMT_QUIRK_FIX_STICKY_TAU | SMT_QUIRK_FIX_SCAN_VERTICAL | \
+                           SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE)
+/* Every entry that takes quirks accepts any combination of the four and acts on the flags of its own stage; another
+ * bit gives SMT_ERR_ARG. */
 
 /* views bit mask */
 #define SMT_VIEW_LEFT 1
@@ -155,6 +168,9 @@ int smt_adcensus_placement(smt_adcensus *h, int *tries, float *store_only_ms);
  * plain = 1 / 0, nt_ms / plain_ms = the calibration times (0 when there was none).  Any pointer may be NULL. */
 int smt_adcensus_store_mode(smt_adcensus *h, int *plain, float *nt_ms, float *plain_ms);
 int smt_adcensus_set_stream(smt_adcensus *h, void *stream);
+/* SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE, from the next smt_adcensus_compute / _compute_batch on (0 = faithful, the default).
+ * Not the `flags` of smt_adcensus_create_ex: those are SMT_ADCENSUS_* values. */
+int smt_adcensus_set_quirks(smt_adcensus *h, unsigned quirks);
 
 /* ComputeADcensus (AD-Census.h:271-294) for SMT_VIEW_LEFT, ComputeADcensusRight
  * (:296-318) for SMT_VIEW_RIGHT, followed -- when dispL / dispR are non-NULL -- by
@@ -267,7 +283,8 @@ typedef struct smt_crossarm_params {
     int chain_tau;    /* 1: `_tao` is a member, sticky across the four direction calls
                             (CrossArm.h:34); 0: by-value per call (CBLSM.h:643) */
     unsigned quirks;  /* SMT_QUIRK_*; 0 = faithful.  CBLSM-style arms have no stride bug:
-                            pass SMT_QUIRK_FIX_RIGHT_ARM_STRIDE for them. */
+                            pass SMT_QUIRK_FIX_RIGHT_ARM_STRIDE for them.  With SMT_QUIRK_FIX_STICKY_TAU
+                            chain_tau has no effect and smt_crossarm_tau reports tau. */
 } smt_crossarm_params;
 
 void smt_crossarm_default_params(smt_crossarm_params *p); /* AD-CensusV1 main.cpp values */
@@ -414,6 +431,8 @@ int smt_scanline_create(int H, int W, int D, int p1, int p2, smt_scanline **out)
 int smt_scanline_create_on(int device, int H, int W, int D, int p1, int p2, smt_scanline **out);
 int smt_scanline_destroy(smt_scanline *h);
 int smt_scanline_set_stream(smt_scanline *h, void *stream);
+/* SMT_QUIRK_FIX_SCAN_VERTICAL for the passes 2 and 3 of smt_scanline_pass / smt_scanline_run (0 = faithful, the default) */
+int smt_scanline_set_quirks(smt_scanline *h, unsigned quirks);
 
 /* ScanlineOptimizer::ScanLine (:104-128): the four passes and ((left+right)+up)+down,
  * written to vol_out (`_ProcessedVolume`).  gray: float32 [H][W] guidance image
@@ -441,6 +460,10 @@ int smt_pipeline_create(int H, int W, int D, const smt_pipeline_params *p, smt_p
 int smt_pipeline_create_on(int device, int H, int W, int D, const smt_pipeline_params *p, smt_pipeline **out);
 int smt_pipeline_destroy(smt_pipeline *h);
 int smt_pipeline_set_stream(smt_pipeline *h, void *stream);
+/* SMT_QUIRK_* for every stage the handle owns (AD-Census, both views' arms, scanline), between runs; 0 = faithful, the
+ * default.  With SMT_QUIRK_FIX_RIGHT_ARM_STRIDE square and portrait pairs (H >= W) run too: arms then never leave
+ * their row; without it H > W gives SMT_ERR_REF_UB as before. */
+int smt_pipeline_set_quirks(smt_pipeline *h, unsigned quirks);
 /* main.cpp:46-92 for `pairs` pairs of uint8 gray images [pairs][H][W] (the images after cvtColor, :19-20), in
  * main.cpp's order with lines 86-89 and 92 enabled: float copies, ComputeADcensus(+Right), CrossArm
  * Initialize + four arm passes + AggregationVertical + WTA on the left and on the right image,

@@ -16,6 +16,10 @@ SMT_ERR_REF_UB = -5
 VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH = 1, 2, 3
 SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD = 1, 2          # flags of smt_fill_the_hole_batch's status
 QUIRK_FIX_RIGHT_ARM_STRIDE = 0x1
+QUIRK_FIX_STICKY_TAU = 0x2
+QUIRK_FIX_SCAN_VERTICAL = 0x4
+QUIRK_FIX_CENSUS_RIGHT_EDGE = 0x8
+QUIRK_FIX_ALL = 0xF
 SAD_FORM_COMPOSED, SAD_FORM_BOX_KEYS, SAD_FORM_BOX_VOLUME = 1, 2, 3
 
 

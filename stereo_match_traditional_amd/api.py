@@ -10,8 +10,10 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH, SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD  # noqa: F401
+from ._lib import (QUIRK_FIX_RIGHT_ARM_STRIDE, QUIRK_FIX_STICKY_TAU, QUIRK_FIX_SCAN_VERTICAL,  # noqa: F401
+                   QUIRK_FIX_CENSUS_RIGHT_EDGE, QUIRK_FIX_ALL)
 
-__all__ = ["MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
+__all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
@@ -93,9 +95,11 @@ class AD_Census:
     def __init__(self):
         self._h = None
 
-    def Initialize(self, leftImage, rightImage, dispRange, row, col, sigmaC, sigmaS, placement_search=True, store_calibration=True):
+    def Initialize(self, leftImage, rightImage, dispRange, row, col, sigmaC, sigmaS, placement_search=True, store_calibration=True,
+                   quirks=0):
         """AD-Census.h:322-344.  placement_search / store_calibration = False skip the two measuring steps of
-        smt_adcensus_create (smt_adcensus_create_ex flags): for handles created per request."""
+        smt_adcensus_create (smt_adcensus_create_ex flags): for handles created per request.  quirks: QUIRK_FIX_*
+        (QUIRK_FIX_CENSUS_RIGHT_EDGE acts here), 0 = the reference's results."""
         self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
         self._L = _dev(leftImage, torch.float32, (row, col), "leftImage")
         self._R = _dev(rightImage, torch.float32, (row, col), "rightImage")
@@ -108,7 +112,13 @@ class AD_Census:
                                            C.c_float(sigmaS), C.c_uint(flags), C.byref(h)), "smt_adcensus_create_ex")
         self._h = h
         self._views = 0
+        if quirks:
+            self.set_quirks(quirks)
         return self
+
+    def set_quirks(self, quirks):
+        """QUIRK_FIX_* from the next Compute* on."""
+        check(lib().smt_adcensus_set_quirks(self._h, C.c_uint(quirks)), "smt_adcensus_set_quirks")
 
     def _bind_stream(self):
         check(lib().smt_adcensus_set_stream(self._h, current_stream_ptr(self.device)), "smt_adcensus_set_stream")
@@ -243,6 +253,8 @@ class CrossArmAggregation:
 
     def Initialize(self, row, col, tao, dispRange, device=None, style="adcensus", quirks=None,
                    sec_length=17, max_length=34, tau_low=6):
+        """quirks: QUIRK_FIX_* (QUIRK_FIX_RIGHT_ARM_STRIDE and QUIRK_FIX_STICKY_TAU act here); None = the style's own
+        (0, the reference's results, for "adcensus")."""
         self.close()
         self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -475,8 +487,9 @@ class ScanlineOptimizer:
     def __init__(self):
         self._h = None
 
-    def Initialize(self, row, col, dispRange, p1, p2, device=None):
-        """:66-79 (the costVolume pointer argument is re-passed to ScanLine anyway)."""
+    def Initialize(self, row, col, dispRange, p1, p2, device=None, quirks=0):
+        """:66-79 (the costVolume pointer argument is re-passed to ScanLine anyway).  quirks: QUIRK_FIX_*
+        (QUIRK_FIX_SCAN_VERTICAL acts here), 0 = the reference's results."""
         self.close()
         self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -485,7 +498,13 @@ class ScanlineOptimizer:
               "smt_scanline_create_on")
         self._h = h
         self._processed = None
+        if quirks:
+            self.set_quirks(quirks)
         return self
+
+    def set_quirks(self, quirks):
+        """QUIRK_FIX_* from the next ScanLine / ScanPass on."""
+        check(lib().smt_scanline_set_quirks(self._h, C.c_uint(quirks)), "smt_scanline_set_quirks")
 
     def ScanLine(self, costVolume, Image, out=None, disp=None):
         """:104-128; returns `_ProcessedVolume`.  Image = float32 gray guidance."""
@@ -1098,7 +1117,9 @@ def scratch_info(device=None):
 class Pipeline:
     """main.cpp:46-92 (scanline and LR check enabled) for batches of gray pairs; the sharding unit of config 3."""
 
-    def __init__(self, row, col, dispRange, device=None, **params):
+    def __init__(self, row, col, dispRange, device=None, quirks=0, **params):
+        """params: the fields of smt_pipeline_params.  quirks: QUIRK_FIX_* for every stage, 0 = the reference's
+        results; QUIRK_FIX_RIGHT_ARM_STRIDE also admits row > col."""
         self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         p = _lib.PipelineParams()
@@ -1111,6 +1132,12 @@ class Pipeline:
         check(lib().smt_pipeline_create_on(_dev_index(self.device), self.row, self.col, self.dispRange, C.byref(p), C.byref(h)),
               "smt_pipeline_create_on")
         self._h = h
+        if quirks:
+            self.set_quirks(quirks)
+
+    def set_quirks(self, quirks):
+        """QUIRK_FIX_* from the next run on (between runs)."""
+        check(lib().smt_pipeline_set_quirks(self._h, C.c_uint(quirks)), "smt_pipeline_set_quirks")
 
     def run(self, grayL, grayR):
         """uint8 [pairs][row][col] (or [row][col]) -> (dispL after LR check, dispR, cls, counts[pairs][2])."""

@@ -46,6 +46,8 @@ struct Tables {
     uint16_t *rank;      // [256][64]: dense rank of lut[ad] + lut[256 + hd] (build_rank), maps-only kernel
     int *flag;           // domain flag
     int WX;
+    int edge_col;        // cenX_L's column for neighbours past the right edge (prep_edges): 0 as the reference reads,
+                         // W-1 (replicate) with SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE
     unsigned long long *stamp;   // diagnostics only (smt_adcensus_diag): 4 counters per workgroup, else null
 };
 
@@ -115,7 +117,7 @@ __device__ __forceinline__ void prep_edges(const float *__restrict__ Lf, const f
 #pragma unroll
             for (int c = -3; c <= 3; c++) {
                 int jj = xl + c;
-                jj = jj >= W ? 0 : jj;                   // neighbour wraps to column 0 (:242-243)
+                jj = jj >= W ? T.edge_col : jj;          // neighbour wraps to column 0 (:242-243), or replicates the edge
                 const bool v = rv && jj >= 0;
                 const unsigned val = (unsigned)(int)Lf[(size_t)ic * W + (jj < 0 ? 0 : jj)];
                 w = (w << 1) | (uint64_t)(v && lc > val);
@@ -1316,6 +1318,16 @@ SMT_API int smt_adcensus_set_stream(smt_adcensus *h, void *s)
     if (!h) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
     h->stream = smt_stream(s);
+    return SMT_OK;
+}
+
+SMT_API int smt_adcensus_set_quirks(smt_adcensus *h, unsigned quirks)
+{
+    if (!h || (quirks & ~SMT_QUIRK_FIX_ALL)) return SMT_ERR_ARG;
+    // every launch takes its Tables (this pair's and, for the table workgroups riding in a cost launch, the next
+    // pair's) by value from these at issue time; no call leaves tables built for the next one
+    const int col = (quirks & SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE) ? h->W - 1 : 0;
+    h->T.edge_col = h->TS[0].edge_col = h->TS[1].edge_col = col;
     return SMT_OK;
 }
 

@@ -89,6 +89,9 @@ __global__ void __launch_bounds__(NT) k_arm_flip(const uint8_t *__restrict__ img
     }
 }
 
+// LOCAL_TAU (SMT_QUIRK_FIX_STICKY_TAU): the threshold belongs to the walk -- tau up to sec, tau_low after it, for every
+// pixel and direction; no flip index and no threshold state are read.
+template <bool LOCAL_TAU>
 __global__ void __launch_bounds__(NT) k_arms(const uint8_t *__restrict__ img, ArmCfg c,
                                              const int *__restrict__ flip, int *armL, int *armR,
                                              int *armT, int *armB, int dir0, int prev_flips,
@@ -100,12 +103,15 @@ __global__ void __launch_bounds__(NT) k_arms(const uint8_t *__restrict__ img, Ar
     if (idx >= c.H * colR) return;
     const int i = idx / colR, j = idx - i * colR;
 
-    int tau_in = *tau_state;
-    if (c.chain && prev_flips)
-        for (int e = 0; e < dir; e++)
-            if (flip[e] != INT_MAX) tau_in = c.tau_low;
-    const int F = flip[dir];
-    const int tauA = (tau_in == c.tau && idx <= F) ? c.tau : c.tau_low;   // k <= sec
+    int tauA = c.tau;                                                     // k <= sec
+    if (!LOCAL_TAU) {
+        int tau_in = *tau_state;
+        if (c.chain && prev_flips)
+            for (int e = 0; e < dir; e++)
+                if (flip[e] != INT_MAX) tau_in = c.tau_low;
+        const int F = flip[dir];
+        tauA = (tau_in == c.tau && idx <= F) ? c.tau : c.tau_low;
+    }
     const int tauB = c.tau_low;                                           // k  > sec
 
     bool far;
@@ -145,9 +151,14 @@ __global__ void __launch_bounds__(NT) k_arms(const uint8_t *__restrict__ img, Ar
 // k_arm_cand writes both candidates (threshold still tau / already tau_low) and finds the first flipping
 // pixel per direction; k_arm_pick selects with the same rule as k_arms.  Same index spaces as above
 // (direction 1 with the stride bug runs over j < H and stores with stride H).
-template <bool GRAY>
+// LOCAL_TAU (SMT_QUIRK_FIX_STICKY_TAU): the "threshold still tau" candidate IS the arm of every pixel, so the kernel
+// stores it to the map (`maps`, an empty argument otherwise) and there is no flip search and no pick.
+struct ArmMaps { int *m[4]; };   // left, right, top, bottom
+struct NoArmMaps {};
+template <bool GRAY, bool LOCAL_TAU = false>
 __global__ void __launch_bounds__(NT) k_arm_cand(const uint8_t *__restrict__ img, ArmCfg c, int *flip, int dir0,
-                                                 const int *__restrict__ tau_state, uint16_t *__restrict__ cand)
+                                                 const int *__restrict__ tau_state, uint16_t *__restrict__ cand,
+                                                 std::conditional_t<LOCAL_TAU, ArmMaps, NoArmMaps> maps)
 {
     const int dir = dir0 + blockIdx.y;
     const int colR = (dir == 1 && !c.fix_right) ? c.H : c.W;
@@ -203,6 +214,11 @@ __global__ void __launch_bounds__(NT) k_arm_cand(const uint8_t *__restrict__ img
         if (saved != kmax && saved < 1 && far) saved = 1;                // stopped by a difference, not by the border
         return saved;
     };
+    if constexpr (LOCAL_TAU) {
+        int *out = dir == 0 ? maps.m[0] : dir == 1 ? maps.m[1] : dir == 2 ? maps.m[2] : maps.m[3];
+        if (live) out[idx] = walk(mhi);                   // idx = i * colR + j: the stride of k_arm_pick
+        return;
+    }
     if (live) cand[(size_t)dir * c.H * c.W + idx] = (uint16_t)(walk(mhi) | (walk(mlo) << 8));
     // first pixel (row-major in this direction's index space) that passes sec neighbours under tau
     const bool qual = live && ((mhi | oob) & lowmask) == 0;
@@ -1375,7 +1391,7 @@ SMT_API int smt_crossarm_create(int H, int W, int D, const smt_crossarm_params *
         h->occ_lds = (waves >= 3 && waves <= 5) ? (160 * 1024 / waves - 512) & ~255 : 0;   // <= 64 KB: no attribute needed
     }
     if (p) h->P = *p; else smt_crossarm_default_params(&h->P);
-    if (h->P.sec_length < 0 || h->P.max_length < 0 || h->P.max_length > 4096) { delete h; return SMT_ERR_ARG; }
+    if (h->P.sec_length < 0 || h->P.max_length < 0 || h->P.max_length > 4096 || (h->P.quirks & ~SMT_QUIRK_FIX_ALL)) { delete h; return SMT_ERR_ARG; }
     int rc = SMT_OK;
     for (int k = 0; k < 4 && rc == SMT_OK; k++) rc = smt_malloc((void **)&h->arm[k], (size_t)H * W * 4);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->flip, 8 * 4);
@@ -1431,14 +1447,24 @@ static const int kFlipInit[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
 static void launch_arms(smt_crossarm *h, const uint8_t *img, const ArmCfg &c, dim3 grid, int dir0, int prev_flips)
 {
     const bool masks = !h->arm_walk && c.sec <= 63 && c.maxlen <= 63 && c.tau >= 0 && c.tau_low >= 0;
+    if (h->P.quirks & SMT_QUIRK_FIX_STICKY_TAU) {         // one launch: nothing to search, nothing to pick
+        // flip, tau_state and cand are null here: k_arm_cand<.., true> returns at its `if constexpr (LOCAL_TAU)` before
+        // any use of them, and nothing above that return may touch them
+        const ArmMaps maps{{h->arm[0], h->arm[1], h->arm[2], h->arm[3]}};
+        if (masks && c.ch == 1) hipLaunchKernelGGL((k_arm_cand<true, true>), grid, dim3(NT), 0, h->stream, img, c, nullptr, dir0, nullptr, nullptr, maps);
+        else if (masks) hipLaunchKernelGGL((k_arm_cand<false, true>), grid, dim3(NT), 0, h->stream, img, c, nullptr, dir0, nullptr, nullptr, maps);
+        else hipLaunchKernelGGL(k_arms<true>, grid, dim3(NT), 0, h->stream, img, c, h->flip, h->arm[0], h->arm[1],
+                                h->arm[2], h->arm[3], dir0, prev_flips, h->flip + 5);
+        return;
+    }
     if (masks) {
-        if (c.ch == 1) hipLaunchKernelGGL(k_arm_cand<true>, grid, dim3(NT), 0, h->stream, img, c, h->flip, dir0, h->flip + 5, h->cand);
-        else hipLaunchKernelGGL(k_arm_cand<false>, grid, dim3(NT), 0, h->stream, img, c, h->flip, dir0, h->flip + 5, h->cand);
+        if (c.ch == 1) hipLaunchKernelGGL(k_arm_cand<true>, grid, dim3(NT), 0, h->stream, img, c, h->flip, dir0, h->flip + 5, h->cand, NoArmMaps{});
+        else hipLaunchKernelGGL(k_arm_cand<false>, grid, dim3(NT), 0, h->stream, img, c, h->flip, dir0, h->flip + 5, h->cand, NoArmMaps{});
         hipLaunchKernelGGL(k_arm_pick, grid, dim3(NT), 0, h->stream, c, h->flip, h->cand, h->arm[0], h->arm[1],
                            h->arm[2], h->arm[3], dir0, prev_flips, h->flip + 5);
     } else {
         hipLaunchKernelGGL(k_arm_flip, grid, dim3(NT), 0, h->stream, img, c, h->flip, dir0, h->flip + 5);
-        hipLaunchKernelGGL(k_arms, grid, dim3(NT), 0, h->stream, img, c, h->flip, h->arm[0], h->arm[1],
+        hipLaunchKernelGGL(k_arms<false>, grid, dim3(NT), 0, h->stream, img, c, h->flip, h->arm[0], h->arm[1],
                            h->arm[2], h->arm[3], dir0, prev_flips, h->flip + 5);
     }
 }
@@ -1472,8 +1498,9 @@ SMT_API int smt_crossarm_arms(smt_crossarm *h, const uint8_t *img, int channels)
     SMT_HIP(hipMemcpyAsync(h->flip, kFlipInit, 16, hipMemcpyHostToDevice, h->stream));
     dim3 grid((unsigned)((N + NT - 1) / NT), 4);
     launch_arms(h, img, c, grid, 0, 1);
-    hipLaunchKernelGGL(k_tau_update, dim3(1), dim3(1), 0, h->stream, h->flip, 0, 4, h->P.chain_tau, h->P.tau_low,
-                       h->flip + 5);
+    if (!(h->P.quirks & SMT_QUIRK_FIX_STICKY_TAU))      // a local threshold leaves no state behind
+        hipLaunchKernelGGL(k_tau_update, dim3(1), dim3(1), 0, h->stream, h->flip, 0, 4, h->P.chain_tau, h->P.tau_low,
+                           h->flip + 5);
     SMT_LAUNCH_CHECK();
     h->have_arms = true;
     return SMT_OK;
@@ -1491,10 +1518,19 @@ SMT_API int smt_crossarm_arm_dir(smt_crossarm *h, const uint8_t *img, int channe
     SMT_HIP(hipMemcpyAsync(h->flip + dir, kFlipInit, 4, hipMemcpyHostToDevice, h->stream));
     dim3 grid((unsigned)((N + NT - 1) / NT), 1);
     launch_arms(h, img, c, grid, dir, 0);
-    hipLaunchKernelGGL(k_tau_update, dim3(1), dim3(1), 0, h->stream, h->flip, dir, 1, h->P.chain_tau, h->P.tau_low,
-                       h->flip + 5);
+    if (!(h->P.quirks & SMT_QUIRK_FIX_STICKY_TAU))
+        hipLaunchKernelGGL(k_tau_update, dim3(1), dim3(1), 0, h->stream, h->flip, dir, 1, h->P.chain_tau, h->P.tau_low,
+                           h->flip + 5);
     SMT_LAUNCH_CHECK();
     h->have_arms = true;
+    return SMT_OK;
+}
+
+// smt_pipeline_set_quirks reaches its two handles through this (smt_common.h); the public way is smt_crossarm_params
+int smt_crossarm_set_quirks_internal(smt_crossarm *h, unsigned quirks)
+{
+    if (!h || (quirks & ~SMT_QUIRK_FIX_ALL)) return SMT_ERR_ARG;
+    h->P.quirks = quirks;
     return SMT_OK;
 }
 
@@ -1502,6 +1538,7 @@ SMT_API int smt_crossarm_tau(smt_crossarm *h, int *tau)
 {
     if (!h || !tau) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
+    if (h->P.quirks & SMT_QUIRK_FIX_STICKY_TAU) { *tau = h->P.tau; return SMT_OK; }   // whatever an earlier faithful call left
     SMT_HIP(hipMemcpyAsync(tau, h->flip + 5, 4, hipMemcpyDeviceToHost, h->stream));
     SMT_HIP(hipStreamSynchronize(h->stream));
     return SMT_OK;

@@ -168,6 +168,19 @@ SMT_API int smt_pipeline_set_stream(smt_pipeline *h, void *s)
     return pipeline_apply_streams(h);
 }
 
+SMT_API int smt_pipeline_set_quirks(smt_pipeline *h, unsigned quirks)
+{
+    if (!h || (quirks & ~SMT_QUIRK_FIX_ALL)) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    // every stage takes the flags it knows; handles a schedule does not use do not exist
+    int rc = smt_crossarm_set_quirks_internal(h->caL, quirks);
+    if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_quirks_internal(h->caR, quirks);
+    if (rc == SMT_OK) rc = smt_scanline_set_quirks(h->so, quirks);
+    for (int k = 0; k < 2 && rc == SMT_OK; k++)
+        if (h->adc[k]) rc = smt_adcensus_set_quirks(h->adc[k], quirks);
+    return rc;
+}
+
 #define PIPE_HIP(call) do { if (rc == SMT_OK && (call) != hipSuccess) rc = SMT_ERR_HIP; } while (0)
 
 // main.cpp:93-94 for pair b, on M after its LR check

@@ -10,7 +10,9 @@
 // minimum with DPP; cost rows are prefetched PF steps ahead so the sequential chain only
 // sees register data.  The reference's quirks are kept: the up/down passes use last[d]
 // for the "d-1" term (:238), step the gray pointer by one element instead of one row
-// (:221, :250) and never update grayLast (:210).
+// (:221, :250) and never update grayLast (:210).  SMT_QUIRK_FIX_SCAN_VERTICAL (smt_scanline_set_quirks) selects
+// a second set of instantiations of the up/down passes (FIXV) that run the left/right recurrence along the
+// column instead: last[d-1], the guide read at the pixel itself (stride W), grayLast updated every step.
 //
 // The reference stores four path volumes and then adds them ((left+right)+up)+down
 // (:124).  Here the left and right passes run CONCURRENTLY in one launch (2H scanlines in
@@ -121,9 +123,11 @@ __device__ __forceinline__ void st_row(float *p, int dl, int D, const float (&sr
 // PASS: 0 left->right, 1 right->left, 2 top->bottom, 3 bottom->top
 // MODE: 0 out = path ; 1 out = out + path ; 2 out = out + path and fused WTA of the sum ;
 //       3 out = (out + add2) + path
-template <int C, int PASS, int MODE, bool FULL>
+// FIXV (PASS >= 2 only): the vertical pass is the horizontal recurrence along a column instead of the reference's
+template <int C, int PASS, int MODE, bool FULL, bool FIXV = false>
 __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int line)
 {
+    static_assert(!FIXV || PASS >= 2, "FIXV is a property of the vertical passes");
     constexpr int PF = (PASS < 2) ? PF_H : PF_V;
     constexpr bool ACC = (MODE >= 1);
     constexpr bool ACC2 = (MODE == 3);
@@ -135,13 +139,16 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
     if (line >= nlines) return;
     const int nsteps = HORIZ ? W : H;                 // pixels on the line
     constexpr int dirn = (PASS == 0 || PASS == 2) ? 1 : -1;
+    constexpr bool RECUR = HORIZ || FIXV;             // last[d-1] and a running grayLast (:172, :177)
 
     // pixel index (flat, in pixels) of step s:  start + s*pstride
     long start, pstride;
     if (HORIZ) { start = (long)line * W + (dirn > 0 ? 0 : W - 1); pstride = dirn; }
     else       { start = (long)(dirn > 0 ? 0 : H - 1) * W + line; pstride = (long)dirn * W; }
-    // gray pointer: horizontal passes follow the pixel; vertical passes step by ONE element (:221,:250)
+    // gray pointer: horizontal passes follow the pixel; vertical passes step by ONE element (:221,:250),
+    // by one row when FIXV
     const float *gp = a.gray + start;
+    const long gstride = FIXV ? pstride : (long)dirn;
     const int dl = lane * C;
     const float *cp = a.cost + dl;
     float *op = out + dl;
@@ -203,7 +210,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
 #pragma unroll
     for (int u = 0; u < PF; u++) {
         const int sp = min(1 + u, slast);
-        gbuf[u] = gp[(long)sp * dirn];
+        gbuf[u] = gp[(long)sp * gstride];
         ld_row<C, FULL>(cp + (start + (long)sp * pstride) * D, dl, D, PAD, cbuf[u]);
         if (ACC) ld_row<C, FULL>(op + (start + (long)sp * pstride) * D, dl, D, 0.0f, obuf[ACC ? u : 0]);
         if (ACC2) ld_row<C, FULL>(qp + (start + (long)sp * pstride) * D, dl, D, 0.0f, qbuf[ACC2 ? u : 0]);
@@ -214,7 +221,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
         const long pix = start + (long)(s) * pstride;                                           \
         const float g = gbuf[u];                                                                \
         const float p2 = ref_max(p1, a.p2 / (fabsf(g - lastgray) + 1.0f)); /* :171 / :232 */    \
-        if (HORIZ) lastgray = g;                                           /* :172 only */      \
+        if (RECUR) lastgray = g;                                           /* :172 only */      \
         const float up_in = dpp_shift_f32<0x138>(last[C - 1], PAD); /* wave_shr:1 */            \
         const float dn_in = dpp_shift_f32<0x130>(last[0], PAD);     /* wave_shl:1 */            \
         const float l4 = minLast + p2;                                                          \
@@ -225,7 +232,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
             float lnext = (k == C - 1) ? dn_in : last[k == C - 1 ? k : k + 1];                  \
             if (dl + k + 1 >= D) lnext = PAD; /* entries past D-1 are the pad */                \
             const float l1 = last[k];                                                           \
-            const float l2 = (HORIZ ? lprev : last[k]) + p1; /* :177 vs :238 (sic) */           \
+            const float l2 = (RECUR ? lprev : last[k]) + p1; /* :177 vs :238 (sic) */           \
             const float l3 = lnext + p1;                                                        \
             const float m = ref_min(ref_min(l1, l2), ref_min(l3, l4));                          \
             const float cs = cbuf[u][k] + m - minLast; /* :180 */                               \
@@ -241,7 +248,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
         minLast = wave_min_f32_dpp(cm);                                                         \
         _Pragma("unroll") for (int k = 0; k < C; k++) last[k] = (FULL || dl + k < D) ? cur[k] : PAD; \
         const int sp = min((s) + PF, slast);                                                    \
-        gbuf[u] = gp[(long)sp * dirn];                                                          \
+        gbuf[u] = gp[(long)sp * gstride];                                                       \
         ld_row<C, FULL>(cp + (start + (long)sp * pstride) * D, dl, D, PAD, cbuf[u]);            \
         if (ACC) ld_row<C, FULL>(op + (start + (long)sp * pstride) * D, dl, D, 0.0f, obuf[ACC ? u : 0]); \
         if (ACC2) ld_row<C, FULL>(qp + (start + (long)sp * pstride) * D, dl, D, 0.0f, qbuf[ACC2 ? u : 0]); \
@@ -271,11 +278,11 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
 #endif
 constexpr int NTLR = SMT_SCAN_NTLR, NTS = SMT_SCAN_NTS;
 template <int PASS> constexpr int scan_nt() { return PASS < 2 ? NTLR : NTS; }
-template <int C, int PASS, int MODE, bool FULL>
+template <int C, int PASS, int MODE, bool FULL, bool FIXV = false>
 __global__ void __launch_bounds__(scan_nt<PASS>()) k_scan(ScanArgs a)
 {
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    scan_body<C, PASS, MODE, FULL>(a, a.out, blockIdx.x * (scan_nt<PASS>() / 64) + wv);
+    scan_body<C, PASS, MODE, FULL, FIXV>(a, a.out, blockIdx.x * (scan_nt<PASS>() / 64) + wv);
 }
 
 // left->right into a.out and right->left into a.out_b, concurrently (blockIdx.y picks the pass)
@@ -295,6 +302,7 @@ struct smt_scanline {
     int H, W, D, p1, p2;
     hipStream_t stream;
     float *scratch;      // one [H][W][D] volume: the right path until the up pass consumes it
+    bool fix_vertical;   // SMT_QUIRK_FIX_SCAN_VERTICAL
 };
 
 SMT_API int smt_scanline_create(int H, int W, int D, int p1, int p2, smt_scanline **out)
@@ -329,6 +337,12 @@ SMT_API int smt_scanline_set_stream(smt_scanline *h, void *s)
     h->stream = smt_stream(s);
     return SMT_OK;
 }
+SMT_API int smt_scanline_set_quirks(smt_scanline *h, unsigned quirks)
+{
+    if (!h || (quirks & ~SMT_QUIRK_FIX_ALL)) return SMT_ERR_ARG;
+    h->fix_vertical = (quirks & SMT_QUIRK_FIX_SCAN_VERTICAL) != 0;       // the other flags belong to other stages
+    return SMT_OK;
+}
 
 template <int C, int MODE, bool FULL>
 static void launch_scan2(smt_scanline *h, int pass, const ScanArgs &a)
@@ -339,8 +353,14 @@ static void launch_scan2(smt_scanline *h, int pass, const ScanArgs &a)
     switch (pass) {
     case 0: hipLaunchKernelGGL((k_scan<C, 0, MODE, FULL>), grid, dim3(nt), 0, h->stream, a); break;
     case 1: hipLaunchKernelGGL((k_scan<C, 1, MODE, FULL>), grid, dim3(nt), 0, h->stream, a); break;
-    case 2: hipLaunchKernelGGL((k_scan<C, 2, MODE, FULL>), grid, dim3(nt), 0, h->stream, a); break;
-    default: hipLaunchKernelGGL((k_scan<C, 3, MODE, FULL>), grid, dim3(nt), 0, h->stream, a); break;
+    case 2:
+        if (h->fix_vertical) hipLaunchKernelGGL((k_scan<C, 2, MODE, FULL, true>), grid, dim3(nt), 0, h->stream, a);
+        else hipLaunchKernelGGL((k_scan<C, 2, MODE, FULL>), grid, dim3(nt), 0, h->stream, a);
+        break;
+    default:
+        if (h->fix_vertical) hipLaunchKernelGGL((k_scan<C, 3, MODE, FULL, true>), grid, dim3(nt), 0, h->stream, a);
+        else hipLaunchKernelGGL((k_scan<C, 3, MODE, FULL>), grid, dim3(nt), 0, h->stream, a);
+        break;
     }
 }
 

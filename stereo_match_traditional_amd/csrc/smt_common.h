@@ -62,6 +62,10 @@ int smt_speckle_enqueue(float *disp, int pairs, size_t stride, int W, int H, int
 int smt_cblsm_v4_box_enqueue(const uint32_t *S, int *const armL[4], int *const armR[4], int H, int W, int D, float *vol,
                              float *disp, int *err_dev, hipStream_t st);
 
+// The SMT_QUIRK_* flags of a cross-arm handle after create (csrc/crossarm.hip), for smt_pipeline_set_quirks: they take
+// effect from the next arms call.  SMT_ERR_ARG for an unknown bit.
+int smt_crossarm_set_quirks_internal(smt_crossarm *h, unsigned quirks);
+
 #ifdef __HIPCC__
 constexpr int WAVE = 64;
 

@@ -2,7 +2,9 @@
 // (AD_Census -> CrossArmAggregation L/R -> ScanlineOptimizer on the left volume -> WTA ->
 // LeftRightConsistency), host buffers in and out, everything computed by libsmt_hip.so.
 // Prints FNV-1a hashes of every product so tests can compare them with the oracle's.
-//   usage: adcensus_main H W D seed
+//   usage: adcensus_main [--fix] H W D seed            (--fix anywhere: SMT_QUIRK_FIX_ALL on every stage of the two
+//                                                       single-pair forms -- the algorithm as it was meant, on any
+//                                                       image shape; without it every reference defect is reproduced)
 //          adcensus_main --images left.png right.png D [disparity_out.png]     (imread -> cvtColor -> pipeline
 //                                                     -> imwrite, the file path of main.cpp:16-20, :115-117)
 //          adcensus_main --batch pairs H W D             (config 5 on every visible GPU, one handle per device)
@@ -78,6 +80,13 @@ static int batch_main(int pairs, int row, int col, int dispRange, bool rccl = fa
 
 int main(int argc, char **argv)
 {
+    unsigned quirks = 0;
+    for (int k = 1; k < argc; k++)
+        if (!strcmp(argv[k], "--fix")) {
+            quirks = SMT_QUIRK_FIX_ALL;
+            for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
+            argc--; k--;
+        }
     int row = argc > 1 ? atoi(argv[1]) : 72, col = argc > 2 ? atoi(argv[2]) : 160;
     int dispRange = argc > 3 ? atoi(argv[3]) : 64;
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 3;
@@ -106,6 +115,7 @@ int main(int argc, char **argv)
         auto t0 = std::chrono::steady_clock::now();
 
         smt::AD_Census ADcensus;
+        ADcensus.setQuirks(quirks);
         ADcensus.Initialize(leftptr.data(), rightptr.data(), dispRange, row, col, sigmaC, sigmaS);
         ADcensus.ComputeADcensus();
         ADcensus.ComputeADcensusRight();
@@ -118,6 +128,7 @@ int main(int argc, char **argv)
                (unsigned long long)fnv(rightDisp.data(), n * 4));
 
         smt::CrossArmAggregation CrossArm;
+        CrossArm.setQuirks(quirks);
         CrossArm.Initialize(row, col, leftptr.data(), rightptr.data(), tao, dispRange);
         CrossArm.ComputeArmLengths(leftGray.data(), 1);
         CrossArm.AggregationVertical(costVolumeLeftPtr, aggL.data());
@@ -130,6 +141,7 @@ int main(int argc, char **argv)
                (unsigned long long)fnv(aggR.data(), V * 4));
 
         smt::ScanlineOptimizer ScanlineOpt;               // main.cpp:86-89 (enabled)
+        ScanlineOpt.setQuirks(quirks);
         ScanlineOpt.Initialize(row, col, dispRange, aggL.data(), p1, p2);
         ScanlineOpt.ScanLine(aggL.data(), leftptr.data());
         ScanlineOpt.WTA(leftDisp.data());

@@ -68,11 +68,18 @@ public:
         row_ = row; col_ = col; D_ = dispRange;
         if (h_) { smt_adcensus_destroy(h_); h_ = nullptr; }
         check(smt_adcensus_create(row, col, dispRange, sigmaC, sigmaS, &h_), "smt_adcensus_create");
+        if (quirks_) check(smt_adcensus_set_quirks(h_, quirks_), "smt_adcensus_set_quirks");
         L_.resize((size_t)row * col); R_.resize((size_t)row * col);
         L_.upload(leftImage); R_.upload(rightImage);
         hostL_.assign((size_t)row * col * dispRange, 0.f);
         hostR_.assign((size_t)row * col * dispRange, 0.f);
         validL_ = validR_ = false;
+    }
+    // SMT_QUIRK_* (SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE acts here); 0 = the reference's results.  Kept across Initialize.
+    void setQuirks(unsigned quirks)
+    {
+        if (h_) check(smt_adcensus_set_quirks(h_, quirks), "smt_adcensus_set_quirks");
+        quirks_ = quirks;
     }
     void ComputeADcensus() { check(smt_adcensus_compute(h_, L_.get(), R_.get(), SMT_VIEW_LEFT, nullptr, nullptr), "compute"); validL_ = false; }
     void ComputeADcensusRight() { check(smt_adcensus_compute(h_, L_.get(), R_.get(), SMT_VIEW_RIGHT, nullptr, nullptr), "compute"); validR_ = false; }
@@ -108,6 +115,7 @@ private:
         check(smt_stream_sync(nullptr), "sync");
     }
     smt_adcensus *h_ = nullptr;
+    unsigned quirks_ = 0;
     int row_ = 0, col_ = 0, D_ = 0;
     DevBuf<float> L_, R_;
     std::vector<float> hostL_, hostR_;
@@ -126,9 +134,13 @@ public:
         smt_crossarm_params p;
         smt_crossarm_default_params(&p);
         p.tau = tao;
+        p.quirks = quirks_;
         check(smt_crossarm_create(row, col, dispRange, &p, &h_), "smt_crossarm_create");
         started_ = false;
     }
+    // SMT_QUIRK_* (SMT_QUIRK_FIX_RIGHT_ARM_STRIDE and SMT_QUIRK_FIX_STICKY_TAU act here); 0 = the reference's results.
+    // They are parameters of the handle: call it before Initialize, which every use of the class starts with.
+    void setQuirks(unsigned quirks) { quirks_ = quirks; }
     // The four Compute*ArmLength(const Mat&) calls of main.cpp:69-72 always come together and in
     // this order (the threshold state chains through them), so they are one call here.
     void ComputeArmLengths(const unsigned char *image, int channels)
@@ -185,6 +197,7 @@ private:
         check(smt_stream_sync(nullptr), "sync");
     }
     smt_crossarm *h_ = nullptr;
+    unsigned quirks_ = 0;
     int row_ = 0, col_ = 0, D_ = 0;
     bool started_ = false;
 };
@@ -199,7 +212,14 @@ public:
         row_ = row; col_ = col; D_ = dispRange;
         if (h_) { smt_scanline_destroy(h_); h_ = nullptr; }
         check(smt_scanline_create(row, col, dispRange, p1, p2, &h_), "smt_scanline_create");
+        if (quirks_) check(smt_scanline_set_quirks(h_, quirks_), "smt_scanline_set_quirks");
         processed_.resize((size_t)row * col * dispRange);
+    }
+    // SMT_QUIRK_* (SMT_QUIRK_FIX_SCAN_VERTICAL acts here); 0 = the reference's results.  Kept across Initialize.
+    void setQuirks(unsigned quirks)
+    {
+        if (h_) check(smt_scanline_set_quirks(h_, quirks), "smt_scanline_set_quirks");
+        quirks_ = quirks;
     }
     void ScanLine(float *costVolume, float *Image)
     {
@@ -218,6 +238,7 @@ public:
     float *DeviceProcessedVolume() { return processed_.get(); }
 private:
     smt_scanline *h_ = nullptr;
+    unsigned quirks_ = 0;
     int row_ = 0, col_ = 0, D_ = 0;
     DevBuf<float> processed_;
 };

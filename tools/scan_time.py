@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Times ScanlineOptimizer::ScanLine at 1920x1080 D=192 (HIP events, 3 rounds of 5) for the library named by
-SMT_HIP_LIB -- A/B of scanline builds in separate processes on one box.  usage: python tools/scan_time.py [tag]"""
+SMT_HIP_LIB -- A/B of scanline builds in separate processes on one box.
+usage: python tools/scan_time.py [tag] [--quirks N]   (N: QUIRK_FIX_* for the scanline handle, default 0)"""
+import argparse
 import json
 import os
 import sys
@@ -9,6 +11,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import stereo_match_traditional_amd as smt
 from stereo_match_traditional_amd import synth
+
+ap = argparse.ArgumentParser()
+ap.add_argument("tag", nargs="?", default="")
+ap.add_argument("--quirks", type=lambda v: int(v, 0), default=0)
+args = ap.parse_args()
 
 DEV = torch.device("cuda:0")
 H, W, D = 1080, 1920, 192
@@ -22,8 +29,10 @@ ca.ComputeArmLengths(Lu)
 agg, out = torch.empty((H, W, D), device=DEV), torch.empty((H, W, D), device=DEV)
 dL = torch.empty((H, W), device=DEV)
 ca.AggregationVertical(adc.GetPtrLeft(), agg)
-so = smt.ScanlineOptimizer().Initialize(H, W, D, 10, 150, DEV)
-res = {"tag": sys.argv[1] if len(sys.argv) > 1 else "", "lib": os.environ.get("SMT_HIP_LIB", "default"), "scanline_ms": []}
+so = smt.ScanlineOptimizer().Initialize(H, W, D, 10, 150, DEV, quirks=args.quirks)
+res = {"tag": args.tag, "lib": os.environ.get("SMT_HIP_LIB", "default"), "scanline_ms": []}
+if args.quirks:
+    res["quirks"] = args.quirks
 for _ in range(3):
     for _ in range(2):
         so.ScanLine(agg, Lf, out, dL)
