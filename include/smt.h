@@ -23,6 +23,17 @@
  *     mutable state too, e.g. CrossArm.h:34 `_tao`).
  *   - reference defects that change results are reproduced by default; see the
  *     SMT_QUIRK_* flags.
+ *   - caller buffers.  A pointer needs the natural alignment of its element type (1 byte for uint8, 4 for float32 /
+ *     int32, 8 for float64) and nothing coarser: kernels that fetch caller bytes as dwords or volumes as 16-byte
+ *     vectors do so with unaligned global accesses, none requires 16-byte alignment of a caller pointer.  No byte
+ *     outside the documented extents of a buffer is written -- not in front of it, not behind it, not in the gap
+ *     between two maps of a strided batch -- and inputs (const pointers) are not written at all.  Outputs are fully
+ *     defined: every element of every non-NULL output is written by the call, whatever the buffer held before,
+ *     including the elements the reference leaves untouched (their value is stated per entry: 0 in the border of
+ *     smt_ncc's map and cost volume, in the last row / column of SAD's right view, 0 / NaN in the costVolume[-1]
+ *     columns of ASW's).  Nothing outside an input's extents reaches a result, and neither does what the library's
+ *     scratch arena held before the call (smt_scratch_poison).  tests/test_bounds_gpu.py holds every entry point
+ *     that takes device buffers to this paragraph.
  */
 #ifndef SMT_H_
 #define SMT_H_
@@ -756,7 +767,7 @@ int smt_sad_crosscheck(const int32_t *dispL, const int32_t *dispR, int H, int W,
  * argMAX with a float32-narrowed running maximum).  L, R uint8 [H][W] unpadded; only the
  * interior winSize <= i < H-winSize, winSize <= j < W-winSize is written, the rest of
  * disp is set to 0.  cost (optional, may be NULL): float64 [H][W][D] per-hypothesis
- * costs for tolerance checks. */
+ * costs for tolerance checks; the costs of the border pixels are 0.0. */
 int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int winSize, int32_t *disp,
             double *cost, void *stream);
 /* Test hook (process-wide): 2 = window statistics once per image + the cross term by v_dot4_u32_u8 (default for
@@ -815,13 +826,17 @@ int smt_asw_selftest_right_keys(int W, int D, int wins, unsigned seed);
  * slot per workgroup in flight: 160 MB at 35 x 35 whatever the image size), 24*H*W bytes after an smt_ncc -- until the
  * process ends or the host asks
  * for it back: smt_scratch_trim synchronises the current device and returns every idle block beyond `keep_bytes` to
- * the driver (hipFree); smt_scratch_info reports what the arena holds / has handed out.
+ * the driver (hipFree); smt_scratch_info reports what the arena holds / has handed out.  smt_scratch_poison (test hook)
+ * synchronises the current device and fills every idle block of it with `byte` (hipMemset), so that the next call finds
+ * hostile scratch instead of its own previous tables: SMT_OK, or SMT_ERR_STATE outside arena mode; no effect on any other
+ * path (tests/test_bounds_gpu.py: results must not move with it).
  * Why not hipMallocAsync: on ROCm 7.2 a stream-ordered pool that trims and grows again hands out a block that is
  * zero-filled while the kernels already run on it (wrong ASW maps in round 2; tools/asw_bisect.py).
  * SMT_SCRATCH_MODE=pool|default|malloc (environment, for that tool) selects a never-trimming hipMemPool / the
  * device's default pool (the failing configuration) / plain hipMalloc per call. */
 int smt_scratch_trim(size_t keep_bytes);
 int smt_scratch_info(size_t *reserved_bytes, size_t *used_bytes);
+int smt_scratch_poison(int byte);
 /* Test hook (process-wide): which ASW formulation runs.  0 (default) = 3 while the whole-image anchor table stays
  * under 6 GiB (SMT_ASW_TABLE_MAX_MB), 6 beyond.  3 = per-row other-image weight tables in LDS, anchor weights from a
  * whole-image table written by a table kernel first (H*W*(2*winSize+3)^2*8 bytes of scratch: 5 GB at 960x540, 35x35),

@@ -13,6 +13,7 @@ SMT_OK = 0
 SMT_ERR_ARG = -1
 SMT_ERR_DOMAIN = -4
 SMT_ERR_REF_UB = -5
+SMT_ERR_STATE = -6          # e.g. smt_scratch_poison outside arena mode
 VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH = 1, 2, 3
 SMT_FILL_UB_LIST, SMT_FILL_UB_THIRD = 1, 2          # flags of smt_fill_the_hole_batch's status
 QUIRK_FIX_RIGHT_ARM_STRIDE = 0x1

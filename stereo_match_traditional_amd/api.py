@@ -17,7 +17,7 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
-           "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info",
+           "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info", "scratch_poison",
            "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow",
            "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow",
            "CrossAggFlow"]
@@ -1104,6 +1104,13 @@ def scratch_trim(keep_bytes=0, device=None):
     """smt_scratch_trim on `device` (default: current): idle scratch of smt_asw / smt_ncc back to the driver."""
     with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
         check(lib().smt_scratch_trim(C.c_size_t(int(keep_bytes))), "smt_scratch_trim")
+
+
+def scratch_poison(byte, device=None):
+    """smt_scratch_poison on `device` (default: current): test hook, fills every idle block of the scratch arena with
+    `byte` (synchronising), so that the next call runs on hostile scratch."""
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        check(lib().smt_scratch_poison(C.c_int(int(byte))), "smt_scratch_poison")
 
 
 def scratch_info(device=None):

@@ -176,6 +176,23 @@ SMT_API int smt_scratch_trim(size_t keep_bytes)
     return SMT_OK;
 }
 
+// Test hook: fills every idle arena block of the current device with `byte`, so that the next call that takes a block
+// finds hostile content in it instead of its own previous tables.  Synchronises the device first (like the trim: a
+// block is idle once its stream has passed the free) and again after the fills.  Arena mode only; touches nothing else.
+SMT_API int smt_scratch_poison(int byte)
+{
+    if (scratch_mode() != MODE_ARENA) return SMT_ERR_STATE;
+    int dev = 0;
+    SMT_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return SMT_ERR_ARG;
+    SMT_HIP(hipDeviceSynchronize());
+    std::lock_guard<std::mutex> lock(g_mu);
+    for (const Block &b : g_blocks)
+        if (b.dev == dev && !b.in_use) SMT_HIP(hipMemset(b.p, byte & 0xFF, b.bytes));
+    SMT_HIP(hipDeviceSynchronize());
+    return SMT_OK;
+}
+
 // Bytes of scratch the library holds from the driver on the current device / has handed out right now.
 SMT_API int smt_scratch_info(size_t *reserved_bytes, size_t *used_bytes)
 {

@@ -1299,6 +1299,9 @@ SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int
     hipStream_t st = smt_stream(stream);
     const int side = 2 * winSize + 1, Hi = H - 2 * winSize, Wi = W - 2 * winSize;
     static const int env_impl = [] { const char *e = getenv("SMT_NCC_IMPL"); return e ? atoi(e) : 0; }();   // debugging aid: overrides smt_ncc_set_impl
+    // the kernels write the costs of interior pixels only: the border's are 0.0, like the border of the map (an output
+    // the caller can read is defined everywhere; `cost` is a checking aid, the extra pass over it is not on a hot path)
+    if (cost && winSize > 0) SMT_HIP(hipMemsetAsync(cost, 0, (size_t)N * D * 8, st));
     if ((env_impl ? env_impl : g_ncc_impl) == 2 && side <= 31) {
         SMT_HIP(hipMemsetAsync(disp, 0, (size_t)N * 4, st));             // border pixels: 0, like k_ncc
         if (Hi <= 0 || Wi <= 0) return SMT_OK;
