@@ -372,17 +372,27 @@ int smt_crossarm_status(smt_crossarm *h); /* synchronising; read-and-clear: repo
  * (the only form for volumes >= 4 GiB, D > 256 and order 2); 2 = pipelined walk.  Every variant produces the same bits;
  * the matrix-pipe forms are measured equal to or slower than the default. */
 int smt_crossarm_set_variant(smt_crossarm *h, int variant);
-/* Tuning hook: width (multiple of 4) of the column strips each XCD sweeps (all variants but 1;
- * variants 3 and 4 round it to 8, 16 or a multiple of 32). */
+/* Tuning hook: width (multiple of 4, 4 .. 4096; anything else is SMT_ERR_ARG -- beyond 4096 the 32-bit grid size of a
+ * small image overflows) of the column strips each XCD sweeps (all variants but 1; variant 0 rounds it up to a multiple
+ * of 16, variants 3 .. 13 to 8, 16 or a multiple of 32). */
 int smt_crossarm_set_strip_width(smt_crossarm *h, int width);
 /* Tuning hook: aggregation waves per SIMD (3, 4 or 5, enforced through an LDS claim per workgroup; 0 = whatever the
  * register count allows, i.e. 6: the default).  Limiting it leaves VGPRs for kernels of other streams, which on this
  * path buys nothing (the scanline passes then run beside the aggregation and both slow down).
  * SMT_AGG_WAVES in the environment overrides the default for every handle. */
 int smt_crossarm_set_occupancy(smt_crossarm *h, int waves_per_simd);
-/* Tuning hook (variants 3-5): 0 = column strips interleaved over the 8 XCDs, 1 = every XCD owns one
- * contiguous band of rows and sweeps it strip by strip.  Placement only; results are identical. */
+/* Tuning hook (variants 3 .. 13, the default included; 0 .. 2 ignore it): 0 = column strips interleaved over the 8 XCDs,
+ * 1 = every XCD owns one contiguous band of rows and sweeps it strip by strip.  Placement only; results are identical. */
 int smt_crossarm_set_sweep(smt_crossarm *h, int sweep);
+/* Test hook, host only (no GPU, no handle): the workgroup-to-pixel map of aggregation variant `variant` on an H x W image
+ * with smt_crossarm_set_strip_width(strip_width) (0 = the width smt_crossarm_set_variant selects) and
+ * smt_crossarm_set_sweep(sweep), through the functions the kernels and the launchers run.  Every workgroup and wave of
+ * the grid the launcher would ask for is enumerated; SMT_ERR_STATE when a pixel is owned twice or by no wave, when a
+ * wave that owns pixels has rows or columns past the image, when a sweep-0 strip (and every strip of variants 0 and 2)
+ * is not on XCD strip % 8, or when a sweep-1 band of rows is not on its own XCD.  Variant 1 checks the plain
+ * (H * W + 3) / 4 grid.  SMT_ERR_ARG: variant outside 0 .. 13, H or W < 1, H * W > INT_MAX, sweep outside 0 .. 1, a width
+ * smt_crossarm_set_strip_width would refuse, or a grid beyond INT_MAX workgroups. */
+int smt_crossarm_selftest_grid(int variant, int H, int W, int strip_width, int sweep);
 
 /* CBLSM.h:327-381 ComputeAD / ComputeADRight on uchar images -> float volume. */
 int smt_cblsm_ad(const uint8_t *L, const uint8_t *R, int H, int W, int D, int view, float *vol,

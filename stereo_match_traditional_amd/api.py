@@ -358,9 +358,11 @@ class CrossArmAggregation:
         wta(AggredCostVolume, disp)
 
     def set_variant(self, variant):
-        """12 = 4x4 pixels per wave sharing union taps, lock-step workgroups (default), 7 = the same with 2x8 tiles,
+        """13 = 4x4 pixels per wave sharing union taps, lock-step workgroups, packed scalar word and fast quotient
+        (default), 12 = the same kernel without the packed scalar word and the fast quotient, 7 = 12 with 2x8 tiles,
         6 = free-running, 4 / 5 / 3 = earlier shared-tap forms, 8-11 = flagged accumulate on the matrix pipe,
-        0 = four pixels per wave, 1 plain walk, 2 pipelined walk (include/smt.h)."""
+        0 = four pixels per wave, 1 plain walk, 2 pipelined walk (include/smt.h).  Also selects the variant's default
+        strip width (8 from variant 7 on, else 16)."""
         check(lib().smt_crossarm_set_variant(self._h, int(variant)), "smt_crossarm_set_variant")
 
     def set_arm_walk(self, on=True):
@@ -368,10 +370,16 @@ class CrossArmAggregation:
         check(lib().smt_crossarm_set_arm_walk(self._h, int(on)), "smt_crossarm_set_arm_walk")
 
     def set_sweep(self, sweep):
+        """Placement hook of variants 3-13: 0 = strips interleaved over the XCDs, 1 = one band of rows per XCD."""
         check(lib().smt_crossarm_set_sweep(self._h, int(sweep)), "smt_crossarm_set_sweep")
 
     def set_strip_width(self, w):
+        """Placement hook: strip width, a multiple of 4 from 4 to 4096 (rounded per variant, include/smt.h)."""
         check(lib().smt_crossarm_set_strip_width(self._h, int(w)), "smt_crossarm_set_strip_width")
+
+    def set_occupancy(self, waves_per_simd):
+        """Aggregation waves per SIMD: 3, 4 or 5 (an LDS claim per workgroup), 0 = no limit (default)."""
+        check(lib().smt_crossarm_set_occupancy(self._h, int(waves_per_simd)), "smt_crossarm_set_occupancy")
 
     def status(self):
         check(lib().smt_crossarm_status(self._h), "smt_crossarm_status")

@@ -262,6 +262,127 @@ template <> struct __attribute__((aligned(8))) vecf<2> { float v[2]; };
 template <> struct vecf<3> { float v[3]; };
 template <> struct __attribute__((aligned(16))) vecf<4> { float v[4]; };
 
+// ---- which pixels a workgroup owns ---------------------------------------------------------------------
+// Index arithmetic on the workgroup index, the strip width, the sweep mode and H, W.  The kernels, the launchers (grid
+// sizes) and the host-only smt_crossarm_selftest_grid all call the functions below, so the grid a launcher asks for and
+// the pixels a kernel reaches cannot drift apart unnoticed.  Workgroups b and b + 8 run on the same XCD
+// (MI355X_MICROARCH.md): XCD b % 8.  NW waves per workgroup throughout.
+constexpr int NW = NT / 64;
+
+// Plain walk (k_aggregate): wave wv of workgroup b owns pixel NW * b + wv, row-major.
+__host__ __device__ __forceinline__ long agg_plain_grid(int N) { return ((long)N + NW - 1) / NW; }
+__host__ __device__ __forceinline__ int agg_plain_map(unsigned b, int wv) { return (int)(b * NW + wv); }
+
+// Strip family (k_aggregate_pipe: PPW = 1 pixel per wave, k_aggregate_quad: PPW = QP): XCD x sweeps the column strips
+// x, x + 8, x + 16, ... of width SW row by row, a workgroup covering NW * PPW adjacent pixels of one row.
+template <int PPW>
+__host__ __device__ __forceinline__ int agg_strip_width(int requested)    // multiple of a workgroup's NW * PPW columns
+{
+    constexpr int bw = PPW * NW;
+    return ((requested + bw - 1) / bw) * bw;
+}
+template <int PPW>
+__host__ __device__ __forceinline__ long agg_strip_grid(int H, int W, int SW)
+{
+    const int nstrips = (W + SW - 1) / SW;
+    const int per_xcd = (nstrips + 7) / 8;               // strips per XCD
+    return 8l * per_xcd * (SW / (PPW * NW)) * H;
+}
+// wave wv of workgroup b: its row, its first column and the strip that holds it; false = owns no pixel
+template <int PPW>
+__host__ __device__ __forceinline__ bool agg_strip_map(unsigned b, int wv, int H, int W, int SW, int &row, int &col, int &strip)
+{
+    const int xcd = b & 7, slot = b >> 3;
+    const int gpr = SW / (PPW * NW);                     // workgroups per strip row
+    const int gps = gpr * H;                             // workgroups per strip
+    strip = xcd + 8 * (slot / gps);
+    const int g = slot % gps;
+    row = g / gpr; col = strip * SW + ((g % gpr) * NW + wv) * PPW;
+    return !(col >= W || strip * SW >= W);
+}
+
+// pixels of the wave's PPW that are columns of the image
+template <int PPW>
+__host__ __device__ __forceinline__ int agg_strip_clip(int W, int col) { return min(PPW, W - col); }
+
+// Tile family (k_aggregate_multi): a wave owns a tile of TH rows x QC = 1 << TWS columns, a workgroup wx x wy tiles
+// (wx * wy = NW: narrow strips stack the waves vertically), i.e. one band of wy * TH rows of one strip's gpr column
+// blocks.  Strip width 8 / 16 / a multiple of 32: 8-wide tiles sit 1x4, 2x2 or 4x1, 4-wide tiles 2x2 at width 8 and
+// 4x1 from 16 on.
+__host__ __device__ __forceinline__ int agg_tile_width(int requested)
+{
+    return requested <= 8 ? 8 : requested <= 16 ? 16 : ((requested + 31) / 32) * 32;
+}
+struct AggTiles { int wx, wy, gpr, nband; };
+template <int TWS, int TH>
+__host__ __device__ __forceinline__ AggTiles agg_tiles(int H, int SW)
+{
+    constexpr int QC = 1 << TWS;
+    AggTiles t;
+    t.wx = min(NW, SW / QC); t.wy = NW / t.wx;
+    t.gpr = SW / (QC * t.wx);
+    t.nband = (H + t.wy * TH - 1) / (t.wy * TH);
+    return t;
+}
+// sweep 0: 8 XCDs x per_xcd strips each x gpr x nband workgroups; sweep 1: 8 XCDs x nstrips x gpr x ceil(nband / 8)
+__host__ __device__ __forceinline__ long agg_tile_grid(const AggTiles &t, int W, int SW, int sweep)
+{
+    const int nstrips = (W + SW - 1) / SW;
+    const int per_xcd = (nstrips + 7) / 8;
+    return sweep == 0 ? 8l * per_xcd * t.gpr * t.nband : 8l * nstrips * t.gpr * ((t.nband + 7) / 8);
+}
+// wave wv of workgroup b: top-left pixel of its tile (may lie off the image: agg_tile_clip); returns the tile geometry
+// it used
+template <int TWS, int TH>
+__host__ __device__ __forceinline__ AggTiles agg_tile_map(unsigned b, int wv, int H, int SW, int sweep, int &row, int &col)
+{
+    constexpr int QC = 1 << TWS;
+    const int xcd = b & 7, slot = b >> 3;
+    const AggTiles t = agg_tiles<TWS, TH>(H, SW);
+    const int wx = t.wx, wy = t.wy, gpr = t.gpr, nband = t.nband;
+    if (sweep == 0) {
+        // strips interleaved over the XCDs: XCD x sweeps strips x, x+8, ... top to bottom
+        const int gps = gpr * nband;
+        const int strip = xcd + 8 * (slot / gps);
+        const int g = slot % gps;
+        row = ((g / gpr) * wy + wv / wx) * TH;
+        col = strip * SW + ((g % gpr) * wx + (wv % wx)) * QC;
+    } else {
+        // XCD x owns the x-th contiguous band of rows and sweeps it strip by strip: the column halo
+        // between neighbouring strips stays inside one XCD's L2 instead of being fetched by two
+        const int nbx = (nband + 7) >> 3;              // workgroup rows per XCD
+        const int gps = gpr * nbx;
+        const int strip = slot / gps;
+        const int g = slot % gps;
+        row = ((xcd * nbx + g / gpr) * wy + wv / wx) * TH;
+        col = strip * SW + ((g % gpr) * wx + (wv % wx)) * QC;
+    }
+    return t;
+}
+// rows and columns of the tile at (row, col) that are pixels of the image; false = none, and the tile is moved to
+// pixel (0, 0) with no rows and no columns (a wave that stays for its workgroup's barriers reads nothing off the image)
+template <int TWS, int TH>
+__host__ __device__ __forceinline__ bool agg_tile_clip(int H, int W, int &row, int &col, int &nrow, int &ncol)
+{
+    constexpr int QC = 1 << TWS;
+    if (row >= H || col >= W) {
+        row = 0; col = 0;
+        ncol = 0; nrow = 0;
+        return false;
+    } else {
+        ncol = min(QC, W - col);
+        nrow = min(TH, H - row);
+    }
+    return true;
+}
+
+// strip width a handle starts with / set_variant selects: the lock-step kernels (7 .. 9, 11 .. 13) want their four waves
+// stacked vertically (8 columns x 8 rows per workgroup: the waves then walk the same columns); the free-running ones
+// measure best with 16-column strips
+constexpr int AGG_MAX_STRIP_WIDTH = 4096;
+inline int agg_default_width(int variant) { return variant >= 7 ? 8 : 16; }
+inline bool agg_width_ok(int w) { return w >= 4 && !(w & 3) && w <= AGG_MAX_STRIP_WIDTH; }
+
 // one wave per pixel; lane owns d = lane*C .. lane*C+C-1 (masked when >= D)
 template <int C, int ORDER>
 __global__ void __launch_bounds__(NT) k_aggregate(const float *__restrict__ vin, float *__restrict__ vout,
@@ -273,7 +394,7 @@ __global__ void __launch_bounds__(NT) k_aggregate(const float *__restrict__ vin,
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int N = H * W;
-    const int p = blockIdx.x * (NT / 64) + wv;
+    const int p = agg_plain_map(blockIdx.x, wv);
     if (p >= N) return;
     const int i = p / W, j = p - i * W;
     const int Ll = armL[p], Rr = armR[p], up = armT[p], dn = armB[p];
@@ -349,13 +470,8 @@ __global__ void __launch_bounds__(NT) k_aggregate_pipe(const float *__restrict__
     // their rectangles' union stays inside that XCD's 4 MB L2.
     int p;
     {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int gpr = SW / (NT / 64);                  // 4-pixel groups per strip row
-        const int gps = gpr * H;                         // groups per strip
-        const int strip = xcd + 8 * (slot / gps);
-        const int g = slot % gps;
-        const int row = g / gpr, col = strip * SW + (g % gpr) * (NT / 64) + wv;
-        if (col >= W || strip * SW >= W) return;
+        int row, col, strip;
+        if (!agg_strip_map<1>(blockIdx.x, wv, H, W, SW, row, col, strip)) return;
         p = row * W + col;
     }
     const int Ll = __builtin_amdgcn_readfirstlane(armL[p]), Rr = __builtin_amdgcn_readfirstlane(armR[p]);
@@ -389,10 +505,15 @@ __global__ void __launch_bounds__(NT) k_aggregate_pipe(const float *__restrict__
     if (!ub) {
         // fast path: every tap is inside the plane.  Lanes compute the byte offsets of the next 64
         // taps in parallel (one division per 64 taps); the tap loop is readlane + load + adds.
+        // o = n / nI through one float multiply, off by at most one and fixed below.  With e = 2^-24: (float)n = n + err(n),
+        // |err(n)| <= n e (0 below 2^24), rI = (1 + d1) / nI and the product rounds once more, so the computed value is
+        // within o' (2 e + e^2) + |err(n)| / nI of o' = n / nI; o' < nO, |err(n)| / nI < nO e.  The truncated result is
+        // floor(o') or floor(o') +- 1 while that bound, about nO 2^-23 + err(n) / nI, stays below 1: it does for nO <= 16383,
+        // i.e. for every arm length smt_crossarm_load_arm_maps lets through (<= 8191), where it is below 0.004.
         const float rI = 1.0f / (float)nI;
         for (int n0 = 0; n0 < total; n0 += 64) {
             const int n = n0 + lane;
-            int o = (int)((float)n * rI);                // n < 4761, nI <= 69: off by at most one, fixed below
+            int o = (int)((float)n * rI);
             int t = n - o * nI;
             if (t < 0) { o--; t += nI; }
             if (t >= nI) { o++; t -= nI; }
@@ -464,15 +585,10 @@ __global__ void __launch_bounds__(NT) k_aggregate_quad(const float *__restrict__
     const int N = H * W;
     int p0, nlive;
     {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int gpr = SW / (QP * (NT / 64));           // blocks per strip row
-        const int gps = gpr * H;
-        const int strip = xcd + 8 * (slot / gps);
-        const int g = slot % gps;
-        const int row = g / gpr, col = strip * SW + ((g % gpr) * (NT / 64) + wv) * QP;
-        if (col >= W || strip * SW >= W) return;
+        int row, col, strip;
+        if (!agg_strip_map<QP>(blockIdx.x, wv, H, W, SW, row, col, strip)) return;
         p0 = row * W + col;
-        nlive = min(QP, W - col);
+        nlive = agg_strip_clip<QP>(W, col);
     }
     int oa[QP], ob[QP], ia[QP], ib[QP], cnt[QP];
     int omin = INT_MAX, omax = INT_MIN, imin = INT_MAX, imax = INT_MIN;
@@ -711,41 +827,15 @@ __global__ void __launch_bounds__(NT, (SKIP == 6 ? (C <= 2 ? 5 : C == 3 ? 4 : 3)
     {
         // XCD x = blockIdx%8 owns the column strips x, x+8, ... of width SW; a workgroup covers
         // wx*8 columns by wy*QR rows (wx*wy = 4 waves), so narrow strips stack the waves vertically.
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int wx = min(NT / 64, SW / QC), wy = (NT / 64) / wx;
-        const int gpr = SW / (QC * wx);
-        const int nband = (H + wy * TH - 1) / (wy * TH);
+        // (agg_tile_map, shared with the launcher and the host self-test)
         int row, col;
-        if (sweep == 0) {
-            // strips interleaved over the XCDs: XCD x sweeps strips x, x+8, ... top to bottom
-            const int gps = gpr * nband;
-            const int strip = xcd + 8 * (slot / gps);
-            const int g = slot % gps;
-            row = ((g / gpr) * wy + wv / wx) * TH;
-            col = strip * SW + ((g % gpr) * wx + (wv % wx)) * QC;
-        } else {
-            // XCD x owns the x-th contiguous band of rows and sweeps it strip by strip: the column halo
-            // between neighbouring strips stays inside one XCD's L2 instead of being fetched by two
-            const int nbx = (nband + 7) >> 3;              // workgroup rows per XCD
-            const int gps = gpr * nbx;
-            const int strip = slot / gps;
-            const int g = slot % gps;
-            row = ((xcd * nbx + g / gpr) * wy + wv / wx) * TH;
-            col = strip * SW + ((g % gpr) * wx + (wv % wx)) * QC;
-        }
+        const AggTiles tl = agg_tile_map<TWS, TH>(blockIdx.x, wv, H, SW, sweep, row, col);
         if (SYNC) {
-            const int roff = (wv / wx) * TH, coff = (wv % wx) * QC;
+            const int roff = (wv / tl.wx) * TH, coff = (wv % tl.wx) * QC;
             ooff = (ORDER == 0) ? coff : roff;
             ioff = (ORDER == 0) ? roff : coff;
         }
-        if (row >= H || col >= W) {
-            if (!SYNC) return;
-            row = 0; col = 0;                              // stays for the barriers; owns no pixel
-            ncol = 0; nrow = 0;
-        } else {
-            ncol = min(QC, W - col);
-            nrow = min(TH, H - row);
-        }
+        if (!agg_tile_clip<TWS, TH>(H, W, row, col, nrow, ncol) && !SYNC) return;   // SYNC: stays for the barriers; owns no pixel
         p0 = row * W + col;
     }
     const int so = (ORDER == 0) ? 1 : W, si = (ORDER == 0) ? W : 1;
@@ -1358,7 +1448,7 @@ struct smt_crossarm {
     int variant;         // aggregation kernel variant (test / tuning hook)
     int strip_w;         // column-strip width of the XCD-aware pixel order (variants 0 and 2)
     int strip_w8;        // the same for variant 3 (8 pixels per wave)
-    int sweep;           // 0: strips interleaved over XCDs, 1: each XCD owns a band of rows (variants 3-5)
+    int sweep;           // 0: strips interleaved over XCDs, 1: each XCD owns a band of rows (variants 3-13)
     float *member;       // 256 x 8 membership flags for variant 3
     uint16_t *cand;      // [4][H][W] arm candidates {threshold still tau, already tau_low} (mask-based arm kernels)
     bool arm_walk;       // test hook: use the neighbour-by-neighbour kernels even when the masks apply
@@ -1383,7 +1473,7 @@ SMT_API int smt_crossarm_create(int H, int W, int D, const smt_crossarm_params *
     smt_crossarm *h = new (std::nothrow) smt_crossarm();
     if (!h) return SMT_ERR_ALLOC;
     h->device = smt_current_device();
-    h->H = H; h->W = W; h->D = D; h->strip_w = 16; h->strip_w8 = 8; h->variant = 13;
+    h->H = H; h->W = W; h->D = D; h->variant = 13; h->strip_w = agg_default_width(0); h->strip_w8 = agg_default_width(h->variant);
     {
         // default: no limit (6 waves per SIMD from the register count), see smt_crossarm_set_occupancy; SMT_AGG_WAVES overrides
         static const int env_waves = [] { const char *e = getenv("SMT_AGG_WAVES"); return e ? atoi(e) : -1; }();
@@ -1558,12 +1648,8 @@ SMT_API int smt_crossarm_arm_maps(smt_crossarm *h, int **l, int **r, int **t, in
 template <int ORDER, int QP>
 static void launch_agg_quad(smt_crossarm *h, const float *vin, float *vout, float *disp)
 {
-    int SW = h->strip_w;
-    const int bw = QP * (NT / 64);
-    SW = ((SW + bw - 1) / bw) * bw;
-    const int nstrips = (h->W + SW - 1) / SW;
-    const int per_xcd = (nstrips + 7) / 8;
-    dim3 grid((unsigned)(8 * per_xcd * (SW / bw) * h->H));
+    const int SW = agg_strip_width<QP>(h->strip_w);
+    dim3 grid((unsigned)agg_strip_grid<QP>(h->H, h->W, SW));
     const int C = (h->D + 63) / 64;
     const bool full = (h->D == 64 * C);
     int *ub = h->flip + 4;
@@ -1586,17 +1672,9 @@ static void launch_agg_quad(smt_crossarm *h, const float *vin, float *vout, floa
 template <int ORDER, int QR, int SKIP, int TWS = 3>
 static void launch_agg_multi(smt_crossarm *h, const float *vin, float *vout, float *disp)
 {
-    // strip width 8 / 16 / multiple of 32: the 4 waves of a workgroup sit 1x4, 2x2 or 4x1 (tiles 8 wide; 4-wide
-    // tiles: 2x2 at strip width 8, 4x1 from 16 on)
-    constexpr int TW = 1 << TWS, TH = (8 * QR) >> TWS;
-    int SW = h->strip_w8;
-    SW = SW <= 8 ? 8 : SW <= 16 ? 16 : ((SW + 31) / 32) * 32;
-    const int wx = SW / TW < 4 ? SW / TW : 4, wy = 4 / wx;
-    const int nstrips = (h->W + SW - 1) / SW;
-    const int per_xcd = (nstrips + 7) / 8;
-    const int nband = (h->H + wy * TH - 1) / (wy * TH);
-    dim3 grid(h->sweep == 0 ? (unsigned)(8 * per_xcd * (SW / (TW * wx)) * nband)
-                            : (unsigned)(8 * nstrips * (SW / (TW * wx)) * ((nband + 7) / 8)));
+    constexpr int TH = (8 * QR) >> TWS;
+    const int SW = agg_tile_width(h->strip_w8);
+    dim3 grid((unsigned)agg_tile_grid(agg_tiles<TWS, TH>(h->H, SW), h->W, SW, h->sweep));
     const int C = (h->D + 63) / 64;
     const bool full = (h->D == 64 * C);
     int *ub = h->flip + 4;
@@ -1628,10 +1706,8 @@ static void launch_agg_multi(smt_crossarm *h, const float *vin, float *vout, flo
 template <int ORDER>
 static void launch_agg_pipe(smt_crossarm *h, const float *vin, float *vout, float *disp)
 {
-    const int SW = h->strip_w;                           // strip width (multiple of 4)
-    const int nstrips = (h->W + SW - 1) / SW;
-    const int per_xcd = (nstrips + 7) / 8;               // strips per XCD
-    dim3 grid((unsigned)(8 * per_xcd * (SW / 4) * h->H));
+    const int SW = agg_strip_width<1>(h->strip_w);       // strip width (multiple of 4)
+    dim3 grid((unsigned)agg_strip_grid<1>(h->H, h->W, SW));
     const int C = (h->D + 63) / 64;
     const bool full = (h->D == 64 * C);
     int *ub = h->flip + 4;
@@ -1654,8 +1730,7 @@ static void launch_agg_pipe(smt_crossarm *h, const float *vin, float *vout, floa
 template <int ORDER>
 static void launch_agg(smt_crossarm *h, const float *vin, float *vout, float *disp)
 {
-    const int N = h->H * h->W;
-    dim3 grid((N + 3) / 4);
+    dim3 grid((unsigned)agg_plain_grid(h->H * h->W));
     const int C = (h->D + 63) / 64;
     int *ub = h->flip + 4;
 #define SMT_AGG(CC)                                                                                   \
@@ -1747,15 +1822,13 @@ SMT_API int smt_crossarm_set_variant(smt_crossarm *h, int variant)
     if (!h || variant < 0 || variant > 13) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
     h->variant = variant;
-    // the lock-step kernel wants its four waves stacked vertically (8 columns x 8 rows per workgroup: the
-    // waves then walk the same columns); the free-running ones measure best with 16-column strips
-    h->strip_w8 = variant >= 7 ? 8 : 16;
+    h->strip_w8 = agg_default_width(variant);
     return SMT_OK;
 }
 
 SMT_API int smt_crossarm_set_strip_width(smt_crossarm *h, int w)
 {
-    if (!h || w < 4 || (w & 3)) return SMT_ERR_ARG;
+    if (!h || !agg_width_ok(w)) return SMT_ERR_ARG;     // above 4096 the 32-bit grid arithmetic of small images overflows
     smt_dev_guard dev_guard(h->device);
     h->strip_w = w; h->strip_w8 = w;
     return SMT_OK;
@@ -1787,6 +1860,99 @@ SMT_API int smt_crossarm_set_sweep(smt_crossarm *h, int sweep)
     smt_dev_guard dev_guard(h->device);
     h->sweep = sweep;
     return SMT_OK;
+}
+
+// Host-side check of the aggregation's workgroup-to-pixel maps (the functions the kernels and the launchers run): see
+// include/smt.h.  Needs no GPU.
+namespace {
+
+// one more owner of pixel (i, j); false = it already had one
+inline bool grid_own(unsigned char *seen, int W, int i, int j)
+{
+    unsigned char &cell = seen[(size_t)i * W + j];
+    if (cell) return false;
+    cell = 1;
+    return true;
+}
+
+template <int PPW>
+int selftest_strips(int H, int W, int requested, unsigned char *seen)
+{
+    const int SW = agg_strip_width<PPW>(requested);
+    const long grid = agg_strip_grid<PPW>(H, W, SW);
+    if (grid <= 0 || grid > INT_MAX) return SMT_ERR_ARG;
+    for (long b = 0; b < grid; b++)
+        for (int wv = 0; wv < NW; wv++) {
+            int row, col, strip;
+            if (!agg_strip_map<PPW>((unsigned)b, wv, H, W, SW, row, col, strip)) continue;
+            if (row < 0 || row >= H || col < 0 || col >= W) return SMT_ERR_STATE;
+            if ((strip & 7) != (int)(b & 7) || col / SW != strip) return SMT_ERR_STATE;     // strip s on XCD s % 8
+            const int nlive = agg_strip_clip<PPW>(W, col);
+            for (int q = 0; q < nlive; q++)
+                if (!grid_own(seen, W, row, col + q)) return SMT_ERR_STATE;
+        }
+    return SMT_OK;
+}
+
+template <int TWS, int TH>
+int selftest_tiles(int H, int W, int requested, int sweep, unsigned char *seen)
+{
+    constexpr int QC = 1 << TWS;
+    const int SW = agg_tile_width(requested);
+    const AggTiles t = agg_tiles<TWS, TH>(H, SW);
+    if (t.wx < 1 || t.wx * t.wy != NW || t.gpr < 1 || t.gpr * t.wx * QC != SW) return SMT_ERR_STATE;
+    const long grid = agg_tile_grid(t, W, SW, sweep);
+    if (grid <= 0 || grid > INT_MAX) return SMT_ERR_ARG;
+    const int nbx = (t.nband + 7) >> 3;
+    for (long b = 0; b < grid; b++)
+        for (int wv = 0; wv < NW; wv++) {
+            int row, col, nrow, ncol;
+            const AggTiles tm = agg_tile_map<TWS, TH>((unsigned)b, wv, H, SW, sweep, row, col);
+            if (tm.wx != t.wx || tm.wy != t.wy || tm.gpr != t.gpr || tm.nband != t.nband) return SMT_ERR_STATE;
+            if (!agg_tile_clip<TWS, TH>(H, W, row, col, nrow, ncol)) continue;
+            if (row < 0 || col < 0 || nrow < 1 || ncol < 1 || nrow > TH || ncol > QC || row + nrow > H || col + ncol > W)
+                return SMT_ERR_STATE;
+            const int strip = col / SW, band = row / (t.wy * TH);       // where the tile lies, not what the map meant
+            if (sweep == 0 ? (strip & 7) != (int)(b & 7) : band / nbx != (int)(b & 7)) return SMT_ERR_STATE;
+            for (int r = 0; r < nrow; r++)
+                for (int c = 0; c < ncol; c++)
+                    if (!grid_own(seen, W, row + r, col + c)) return SMT_ERR_STATE;
+        }
+    return SMT_OK;
+}
+
+}  // namespace
+
+SMT_API int smt_crossarm_selftest_grid(int variant, int H, int W, int strip_width, int sweep)
+{
+    if (variant < 0 || variant > 13 || H <= 0 || W <= 0 || (size_t)H * W > (size_t)INT_MAX || sweep < 0 || sweep > 1 ||
+        (strip_width != 0 && !agg_width_ok(strip_width)))
+        return SMT_ERR_ARG;
+    const int w = strip_width ? strip_width : agg_default_width(variant);
+    const size_t N = (size_t)H * W;
+    unsigned char *seen = new (std::nothrow) unsigned char[N]();
+    if (!seen) return SMT_ERR_ALLOC;
+    int rc = SMT_OK;
+    // the kernel family and tile shape of each variant: the dispatch of smt_crossarm_aggregate
+    if (variant == 1) {
+        const long grid = agg_plain_grid((int)N);
+        for (long b = 0; b < grid && rc == SMT_OK; b++)
+            for (int wv = 0; wv < NW; wv++) {
+                const int p = agg_plain_map((unsigned)b, wv);
+                if (p < 0) { rc = SMT_ERR_STATE; break; }
+                if ((size_t)p >= N) continue;
+                if (!grid_own(seen, W, p / W, p % W)) { rc = SMT_ERR_STATE; break; }
+            }
+    }
+    else if (variant == 0) rc = selftest_strips<4>(H, W, w, seen);
+    else if (variant == 2) rc = selftest_strips<1>(H, W, w, seen);
+    else if (variant == 3) rc = selftest_tiles<3, 1>(H, W, w, sweep, seen);
+    else if (variant <= 9) rc = selftest_tiles<3, 2>(H, W, w, sweep, seen);
+    else rc = selftest_tiles<2, 4>(H, W, w, sweep, seen);
+    for (size_t p = 0; p < N && rc == SMT_OK; p++)
+        if (!seen[p]) rc = SMT_ERR_STATE;
+    delete[] seen;
+    return rc;
 }
 
 SMT_API int smt_crossarm_status(smt_crossarm *h)

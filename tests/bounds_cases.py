@@ -1248,6 +1248,7 @@ NOT_CALLER_BUFFER = {
     "smt_crossarm_set_arm_walk": "setter", "smt_crossarm_arm_maps": "accessor of library-owned maps",
     "smt_crossarm_status": "status", "smt_crossarm_set_variant": "setter", "smt_crossarm_set_strip_width": "setter",
     "smt_crossarm_set_occupancy": "setter", "smt_crossarm_set_sweep": "setter",
+    "smt_crossarm_selftest_grid": "host-only selftest",
     "smt_scanline_create": "create", "smt_scanline_create_on": "create", "smt_scanline_destroy": "destroy",
     "smt_scanline_set_stream": "setter", "smt_scanline_set_quirks": "setter",
     "smt_pipeline_default_params": "host struct out", "smt_pipeline_create": "create", "smt_pipeline_create_on": "create",
