@@ -264,6 +264,22 @@ int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep);
  * lut[ad] + lut[256+hd] it stands for (order preserved, equal ranks exactly when the bits are equal).  SMT_OK or
  * SMT_ERR_STATE; SMT_ERR_ARG unless both sigmas are > 0. */
 int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
+/* Shared maps-only form of smt_adcensus_compute_batch (adcensus.hip, k_cost_maps_shared).  For 3 <= j' and j' + d <= W-4
+ * the right view's cost(i, j', d) is bit for bit the left view's cost(i, j' + d, d), so for the pairs of a batch that
+ * write maps only (both maps requested, D <= 256, W >= D + 6) the right map of the columns 3 <= j' <= W-3-D is taken
+ * from keys (cost bits << 32 | d) that the left pass publishes; the other right columns keep the right-view arithmetic.
+ * Maps are those of the two-view kernel, bit for bit.  The host takes this form for D <= 192 and keeps the two-view
+ * kernel for 192 < D <= 256, where it measured slower.
+ *   SMT_MAPS_SHARED=0 in the environment (read at every call, like SMT_MAPS_CHUNKS / SMT_MAPS_KERNEL / SMT_OVERLAP)
+ *   keeps the two-view kernel everywhere, SMT_MAPS_SHARED=force takes the shared form for every D <= 256 with
+ *   W >= D + 6: same-process A/Bs and tests.  SMT_MAPS_KERNEL=rank selects the rank kernel as before.
+ * Test hook, host only (no GPU), exported by the library and declared in csrc/adcensus_internal.h:
+ *   int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
+ * walks the runs of K chunks per workgroup, the key ring, its flushes and the key-map merges of that form through the
+ * kernel's own index functions over pseudo-random left-view costs with many exact ties (seed % 3: 0 a palette with
+ * ties, 1 every cost equal, 2 mostly distinct).  SMT_OK iff every right pixel of the columns 3 .. W-3-D ends with the
+ * first minimum of its diagonal, written once, and every other right pixel is left to the right-view chunks, once;
+ * SMT_ERR_STATE otherwise; SMT_ERR_ARG unless H, W >= 1, 1 <= D <= 256, 1 <= K <= 64. */
 
 /* Synchronises the stream and returns SMT_ERR_DOMAIN if any pixel seen since the previous
  * smt_adcensus_status call (or since create) was not an integer in 0..255 (then those pairs' volumes

@@ -402,6 +402,44 @@ __device__ __forceinline__ void st_stream(__amdgpu_buffer_rsrc_t r, unsigned vof
     }
 }
 
+// ---- rules of the shared maps-only form (k_cost_maps_shared), host and device ----------------------------------------
+// For 3 <= j' and j' + d <= W-4 the right view's cost(i, j', d) is bit for bit the left view's cost(i, j' + d, d): the
+// edge-extended censuses equal the ordinary ones there, both column masks are all ones and the row masks are the same
+// row, and neither AD clamp acts.  So the right map of the IDENTITY SET of columns 3 <= j' <= W-3-D (every d < D) is
+// the first minimum along a diagonal of the left view's costs, which the left pass publishes as keys:
+//   key = cost bits << 32 | d; costs are >= +0, so the unsigned minimum is the smallest cost, then the smallest d --
+//   the reference's first strict minimum.  SH_NOKEY (all ones) is no key: d < 512.
+// Right pixels outside the set keep the VIEW 1 body, which runs over chunk 0 and the chunks from shared_right_tail()
+// on and writes only what is outside the set.  Runs of chunks are those of chunk_decode (below).
+#ifndef SMT_SHARED_KNOCKOUT
+#define SMT_SHARED_KNOCKOUT 0      // measurement builds only (wrong maps): 1 no LDS publishes, 2 no key-map merges
+#endif
+constexpr int SH_RING = 512;                                 // key ring, indexed by right column mod 512
+constexpr int SH_RING_N = SH_RING + 4;                       // + the spill slots of shared_ring_base()
+constexpr unsigned long long SH_NOKEY = ~0ull;
+__host__ __device__ inline int shared_id_hi(int W, int D) { return W - 3 - D; }           // the set is [3, hi]; empty when hi < 3
+__host__ __device__ inline bool shared_in_set(int c, int idhi) { return (unsigned)(c - 3) <= (unsigned)(idhi - 3) && idhi >= 3; }
+__host__ __device__ inline unsigned long long shared_key(unsigned cost_bits, int d) { return ((unsigned long long)cost_bits << 32) | (unsigned)d; }
+// right-view chunks that are still computed (set not empty): e = 0 is chunk 0, e >= 1 is chunk tail + e - 1
+__host__ __device__ inline int shared_right_tail(int W, int D) { const int b = (shared_id_hi(W, D) + 1) >> 6; return b < 1 ? 1 : b; }
+__host__ __device__ inline int shared_right_chunks(int nbx, int W, int D) { return 1 + nbx - shared_right_tail(W, D); }
+__host__ __device__ inline int shared_right_chunk(int e, int W, int D) { return e == 0 ? 0 : shared_right_tail(W, D) + e - 1; }
+// A lane publishes its C hypotheses d = dl .. dl+C-1 of left pixel j to the right columns t - k, t = j - dl: ring slot
+// base + (C-1-k) with base = (t - (C-1)) mod 512, one address computation per pixel.  A column c with c mod 512 < C-1
+// can therefore land in slot c mod 512 or in the spill slot 512 + c mod 512; the flush takes the minimum of the two.
+__host__ __device__ inline int shared_ring_base(int t, int C) { return (int)((unsigned)(t - (C - 1)) & (unsigned)(SH_RING - 1)); }
+// Columns flushed after left chunk bx of a run: those no later chunk of the run reaches, (64bx - D, 64bx + 64 - D], or
+// at the run's end everything still in the ring, (64bx - D, 64bx + 63]; both cut to the identity set.  Between two
+// flushes at most D + 127 <= 383 columns are live (D <= 256), so no two share a slot.
+__host__ __device__ inline void shared_flush_range(int bx, int D, bool end, int idhi, int &lo, int &hi)
+{
+    lo = 64 * bx - D + 1; hi = end ? 64 * bx + 63 : 64 * bx + 64 - D;
+    lo = lo < 3 ? 3 : lo; hi = hi > idhi ? idhi : hi;
+}
+// The whole diagonal j' .. j'+D-1 of right column c lies in the run's left columns [S, E]: the ring holds its final key,
+// written straight to the map.  Otherwise the key is partial and merged through the handle's key map.
+__host__ __device__ inline bool shared_complete(int c, int S, int E, int D) { return c >= S && c + D - 1 <= E; }
+
 struct __attribute__((aligned(16))) Anchor { uint64_t cen, mask; };
 
 // LDS of the maps-only kernel (k_cost_maps2p): its table plus the staged operands, one set shared by both views
@@ -433,11 +471,17 @@ template <int MODE> struct MapsCfg {
 // unused) and use the LDS of k_cost_maps2p (`ml`: staged operands in set `buf`, written by MapsStage, and the table the
 // kernel has filled: MODE 1 the 320-float LUT, MODE 2 the 256 x 64 rank table, Tables::rank).  MODE 2 stages the image values x64, so that v_sad_u16(va, vx, hd) is the rank
 // index 64*AD + hd, and its WTA key is rank << 16 | d: one wave min, no tie-break.
-template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME>
+// SHR (MODE_MAPS_FLOAT; k_cost_maps_shared).  VIEW 0: every hypothesis whose right column j - d is in the identity set
+// [3, idhi] also publishes its key to `ring` with an LDS 64-bit atomic min.  VIEW 1: the map columns [skip_lo, skip_hi]
+// are not written, and a wave whose pixels all lie inside does nothing.
+template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME, bool SHR = false>
 __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tables &T, float *__restrict__ vol,
                                                float *__restrict__ disp, int i, int bx,
-                                               MapsLds<C, MapsCfg<MODE>::TABN, MapsCfg<MODE>::NBUF> *ml = nullptr, int buf = 0)
+                                               MapsLds<C, MapsCfg<MODE>::TABN, MapsCfg<MODE>::NBUF> *ml = nullptr, int buf = 0,
+                                               unsigned long long *ring = nullptr, int idhi = 0, int skip_lo = 1, int skip_hi = 0)
 {
+    static_assert(!SHR || MODE == MODE_MAPS_FLOAT, "");
+    constexpr bool PUB = SHR && VIEW == 0, SKIP = SHR && VIEW == 1;
     constexpr bool STORE = MODE == MODE_VOLUME;
     constexpr unsigned VSCALE = MODE == MODE_MAPS_RANK ? 64u : 4u;
     constexpr int DM = 64 * C;                               // largest D this instantiation serves
@@ -521,7 +565,8 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
     const unsigned ooff = (unsigned)dlr * 4u;
     unsigned osoff = 0;                                      // scalar byte offset of the current pixel in the wave's run
     int res = 0;
-    const int npx = min(FPW, W - (j0 + p0));                 // uniform; may be <= 0
+    int npx = min(FPW, W - (j0 + p0));                       // uniform; may be <= 0
+    if (SKIP && j0 + p0 >= skip_lo && j0 + p0 + FPW - 1 <= skip_hi) npx = 0;
     __amdgpu_buffer_rsrc_t orsrc;
     if (STORE)
         orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(vol + ((size_t)i * W + j0 + p0) * D), 0,
@@ -530,8 +575,14 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
     // all ones and the two ANDs per hypothesis can be dropped (bit 63 is 0 in every table entry)
     const bool interior = (i >= 4) && (i < H - 4) && (j0 + p0 >= 3) && (j0 + p0 + npx - 1 <= W - 4);
 
-    auto run = [&](auto masked_tag) {
+    // every (pixel, hypothesis) of this wave publishes: no per-hypothesis column test
+    const bool allin = PUB && (j0 + p0) - (D - 1) >= 3 && j0 + p0 + npx - 1 <= idhi;
+    typedef __attribute__((address_space(3))) unsigned long long *lds_key_p;
+    const lds_key_p ring3 = (lds_key_p)ring;
+
+    auto run = [&](auto masked_tag, auto allin_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
+        constexpr bool ALLIN = decltype(allin_tag)::value;
         // The anchor entries are read at wave-uniform LDS addresses.  The two addresses live in VGPRs that advance
         // once per group of C pixels (the pixels of a group use immediate offsets); left to itself the compiler keeps
         // them in SGPRs and spends two v_mov per pixel to feed the ds_read.
@@ -612,6 +663,15 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                         const int wd = first * C + kk;       // wave-uniform
                         res = (lane == q) ? wd : res;
                     }
+                    if constexpr (PUB && SMT_SHARED_KNOCKOUT != 1) {
+                        const int tcol = (j0 + p0 + q) - dl;                 // right column of hypothesis k = 0
+                        const lds_key_p rp = ring3 + shared_ring_base(tcol, C);
+#pragma unroll
+                        for (int k = 0; k < C; k++)
+                            if (ok[k] && (ALLIN || shared_in_set(tcol - k, idhi)))
+                                (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
+                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                     // the new entry replaces the one that just left the window
                     const int ns = (VIEW == 0) ? (u + 1) % C : u % C;
                     rc[ns] = nc; rv[ns] = nv;
@@ -621,9 +681,15 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
             nx_a += 8u * C; nv_a += 2u * C;
         }
     };
-    if (interior) run(std::false_type{});
-    else run(std::true_type{});
-    if (disp && lane < npx) disp[(size_t)i * W + j0 + p0 + lane] = (float)res;
+    if constexpr (PUB) {
+        if (allin) { if (interior) run(std::false_type{}, std::true_type{}); else run(std::true_type{}, std::true_type{}); }
+        else { if (interior) run(std::false_type{}, std::false_type{}); else run(std::true_type{}, std::false_type{}); }
+    } else {
+        if (interior) run(std::false_type{}, std::false_type{});
+        else run(std::true_type{}, std::false_type{});
+    }
+    const int jw = j0 + p0 + lane;
+    if (disp && lane < npx && !(SKIP && jw >= skip_lo && jw <= skip_hi)) disp[(size_t)i * W + jw] = (float)res;
 }
 
 // Workgroup -> 64-pixel chunk.  The chunks of a launch form one linear space (view, row, chunk-in-row)
@@ -883,6 +949,129 @@ __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables 
     }
 }
 
+// One flush of the key ring (shared_flush_range's columns lo .. hi of row i, run [S, E]): complete keys go to the map,
+// partial ones to the handle's key map with one agent-scope atomic min each; the slots are reset.
+template <int C>
+__device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, int W, int D, int lo, int hi, int S, int E,
+                                             float *__restrict__ dispR, unsigned long long *__restrict__ keys)
+{
+    for (int c = lo + (int)threadIdx.x; c <= hi; c += NT) {
+        const int s = c & (SH_RING - 1);
+        unsigned long long k = ring[s];
+        ring[s] = SH_NOKEY;
+        if (s < C - 1) { k = min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
+        const size_t p = (size_t)i * W + c;
+        if (shared_complete(c, S, E, D)) dispR[p] = (float)(unsigned)k;
+        else if (k != SH_NOKEY && SMT_SHARED_KNOCKOUT != 2) atomicMin(&keys[p], k);
+    }
+}
+
+// Shared maps-only form: both maps of a pair from (nearly) one cost evaluation per hypothesis.  The first `nleft`
+// cost workgroups run the VIEW 0 body over runs of K consecutive chunks (chunk_decode over the left view alone) and
+// publish the keys of the identity set to a per-workgroup ring; a chunk's finished columns are flushed after the next
+// chunk's barrier, beside that chunk's arithmetic (their slots are disjoint, shared_flush_range), a run's last columns
+// between two barriers when the row or the workgroup ends.  The remaining cost workgroups run the VIEW 1 body over
+// the right view's edge chunks (shared_right_chunk) and write the columns outside the set.  k_shared_finish turns the
+// merged partial keys into map entries.  Table workgroups, LUT and staging are those of k_cost_maps2p.
+#ifndef SMT_SHARED_MIN_WAVES
+#define SMT_SHARED_MIN_WAVES 7     // waves per SIMD the register allocation must allow; measured 1 / 7 / 8: DESIGN.md section 4
+#endif
+template <int C, bool FULL>
+__global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(int H, int W, int D, Tables T, float *__restrict__ disp0,
+                                                         float *__restrict__ disp1, unsigned long long *__restrict__ keys,
+                                                         int nbx, int K, int nleft, int ncost, int nprep,
+                                                         const float *__restrict__ nL, const float *__restrict__ nR,
+                                                         Tables Tn, int ptx)
+{
+    static_assert(PNT == NT, "");
+    constexpr int MODE = MODE_MAPS_FLOAT;
+    constexpr int TABN = MapsCfg<MODE>::TABN, NBUF = MapsCfg<MODE>::NBUF;
+    __shared__ MapsLds<C, TABN, NBUF> lds;
+    __shared__ unsigned long long ring[SH_RING_N];
+    uint16_t *s_tab = lds.tab;
+    long b = blockIdx.x;
+    if (nprep > 0) {
+        const FusedGrid f = fused_grid(ncost, nprep);
+        int idx;
+        const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
+        b = idx * 8 + (int)(blockIdx.x & 7);
+        if (table) {
+            uint32_t (*sw)[PSW] = (uint32_t (*)[PSW])s_tab;
+            if (b < nprep) prep_tile(nL, nR, H, W, Tn, (int)b % ptx, (int)b / ptx, ptx, sw, sw + PSR);
+            return;
+        }
+    }
+    const int tid = threadIdx.x;
+    for (int e = tid; e < 320; e += NT) ((float *)s_tab)[e] = T.lut[e];
+    const int Dd = FULL ? 64 * C : D;
+    const int idhi = shared_id_hi(W, Dd);
+    const bool right = b >= nleft;                                         // workgroup-uniform
+    if (right) b -= nleft;
+    else for (int e = tid; e < SH_RING_N; e += NT) ring[e] = SH_NOKEY;
+    const int nch = right ? shared_right_chunks(nbx, W, Dd) : nbx;
+    auto next = [&](int t, int &i, int &bx) {
+        int view;
+        if (t >= K || !chunk_decode(nch, H, 1, K, b, t, view, i, bx)) return K;
+        if (right) bx = shared_right_chunk(bx, W, Dd);
+        return t;
+    };
+    MapsStage<C, FULL> st;
+    int i = 0, bx = 0;
+    int t = next(0, i, bx);
+    if (t < K) st.load(right ? 1 : 0, i, bx, W, D, T);
+    int buf = 0;
+    if (right) {
+        while (t < K) {
+            st.template store<4u>(lds, buf, D);
+            __syncthreads();
+            const int ci = i, cbx = bx;
+            t = next(t + 1, i, bx);
+            if (t < K) st.load(1, i, bx, W, D, T);
+            cost_fast_body<C, 1, FULL, true, MODE, true>(H, W, D, T, nullptr, disp1, ci, cbx, &lds, buf, nullptr, idhi, 3, idhi);
+            buf ^= 1;
+        }
+        return;
+    }
+    // pending flush: the previous chunk's columns (all workgroup-uniform)
+    bool pend = false, pend_end = false;
+    int pi = 0, plo = 0, phi = -1, pS = 0, pE = 0;
+    int S = -1;                                                            // first left column of the current run
+    while (t < K) {
+        st.template store<4u>(lds, buf, D);
+        __syncthreads();                                                   // every wave has published the previous chunk
+        if (pend) {
+            shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, disp1, keys);
+            if (pend_end) __syncthreads();                                 // the next run may use any slot
+        }
+        const int ci = i, cbx = bx;
+        t = next(t + 1, i, bx);
+        if (t < K) st.load(0, i, bx, W, D, T);
+        if (S < 0) S = 64 * cbx;
+        cost_fast_body<C, 0, FULL, true, MODE, true>(H, W, D, T, nullptr, disp0, ci, cbx, &lds, buf, ring, idhi);
+        pend = true; pend_end = t >= K || i != ci;                         // consecutive chunks: same row <=> same run
+        pi = ci; pS = S; pE = 64 * cbx + 63;
+        shared_flush_range(cbx, Dd, pend_end, idhi, plo, phi);
+        if (pend_end) S = -1;
+        buf ^= 1;
+    }
+    if (pend) {
+        __syncthreads();
+        shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, disp1, keys);
+    }
+}
+
+// Partial keys of the shared form -> map entries; the consumed keys are reset for the next pair.
+__global__ void __launch_bounds__(256) k_shared_finish(unsigned long long *__restrict__ keys, int H, int W, int idhi,
+                                                       float *__restrict__ dispR)
+{
+    const int n = idhi - 2;                                                // columns 3 .. idhi
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (size_t)H * n) return;
+    const size_t p = (q / n) * W + 3 + q % n;
+    const unsigned long long k = keys[p];
+    if (k != SH_NOKEY) { dispR[p] = (float)(unsigned)k; keys[p] = SH_NOKEY; }
+}
+
 // Store-only twin of k_cost_fast2<C, true>: the same grid, workgroup -> chunk order and streaming stores
 // of 64*C*4 bytes per pixel-wave, no tables, no arithmetic.  What it reaches on the handle's own volumes
 // is the ceiling the memory system gives this store pattern in this process (smt_adcensus_diag).
@@ -962,6 +1151,7 @@ struct smt_adcensus {
     float store_mode_ms[2];   // calibration: kernel ms with streaming / plain stores (0: not calibrated)
     int place_tries;     // candidate volume pairs tried by place_volumes
     float place_ms;      // store-only time of the pair that was kept (0: no search)
+    unsigned long long *skeys;   // [H][W] key map of the shared maps-only form: SH_NOKEY between launches
 };
 
 SMT_API const char *smt_strerror(int s)
@@ -1231,6 +1421,7 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
         }
         alloc((void **)&h->TS[t].mask, N * 8);
     }
+    alloc((void **)&h->skeys, N * 8);
     h->T = h->TS[0];
     if (rc != SMT_OK) { smt_adcensus_destroy(h); return rc; }
     if (hipStreamCreateWithFlags(&h->prep_stream, hipStreamNonBlocking) != hipSuccess ||
@@ -1254,7 +1445,7 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
     // GetPtrLeft/Right before the first Compute* reads zeros
     if (!rank_ok || hipMemcpy(h->TS[0].lut, lut, sizeof(lut), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(h->vol[0], 0, V * 4) != hipSuccess || hipMemset(h->vol[1], 0, V * 4) != hipSuccess ||
-        hipMemset(h->TS[0].flag, 0, 4) != hipSuccess) {
+        hipMemset(h->TS[0].flag, 0, 4) != hipSuccess || hipMemset(h->skeys, 0xFF, N * 8) != hipSuccess) {
         smt_adcensus_destroy(h);
         return SMT_ERR_HIP;
     }
@@ -1304,6 +1495,7 @@ SMT_API int smt_adcensus_destroy(smt_adcensus *h)
         (void)hipFree(h->TS[t].mask);
     }
     (void)hipFree(h->TS[0].lut); (void)hipFree(h->TS[0].rank); (void)hipFree(h->TS[0].flag);
+    (void)hipFree(h->skeys);
     if (h->ev) {
         for (int k = 0; k < SMT_TIMING_SLOTS * 4; k++) (void)hipEventDestroy(h->ev[k]);
         delete[] h->ev_merged;
@@ -1353,6 +1545,24 @@ static int maps_chunks()
     return k >= 1 && k <= 64 ? k : 4;
 }
 
+// SMT_MAPS_SHARED=0 in the environment (read at every call) keeps the two-view k_cost_maps2p where the shared form
+// (k_cost_maps_shared) would run: same-process A/Bs and tests.
+static bool maps_shared()
+{
+    const char *env = getenv("SMT_MAPS_SHARED");
+    return !(env && env[0] == '0' && env[1] == 0);
+}
+// The shapes the shared form serves: an identity set that is not empty, and D <= 192.  With four hypotheses per lane
+// (192 < D <= 256) the lanes' publishes are 32 bytes apart, a 4-way bank conflict, the kernel needs 93 VGPRs and the
+// identity set is a smaller part of the row; measured at 1242 x 375 D = 256 it loses 7 % to the two-view kernel
+// (DESIGN.md section 4).  SMT_MAPS_SHARED=force in the environment takes it wherever the set is not empty (tests).
+static bool maps_shared_shape(int W, int D)
+{
+    if (shared_id_hi(W, D) < 3) return false;
+    const char *env = getenv("SMT_MAPS_SHARED");
+    return D <= 192 || (env && env[0] == 'f');
+}
+
 template <int C, bool FULL>
 static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL, const float *nR, bool maps)
 {
@@ -1372,6 +1582,20 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
         }
         const Tables &Tn = h->TS[(h->n_pairs + 1) & 1];
         const char *env = getenv("SMT_MAPS_KERNEL");
+        const int idhi = shared_id_hi(h->W, h->D);
+        if (!(env && env[0] == 'r') && dL && dR && maps_shared_shape(h->W, h->D) && maps_shared()) {
+            // left-view runs + the right view's edge chunks, then the finishing launch, all on the caller's stream
+            const int nleft = maps_groups(nbx, h->H, 1, K);
+            const int ncs = nleft + maps_groups(shared_right_chunks(nbx, h->W, h->D), h->H, 1, K);
+            const unsigned gs = nL ? 8u * (unsigned)fused_grid(ncs, nprep).groups : (unsigned)ncs;
+            hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
+                               h->skeys, nbx, K, nleft, ncs, nprep, nL, nR, Tn, ptx);
+            const size_t nf = (size_t)h->H * (idhi - 2);
+            if (SMT_SHARED_KNOCKOUT != 2)
+                hipLaunchKernelGGL(k_shared_finish, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, h->stream, h->skeys, h->H,
+                                   h->W, idhi, dR);
+            return;
+        }
         if (env && env[0] == 'r')
             hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_RANK>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
                                h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx);
@@ -1636,6 +1860,120 @@ SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
     for (long c = 0; c < nb && rc == SMT_OK; c++) if (!seen[c]) rc = SMT_ERR_STATE;
     delete[] seen;
     if (rc == SMT_OK && nprep > 0) rc = smt_adcensus_selftest_fused_grid(ncost, nprep);
+    return rc;
+}
+
+// Host-side walk of the shared maps-only form (k_cost_maps_shared + k_shared_finish) over pseudo-random left-view costs
+// with many exact ties, through the kernel's own index functions: chunk_decode / maps_groups for the runs, the lane ->
+// hypothesis split and shared_ring_base for the publishes, shared_flush_range / shared_complete for the flushes (a
+// chunk's flush is applied after the next chunk's publishes, as on the device, and must not meet a slot those touched),
+// the key map for the partial keys, shared_right_chunk(s) for the VIEW 1 chunks.  SMT_OK iff every identity-set right
+// pixel ends with the first minimum of its diagonal, written exactly once, and every other right pixel is written by
+// the VIEW 1 chunks alone, exactly once.  Needs no GPU.
+SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed)
+{
+    if (H <= 0 || W <= 0 || D <= 0 || D > 256 || K < 1 || K > 64 || (long)H * W > (1L << 24)) return SMT_ERR_ARG;
+    const int C = (D + 63) / 64, nbx = (W + FTJ - 1) / FTJ, idhi = shared_id_hi(W, D);
+    const size_t N = (size_t)H * W;
+    // costs: a small palette of floats >= +0 (ties), every cost equal (seed % 3 == 1), or mostly distinct
+    static const float pal[] = {0.0f, 0.0f, 0.25f, 0.25f, 1.5f, 0.7265625f, 0.7265625f, 1.9999999f, 0.25f, 1e-30f};
+    auto cost_bits = [&](int i, int j, int d) {
+        uint32_t x = (uint32_t)i * 0x9E3779B1u ^ (uint32_t)j * 0x85EBCA77u ^ (uint32_t)d * 0xC2B2AE3Du ^ seed * 0x27D4EB2Fu;
+        x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
+        float f = seed % 3 == 1 ? 0.5f : (seed % 3 == 2 && (x & 3)) ? (float)(x >> 12) * (1.0f / 1048576.0f) : pal[(x >> 4) % 10];
+        uint32_t bits;
+        memcpy(&bits, &f, 4);
+        return bits;
+    };
+    unsigned long long *keys = new (std::nothrow) unsigned long long[N];
+    unsigned *val = new (std::nothrow) unsigned[N]();
+    unsigned char *nw = new (std::nothrow) unsigned char[N]();           // writers of each right pixel: shared path
+    unsigned char *nv = new (std::nothrow) unsigned char[N]();           //                              VIEW 1 path
+    int rc = (keys && val && nw && nv) ? SMT_OK : SMT_ERR_ALLOC;
+    for (size_t p = 0; rc == SMT_OK && p < N; p++) keys[p] = SH_NOKEY;
+    if (rc == SMT_OK && idhi >= 3) {
+        const int nleft = maps_groups(nbx, H, 1, K);
+        unsigned long long ring[SH_RING_N];
+        long stamp[SH_RING_N];                                            // serial of the last chunk that published to a slot
+        for (long b = 0; b < nleft && rc == SMT_OK; b++) {
+            for (int e = 0; e < SH_RING_N; e++) { ring[e] = SH_NOKEY; stamp[e] = -1; }
+            auto flush = [&](int i, int lo, int hi, int S, int E, long serial, bool end) {
+                for (int c = lo; c <= hi; c++) {
+                    const int s = c & (SH_RING - 1);
+                    if (!end && (stamp[s] > serial || (s < C - 1 && stamp[SH_RING + s] > serial))) rc = SMT_ERR_STATE;
+                    unsigned long long k = ring[s];
+                    ring[s] = SH_NOKEY;
+                    if (s < C - 1) { k = std::min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
+                    const size_t p = (size_t)i * W + c;
+                    if (shared_complete(c, S, E, D)) {
+                        if (k == SH_NOKEY) rc = SMT_ERR_STATE;
+                        val[p] = (unsigned)k; nw[p]++;
+                    } else if (k != SH_NOKEY) keys[p] = std::min(keys[p], k);
+                }
+            };
+            bool pend = false, pend_end = false;
+            int pi = 0, plo = 0, phi = -1, pS = 0, pE = 0, S = -1;
+            long serial = 0;
+            int view, i, bx, ni, nbxn;
+            bool have = chunk_decode(nbx, H, 1, K, b, 0, view, i, bx);
+            for (int t = 0; have && rc == SMT_OK; t++, serial++) {
+                if (pend && pend_end) { flush(pi, plo, phi, pS, pE, serial - 1, true); pend = false; }
+                const bool more = t + 1 < K && chunk_decode(nbx, H, 1, K, b, t + 1, view, ni, nbxn);
+                if (S < 0) S = 64 * bx;
+                for (int q = 0; q < FTJ && 64 * bx + q < W; q++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int k = 0; k < C; k++) {
+                            const int dl = lane * C, d = dl + k, tcol = 64 * bx + q - dl;
+                            if (d >= D || !shared_in_set(tcol - k, idhi)) continue;
+                            const int s = shared_ring_base(tcol, C) + (C - 1 - k);
+                            ring[s] = std::min(ring[s], shared_key(cost_bits(i, 64 * bx + q, d), d));
+                            stamp[s] = serial;
+                        }
+                if (pend) flush(pi, plo, phi, pS, pE, serial - 1, false);     // beside this chunk's publishes on the device
+                pend = true; pend_end = !more || ni != i;
+                if (more && ni == i && nbxn != bx + 1) rc = SMT_ERR_STATE;
+                pi = i; pS = S; pE = 64 * bx + 63;
+                shared_flush_range(bx, D, pend_end, idhi, plo, phi);
+                if (pend_end) S = -1;
+                have = more; i = ni; bx = nbxn;
+            }
+            if (pend && rc == SMT_OK) flush(pi, plo, phi, pS, pE, serial - 1, true);
+            for (int e = 0; e < SH_RING_N; e++) if (ring[e] != SH_NOKEY) rc = SMT_ERR_STATE;   // nothing left behind
+        }
+        // the finishing launch
+        for (int i = 0; i < H; i++)
+            for (int c = 3; c <= idhi; c++) {
+                const size_t p = (size_t)i * W + c;
+                if (keys[p] != SH_NOKEY) { val[p] = (unsigned)keys[p]; nw[p]++; keys[p] = SH_NOKEY; }
+            }
+        // the VIEW 1 workgroups
+        const int nre = shared_right_chunks(nbx, W, D), nright = maps_groups(nre, H, 1, K);
+        for (long b = 0; b < nright; b++)
+            for (int t = 0; t < K; t++) {
+                int view, i, e;
+                if (!chunk_decode(nre, H, 1, K, b, t, view, i, e)) break;
+                const int bx = shared_right_chunk(e, W, D);
+                if (bx < 0 || bx >= nbx) { rc = SMT_ERR_STATE; break; }
+                for (int q = 0; q < FTJ && 64 * bx + q < W; q++)
+                    if (!(64 * bx + q >= 3 && 64 * bx + q <= idhi)) nv[(size_t)i * W + 64 * bx + q]++;
+            }
+    }
+    for (int i = 0; i < H && rc == SMT_OK; i++)
+        for (int c = 0; c < W && rc == SMT_OK; c++) {
+            const size_t p = (size_t)i * W + c;
+            if (idhi < 3) { if (nw[p] || nv[p]) rc = SMT_ERR_STATE; continue; }   // the two-view kernel serves this shape
+            if (!shared_in_set(c, idhi)) { if (nw[p] != 0 || nv[p] != 1) rc = SMT_ERR_STATE; continue; }
+            float mn = 0.0f;
+            int want = 0;
+            for (int d = 0; d < D; d++) {
+                const uint32_t bits = cost_bits(i, c + d, d);
+                float f;
+                memcpy(&f, &bits, 4);
+                if (d == 0 || f < mn) { mn = f; want = d; }
+            }
+            if (nw[p] != 1 || nv[p] != 0 || val[p] != (unsigned)want || keys[p] != SH_NOKEY) rc = SMT_ERR_STATE;
+        }
+    delete[] keys; delete[] val; delete[] nw; delete[] nv;
     return rc;
 }
 

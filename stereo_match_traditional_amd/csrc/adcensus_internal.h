@@ -15,3 +15,5 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
                          bool last_volumes);
 // Both views of this handle take the register-window kernels (D <= 256), so sched 2 and the maps-only kernel apply.
 bool adcensus_fused_both_views(const smt_adcensus *h);
+// Host-only selftest of the shared maps-only form's run / ring / flush / merge arithmetic (documented in include/smt.h).
+SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
