@@ -197,8 +197,12 @@ int smt_adcensus_compute(smt_adcensus *h, const float *L, const float *R, int vi
  * [pairs][H][W].  The volumes are reused per pair and after the call hold the LAST pair's costs:
  * with both views and D <= 256 the volumes of pairs 0 .. pairs-2 are not written at all (those pairs
  * take a maps-only kernel; a view whose map is NULL then does no cost work), elsewhere they are
- * overwritten by the next pair.  SMT_BATCH_VOLUMES=all in the environment (read at every call)
- * writes every pair's volumes as before, for same-process comparisons.  This is the sharding unit of the multi-GPU configuration.  The census tables
+ * overwritten by the next pair.  There, until smt_adcensus_volume has been called on the handle once, the last
+ * pair takes the maps-only kernel too and its volumes are written by the first smt_adcensus_volume call that
+ * follows the batch (dropped if another compute comes first); once a pointer has been lent, every batch writes
+ * its last pair's volumes itself.  SMT_BATCH_VOLUMES in the environment (read at every call), for
+ * same-process comparisons: `last` writes the last pair's volumes in the batch whatever has been lent, `all`
+ * writes every pair's.  This is the sharding unit of the multi-GPU configuration.  The census tables
  * are double-buffered inside the handle: with both views and D <= 256 the table workgroups of pair
  * b+1 are spread through the grid of pair b's cost launch (one launch per pair, one stream); single
  * views and D > 256 build them on an internal stream beside pair b's cost kernel.  SMT_OVERLAP =
@@ -245,7 +249,11 @@ int smt_host_free(void *p);
 int smt_adcensus_host_selftest_schedule(int pairs, int chunk);
 
 /* GetPtrLeft / GetPtrRight (AD-Census.h:50-72): borrowed device pointer, valid until
- * destroy. view = SMT_VIEW_LEFT or SMT_VIEW_RIGHT. */
+ * destroy. view = SMT_VIEW_LEFT or SMT_VIEW_RIGHT.  The first call on a handle ends the deferral of
+ * smt_adcensus_compute_batch's last pair for good; if that pair's volumes are pending it writes both with one
+ * launch of the both-views cost kernel on the handle's stream and waits for it (with smt_adcensus_timing on,
+ * that launch is one more entry of smt_adcensus_kernel_times, with ~0 for the tables).  Every later call only
+ * returns the pointer. */
 int smt_adcensus_volume(smt_adcensus *h, int view, float **vol);
 
 /* Test hook: on != 0 routes the pair through the first-version table-lookup kernel (a second,

@@ -146,7 +146,10 @@ class AD_Census:
 
     def ComputeBatch(self, L, R, leftdisp, rightDisp, views=VIEW_BOTH):
         """[pairs][row][col] batches (smt_adcensus_compute_batch).  Afterwards the volumes hold the last pair's costs;
-        with both views and D <= 256 the other pairs' volumes are never written (SMT_BATCH_VOLUMES=all writes them)."""
+        with both views and D <= 256 the other pairs' volumes are never written (SMT_BATCH_VOLUMES=all writes them).
+        There, until GetPtrLeft / GetPtrRight / WTA has been called once on this object, the last pair's volumes are
+        written by the first such call after the batch, not by the batch; from then on every batch writes them itself
+        (SMT_BATCH_VOLUMES=last: always)."""
         pairs = L.shape[0]
         _dev(L, torch.float32, (pairs, self.row, self.col), "L")
         _dev(R, torch.float32, (pairs, self.row, self.col), "R")

@@ -1152,6 +1152,14 @@ struct smt_adcensus {
     int place_tries;     // candidate volume pairs tried by place_volumes
     float place_ms;      // store-only time of the pair that was kept (0: no search)
     unsigned long long *skeys;   // [H][W] key map of the shared maps-only form: SH_NOKEY between launches
+    // Deferred volumes of a batch's last pair (smt_adcensus_compute_batch, smt_adcensus_volume).  vol_lent: a caller
+    // has been given a volume pointer, so every batch from then on writes its last pair's volumes itself.
+    // vol_pending: the last pair took the maps-only path and its volumes are still to be written, by the both-views
+    // cost kernel on T.  All that launch needs stays in the handle until the next compute replaces the pending state:
+    // T is the pair's table set (nothing rebuilds it; the quirk state of the pair is in the tables' contents, and
+    // smt_adcensus_set_quirks changes only edge_col, which the table kernels alone read) and plain_stores is fixed at
+    // create.
+    bool vol_lent, vol_pending;
 };
 
 SMT_API const char *smt_strerror(int s)
@@ -1663,6 +1671,7 @@ static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int vi
     const int H = h->H, W = h->W, D = h->D;
     const int set = (int)(h->n_pairs & 1);
     h->T = h->TS[set];
+    h->vol_pending = false;                                  // never observable: dropped with the tables they would come from
     const bool timed = h->timing && (h->n_seen++ % h->timing_stride) == 0;
     const long slot = h->n_timed % SMT_TIMING_SLOTS;
     hipEvent_t *ev = timed ? h->ev + 4 * slot : nullptr;
@@ -1763,6 +1772,36 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
 
 bool adcensus_fused_both_views(const smt_adcensus *h) { return fast_both_views(h, SMT_VIEW_BOTH); }
 
+// The volumes of a batch's deferred last pair, written now: the both-views cost kernel with null maps on the pair's
+// tables (h->T, see vol_pending), on the handle's stream behind the batch's launches -- where an eager last pair would
+// have stored them -- and waits for it.  The cost kernels do not touch the domain flag (k_prep raises it), so smt_adcensus_status reports
+// what it would have.  With timing on, the launch is recorded like a pair whose tables were already built.
+static int materialise_volumes(smt_adcensus *h)
+{
+    if (!h->vol_pending) return SMT_OK;
+    const long slot = h->n_timed % SMT_TIMING_SLOTS;
+    hipEvent_t *ev = h->timing ? h->ev + 4 * slot : nullptr;
+    if (ev) { (void)hipEventRecord(ev[0], h->stream); (void)hipEventRecord(ev[1], h->stream); h->ev_merged[slot] = true; }
+    switch ((h->D + 63) / 64 * 2 + (h->D % 64 == 0 ? 1 : 0)) {
+    case 3: launch_fast<1, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 5: launch_fast<2, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 7: launch_fast<3, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 9: launch_fast<4, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 2: launch_fast<1, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 4: launch_fast<2, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 6: launch_fast<3, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    case 8: launch_fast<4, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
+    default: return SMT_ERR_STATE;                           // only fast_both_views pairs are deferred
+    }
+    if (ev) { (void)hipEventRecord(ev[3], h->stream); h->n_timed++; }
+    h->vol_pending = false;
+    SMT_LAUNCH_CHECK();
+    // A caller that synchronised the stream after its batch could read an eager last pair's volumes from anywhere;
+    // keep that true.  This happens at most once per handle: after the first lend nothing is deferred.
+    SMT_HIP(hipStreamSynchronize(h->stream));
+    return SMT_OK;
+}
+
 SMT_API int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const float *R, int pairs,
                                        int views, float *dispL, float *dispR)
 {
@@ -1775,17 +1814,28 @@ SMT_API int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const fl
         SMT_HIP(hipStreamWaitEvent(h->prep_stream, h->in_ready, 0));
     }
     // Only the last pair's volumes stay readable (every pair writes the same two), so pairs 0 .. pairs-2 of the
-    // both-views register-window path take the maps-only kernel.  SMT_BATCH_VOLUMES=all in the environment (read at
-    // every call) writes every pair's volumes as before: same-process A/Bs and tests.
+    // both-views register-window path take the maps-only kernel.  The last pair takes it too while no volume pointer
+    // of this handle has been lent (nobody can read them yet): its volumes are then pending, written by
+    // smt_adcensus_volume if it is called before the next compute.  SMT_BATCH_VOLUMES in the environment (read at
+    // every call): `last` writes the last pair's volumes in the batch itself whatever has been lent, `all` writes
+    // every pair's, as the first versions did: same-process A/Bs and tests.
     const char *venv = getenv("SMT_BATCH_VOLUMES");
     const bool all_volumes = venv && strcmp(venv, "all") == 0;
-    return adcensus_batch_pairs(h, L, R, pairs, views, dispL, dispR, sched, false, nullptr, nullptr, !all_volumes, true);
+    const bool eager_last = venv && strcmp(venv, "last") == 0;
+    const bool defer = !all_volumes && !eager_last && !h->vol_lent && fast_both_views(h, views);
+    const int rc = adcensus_batch_pairs(h, L, R, pairs, views, dispL, dispR, sched, false, nullptr, nullptr, !all_volumes, !defer);
+    h->vol_pending = defer && rc == SMT_OK;
+    return rc;
 }
 
 SMT_API int smt_adcensus_volume(smt_adcensus *h, int view, float **vol)
 {
     if (!h || !vol || (view != SMT_VIEW_LEFT && view != SMT_VIEW_RIGHT)) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
+    // lending is for good: a pointer handed out stays valid until destroy, so nothing is deferred after this call
+    h->vol_lent = true;
+    const int rc = materialise_volumes(h);
+    if (rc != SMT_OK) return rc;
     *vol = h->vol[view == SMT_VIEW_LEFT ? 0 : 1];
     return SMT_OK;
 }
@@ -2128,6 +2178,7 @@ static int smt_adcensus_diag_impl(smt_adcensus *h, int reps, float *sclk_mhz, fl
     }
     SMT_HIP(hipEventRecord(e[2], h->stream));
     SMT_LAUNCH_CHECK();
+    h->vol_pending = false;                                  // the stamped launches have just written the pair's volumes
     SMT_HIP(hipEventSynchronize(e[2]));
     float a = 0, b = 0;
     SMT_HIP(hipEventElapsedTime(&a, e[0], e[1]));
