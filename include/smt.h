@@ -275,18 +275,26 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
 /* Shared maps-only form of smt_adcensus_compute_batch (adcensus.hip, k_cost_maps_shared).  For 3 <= j' and j' + d <= W-4
  * the right view's cost(i, j', d) is bit for bit the left view's cost(i, j' + d, d), so for the pairs of a batch that
  * write maps only (both maps requested, D <= 256, W >= D + 6) the right map of the columns 3 <= j' <= W-3-D is taken
- * from keys (cost bits << 32 | d) that the left pass publishes; the other right columns keep the right-view arithmetic.
+ * from keys (cost bits << 32 | d) that the left pass publishes.  The columns j' > W-3-D get the keys of their
+ * hypotheses with j' + d <= W-4 the same way; what is left to them are the edge hypotheses W-3 <= j' + d <= W+3 (the
+ * cost is constant in d past W+3-j', so later ones cannot be a first minimum), which the finishing launch evaluates
+ * with the right view's arithmetic and merges into the key, as it evaluates every hypothesis of the columns 0..2.
  * Maps are those of the two-view kernel, bit for bit.  The host takes this form for D <= 192 and keeps the two-view
  * kernel for 192 < D <= 256, where it measured slower.
  *   SMT_MAPS_SHARED=0 in the environment (read at every call, like SMT_MAPS_CHUNKS / SMT_MAPS_KERNEL / SMT_OVERLAP)
  *   keeps the two-view kernel everywhere, SMT_MAPS_SHARED=force takes the shared form for every D <= 256 with
  *   W >= D + 6: same-process A/Bs and tests.  SMT_MAPS_KERNEL=rank selects the rank kernel as before.
+ *   SMT_SHARED_EDGES=wg in the environment (read at every call) publishes the columns 3 .. W-3-D only and runs the
+ *   right-view body in workgroups of its own over the 64-pixel chunks that hold the other columns, as before the edge
+ *   hypotheses moved to the finishing launch: same-process A/Bs and tests, same maps.
  * Test hook, host only (no GPU), exported by the library and declared in csrc/adcensus_internal.h:
  *   int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
  * walks the runs of K chunks per workgroup, the key ring, its flushes and the key-map merges of that form through the
- * kernel's own index functions over pseudo-random left-view costs with many exact ties (seed % 3: 0 a palette with
- * ties, 1 every cost equal, 2 mostly distinct).  SMT_OK iff every right pixel of the columns 3 .. W-3-D ends with the
- * first minimum of its diagonal, written once, and every other right pixel is left to the right-view chunks, once;
+ * kernel's own index functions over pseudo-random costs with many exact ties (seed % 3: 0 a palette with ties, 1 every
+ * cost equal, 2 mostly distinct; the right view's edge hypotheses have pseudo-costs of their own).  SMT_OK iff every
+ * right pixel is written exactly once, with the first minimum over its shared and its edge hypotheses, every ring ends
+ * empty and the key map is reset (under SMT_SHARED_EDGES=wg: the columns 3 .. W-3-D so, every other right pixel left
+ * to the right-view chunks, once);
  * SMT_ERR_STATE otherwise; SMT_ERR_ARG unless H, W >= 1, 1 <= D <= 256, 1 <= K <= 64. */
 
 /* Synchronises the stream and returns SMT_ERR_DOMAIN if any pixel seen since the previous

@@ -405,12 +405,19 @@ __device__ __forceinline__ void st_stream(__amdgpu_buffer_rsrc_t r, unsigned vof
 // ---- rules of the shared maps-only form (k_cost_maps_shared), host and device ----------------------------------------
 // For 3 <= j' and j' + d <= W-4 the right view's cost(i, j', d) is bit for bit the left view's cost(i, j' + d, d): the
 // edge-extended censuses equal the ordinary ones there, both column masks are all ones and the row masks are the same
-// row, and neither AD clamp acts.  So the right map of the IDENTITY SET of columns 3 <= j' <= W-3-D (every d < D) is
-// the first minimum along a diagonal of the left view's costs, which the left pass publishes as keys:
+// row, and neither AD clamp acts.  The left pass publishes these costs as keys to the right columns they belong to:
 //   key = cost bits << 32 | d; costs are >= +0, so the unsigned minimum is the smallest cost, then the smallest d --
 //   the reference's first strict minimum.  SH_NOKEY (all ones) is no key: d < 512.
-// Right pixels outside the set keep the VIEW 1 body, which runs over chunk 0 and the chunks from shared_right_tail()
-// on and writes only what is outside the set.  Runs of chunks are those of chunk_decode (below).
+// A left hypothesis (j, d) publishes when j <= W-4 and 3 <= j - d <= pubhi (shared_publishes).  Two forms:
+//   edges finished apart (default, pubhi = W-4): every shareable cost is published.  The columns of the IDENTITY SET
+//     3 <= j' <= W-3-D get all their D hypotheses that way.  A column j' > W-3-D lacks the EDGE HYPOTHESES with
+//     j' + d >= W-3; the VIEW 1 staging clamps the census index to W+3 and the value index to W-1, so the cost is
+//     constant in d from W+3-j' on and only d <= W+3-j' can be a first minimum: at most 7 per column
+//     (shared_edge_range).  Columns 0..2 share nothing.  k_shared_finish evaluates the edge hypotheses from the tables
+//     and merges them with the column's key.
+//   SMT_SHARED_EDGES=wg (pubhi = W-3-D): only the identity set is published; right pixels outside it keep the VIEW 1
+//     body, which k_shared_right_edges runs over chunk 0 and the chunks from shared_right_tail() on.
+// Runs of chunks are those of chunk_decode (below).
 #ifndef SMT_SHARED_KNOCKOUT
 #define SMT_SHARED_KNOCKOUT 0      // measurement builds only (wrong maps): 1 no LDS publishes, 2 no key-map merges
 #endif
@@ -418,7 +425,10 @@ constexpr int SH_RING = 512;                                 // key ring, indexe
 constexpr int SH_RING_N = SH_RING + 4;                       // + the spill slots of shared_ring_base()
 constexpr unsigned long long SH_NOKEY = ~0ull;
 __host__ __device__ inline int shared_id_hi(int W, int D) { return W - 3 - D; }           // the set is [3, hi]; empty when hi < 3
-__host__ __device__ inline bool shared_in_set(int c, int idhi) { return (unsigned)(c - 3) <= (unsigned)(idhi - 3) && idhi >= 3; }
+__host__ __device__ inline int shared_pub_hi(int W, int D, bool edges) { return edges ? W - 4 : shared_id_hi(W, D); }
+__host__ __device__ inline bool shared_in_set(int c, int hi) { return (unsigned)(c - 3) <= (unsigned)(hi - 3) && hi >= 3; }
+// left pixel j publishes a hypothesis to right column c = j - d (j <= W-4 is implied where pubhi = W-3-D)
+__host__ __device__ inline bool shared_publishes(int j, int c, int W, int pubhi) { return j <= W - 4 && shared_in_set(c, pubhi); }
 __host__ __device__ inline unsigned long long shared_key(unsigned cost_bits, int d) { return ((unsigned long long)cost_bits << 32) | (unsigned)d; }
 // right-view chunks that are still computed (set not empty): e = 0 is chunk 0, e >= 1 is chunk tail + e - 1
 __host__ __device__ inline int shared_right_tail(int W, int D) { const int b = (shared_id_hi(W, D) + 1) >> 6; return b < 1 ? 1 : b; }
@@ -429,16 +439,24 @@ __host__ __device__ inline int shared_right_chunk(int e, int W, int D) { return 
 // can therefore land in slot c mod 512 or in the spill slot 512 + c mod 512; the flush takes the minimum of the two.
 __host__ __device__ inline int shared_ring_base(int t, int C) { return (int)((unsigned)(t - (C - 1)) & (unsigned)(SH_RING - 1)); }
 // Columns flushed after left chunk bx of a run: those no later chunk of the run reaches, (64bx - D, 64bx + 64 - D], or
-// at the run's end everything still in the ring, (64bx - D, 64bx + 63]; both cut to the identity set.  Between two
-// flushes at most D + 127 <= 383 columns are live (D <= 256), so no two share a slot.
-__host__ __device__ inline void shared_flush_range(int bx, int D, bool end, int idhi, int &lo, int &hi)
+// at the run's end everything still in the ring, (64bx - D, 64bx + 63]; both cut to the published columns [3, pubhi].
+// Between two flushes at most D + 127 <= 383 columns are live (D <= 256), so no two share a slot.
+__host__ __device__ inline void shared_flush_range(int bx, int D, bool end, int pubhi, int &lo, int &hi)
 {
     lo = 64 * bx - D + 1; hi = end ? 64 * bx + 63 : 64 * bx + 64 - D;
-    lo = lo < 3 ? 3 : lo; hi = hi > idhi ? idhi : hi;
+    lo = lo < 3 ? 3 : lo; hi = hi > pubhi ? pubhi : hi;
 }
-// The whole diagonal j' .. j'+D-1 of right column c lies in the run's left columns [S, E]: the ring holds its final key,
-// written straight to the map.  Otherwise the key is partial and merged through the handle's key map.
+// The whole diagonal j' .. j'+D-1 of right column c lies in the run's left columns [S, E] and in the identity set: the
+// ring holds its final key, written straight to the map.  Otherwise the key is partial and merged through the handle's
+// key map: with the other runs' keys, and past the identity set with the edge hypotheses (never complete).
 __host__ __device__ inline bool shared_complete(int c, int S, int E, int D) { return c >= S && c + D - 1 <= E; }
+__host__ __device__ inline bool shared_complete(int c, int S, int E, int D, int idhi) { return c <= idhi && shared_complete(c, S, E, D); }
+// Edge hypotheses of right column c, evaluated by k_shared_finish: d in [lo, hi] (columns 0..2: every d that can win).
+__host__ __device__ inline void shared_edge_range(int c, int W, int D, int &lo, int &hi)
+{
+    lo = c >= 3 && W - 3 - c > 0 ? W - 3 - c : 0;
+    hi = W + 3 - c < D - 1 ? W + 3 - c : D - 1;
+}
 
 struct __attribute__((aligned(16))) Anchor { uint64_t cen, mask; };
 
@@ -471,14 +489,14 @@ template <int MODE> struct MapsCfg {
 // unused) and use the LDS of k_cost_maps2p (`ml`: staged operands in set `buf`, written by MapsStage, and the table the
 // kernel has filled: MODE 1 the 320-float LUT, MODE 2 the 256 x 64 rank table, Tables::rank).  MODE 2 stages the image values x64, so that v_sad_u16(va, vx, hd) is the rank
 // index 64*AD + hd, and its WTA key is rank << 16 | d: one wave min, no tie-break.
-// SHR (MODE_MAPS_FLOAT; k_cost_maps_shared).  VIEW 0: every hypothesis whose right column j - d is in the identity set
-// [3, idhi] also publishes its key to `ring` with an LDS 64-bit atomic min.  VIEW 1: the map columns [skip_lo, skip_hi]
-// are not written, and a wave whose pixels all lie inside does nothing.
+// SHR (MODE_MAPS_FLOAT).  VIEW 0 (k_cost_maps_shared): every hypothesis that shared_publishes() also sends its key to
+// `ring` with an LDS 64-bit atomic min.  VIEW 1 (k_shared_right_edges): the map columns [skip_lo, skip_hi] are not
+// written, and a wave whose pixels all lie inside does nothing.
 template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME, bool SHR = false>
 __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tables &T, float *__restrict__ vol,
                                                float *__restrict__ disp, int i, int bx,
                                                MapsLds<C, MapsCfg<MODE>::TABN, MapsCfg<MODE>::NBUF> *ml = nullptr, int buf = 0,
-                                               unsigned long long *ring = nullptr, int idhi = 0, int skip_lo = 1, int skip_hi = 0)
+                                               unsigned long long *ring = nullptr, int pubhi = 0, int skip_lo = 1, int skip_hi = 0)
 {
     static_assert(!SHR || MODE == MODE_MAPS_FLOAT, "");
     constexpr bool PUB = SHR && VIEW == 0, SKIP = SHR && VIEW == 1;
@@ -575,8 +593,8 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
     // all ones and the two ANDs per hypothesis can be dropped (bit 63 is 0 in every table entry)
     const bool interior = (i >= 4) && (i < H - 4) && (j0 + p0 >= 3) && (j0 + p0 + npx - 1 <= W - 4);
 
-    // every (pixel, hypothesis) of this wave publishes: no per-hypothesis column test
-    const bool allin = PUB && (j0 + p0) - (D - 1) >= 3 && j0 + p0 + npx - 1 <= idhi;
+    // every (pixel, hypothesis) of this wave publishes (pubhi <= W-4): no per-hypothesis column test
+    const bool allin = PUB && (j0 + p0) - (D - 1) >= 3 && j0 + p0 + npx - 1 <= pubhi;
     typedef __attribute__((address_space(3))) unsigned long long *lds_key_p;
     const lds_key_p ring3 = (lds_key_p)ring;
 
@@ -668,7 +686,7 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                         const lds_key_p rp = ring3 + shared_ring_base(tcol, C);
 #pragma unroll
                         for (int k = 0; k < C; k++)
-                            if (ok[k] && (ALLIN || shared_in_set(tcol - k, idhi)))
+                            if (ok[k] && (ALLIN || shared_publishes(j0 + p0 + q, tcol - k, W, pubhi)))
                                 (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
@@ -953,7 +971,7 @@ __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables 
 // partial ones to the handle's key map with one agent-scope atomic min each; the slots are reset.
 template <int C>
 __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, int W, int D, int lo, int hi, int S, int E,
-                                             float *__restrict__ dispR, unsigned long long *__restrict__ keys)
+                                             int idhi, float *__restrict__ dispR, unsigned long long *__restrict__ keys)
 {
     for (int c = lo + (int)threadIdx.x; c <= hi; c += NT) {
         const int s = c & (SH_RING - 1);
@@ -961,25 +979,25 @@ __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, in
         ring[s] = SH_NOKEY;
         if (s < C - 1) { k = min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
         const size_t p = (size_t)i * W + c;
-        if (shared_complete(c, S, E, D)) dispR[p] = (float)(unsigned)k;
+        if (shared_complete(c, S, E, D, idhi)) dispR[p] = (float)(unsigned)k;
         else if (k != SH_NOKEY && SMT_SHARED_KNOCKOUT != 2) atomicMin(&keys[p], k);
     }
 }
 
-// Shared maps-only form: both maps of a pair from (nearly) one cost evaluation per hypothesis.  The first `nleft`
-// cost workgroups run the VIEW 0 body over runs of K consecutive chunks (chunk_decode over the left view alone) and
-// publish the keys of the identity set to a per-workgroup ring; a chunk's finished columns are flushed after the next
-// chunk's barrier, beside that chunk's arithmetic (their slots are disjoint, shared_flush_range), a run's last columns
-// between two barriers when the row or the workgroup ends.  The remaining cost workgroups run the VIEW 1 body over
-// the right view's edge chunks (shared_right_chunk) and write the columns outside the set.  k_shared_finish turns the
-// merged partial keys into map entries.  Table workgroups, LUT and staging are those of k_cost_maps2p.
+// Shared maps-only form: both maps of a pair from one cost evaluation per shareable hypothesis.  The cost workgroups
+// run the VIEW 0 body over runs of K consecutive chunks (chunk_decode over the left view alone) and publish the keys of
+// the columns [3, pubhi] to a per-workgroup ring; a chunk's finished columns are flushed after the next chunk's
+// barrier, beside that chunk's arithmetic (their slots are disjoint, shared_flush_range), a run's last columns between
+// two barriers when the row or the workgroup ends.  k_shared_finish turns the merged partial keys into map entries and
+// adds the edge hypotheses; with SMT_SHARED_EDGES=wg k_shared_right_edges writes the columns outside the identity set
+// instead.  Table workgroups, LUT and staging are those of k_cost_maps2p.
 #ifndef SMT_SHARED_MIN_WAVES
 #define SMT_SHARED_MIN_WAVES 7     // waves per SIMD the register allocation must allow; measured 1 / 7 / 8: DESIGN.md section 4
 #endif
 template <int C, bool FULL>
 __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(int H, int W, int D, Tables T, float *__restrict__ disp0,
                                                          float *__restrict__ disp1, unsigned long long *__restrict__ keys,
-                                                         int nbx, int K, int nleft, int ncost, int nprep,
+                                                         int nbx, int K, int pubhi, int ncost, int nprep,
                                                          const float *__restrict__ nL, const float *__restrict__ nR,
                                                          Tables Tn, int ptx)
 {
@@ -1005,33 +1023,17 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
     for (int e = tid; e < 320; e += NT) ((float *)s_tab)[e] = T.lut[e];
     const int Dd = FULL ? 64 * C : D;
     const int idhi = shared_id_hi(W, Dd);
-    const bool right = b >= nleft;                                         // workgroup-uniform
-    if (right) b -= nleft;
-    else for (int e = tid; e < SH_RING_N; e += NT) ring[e] = SH_NOKEY;
-    const int nch = right ? shared_right_chunks(nbx, W, Dd) : nbx;
+    for (int e = tid; e < SH_RING_N; e += NT) ring[e] = SH_NOKEY;
     auto next = [&](int t, int &i, int &bx) {
         int view;
-        if (t >= K || !chunk_decode(nch, H, 1, K, b, t, view, i, bx)) return K;
-        if (right) bx = shared_right_chunk(bx, W, Dd);
+        if (t >= K || !chunk_decode(nbx, H, 1, K, b, t, view, i, bx)) return K;
         return t;
     };
     MapsStage<C, FULL> st;
     int i = 0, bx = 0;
     int t = next(0, i, bx);
-    if (t < K) st.load(right ? 1 : 0, i, bx, W, D, T);
+    if (t < K) st.load(0, i, bx, W, D, T);
     int buf = 0;
-    if (right) {
-        while (t < K) {
-            st.template store<4u>(lds, buf, D);
-            __syncthreads();
-            const int ci = i, cbx = bx;
-            t = next(t + 1, i, bx);
-            if (t < K) st.load(1, i, bx, W, D, T);
-            cost_fast_body<C, 1, FULL, true, MODE, true>(H, W, D, T, nullptr, disp1, ci, cbx, &lds, buf, nullptr, idhi, 3, idhi);
-            buf ^= 1;
-        }
-        return;
-    }
     // pending flush: the previous chunk's columns (all workgroup-uniform)
     bool pend = false, pend_end = false;
     int pi = 0, plo = 0, phi = -1, pS = 0, pE = 0;
@@ -1040,36 +1042,116 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
         st.template store<4u>(lds, buf, D);
         __syncthreads();                                                   // every wave has published the previous chunk
         if (pend) {
-            shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, disp1, keys);
+            shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, idhi, disp1, keys);
             if (pend_end) __syncthreads();                                 // the next run may use any slot
         }
         const int ci = i, cbx = bx;
         t = next(t + 1, i, bx);
         if (t < K) st.load(0, i, bx, W, D, T);
         if (S < 0) S = 64 * cbx;
-        cost_fast_body<C, 0, FULL, true, MODE, true>(H, W, D, T, nullptr, disp0, ci, cbx, &lds, buf, ring, idhi);
+        cost_fast_body<C, 0, FULL, true, MODE, true>(H, W, D, T, nullptr, disp0, ci, cbx, &lds, buf, ring, pubhi);
         pend = true; pend_end = t >= K || i != ci;                         // consecutive chunks: same row <=> same run
         pi = ci; pS = S; pE = 64 * cbx + 63;
-        shared_flush_range(cbx, Dd, pend_end, idhi, plo, phi);
+        shared_flush_range(cbx, Dd, pend_end, pubhi, plo, phi);
         if (pend_end) S = -1;
         buf ^= 1;
     }
     if (pend) {
         __syncthreads();
-        shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, disp1, keys);
+        shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, idhi, disp1, keys);
     }
 }
 
-// Partial keys of the shared form -> map entries; the consumed keys are reset for the next pair.
-__global__ void __launch_bounds__(256) k_shared_finish(unsigned long long *__restrict__ keys, int H, int W, int idhi,
-                                                       float *__restrict__ dispR)
+// SMT_SHARED_EDGES=wg: the VIEW 1 body over the right view's edge chunks (shared_right_chunk), K per workgroup; writes
+// the right map's columns outside the identity set.  A launch of its own behind k_cost_maps_shared.
+template <int C, bool FULL>
+__global__ void __launch_bounds__(NT) k_shared_right_edges(int H, int W, int D, Tables T, float *__restrict__ disp1, int nbx, int K)
 {
-    const int n = idhi - 2;                                                // columns 3 .. idhi
+    constexpr int MODE = MODE_MAPS_FLOAT;
+    constexpr int TABN = MapsCfg<MODE>::TABN, NBUF = MapsCfg<MODE>::NBUF;
+    __shared__ MapsLds<C, TABN, NBUF> lds;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < 320; e += NT) ((float *)lds.tab)[e] = T.lut[e];
+    const int Dd = FULL ? 64 * C : D;
+    const int idhi = shared_id_hi(W, Dd);
+    const int nch = shared_right_chunks(nbx, W, Dd);
+    const long b = blockIdx.x;
+    auto next = [&](int t, int &i, int &bx) {
+        int view;
+        if (t >= K || !chunk_decode(nch, H, 1, K, b, t, view, i, bx)) return K;
+        bx = shared_right_chunk(bx, W, Dd);
+        return t;
+    };
+    MapsStage<C, FULL> st;
+    int i = 0, bx = 0;
+    int t = next(0, i, bx);
+    if (t < K) st.load(1, i, bx, W, D, T);
+    int buf = 0;
+    while (t < K) {
+        st.template store<4u>(lds, buf, D);
+        __syncthreads();
+        const int ci = i, cbx = bx;
+        t = next(t + 1, i, bx);
+        if (t < K) st.load(1, i, bx, W, D, T);
+        cost_fast_body<C, 1, FULL, true, MODE, true>(H, W, D, T, nullptr, disp1, ci, cbx, &lds, buf, nullptr, idhi, 3, idhi);
+        buf ^= 1;
+    }
+}
+
+// Right-view cost of (i, j', d) straight from the tables, with the arithmetic of cost_fast_body's VIEW 1: the census
+// index clamped to W+3, the value index to W-1, the anchor's tap mask, lut[ad] + lut[256 + hd].  j' + d >= 0.
+__device__ __forceinline__ unsigned long long shared_edge_key(const Tables &T, int i, int W, uint64_t acen, uint64_t amask,
+                                                              int va, int x, int d)
+{
+    const int xc = x > W + 3 ? W + 3 : x, xv = x > W - 1 ? W - 1 : x;
+    const int hd = __popcll((acen ^ T.cenX[1][(size_t)i * T.WX + xc]) & amask);
+    const int vx = T.u8[0][(size_t)i * W + xv];
+    const int ad = va > vx ? va - vx : vx - va;
+    const float c = T.lut[ad] + T.lut[256 + hd];
+    return shared_key(__float_as_uint(c), d);
+}
+
+// Partial keys of the shared form -> map entries; the consumed keys are reset for the next pair.  edges == 0
+// (SMT_SHARED_EDGES=wg): one thread per pixel of the identity set.  edges != 0: one thread per pixel of the columns
+// 3 .. W-1, which past the identity set merges the column's edge hypotheses (shared_edge_range, at most 7) into the key
+// and always writes; the blocks from nb1 on take the columns 0..2, one wave per pixel, every hypothesis an edge one.
+// T: the tables of the pair just computed (the launch before this one wrote the other set).
+__global__ void __launch_bounds__(256) k_shared_finish(unsigned long long *__restrict__ keys, int H, int W, int D, int idhi,
+                                                       float *__restrict__ dispR, int edges, unsigned nb1, Tables T)
+{
+    if (blockIdx.x >= nb1) {                                               // columns 0..2
+        const size_t w = (size_t)(blockIdx.x - nb1) * 4 + (threadIdx.x >> 6);
+        if (w >= (size_t)H * 3) return;
+        const int i = (int)(w / 3), c = (int)(w % 3), lane = threadIdx.x & 63;
+        const size_t p = (size_t)i * W + c;
+        const uint64_t acen = T.cenA[1][p], amask = T.mask[p];
+        const int va = T.u8[1][p];
+        int lo, hi;
+        shared_edge_range(c, W, D, lo, hi);
+        unsigned long long k = SH_NOKEY;
+        for (int d = lo + lane; d <= hi; d += 64) k = min(k, shared_edge_key(T, i, W, acen, amask, va, c + d, d));
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) k = min(k, (unsigned long long)__shfl_xor((long long)k, s));
+        if (lane == 0) dispR[p] = (float)(unsigned)k;
+        return;
+    }
+    const int n = edges ? W - 3 : idhi - 2;                                // columns 3 .. W-1 or 3 .. idhi
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= (size_t)H * n) return;
-    const size_t p = (q / n) * W + 3 + q % n;
-    const unsigned long long k = keys[p];
-    if (k != SH_NOKEY) { dispR[p] = (float)(unsigned)k; keys[p] = SH_NOKEY; }
+    const int i = (int)(q / n), c = 3 + (int)(q % n);
+    const size_t p = (size_t)i * W + c;
+    unsigned long long k = c <= W - 4 ? keys[p] : SH_NOKEY;                // nothing is published to the last three
+    if (c <= idhi) {
+        if (k != SH_NOKEY) { dispR[p] = (float)(unsigned)k; keys[p] = SH_NOKEY; }
+        return;
+    }
+    if (k != SH_NOKEY) keys[p] = SH_NOKEY;
+    const uint64_t acen = T.cenA[1][p], amask = T.mask[p];
+    const int va = T.u8[1][p];
+    int lo, hi;
+    shared_edge_range(c, W, D, lo, hi);
+    for (int d = lo; d <= hi; d++) k = min(k, shared_edge_key(T, i, W, acen, amask, va, c + d, d));
+    dispR[p] = (float)(unsigned)k;
 }
 
 // Store-only twin of k_cost_fast2<C, true>: the same grid, workgroup -> chunk order and streaming stores
@@ -1560,6 +1642,15 @@ static bool maps_shared()
     const char *env = getenv("SMT_MAPS_SHARED");
     return !(env && env[0] == '0' && env[1] == 0);
 }
+// SMT_SHARED_EDGES=wg in the environment (read at every call) keeps the right view's edge chunks in VIEW 1 workgroups
+// (k_shared_right_edges) and publishes the identity set alone, where by default every shareable column is published and
+// k_shared_finish adds the edge hypotheses: tests and same-process A/Bs.  The edge chunks then run in a launch of their
+// own behind the shared one, not as extra workgroups of its grid: the hook's timing is not the earlier form's.
+static bool shared_edges_finish()
+{
+    const char *env = getenv("SMT_SHARED_EDGES");
+    return !(env && env[0] == 'w' && env[1] == 'g' && env[2] == 0);
+}
 // The shapes the shared form serves: an identity set that is not empty, and D <= 192.  With four hypotheses per lane
 // (192 < D <= 256) the lanes' publishes are 32 bytes apart, a 4-way bank conflict, the kernel needs 93 VGPRs and the
 // identity set is a smaller part of the row; measured at 1242 x 375 D = 256 it loses 7 % to the two-view kernel
@@ -1592,16 +1683,20 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
         const char *env = getenv("SMT_MAPS_KERNEL");
         const int idhi = shared_id_hi(h->W, h->D);
         if (!(env && env[0] == 'r') && dL && dR && maps_shared_shape(h->W, h->D) && maps_shared()) {
-            // left-view runs + the right view's edge chunks, then the finishing launch, all on the caller's stream
-            const int nleft = maps_groups(nbx, h->H, 1, K);
-            const int ncs = nleft + maps_groups(shared_right_chunks(nbx, h->W, h->D), h->H, 1, K);
+            // the left-view runs, then the finishing launch (or the VIEW 1 edge chunks and it), all on the caller's stream
+            const bool edges = shared_edges_finish();
+            const int ncs = maps_groups(nbx, h->H, 1, K);
             const unsigned gs = nL ? 8u * (unsigned)fused_grid(ncs, nprep).groups : (unsigned)ncs;
             hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
-                               h->skeys, nbx, K, nleft, ncs, nprep, nL, nR, Tn, ptx);
-            const size_t nf = (size_t)h->H * (idhi - 2);
+                               h->skeys, nbx, K, shared_pub_hi(h->W, h->D, edges), ncs, nprep, nL, nR, Tn, ptx);
+            if (!edges)
+                hipLaunchKernelGGL((k_shared_right_edges<C, FULL>), dim3((unsigned)maps_groups(shared_right_chunks(nbx, h->W, h->D), h->H, 1, K)),
+                                   dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dR, nbx, K);
+            const size_t nf = (size_t)h->H * (edges ? h->W - 3 : idhi - 2);
+            const unsigned nb1 = (unsigned)((nf + 255) / 256), nb0 = edges ? (unsigned)(((size_t)h->H * 3 + 3) / 4) : 0u;
             if (SMT_SHARED_KNOCKOUT != 2)
-                hipLaunchKernelGGL(k_shared_finish, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, h->stream, h->skeys, h->H,
-                                   h->W, idhi, dR);
+                hipLaunchKernelGGL(k_shared_finish, dim3(nb1 + nb0), dim3(256), 0, h->stream, h->skeys, h->H, h->W, h->D, idhi,
+                                   dR, edges ? 1 : 0, nb1, h->T);
             return;
         }
         if (env && env[0] == 'r')
@@ -1913,27 +2008,37 @@ SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
     return rc;
 }
 
-// Host-side walk of the shared maps-only form (k_cost_maps_shared + k_shared_finish) over pseudo-random left-view costs
-// with many exact ties, through the kernel's own index functions: chunk_decode / maps_groups for the runs, the lane ->
-// hypothesis split and shared_ring_base for the publishes, shared_flush_range / shared_complete for the flushes (a
-// chunk's flush is applied after the next chunk's publishes, as on the device, and must not meet a slot those touched),
-// the key map for the partial keys, shared_right_chunk(s) for the VIEW 1 chunks.  SMT_OK iff every identity-set right
-// pixel ends with the first minimum of its diagonal, written exactly once, and every other right pixel is written by
-// the VIEW 1 chunks alone, exactly once.  Needs no GPU.
+// Host-side walk of the shared maps-only form (k_cost_maps_shared + k_shared_finish) over pseudo-random costs with many
+// exact ties, through the kernel's own index functions: chunk_decode / maps_groups for the runs, the lane -> hypothesis
+// split, shared_publishes and shared_ring_base for the publishes, shared_flush_range / shared_complete for the flushes
+// (a chunk's flush is applied after the next chunk's publishes, as on the device, and must not meet a slot those
+// touched), the key map for the partial keys, shared_edge_range for the finishing launch's edge hypotheses -- or, with
+// SMT_SHARED_EDGES=wg in the environment, shared_right_chunk(s) for the VIEW 1 chunks.  The right view's pseudo-cost of
+// (i, j', d) is the left one of (i, j' + d, d) where the identity holds and a cost of its own elsewhere, constant in d
+// from W+3-j' on as the staging clamps make it.  SMT_OK iff every right pixel is written exactly once, with the first
+// minimum over all its D hypotheses where the walk computes it (every column by default, the identity set with wg),
+// every ring ends empty and the key map is reset.  Needs no GPU.
 SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed)
 {
     if (H <= 0 || W <= 0 || D <= 0 || D > 256 || K < 1 || K > 64 || (long)H * W > (1L << 24)) return SMT_ERR_ARG;
     const int C = (D + 63) / 64, nbx = (W + FTJ - 1) / FTJ, idhi = shared_id_hi(W, D);
+    const bool edges = shared_edges_finish();
+    const int pubhi = shared_pub_hi(W, D, edges);
     const size_t N = (size_t)H * W;
     // costs: a small palette of floats >= +0 (ties), every cost equal (seed % 3 == 1), or mostly distinct
     static const float pal[] = {0.0f, 0.0f, 0.25f, 0.25f, 1.5f, 0.7265625f, 0.7265625f, 1.9999999f, 0.25f, 1e-30f};
-    auto cost_bits = [&](int i, int j, int d) {
-        uint32_t x = (uint32_t)i * 0x9E3779B1u ^ (uint32_t)j * 0x85EBCA77u ^ (uint32_t)d * 0xC2B2AE3Du ^ seed * 0x27D4EB2Fu;
+    auto hash_bits = [&](int i, int j, int d, unsigned salt) {
+        uint32_t x = (uint32_t)i * 0x9E3779B1u ^ (uint32_t)j * 0x85EBCA77u ^ (uint32_t)d * 0xC2B2AE3Du ^ seed * 0x27D4EB2Fu ^ salt;
         x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
         float f = seed % 3 == 1 ? 0.5f : (seed % 3 == 2 && (x & 3)) ? (float)(x >> 12) * (1.0f / 1048576.0f) : pal[(x >> 4) % 10];
         uint32_t bits;
         memcpy(&bits, &f, 4);
         return bits;
+    };
+    auto cost_bits = [&](int i, int j, int d) { return hash_bits(i, j, d, 0u); };          // left view
+    auto right_bits = [&](int i, int c, int d) {                                           // right view
+        if (c >= 3 && c + d <= W - 4) return cost_bits(i, c + d, d);
+        return hash_bits(i, c, std::min(d, W + 3 - c), 0x5BD1E995u);
     };
     unsigned long long *keys = new (std::nothrow) unsigned long long[N];
     unsigned *val = new (std::nothrow) unsigned[N]();
@@ -1955,7 +2060,7 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                     ring[s] = SH_NOKEY;
                     if (s < C - 1) { k = std::min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
                     const size_t p = (size_t)i * W + c;
-                    if (shared_complete(c, S, E, D)) {
+                    if (shared_complete(c, S, E, D, idhi)) {
                         if (k == SH_NOKEY) rc = SMT_ERR_STATE;
                         val[p] = (unsigned)k; nw[p]++;
                     } else if (k != SH_NOKEY) keys[p] = std::min(keys[p], k);
@@ -1974,7 +2079,7 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                     for (int lane = 0; lane < 64; lane++)
                         for (int k = 0; k < C; k++) {
                             const int dl = lane * C, d = dl + k, tcol = 64 * bx + q - dl;
-                            if (d >= D || !shared_in_set(tcol - k, idhi)) continue;
+                            if (d >= D || !shared_publishes(64 * bx + q, tcol - k, W, pubhi)) continue;
                             const int s = shared_ring_base(tcol, C) + (C - 1 - k);
                             ring[s] = std::min(ring[s], shared_key(cost_bits(i, 64 * bx + q, d), d));
                             stamp[s] = serial;
@@ -1983,7 +2088,7 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                 pend = true; pend_end = !more || ni != i;
                 if (more && ni == i && nbxn != bx + 1) rc = SMT_ERR_STATE;
                 pi = i; pS = S; pE = 64 * bx + 63;
-                shared_flush_range(bx, D, pend_end, idhi, plo, phi);
+                shared_flush_range(bx, D, pend_end, pubhi, plo, phi);
                 if (pend_end) S = -1;
                 have = more; i = ni; bx = nbxn;
             }
@@ -1992,12 +2097,22 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
         }
         // the finishing launch
         for (int i = 0; i < H; i++)
-            for (int c = 3; c <= idhi; c++) {
+            for (int c = edges ? 0 : 3; c <= (edges ? W - 1 : idhi); c++) {
                 const size_t p = (size_t)i * W + c;
-                if (keys[p] != SH_NOKEY) { val[p] = (unsigned)keys[p]; nw[p]++; keys[p] = SH_NOKEY; }
+                if (shared_in_set(c, idhi)) {
+                    if (keys[p] != SH_NOKEY) { val[p] = (unsigned)keys[p]; nw[p]++; keys[p] = SH_NOKEY; }
+                    continue;
+                }
+                unsigned long long k = c >= 3 && c <= W - 4 ? keys[p] : SH_NOKEY;
+                if (c >= 3 && c <= W - 4) keys[p] = SH_NOKEY;
+                int lo, hi;
+                shared_edge_range(c, W, D, lo, hi);
+                for (int d = lo; d <= hi; d++) k = std::min(k, shared_key(right_bits(i, c, d), d));
+                if (k == SH_NOKEY) rc = SMT_ERR_STATE;
+                val[p] = (unsigned)k; nw[p]++;
             }
         // the VIEW 1 workgroups
-        const int nre = shared_right_chunks(nbx, W, D), nright = maps_groups(nre, H, 1, K);
+        const int nre = shared_right_chunks(nbx, W, D), nright = edges ? 0 : maps_groups(nre, H, 1, K);
         for (long b = 0; b < nright; b++)
             for (int t = 0; t < K; t++) {
                 int view, i, e;
@@ -2012,16 +2127,17 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
         for (int c = 0; c < W && rc == SMT_OK; c++) {
             const size_t p = (size_t)i * W + c;
             if (idhi < 3) { if (nw[p] || nv[p]) rc = SMT_ERR_STATE; continue; }   // the two-view kernel serves this shape
-            if (!shared_in_set(c, idhi)) { if (nw[p] != 0 || nv[p] != 1) rc = SMT_ERR_STATE; continue; }
+            if (keys[p] != SH_NOKEY) rc = SMT_ERR_STATE;
+            if (!edges && !shared_in_set(c, idhi)) { if (nw[p] != 0 || nv[p] != 1) rc = SMT_ERR_STATE; continue; }
             float mn = 0.0f;
             int want = 0;
             for (int d = 0; d < D; d++) {
-                const uint32_t bits = cost_bits(i, c + d, d);
+                const uint32_t bits = right_bits(i, c, d);
                 float f;
                 memcpy(&f, &bits, 4);
                 if (d == 0 || f < mn) { mn = f; want = d; }
             }
-            if (nw[p] != 1 || nv[p] != 0 || val[p] != (unsigned)want || keys[p] != SH_NOKEY) rc = SMT_ERR_STATE;
+            if (nw[p] != 1 || nv[p] != 0 || val[p] != (unsigned)want) rc = SMT_ERR_STATE;
         }
     delete[] keys; delete[] val; delete[] nw; delete[] nv;
     return rc;
