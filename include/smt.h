@@ -287,6 +287,11 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  *   SMT_SHARED_EDGES=wg in the environment (read at every call) publishes the columns 3 .. W-3-D only and runs the
  *   right-view body in workgroups of its own over the 64-pixel chunks that hold the other columns, as before the edge
  *   hypotheses moved to the finishing launch: same-process A/Bs and tests, same maps.
+ *   SMT_SHARED_WALK=chunk in the environment (read at every call) keeps the chunk-wise left pass, which stages, walks
+ *   (16 pixels per wave) and flushes every 64-pixel chunk by itself, where by default a workgroup stages a run of up to
+ *   4 consecutive chunks of one row once, every wave walks a contiguous quarter of it in one pass and the run's columns
+ *   are flushed once: same-process A/Bs and tests, same maps.  smt_adcensus_selftest_shared_keys follows the walk the
+ *   environment selects.
  * Test hook, host only (no GPU), exported by the library and declared in csrc/adcensus_internal.h:
  *   int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
  * walks the runs of K chunks per workgroup, the key ring, its flushes and the key-map merges of that form through the

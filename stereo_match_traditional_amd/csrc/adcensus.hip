@@ -440,11 +440,39 @@ __host__ __device__ inline int shared_right_chunk(int e, int W, int D) { return 
 __host__ __device__ inline int shared_ring_base(int t, int C) { return (int)((unsigned)(t - (C - 1)) & (unsigned)(SH_RING - 1)); }
 // Columns flushed after left chunk bx of a run: those no later chunk of the run reaches, (64bx - D, 64bx + 64 - D], or
 // at the run's end everything still in the ring, (64bx - D, 64bx + 63]; both cut to the published columns [3, pubhi].
-// Between two flushes at most D + 127 <= 383 columns are live (D <= 256), so no two share a slot.
+// The chunk-wise walk (SMT_SHARED_WALK=chunk) has at most D + 127 <= 383 columns live between two flushes (D <= 256);
+// the run walk publishes a whole run of at most SH_RUN = 4 chunks before its one flush (shared_run_flush_range), so at
+// most 256 + D - 1 <= 511 columns are live.  Either way no two live columns share a slot of the ring of 512.
 __host__ __device__ inline void shared_flush_range(int bx, int D, bool end, int pubhi, int &lo, int &hi)
 {
     lo = 64 * bx - D + 1; hi = end ? 64 * bx + 63 : 64 * bx + 64 - D;
     lo = lo < 3 ? 3 : lo; hi = hi > pubhi ? pubhi : hi;
+}
+// Run walk.  A workgroup's chunks (chunk_decode over the left view alone, t = 0 .. K-1) are consecutive in the linear
+// (row, chunk-in-row) space, so its first chunk (i, bx) and their number describe them: shared_wg_chunks, one division
+// per workgroup.  Consecutive chunks of one row form a run; a run longer than SH_RUN chunks is cut into sub-runs of
+// SH_RUN from its start, each a run in every respect (shared_run_len: chunks of the run that starts at chunk bx with
+// `left` chunks of the workgroup to go).  The one flush of run [S, E] takes every column the run published to.
+constexpr int SH_RUN = 4;
+__host__ __device__ inline int shared_wg_chunks(int nbx, int H, int K, long b, int &i, int &bx)
+{
+    const long nb = (long)nbx * H, per = (nb + 7) >> 3, cl = (b >> 3) * K;
+    if (cl >= per) return 0;
+    const long c = (b & 7) * per + cl;
+    if (c >= nb) return 0;
+    i = (int)(c / nbx);
+    bx = (int)(c - (long)i * nbx);
+    long n = per - cl < nb - c ? per - cl : nb - c;
+    return (int)(n < K ? n : K);
+}
+__host__ __device__ inline int shared_run_len(int nbx, int bx, int left)
+{
+    const int n = nbx - bx < SH_RUN ? nbx - bx : SH_RUN;
+    return n < left ? n : left;
+}
+__host__ __device__ inline void shared_run_flush_range(int S, int E, int D, int pubhi, int &lo, int &hi)
+{
+    lo = S - D + 1 < 3 ? 3 : S - D + 1; hi = E > pubhi ? pubhi : E;
 }
 // The whole diagonal j' .. j'+D-1 of right column c lies in the run's left columns [S, E] and in the identity set: the
 // ring holds its final key, written straight to the map.  Otherwise the key is partial and merged through the handle's
@@ -489,9 +517,13 @@ template <int MODE> struct MapsCfg {
 // unused) and use the LDS of k_cost_maps2p (`ml`: staged operands in set `buf`, written by MapsStage, and the table the
 // kernel has filled: MODE 1 the 320-float LUT, MODE 2 the 256 x 64 rank table, Tables::rank).  MODE 2 stages the image values x64, so that v_sad_u16(va, vx, hd) is the rank
 // index 64*AD + hd, and its WTA key is rank << 16 | d: one wave min, no tie-break.
-// SHR (MODE_MAPS_FLOAT).  VIEW 0 (k_cost_maps_shared): every hypothesis that shared_publishes() also sends its key to
+// SHR (MODE_MAPS_FLOAT).  VIEW 0 (k_cost_maps_shared_chunks, the SMT_SHARED_WALK=chunk hook): every hypothesis that shared_publishes() also sends its key to
 // `ring` with an LDS 64-bit atomic min.  VIEW 1 (k_shared_right_edges): the map columns [skip_lo, skip_hi] are not
 // written, and a wave whose pixels all lie inside does nothing.
+// TWIN: shared_run_walk (below, the default left pass of the shared form) repeats this body's VIEW 0 MODE_MAPS_FLOAT
+// publishing path -- window rotation, WTA tie-break, publish -- over a staged run; only p0, npx and the staged base
+// differ.  A change to that path here belongs there too (tests/test_adcensus_shared_runs_gpu.py compares the two walks
+// map for map).  The copy goes when the chunk-wise kernel, kept as an A/B hook, is retired.
 template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME, bool SHR = false>
 __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tables &T, float *__restrict__ vol,
                                                float *__restrict__ disp, int i, int bx,
@@ -984,7 +1016,8 @@ __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, in
     }
 }
 
-// Shared maps-only form: both maps of a pair from one cost evaluation per shareable hypothesis.  The cost workgroups
+// Shared maps-only form, chunk-wise walk (SMT_SHARED_WALK=chunk; the default is k_cost_maps_shared below, which walks a
+// run in one pass): both maps of a pair from one cost evaluation per shareable hypothesis.  The cost workgroups
 // run the VIEW 0 body over runs of K consecutive chunks (chunk_decode over the left view alone) and publish the keys of
 // the columns [3, pubhi] to a per-workgroup ring; a chunk's finished columns are flushed after the next chunk's
 // barrier, beside that chunk's arithmetic (their slots are disjoint, shared_flush_range), a run's last columns between
@@ -995,7 +1028,7 @@ __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, in
 #define SMT_SHARED_MIN_WAVES 7     // waves per SIMD the register allocation must allow; measured 1 / 7 / 8: DESIGN.md section 4
 #endif
 template <int C, bool FULL>
-__global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(int H, int W, int D, Tables T, float *__restrict__ disp0,
+__global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared_chunks(int H, int W, int D, Tables T, float *__restrict__ disp0,
                                                          float *__restrict__ disp1, unsigned long long *__restrict__ keys,
                                                          int nbx, int K, int pubhi, int ncost, int nprep,
                                                          const float *__restrict__ nL, const float *__restrict__ nR,
@@ -1059,6 +1092,251 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
     if (pend) {
         __syncthreads();
         shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, idhi, disp1, keys);
+    }
+}
+
+// ---- the shared form with runs walked in one pass -----------------------------------------------------------------
+// LDS of k_cost_maps_shared: the table area of MapsLds (the LUT; a table workgroup's tile) and ONE staging set that holds
+// a whole run of up to SH_RUN chunks: its anchors and the ext entries S-(D-1)-XPAD .. E+XPAD.
+template <int C> struct RunLds {
+    static constexpr int NA = SH_RUN * FTJ;                  // anchors of a run
+    static constexpr int NXR = NA + 64 * C + 2 * XPAD;       // ext entries of a run
+    uint16_t tab[PREP_LDS_U16];
+    Anchor anc[NA];
+    uint64_t cenx[NXR];
+    uint16_t valx[NXR];
+    uint16_t vala[NA];
+};
+
+// Operands of one run, through registers like MapsStage: same entries, clamps and x4 value scaling, VIEW 0.  Unlike
+// MapsStage's, the loads of a workgroup's second run (a row change inside it, or K > SH_RUN) are issued behind the first
+// run's walk, not held across it, so only the barrier and the flush cover their latency.
+template <int C, bool FULL>
+struct RunStage {
+    static constexpr int NE = (RunLds<C>::NXR + NT - 1) / NT;               // staged entries per thread
+    static_assert(RunLds<C>::NA <= NT, "one anchor per thread");
+    uint64_t cen[NE];
+    unsigned val[NE];
+    Anchor anc;
+    unsigned va;
+    __device__ __forceinline__ void load(int i, int S, int n, int W, int Drt, const Tables &T)
+    {
+        const int D = FULL ? 64 * C : Drt, NX = n * FTJ + D, tid = threadIdx.x;
+        const uint64_t *cenX = T.cenX[0] + (size_t)i * T.WX;
+        const uint8_t *extv = T.u8[1] + (size_t)i * W;
+        const int xbase = S - (D - 1);
+#pragma unroll
+        for (int m = 0; m < NE; m++) {
+            const int e = tid - (FULL ? 0 : XPAD) + m * NT;
+            if (e < NX + (FULL ? 0 : XPAD)) {
+                const int x = xbase + e;
+                int xc = x < -3 ? -3 : (x > W - 1 ? W - 1 : x);
+                const int xv = xc < 0 ? 0 : xc;
+                xc += 3;
+                cen[m] = cenX[xc];
+                val[m] = extv[xv];
+            }
+        }
+        if (tid < n * FTJ) {
+            const int j = min(S + tid, W - 1);
+            anc.cen = T.cenA[0][(size_t)i * W + j];
+            anc.mask = T.mask[(size_t)i * W + j];
+            va = T.u8[0][(size_t)i * W + j];
+        }
+    }
+    __device__ __forceinline__ void store(RunLds<C> &ml, int n, int Drt) const
+    {
+        const int D = FULL ? 64 * C : Drt, NX = n * FTJ + D, tid = threadIdx.x;
+#pragma unroll
+        for (int m = 0; m < NE; m++) {
+            const int e = tid - (FULL ? 0 : XPAD) + m * NT;
+            if (e < NX + (FULL ? 0 : XPAD)) {
+                ml.cenx[XPAD + e] = cen[m];
+                ml.valx[XPAD + e] = (uint16_t)(4u * val[m]);
+            }
+        }
+        if (tid < n * FTJ) { ml.anc[tid] = anc; ml.vala[tid] = (uint16_t)(4u * va); }
+    }
+};
+
+// TWIN of the VIEW 0 publishing body of cost_fast_body (MODE_MAPS_FLOAT), see the note there, over a staged run of n
+// chunks from left column S of row i: wave w walks the 16 n consecutive pixels from S + 16 n w in one pass.  The register window and the four LDS address
+// registers carry through the walk; the interior and all-in tests are taken per wave (per 16-pixel segment inside one
+// loop, the four variants' loop invariants are all live at once and the kernel spills).  Same arithmetic, same keys,
+// same winners as cost_fast_body.
+template <int C, bool FULL>
+__device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__restrict__ disp, int i, int S, int n,
+                                                const RunLds<C> *ml, unsigned long long *ring, int pubhi)
+{
+    const int D = FULL ? 64 * C : Drt;
+    const Anchor *s_anc = ml->anc;
+    const uint16_t *s_vala = ml->vala;
+    const uint64_t *s_cenx = ml->cenx + XPAD;                // entry e in [-XPAD, n * FTJ + D + XPAD): column S-(D-1)+e
+    const uint16_t *s_valx = ml->valx + XPAD;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p0 = wid * (FPW * n);                          // the wave's first pixel in the run
+    const int dlr = lane * C;                                // first hypothesis of this lane
+    const int dl = (FULL || dlr < D) ? dlr : 0;              // lanes entirely past D shadow lane 0
+    bool ok[C];
+#pragma unroll
+    for (int k = 0; k < C; k++) ok[k] = FULL || (dlr + k < D);
+    // ext entry of (pixel p, hypothesis dl+k): p + (D-1) - dl - k; the register ring of cost_fast_body, VIEW 0
+    const int e0 = p0 + (D - 1) - dl;
+    uint64_t rc[C];
+    unsigned rv[C];
+#pragma unroll
+    for (int k = 0; k < C; k++) {
+        const int slot = ((-k % C) + C) % C;
+        rc[slot] = s_cenx[e0 - k];
+        rv[slot] = s_valx[e0 - k];
+    }
+    const char *lutA = (const char *)ml->tab;
+    const float *lutC = (const float *)ml->tab + 256;
+    int res = 0;
+    const int jw0 = S + p0;
+    const int npx = min(FPW * n, W - jw0);                   // uniform; may be <= 0
+    typedef __attribute__((address_space(3))) unsigned long long *lds_key_p;
+    typedef const __attribute__((address_space(3))) uint64_t *lds_u64_p;
+    typedef const __attribute__((address_space(3))) uint16_t *lds_u16_p;
+    const lds_key_p ring3 = (lds_key_p)ring;
+    // wave-uniform anchor addresses and the lane's ext addresses in VGPRs, advanced once per group of C pixels
+    uint32_t anc_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) Anchor *)(s_anc + p0);
+    uint32_t val_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint16_t *)(s_vala + p0);
+    uint32_t nx_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint64_t *)(s_cenx + e0);
+    uint32_t nv_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint16_t *)(s_valx + e0);
+    asm volatile("" : "+v"(anc_a), "+v"(val_a), "+v"(nx_a), "+v"(nv_a));
+
+    auto walk = [&](auto masked_tag, auto allin_tag) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        constexpr bool ALLIN = decltype(allin_tag)::value;
+#pragma unroll 1
+        for (int g = 0; g < npx; g += C) {
+#pragma unroll
+            for (int u = 0; u < C; u++) {
+                const int q = g + u;
+                if (q < npx) {
+                    Anchor a;
+                    if (MASKED) {                                            // one ds_read_b128
+                        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+                        const u64x2 v = *(const __attribute__((address_space(3))) u64x2 *)(size_t)(anc_a + 16u * u);
+                        a.cen = v.x; a.mask = v.y;
+                    }
+                    else { a.cen = *(lds_u64_p)(size_t)(anc_a + 16u * u); a.mask = 0; }
+                    const unsigned va = *(lds_u16_p)(size_t)(val_a + 2u * u);
+                    // entry that joins the ring for the next pixel (always inside the staged range)
+                    const uint64_t nc = *(lds_u64_p)(size_t)(nx_a + 8u * (unsigned)(u + 1));
+                    const unsigned nv = *(lds_u16_p)(size_t)(nv_a + 2u * (unsigned)(u + 1));
+                    float c[C];
+                    unsigned key[C];
+#pragma unroll
+                    for (int k = 0; k < C; k++) {
+                        const int slot = (((u - k) % C) + C) % C;            // E(q-k) with q = u (mod C)
+                        uint64_t x = a.cen ^ rc[slot];
+                        if (MASKED) x &= a.mask;
+                        const int hd = __popcll(x);
+                        const unsigned ad4 = __builtin_amdgcn_sad_u16(va, rv[slot], 0u);   // 4*|va - vx|
+                        c[k] = *(const float *)(lutA + ad4) + lutC[hd];
+                        key[k] = ok[k] ? __float_as_uint(c[k]) : 0xFFFFFFFFu;
+                    }
+                    unsigned ml0 = key[0];
+#pragma unroll
+                    for (int k = 1; k < C; k++) ml0 = min(ml0, key[k]);
+                    const unsigned m = wave_min_u32(ml0);
+                    const unsigned long long b = __ballot(ml0 == m);
+                    const int first = __builtin_ctzll(b);
+                    int kk = C - 1;
+#pragma unroll
+                    for (int k = C - 2; k >= 0; k--)
+                        if ((unsigned)__builtin_amdgcn_readlane((int)key[k], first) == m) kk = k;
+                    const int wd = first * C + kk;           // wave-uniform
+                    res = (lane == q) ? wd : res;            // q <= 63
+                    if constexpr (SMT_SHARED_KNOCKOUT != 1) {
+                        const int tcol = (jw0 + q) - dl;                     // right column of hypothesis k = 0
+                        const lds_key_p rp = ring3 + shared_ring_base(tcol, C);
+#pragma unroll
+                        for (int k = 0; k < C; k++)
+                            if (ok[k] && (ALLIN || shared_publishes(jw0 + q, tcol - k, W, pubhi)))
+                                (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
+                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    // the new entry replaces the one that just left the window
+                    rc[(u + 1) % C] = nc; rv[(u + 1) % C] = nv;
+                }
+            }
+            anc_a += 16u * C; val_a += 2u * C;
+            nx_a += 8u * C; nv_a += 2u * C;
+        }
+    };
+    // per wave, as in cost_fast_body.  interior: every pixel has all 63 taps inside the image, the tap mask is all ones;
+    // all-in: every (pixel, hypothesis) publishes (pubhi <= W-4), no per-hypothesis column test
+    const bool interior = (i >= 4) && (i < H - 4) && jw0 >= 3 && jw0 + npx - 1 <= W - 4;
+    const bool allin = jw0 - (D - 1) >= 3 && jw0 + npx - 1 <= pubhi;
+    if (allin) { if (interior) walk(std::false_type{}, std::true_type{}); else walk(std::true_type{}, std::true_type{}); }
+    else { if (interior) walk(std::false_type{}, std::false_type{}); else walk(std::true_type{}, std::false_type{}); }
+    if (lane < npx) disp[(size_t)i * W + jw0 + lane] = (float)res;
+}
+
+// Shared maps-only form, runs walked in one pass (the default; SMT_SHARED_WALK=chunk keeps k_cost_maps_shared_chunks).
+// Workgroup -> chunks, the fused table grid, the publishes and the key merges are those of the chunk-wise kernel.  Per
+// run (shared_run_len) of n <= SH_RUN chunks: stage once, barrier, every wave walks its quarter of the run and publishes
+// to the ring, barrier, flush every column the run published to (shared_run_flush_range) as an end flush -- complete
+// keys to the map, partial ones to the key map, slots reset.  The next run's staging store follows the flush and the
+// barrier behind it frees the ring and shows the staged set.  Every column still yields one key per run and the merges
+// are minima, so the maps and the final key-map state are the chunk-wise kernel's, bit for bit.
+template <int C, bool FULL>
+__global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(int H, int W, int D, Tables T, float *__restrict__ disp0,
+                                                         float *__restrict__ disp1, unsigned long long *__restrict__ keys,
+                                                         int nbx, int K, int pubhi, int ncost, int nprep,
+                                                         const float *__restrict__ nL, const float *__restrict__ nR,
+                                                         Tables Tn, int ptx)
+{
+    static_assert(PNT == NT, "");
+    static_assert(2 * PSR * PSW * 4 <= PREP_LDS_U16 * 2 && 320 * 4 <= PREP_LDS_U16 * 2, "");
+    __shared__ RunLds<C> lds;
+    __shared__ unsigned long long ring[SH_RING_N];
+    long b = blockIdx.x;
+    if (nprep > 0) {
+        const FusedGrid f = fused_grid(ncost, nprep);
+        int idx;
+        const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
+        b = idx * 8 + (int)(blockIdx.x & 7);
+        if (table) {
+            uint32_t (*sw)[PSW] = (uint32_t (*)[PSW])lds.tab;
+            if (b < nprep) prep_tile(nL, nR, H, W, Tn, (int)b % ptx, (int)b / ptx, ptx, sw, sw + PSR);
+            return;
+        }
+    }
+    const int tid = threadIdx.x;
+    int i = 0, bx = 0;
+    int left = shared_wg_chunks(nbx, H, K, b, i, bx);                      // workgroup-uniform
+    if (left == 0) return;
+    for (int e = tid; e < 320; e += NT) ((float *)lds.tab)[e] = T.lut[e];
+    const int Dd = FULL ? 64 * C : D;
+    const int idhi = shared_id_hi(W, Dd);
+    for (int e = tid; e < SH_RING_N; e += NT) ring[e] = SH_NOKEY;
+    RunStage<C, FULL> st;
+    int n = shared_run_len(nbx, bx, left);
+    st.load(i, FTJ * bx, n, W, D, T);
+    for (;;) {
+        st.store(lds, n, D);
+        __syncthreads();                                                   // the set is staged; the ring is free
+        const int ci = i, cS = FTJ * bx, cn = n;
+        left -= n; bx += n;
+        if (bx == nbx) { bx = 0; i++; }
+        n = shared_run_len(nbx, bx, left);
+        shared_run_walk<C, FULL>(H, W, D, disp0, ci, cS, cn, &lds, ring, pubhi);
+        // A second run (a row change inside the workgroup, or K > SH_RUN) loads behind the walk, in flight across the
+        // barrier and the flush: held across the walk its 11 registers would push the walk into scratch.  At K = 4
+        // about one workgroup in ten has a second run; the exposed latency at K > 4 has not been measured.
+        if (n > 0) st.load(i, FTJ * bx, n, W, D, T);
+        __syncthreads();                                                   // every wave has published the run
+        const int cE = cS + FTJ * cn - 1;
+        int lo, hi;
+        shared_run_flush_range(cS, cE, Dd, pubhi, lo, hi);
+        shared_flush<C>(ring, ci, W, Dd, lo, hi, cS, cE, idhi, disp1, keys);
+        if (n <= 0) break;
     }
 }
 
@@ -1651,6 +1929,14 @@ static bool shared_edges_finish()
     const char *env = getenv("SMT_SHARED_EDGES");
     return !(env && env[0] == 'w' && env[1] == 'g' && env[2] == 0);
 }
+// SMT_SHARED_WALK=chunk in the environment (read at every call) keeps the chunk-wise kernel (k_cost_maps_shared_chunks:
+// one staging, one prologue and one flush per 64-pixel chunk) where by default a run of up to SH_RUN chunks is staged
+// once and walked in one pass (k_cost_maps_shared): tests and same-process A/Bs, same maps.
+static bool shared_walk_runs()
+{
+    const char *env = getenv("SMT_SHARED_WALK");
+    return !(env && strcmp(env, "chunk") == 0);
+}
 // The shapes the shared form serves: an identity set that is not empty, and D <= 192.  With four hypotheses per lane
 // (192 < D <= 256) the lanes' publishes are 32 bytes apart, a 4-way bank conflict, the kernel needs 93 VGPRs and the
 // identity set is a smaller part of the row; measured at 1242 x 375 D = 256 it loses 7 % to the two-view kernel
@@ -1687,8 +1973,12 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
             const bool edges = shared_edges_finish();
             const int ncs = maps_groups(nbx, h->H, 1, K);
             const unsigned gs = nL ? 8u * (unsigned)fused_grid(ncs, nprep).groups : (unsigned)ncs;
-            hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
-                               h->skeys, nbx, K, shared_pub_hi(h->W, h->D, edges), ncs, nprep, nL, nR, Tn, ptx);
+            if (shared_walk_runs())
+                hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
+                                   h->skeys, nbx, K, shared_pub_hi(h->W, h->D, edges), ncs, nprep, nL, nR, Tn, ptx);
+            else
+                hipLaunchKernelGGL((k_cost_maps_shared_chunks<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
+                                   h->skeys, nbx, K, shared_pub_hi(h->W, h->D, edges), ncs, nprep, nL, nR, Tn, ptx);
             if (!edges)
                 hipLaunchKernelGGL((k_shared_right_edges<C, FULL>), dim3((unsigned)maps_groups(shared_right_chunks(nbx, h->W, h->D), h->H, 1, K)),
                                    dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dR, nbx, K);
@@ -2009,20 +2299,25 @@ SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
 }
 
 // Host-side walk of the shared maps-only form (k_cost_maps_shared + k_shared_finish) over pseudo-random costs with many
-// exact ties, through the kernel's own index functions: chunk_decode / maps_groups for the runs, the lane -> hypothesis
-// split, shared_publishes and shared_ring_base for the publishes, shared_flush_range / shared_complete for the flushes
-// (a chunk's flush is applied after the next chunk's publishes, as on the device, and must not meet a slot those
-// touched), the key map for the partial keys, shared_edge_range for the finishing launch's edge hypotheses -- or, with
-// SMT_SHARED_EDGES=wg in the environment, shared_right_chunk(s) for the VIEW 1 chunks.  The right view's pseudo-cost of
-// (i, j', d) is the left one of (i, j' + d, d) where the identity holds and a cost of its own elsewhere, constant in d
-// from W+3-j' on as the staging clamps make it.  SMT_OK iff every right pixel is written exactly once, with the first
-// minimum over all its D hypotheses where the walk computes it (every column by default, the identity set with wg),
-// every ring ends empty and the key map is reset.  Needs no GPU.
+// exact ties, through the kernel's own index functions.  The left pass follows the walk the environment selects:
+//   run walk (default): shared_wg_chunks / shared_run_len give a workgroup's sub-runs of at most SH_RUN chunks
+//     (checked against chunk_decode); a whole run is published, which must not put two columns into one ring slot,
+//     then flushed once as an end flush over shared_run_flush_range.
+//   chunk-wise walk (SMT_SHARED_WALK=chunk): chunk_decode / maps_groups give the runs; a chunk's flush over
+//     shared_flush_range is applied after the next chunk's publishes, as on the device, and must not meet a slot those
+//     touched.
+// Both use the lane -> hypothesis split, shared_publishes and shared_ring_base for the publishes, shared_complete and
+// the key map for the partial keys.  Then the finishing launch's edge hypotheses over shared_edge_range; with
+// SMT_SHARED_EDGES=wg in the environment, shared_right_chunk(s) for the VIEW 1 chunks instead.
+// The right view's pseudo-cost of (i, j', d) is the left one of (i, j' + d, d) where the identity holds and a cost of
+// its own elsewhere, constant in d from W+3-j' on as the staging clamps make it.  SMT_OK iff every right pixel is
+// written exactly once, with the first minimum over all its D hypotheses where the walk computes it (every column by
+// default, the identity set with wg), every ring ends empty and the key map is reset.  Needs no GPU.
 SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed)
 {
     if (H <= 0 || W <= 0 || D <= 0 || D > 256 || K < 1 || K > 64 || (long)H * W > (1L << 24)) return SMT_ERR_ARG;
     const int C = (D + 63) / 64, nbx = (W + FTJ - 1) / FTJ, idhi = shared_id_hi(W, D);
-    const bool edges = shared_edges_finish();
+    const bool edges = shared_edges_finish(), runs = shared_walk_runs();
     const int pubhi = shared_pub_hi(W, D, edges);
     const size_t N = (size_t)H * W;
     // costs: a small palette of floats >= +0 (ties), every cost equal (seed % 3 == 1), or mostly distinct
@@ -2066,10 +2361,42 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                     } else if (k != SH_NOKEY) keys[p] = std::min(keys[p], k);
                 }
             };
+            int view, i, bx, ni, nbxn;
+            if (runs) {
+                // run walk: sub-runs of SH_RUN, the publishes of the whole run, then its one end flush
+                int left = shared_wg_chunks(nbx, H, K, b, i, bx);
+                for (int t = 0; t < K; t++)                                   // the chunks are chunk_decode's
+                    if (chunk_decode(nbx, H, 1, K, b, t, view, ni, nbxn) != (t < left)) rc = SMT_ERR_STATE;
+                int owner[SH_RING_N];                                         // right column that holds a slot in this run
+                for (int t = 0; left > 0 && rc == SMT_OK;) {
+                    const int n = shared_run_len(nbx, bx, left);
+                    if (n < 1 || n > SH_RUN) { rc = SMT_ERR_STATE; break; }
+                    for (int u = 0; u < n; u++)
+                        if (!chunk_decode(nbx, H, 1, K, b, t + u, view, ni, nbxn) || ni != i || nbxn != bx + u) rc = SMT_ERR_STATE;
+                    const int S = 64 * bx, E = S + 64 * n - 1;
+                    for (int e = 0; e < SH_RING_N; e++) owner[e] = -1;
+                    for (int j = S; j <= E && j < W; j++)
+                        for (int lane = 0; lane < 64; lane++)
+                            for (int k = 0; k < C; k++) {
+                                const int dl = lane * C, d = dl + k, tcol = j - dl;
+                                if (d >= D || !shared_publishes(j, tcol - k, W, pubhi)) continue;
+                                const int s = shared_ring_base(tcol, C) + (C - 1 - k);
+                                if (owner[s] != -1 && owner[s] != tcol - k) rc = SMT_ERR_STATE;   // two live columns in a slot
+                                owner[s] = tcol - k;
+                                ring[s] = std::min(ring[s], shared_key(cost_bits(i, j, d), d));
+                            }
+                    int lo, hi;
+                    shared_run_flush_range(S, E, D, pubhi, lo, hi);
+                    flush(i, lo, hi, S, E, 0, true);
+                    for (int e = 0; e < SH_RING_N; e++) if (ring[e] != SH_NOKEY) rc = SMT_ERR_STATE;   // free for the next run
+                    left -= n; t += n; bx += n;
+                    if (bx == nbx) { bx = 0; i++; }
+                }
+                continue;
+            }
             bool pend = false, pend_end = false;
             int pi = 0, plo = 0, phi = -1, pS = 0, pE = 0, S = -1;
             long serial = 0;
-            int view, i, bx, ni, nbxn;
             bool have = chunk_decode(nbx, H, 1, K, b, 0, view, i, bx);
             for (int t = 0; have && rc == SMT_OK; t++, serial++) {
                 if (pend && pend_end) { flush(pi, plo, phi, pS, pE, serial - 1, true); pend = false; }

@@ -1,0 +1,138 @@
+"""The shared maps-only form of smt_adcensus_compute_batch with runs walked in one pass (adcensus.hip, k_cost_maps_shared):
+a workgroup stages a run of up to SH_RUN = 4 consecutive chunks of one row once, every wave walks a contiguous quarter of
+it, and the run's columns are flushed once.  Every map of every pair, NaN-prefilled, against the oracle's WTA and against
+the same call under SMT_MAPS_SHARED=0 (the two-view kernel) and SMT_SHARED_WALK=chunk (the chunk-wise kernel), and a
+second identical call (the key map was left reset), at the shapes of adcensus_shared_runs_cases.py: short ones, and the
+smallest that reach a 4-chunk run (64 pixels per wave), a row change inside a workgroup, sub-runs, a walk cut by W, every
+C and 511 live columns, the ring's bound (test_adcensus_shared_runs_cpu.py asserts that they do); ties everywhere; one
+map requested (the two-view kernel serves those calls, as test_adcensus_shared_edges_gpu.py establishes)."""
+import ctypes as C
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from adcensus_shared_runs_cases import CHUNKS, SHAPES  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+B = 2
+ENV = ("SMT_MAPS_SHARED", "SMT_SHARED_EDGES", "SMT_SHARED_WALK", "SMT_MAPS_KERNEL", "SMT_BATCH_VOLUMES", "SMT_OVERLAP",
+       "SMT_MAPS_CHUNKS")
+_ORACLE = None
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _env(mp, name, value):
+    if value is None: mp.delenv(name, raising=False)
+    else: mp.setenv(name, value)
+
+
+def _batch(adc, Lb, Rb, maps="both"):
+    from stereo_match_traditional_amd._lib import lib, VIEW_BOTH
+    n, H, W = Lb.shape
+    dl = torch.full((n, H, W), float("nan"), device=Lb.device) if maps in ("both", "left") else None
+    dr = torch.full((n, H, W), float("nan"), device=Lb.device) if maps in ("both", "right") else None
+    adc._bind_stream()
+    assert lib().smt_adcensus_compute_batch(adc._h, _p(Lb), _p(Rb), n, VIEW_BOTH, _p(dl), _p(dr)) == 0
+    adc.status()
+    return (None if dl is None else dl.cpu().numpy()), (None if dr is None else dr.cpu().numpy())
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to("cuda:0")
+
+
+def _handle(smt, Lb, Rb, D):
+    _, H, W = Lb.shape
+    return smt.AD_Census().Initialize(Lb[0], Rb[0], D, H, W, 10.0, 30.0, placement_search=False, store_calibration=False)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(H, W, D):
+    """images and the oracle's maps of every pair, computed once per shape"""
+    O = _ORACLE
+    Ls, Rs = zip(*[O.synth_pair(H, W, D, 8100 + 13 * b + W, noise=(b % 2 == 0)) for b in range(B)])
+    maps = [(O.wta(O.adcensus_view(Ls[b], Rs[b], D, 10.0, 30.0, 0)), O.wta(O.adcensus_view(Ls[b], Rs[b], D, 10.0, 30.0, 1)))
+            for b in range(B)]
+    for a, c in maps:
+        a.setflags(write=False); c.setflags(write=False)
+    return np.stack(Ls), np.stack(Rs), maps
+
+
+@pytest.fixture(autouse=True)
+def _oracle(O, monkeypatch):
+    global _ORACLE
+    _ORACLE = O
+    for name in ENV:
+        monkeypatch.delenv(name, raising=False)
+
+
+def _check(dl, dr, maps, what):
+    for b, (ml, mr) in enumerate(maps):
+        assert np.array_equal(dl[b], ml), ("left", b, np.argwhere(dl[b] != ml)[:4].tolist()) + what
+        assert np.array_equal(dr[b], mr), ("right", b, np.argwhere(dr[b] != mr)[:4].tolist()) + what
+
+
+@pytest.mark.parametrize("H,W,D,form", SHAPES)
+def test_batch_against_the_oracle_and_the_other_forms(smt, H, W, D, form, monkeypatch):
+    Ls, Rs, maps = _case(H, W, D)
+    Lb, Rb = _dev(Ls), _dev(Rs)
+    adc = _handle(smt, Lb, Rb, D)
+    _env(monkeypatch, "SMT_MAPS_SHARED", form)
+    for K in CHUNKS:
+        _env(monkeypatch, "SMT_MAPS_CHUNKS", K)
+        dl, dr = _batch(adc, Lb, Rb)
+        _check(dl, dr, maps, (K, "runs"))
+        monkeypatch.setenv("SMT_SHARED_WALK", "chunk")
+        dlc, drc = _batch(adc, Lb, Rb)
+        monkeypatch.delenv("SMT_SHARED_WALK")
+        _check(dlc, drc, maps, (K, "chunk"))
+        monkeypatch.setenv("SMT_MAPS_SHARED", "0")
+        dl0, dr0 = _batch(adc, Lb, Rb)
+        _env(monkeypatch, "SMT_MAPS_SHARED", form)
+        for a, b in ((dl, dlc), (dr, drc), (dl, dl0), (dr, dr0)):
+            assert np.array_equal(a, b), K
+        # the key map was left reset: the same call again gives the same maps
+        dl2, dr2 = _batch(adc, Lb, Rb)
+        assert np.array_equal(dl, dl2) and np.array_equal(dr, dr2), K
+    adc.close()
+
+
+@pytest.mark.parametrize("H,W,D,form", [(6, 330, 192, None), (8, 700, 256, "force")])
+def test_constant_images_tie_everywhere(smt, H, W, D, form, monkeypatch):
+    """every cost of a pixel is equal, edge hypotheses included: both maps are 0 everywhere"""
+    Lb = torch.full((B, H, W), 77.0, device="cuda:0")
+    Rb = torch.full((B, H, W), 77.0, device="cuda:0")
+    adc = _handle(smt, Lb, Rb, D)
+    _env(monkeypatch, "SMT_MAPS_SHARED", form)
+    for K in CHUNKS:
+        _env(monkeypatch, "SMT_MAPS_CHUNKS", K)
+        dl, dr = _batch(adc, Lb, Rb)
+        assert np.array_equal(dl, np.zeros((B, H, W), np.float32)), K
+        assert np.array_equal(dr, np.zeros((B, H, W), np.float32)), K
+    adc.close()
+
+
+@pytest.mark.parametrize("which", ["left", "right"])
+def test_one_map_requested(smt, which, monkeypatch):
+    H, W, D = 6, 330, 192
+    Ls, Rs, maps = _case(H, W, D)
+    Lb, Rb = _dev(Ls), _dev(Rs)
+    adc = _handle(smt, Lb, Rb, D)
+    dl, dr = _batch(adc, Lb, Rb, which)
+    for b in range(B):
+        if which == "left": assert dr is None and np.array_equal(dl[b], maps[b][0]), b
+        else: assert dl is None and np.array_equal(dr[b], maps[b][1]), b
+    # and both maps from the same handle afterwards
+    dl, dr = _batch(adc, Lb, Rb)
+    _check(dl, dr, maps, (which,))
+    adc.close()
