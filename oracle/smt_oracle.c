@@ -769,7 +769,10 @@ ORC_API void orc_sad_crosscheck(const int32_t *dL, const int32_t *dR, int H, int
             int lv = dL[i * W + j];
             long idx = (long)i * W + j - lv;                           /* :204 flat pointer arithmetic */
             int rv = (idx >= 0 && idx < (long)H * W) ? dR[idx] : 0;
-            int diff = abs(lv - rv);
+            /* abs(lv - rv) as x86 computes it (signed overflow is undefined in C): the subtraction wraps, and the
+             * negation of INT_MIN is INT_MIN, which is not above the threshold */
+            int sub = (int)((unsigned)lv - (unsigned)rv);
+            int diff = sub < 0 ? (int)(0u - (unsigned)sub) : sub;
             if (diff > 5) {
                 cls[i * W + j] = (lv < rv) ? 1 : 2;
                 out[i * W + j] = INT32_MIN;

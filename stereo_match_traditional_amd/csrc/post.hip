@@ -130,7 +130,10 @@ __global__ void __launch_bounds__(NT) k_sad_crosscheck(const int32_t *__restrict
     const int lv = dL[p];
     const long idx = (long)p - lv;                                        // flat pointer arithmetic, Sad.h:204
     const int rv = (idx >= 0 && idx < n) ? dR[idx] : 0;
-    const int diff = abs(lv - rv);
+    // abs(leftvalue - rightvalue) :205 as x86 computes it: the subtraction wraps and the negation of INT_MIN is INT_MIN
+    // (signed overflow, undefined in C++; left to the compiler, `abs(lv - rv) > 5` came out true for INT_MIN here)
+    const int sub = (int)((unsigned)lv - (unsigned)rv);
+    const int diff = sub < 0 ? (int)(0u - (unsigned)sub) : sub;
     if (diff > 5) {                                                       // diffthreshold :192
         cls[p] = (lv < rv) ? 1 : 2;
         out[p] = INT32_MIN;                                               // int(inf) on x86

@@ -20,6 +20,96 @@ INT_MIN = -(2 ** 31)
 D_EDGES = (1, 5, 63, 64, 65, 100, 192, 255, 256, 257, 320, 512)
 
 
+HOSTILE_LR = ((1, 1, 71, 0), (1, 9, 72, 1), (7, 1, 73, 2), (5, 300, 74, -1), (33, 77, 75, 1))     # (H, W, seed, gate)
+
+
+def hostile_lr_maps(H, W, seed):
+    """(dL, dR) float32 [H][W] for LeftRightConsistency: a valid integer base -- a third of the pixels consistent in both
+    views, the rest random small integers -- plus sprinkles of what a disparity map is not supposed to hold: fractional
+    parts .25 / .5 / .75 (the x.5 ties of j - d + 0.5 among them), negative disparities, -0.0, NaN, +-inf, +-3e9, 1e30, a
+    denormal, in either map; left disparities that put col_right = (int)(j - d + 0.5) on -1, 0, W - 1 and W; right
+    disparities that put col_rl = (int)(col_right + dR + 0.5) on 0, j, W - 1 and W."""
+    rng = np.random.default_rng(seed)
+    top = max(1, min(W, 12))
+    dL = rng.integers(0, top, (H, W)).astype(np.float32)
+    dR = rng.integers(0, top, (H, W)).astype(np.float32)
+    jj = np.broadcast_to(np.arange(W), (H, W))
+    ii = np.broadcast_to(np.arange(H)[:, None], (H, W))
+    cr = jj - dL.astype(np.int64)
+    ok = (cr >= 0) & (rng.random((H, W)) < 0.33)
+    dR[ii[ok], cr[ok]] = dL[ok]                                           # consistent pixels
+    special = np.array([np.nan, np.inf, -np.inf, 3e9, -3e9, 1e30, 1e-40, -0.0], np.float32)
+    for m in (dL, dR):
+        r = rng.random((H, W))
+        frac = r < 0.12
+        m[frac] += rng.choice(np.array([0.25, 0.5, 0.75], np.float32), int(frac.sum()))
+        neg = (r >= 0.12) & (r < 0.18)
+        m[neg] = -m[neg] - rng.choice(np.array([0.0, 0.5, 1.0, 1.5], np.float32), int(neg.sum()))
+        sp = (r >= 0.18) & (r < 0.26)
+        m[sp] = rng.choice(special, int(sp.sum()))
+    # col_right on -1 (j - d + 0.5 = -1.5, and -1.0 exactly), 0 (from +0.5 and from -0.5: truncation toward zero), W - 1, W
+    r = rng.random((H, W))
+    for lo, hi, off in ((0.00, 0.02, 2.0), (0.02, 0.04, 1.5), (0.04, 0.06, 0.0), (0.06, 0.08, 1.0), (0.08, 0.10, 1.0 - W),
+                        (0.10, 0.12, -float(W))):
+        m = (r >= lo) & (r < hi)
+        dL[m] = (jj[m] + off).astype(np.float32)
+    # col_rl on 0, j, W - 1 and W: through pixels whose col_right is inside the row
+    r = rng.random((H, W))
+    with np.errstate(invalid="ignore"):
+        c = np.trunc(jj.astype(np.float32) - dL + np.float32(0.5))
+    inside = np.isfinite(c) & (c >= 0) & (c < W)
+    for k, (lo, hi) in enumerate(((0.00, 0.04), (0.04, 0.08), (0.08, 0.12), (0.12, 0.16))):
+        m = inside & (r >= lo) & (r < hi)
+        cc = c[m].astype(np.int64)
+        target = (np.zeros_like(cc), jj[m], np.full_like(cc, W - 1), np.full_like(cc, W))[k]
+        # (a right disparity that leads back to j exactly is consistent; a quarter more still lands on j and is a
+        # mismatch under the gates below 1, the only ones that can reach col_rl == j)
+        dR[ii[m], cc] = (target - cc).astype(np.float32) + np.float32(0.25 if k == 1 else 0.0)
+    return dL, dR
+
+
+def d2i(x):
+    """the oracle's orc_d2i on float64 values: truncation toward zero, INT_MIN where the value does not fit an int"""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore"):
+        fits = (x > -2147483649.0) & (x < 2147483648.0)
+        return np.where(fits, np.trunc(np.where(fits, x, 0.0)), float(INT_MIN)).astype(np.int64)
+
+
+def chain_counts(dL, dR, gate, after):
+    """Over the pixels the LR check classifies through leftDisp[i][col_rl] with col_rl < j (PostProcessing.h:110-118): how
+    many of those pixels col_rl had been rejected before (the reference reads the +inf it wrote there; smt_lrcheck
+    recomputes that in lr_rejected), how many had not, and on how many the class depends on it.  `after`: the oracle's
+    leftDisp after the check (+inf = rejected).  Also the sets of col_right and col_rl values met at the row ends."""
+    H, W = dL.shape
+    rejected = kept = decides = 0
+    ends_cr, ends_crl = set(), set()
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(H):
+            for j in range(W):
+                d = dL[i, j]
+                if d == np.inf:
+                    continue
+                cr = int(d2i(np.float64(np.float32(j) - d) + 0.5))
+                if cr in (-1, 0, W - 1, W):
+                    ends_cr.add(cr)
+                if not 0 <= cr < W:
+                    continue
+                dr = dR[i, cr]
+                if not np.abs(d - dr) > np.float32(gate):
+                    continue
+                crl = int(d2i(np.float64(np.float32(cr) + dr) + 0.5))
+                if crl in (0, W - 1, W) or crl == j:
+                    ends_crl.add("j" if crl == j and crl not in (0, W - 1) else crl)
+                if 0 < crl < j:
+                    if after[i, crl] == np.inf:
+                        rejected += 1
+                        decides += not (dL[i, crl] > d)                 # without the chain: class 2; with it: class 1
+                    else:
+                        kept += 1
+    return rejected, kept, decides, ends_cr, ends_crl
+
+
 def smooth_img(H, W, seed, step=3):
     """piecewise-smooth image with long flat runs so arms pass 17 and the sticky threshold flips
     (the generator of tests/test_pipeline_gpu.py)"""
@@ -134,6 +224,12 @@ def _cases():
     for (H, W, seed, gate) in [(20, 60, 1, 2), (9, 200, 2, 1), (30, 31, 3, 5), (1, 50, 4, 2), (40, 1, 5, 1)]:
         c.append(dict(kind="lrcheck", name=f"lr_{H}x{W}", H=H, W=W, seed=seed, gate=gate))
         c.append(dict(kind="lrvariant", name=f"lrv_{H}x{W}", H=H, W=W, seed=seed, gate=gate))
+
+    # the in-place LR check on hostile maps (hostile_lr_maps): fractions and x.5 ties, negative, non-finite and
+    # out-of-int disparities, columns landing on -1, 0, W - 1 and W; the shapes and gates of
+    # tests/test_consistency_hostile_gpu.py, one gate per shape here
+    for (H, W, seed, gate) in HOSTILE_LR:
+        c.append(dict(kind="lrcheck", name=f"lr_hostile_{H}x{W}", H=H, W=W, seed=seed, gate=gate, hostile=True))
 
     # FillTheHole: lists in LeftRightConsistency's own (row, col) form need row >= col to stay inside the swapped
     # extents; the generator draws pairs inside them
@@ -252,6 +348,9 @@ def inputs(case, O):
         return _scan_inputs(case)
     if k in ("lrcheck", "lrvariant"):
         H, W = case["H"], case["W"]
+        if case.get("hostile"):
+            dL, dR = hostile_lr_maps(H, W, case["seed"])
+            return dict(dL=dL, dR=dR)
         rng = np.random.default_rng(case["seed"])
         dL = rng.integers(0, 24, (H, W)).astype(np.float32)
         dR = rng.integers(0, 24, (H, W)).astype(np.float32)

@@ -108,6 +108,35 @@ def test_nan_first_pixel_changes_the_whole_line(O):
     assert (got[:, 1, 10:] != other[:, 1, 10:]).any(axis=1).all()
 
 
+def test_hostile_maps_hold_what_they_promise(O):
+    """checked on the oracle alone: every kind of value is there, the columns land on the row ends, and the chain that
+    lr_rejected recomputes is exercised both ways and decides classes"""
+    H, W, seed, _ = RP.HOSTILE_LR[-1]
+    dL, dR = RP.hostile_lr_maps(H, W, seed)
+    for m in (dL, dR):
+        assert np.isnan(m).any() and (m == np.inf).any() and (m == -np.inf).any()
+        assert (m == np.float32(3e9)).any() and (m == np.float32(-3e9)).any() and (m == np.float32(1e30)).any()
+        assert ((m != 0) & (np.abs(m) < np.finfo(np.float32).tiny)).any()                       # the denormal
+        assert (np.signbit(m) & (m == 0)).any()                                                # -0.0
+        fin = m[np.isfinite(m) & (np.abs(m) < 1e6)]
+        assert {0.25, 0.5, 0.75} <= set(np.round(np.abs(fin) % 1, 2).tolist())
+        assert (fin < 0).any()
+    for gate in (0, 1, 2, -1):
+        after, cls, _, _ = O.lrcheck(dL, dR, gate)
+        rejected, kept, decides, ends_cr, ends_crl = RP.chain_counts(dL, dR, gate, after)
+        # (under a negative gate every comparable pixel is rejected: nothing is left to be kept)
+        assert rejected > 0 and decides > 0 and (kept > 0 or gate < 0), (gate, rejected, kept, decides)
+        assert ends_cr == {-1, 0, W - 1, W}, (gate, ends_cr)
+        # col_rl == j needs |d - dR| <= 1 up to the roundings: only the gates below 1 call that a mismatch
+        assert ends_crl >= ({0, "j", W - 1, W} if gate < 1 else {0, W - 1, W}), (gate, ends_crl)
+        assert set(np.unique(cls).tolist()) == {0, 1, 2}, gate
+    # an x.5 tie of j - d + 0.5 on both sides of zero: -0.5 truncates to column 0, not to -1
+    jj = np.broadcast_to(np.arange(W, dtype=np.float32), (H, W))
+    with np.errstate(invalid="ignore"):
+        t = jj - dL + np.float32(0.5)
+        assert (t == -0.5).any() and (t == -1.0).any() and (np.isfinite(t) & (t > 0) & (t % 1 == 0.5)).any()
+
+
 def test_reference_builds_are_clean_under_asan():
     """`make -C oracle ref-asan`: the two reference wrappers built with AddressSanitizer run every admitted case once
     (host code; leaks are not reported, the reference leaks by design).  Skipped as the reference build is where the
