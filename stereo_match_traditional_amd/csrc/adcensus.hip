@@ -1169,6 +1169,12 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
                                                 const RunLds<C> *ml, unsigned long long *ring, int pubhi)
 {
     const int D = FULL ? 64 * C : Drt;
+    // The vector-instruction trims below (the winner's v_writelane, the untied first DPP step, 32-bit window values, the
+    // stepped ring address) are taken by the D = 192 kernel only: it is the form they were measured to pay in.  At
+    // C = 2 the same four measured slower at 720p x 128 in every run, with the stepped address (64 -> 70 VGPRs, 8 -> 7
+    // waves per SIMD) and without it, and the other forms gain scratch with the stepped address; those compile to the
+    // code they had.
+    constexpr bool TRIM = C == 3 && FULL;
     const Anchor *s_anc = ml->anc;
     const uint16_t *s_vala = ml->vala;
     const uint64_t *s_cenx = ml->cenx + XPAD;                // entry e in [-XPAD, n * FTJ + D + XPAD): column S-(D-1)+e
@@ -1192,6 +1198,8 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
         rc[slot] = s_cenx[e0 - k];
         rv[slot] = s_valx[e0 - k];
     }
+#pragma unroll
+    for (int k = 0; k < C; k++) if constexpr (TRIM) asm("" : "+v"(rv[k]));   // 32-bit values from here on (see the walk)
     const char *lutA = (const char *)ml->tab;
     const float *lutC = (const float *)ml->tab + 256;
     int res = 0;
@@ -1207,6 +1215,12 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
     uint32_t nx_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint64_t *)(s_cenx + e0);
     uint32_t nv_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint16_t *)(s_valx + e0);
     asm volatile("" : "+v"(anc_a), "+v"(val_a), "+v"(nx_a), "+v"(nv_a));
+    // byte offset in the ring of slot shared_ring_base(t, C) of the pixel at hand, t = j - dl: advanced by one slot per
+    // pixel and wrapped, where computing it from the column takes two more vector instructions per pixel, at the price of
+    // one more live register
+    constexpr bool RING_STEP = TRIM;
+    const uint32_t ring_b = (uint32_t)(size_t)ring3;
+    uint32_t ra = 8u * (uint32_t)shared_ring_base(jw0 - dl, C);
 
     auto walk = [&](auto masked_tag, auto allin_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
@@ -1243,7 +1257,10 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
                     unsigned ml0 = key[0];
 #pragma unroll
                     for (int k = 1; k < C; k++) ml0 = min(ml0, key[k]);
-                    const unsigned m = wave_min_u32(ml0);
+                    // ml0 is compared against the minimum below, so the untied form saves its copy per pixel
+                    unsigned m;
+                    if constexpr (TRIM) m = wave_min_u32_untied(ml0);
+                    else m = wave_min_u32(ml0);
                     const unsigned long long b = __ballot(ml0 == m);
                     const int first = __builtin_ctzll(b);
                     int kk = C - 1;
@@ -1251,18 +1268,33 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
                     for (int k = C - 2; k >= 0; k--)
                         if ((unsigned)__builtin_amdgcn_readlane((int)key[k], first) == m) kk = k;
                     const int wd = first * C + kk;           // wave-uniform
-                    res = (lane == q) ? wd : res;            // q <= 63
+                    // lane q keeps pixel q's winner (q <= 63): one v_writelane where (lane == q) ? wd : res took a
+                    // compare and a move under a saved exec mask.  This compiler has no writelane builtin, hence the
+                    // statement.  Both sources are scalar and gfx9 reads one SGPR per vector instruction, so the lane
+                    // goes in m0.  No wait states are needed: on gfx9 only a lane select in an SGPR that a vector
+                    // instruction wrote has a hazard, and m0 is written by the s_mov.  The compiler warns about the m0
+                    // clobber (-Winline-asm) at each instantiation; the kernel uses m0 nowhere else.
+                    if constexpr (TRIM)
+                        asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(res) : "s"(__builtin_amdgcn_readfirstlane(wd)), "s"(q) : "m0");
+                    else res = (lane == q) ? wd : res;
                     if constexpr (SMT_SHARED_KNOCKOUT != 1) {
                         const int tcol = (jw0 + q) - dl;                     // right column of hypothesis k = 0
-                        const lds_key_p rp = ring3 + shared_ring_base(tcol, C);
+                        lds_key_p rp;
+                        if constexpr (RING_STEP) rp = (lds_key_p)(size_t)(ring_b + ra);
+                        else rp = ring3 + shared_ring_base(tcol, C);
 #pragma unroll
                         for (int k = 0; k < C; k++)
                             if (ok[k] && (ALLIN || shared_publishes(jw0 + q, tcol - k, W, pubhi)))
                                 (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
-                    // the new entry replaces the one that just left the window
-                    rc[(u + 1) % C] = nc; rv[(u + 1) % C] = nv;
+                    if constexpr (RING_STEP) ra = (ra + 8u) & (8u * SH_RING - 1u);
+                    // the new entry replaces the one that just left the window.  The value is made a 32-bit one here:
+                    // carried round the loop as the 16 bits it was loaded as, it is zero-extended again at every use
+                    // (one v_and per pixel), though ds_read_u16 already returned it so
+                    unsigned nv32 = nv;
+                    if constexpr (TRIM) asm("" : "+v"(nv32));
+                    rc[(u + 1) % C] = nc; rv[(u + 1) % C] = nv32;
                 }
             }
             anc_a += 16u * C; val_a += 2u * C;

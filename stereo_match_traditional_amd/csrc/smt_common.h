@@ -101,16 +101,31 @@ __device__ __forceinline__ unsigned dpp_u32(unsigned v)
     // old = identity of umin so the DPP combiner can fold the move into v_min_u32_dpp
     return (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROW_MASK, 0xF, false);
 }
-// minimum over the wave of unsigned keys, returned wave-uniform (SGPR).
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+// the steps of the wave minimum behind the first quad_perm step, shared by the two forms below
+__device__ __forceinline__ unsigned wave_min_u32_tail(unsigned v)
 {
-    v = min(v, dpp_u32<0xB1, 0xF>(v));    // quad_perm [1,0,3,2]
     v = min(v, dpp_u32<0x4E, 0xF>(v));    // quad_perm [2,3,0,1]
     v = min(v, dpp_u32<0x141, 0xF>(v));   // row_half_mirror
     v = min(v, dpp_u32<0x140, 0xF>(v));   // row_mirror      -> every lane holds its row's min
     v = min(v, dpp_u32<0x142, 0xA>(v));   // row_bcast15 into rows 1,3
     v = min(v, dpp_u32<0x143, 0xC>(v));   // row_bcast31 into rows 2,3 -> lane 63 holds the min
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+// minimum over the wave of unsigned keys, returned wave-uniform (SGPR).
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+{
+    v = min(v, dpp_u32<0xB1, 0xF>(v));    // quad_perm [1,0,3,2]
+    return wave_min_u32_tail(v);
+}
+// wave_min_u32 for a caller that needs v again afterwards.  The compiler's DPP form ties source and destination, so the
+// first step above copies such a v first; here that step is written out untied.  Every lane of a quad_perm is valid, so
+// the value is the same.  The s_nops are the two wait states between a vector write and a DPP read of the same register,
+// on both sides of the step.
+__device__ __forceinline__ unsigned wave_min_u32_untied(unsigned v)
+{
+    unsigned w;
+    asm("s_nop 1\n\tv_min_u32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\ts_nop 1" : "=v"(w) : "v"(v));
+    return wave_min_u32_tail(w);
 }
 // order-preserving map float -> uint32 (handles negatives; NaNs are not ordered -- wave_wta gives them
 // the reference's semantics)
