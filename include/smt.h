@@ -284,22 +284,15 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  *   SMT_MAPS_SHARED=0 in the environment (read at every call, like SMT_MAPS_CHUNKS / SMT_MAPS_KERNEL / SMT_OVERLAP)
  *   keeps the two-view kernel everywhere, SMT_MAPS_SHARED=force takes the shared form for every D <= 256 with
  *   W >= D + 6: same-process A/Bs and tests.  SMT_MAPS_KERNEL=rank selects the rank kernel as before.
- *   SMT_SHARED_EDGES=wg in the environment (read at every call) publishes the columns 3 .. W-3-D only and runs the
- *   right-view body in workgroups of its own over the 64-pixel chunks that hold the other columns, as before the edge
- *   hypotheses moved to the finishing launch: same-process A/Bs and tests, same maps.
- *   SMT_SHARED_WALK=chunk in the environment (read at every call) keeps the chunk-wise left pass, which stages, walks
- *   (16 pixels per wave) and flushes every 64-pixel chunk by itself, where by default a workgroup stages a run of up to
- *   4 consecutive chunks of one row once, every wave walks a contiguous quarter of it in one pass and the run's columns
- *   are flushed once: same-process A/Bs and tests, same maps.  smt_adcensus_selftest_shared_keys follows the walk the
- *   environment selects.
+ * In the left pass a workgroup stages a run of up to 4 consecutive 64-pixel chunks of one row once, every wave walks a
+ * contiguous quarter of it in one pass and the run's columns are flushed once.
  * Test hook, host only (no GPU), exported by the library and declared in csrc/adcensus_internal.h:
  *   int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
  * walks the runs of K chunks per workgroup, the key ring, its flushes and the key-map merges of that form through the
  * kernel's own index functions over pseudo-random costs with many exact ties (seed % 3: 0 a palette with ties, 1 every
  * cost equal, 2 mostly distinct; the right view's edge hypotheses have pseudo-costs of their own).  SMT_OK iff every
  * right pixel is written exactly once, with the first minimum over its shared and its edge hypotheses, every ring ends
- * empty and the key map is reset (under SMT_SHARED_EDGES=wg: the columns 3 .. W-3-D so, every other right pixel left
- * to the right-view chunks, once);
+ * empty and the key map is reset;
  * SMT_ERR_STATE otherwise; SMT_ERR_ARG unless H, W >= 1, 1 <= D <= 256, 1 <= K <= 64. */
 
 /* Synchronises the stream and returns SMT_ERR_DOMAIN if any pixel seen since the previous

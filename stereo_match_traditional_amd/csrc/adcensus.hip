@@ -408,15 +408,12 @@ __device__ __forceinline__ void st_stream(__amdgpu_buffer_rsrc_t r, unsigned vof
 // row, and neither AD clamp acts.  The left pass publishes these costs as keys to the right columns they belong to:
 //   key = cost bits << 32 | d; costs are >= +0, so the unsigned minimum is the smallest cost, then the smallest d --
 //   the reference's first strict minimum.  SH_NOKEY (all ones) is no key: d < 512.
-// A left hypothesis (j, d) publishes when j <= W-4 and 3 <= j - d <= pubhi (shared_publishes).  Two forms:
-//   edges finished apart (default, pubhi = W-4): every shareable cost is published.  The columns of the IDENTITY SET
-//     3 <= j' <= W-3-D get all their D hypotheses that way.  A column j' > W-3-D lacks the EDGE HYPOTHESES with
-//     j' + d >= W-3; the VIEW 1 staging clamps the census index to W+3 and the value index to W-1, so the cost is
-//     constant in d from W+3-j' on and only d <= W+3-j' can be a first minimum: at most 7 per column
-//     (shared_edge_range).  Columns 0..2 share nothing.  k_shared_finish evaluates the edge hypotheses from the tables
-//     and merges them with the column's key.
-//   SMT_SHARED_EDGES=wg (pubhi = W-3-D): only the identity set is published; right pixels outside it keep the VIEW 1
-//     body, which k_shared_right_edges runs over chunk 0 and the chunks from shared_right_tail() on.
+// A left hypothesis (j, d) publishes when j <= W-4 and 3 <= j - d <= pubhi (shared_publishes), pubhi = W-4
+// (shared_pub_hi): every shareable cost is published.  The columns of the IDENTITY SET 3 <= j' <= W-3-D get all their D
+// hypotheses that way.  A column j' > W-3-D lacks the EDGE HYPOTHESES with j' + d >= W-3; the VIEW 1 staging clamps the
+// census index to W+3 and the value index to W-1, so the cost is constant in d from W+3-j' on and only d <= W+3-j' can
+// be a first minimum: at most 7 per column (shared_edge_range).  Columns 0..2 share nothing.  k_shared_finish evaluates
+// the edge hypotheses from the tables and merges them with the column's key.
 // Runs of chunks are those of chunk_decode (below).
 #ifndef SMT_SHARED_KNOCKOUT
 #define SMT_SHARED_KNOCKOUT 0      // measurement builds only (wrong maps): 1 no LDS publishes, 2 no key-map merges
@@ -425,29 +422,17 @@ constexpr int SH_RING = 512;                                 // key ring, indexe
 constexpr int SH_RING_N = SH_RING + 4;                       // + the spill slots of shared_ring_base()
 constexpr unsigned long long SH_NOKEY = ~0ull;
 __host__ __device__ inline int shared_id_hi(int W, int D) { return W - 3 - D; }           // the set is [3, hi]; empty when hi < 3
-__host__ __device__ inline int shared_pub_hi(int W, int D, bool edges) { return edges ? W - 4 : shared_id_hi(W, D); }
+__host__ __device__ inline int shared_pub_hi(int W) { return W - 4; }                     // last published right column
 __host__ __device__ inline bool shared_in_set(int c, int hi) { return (unsigned)(c - 3) <= (unsigned)(hi - 3) && hi >= 3; }
-// left pixel j publishes a hypothesis to right column c = j - d (j <= W-4 is implied where pubhi = W-3-D)
+// left pixel j publishes a hypothesis to right column c = j - d
 __host__ __device__ inline bool shared_publishes(int j, int c, int W, int pubhi) { return j <= W - 4 && shared_in_set(c, pubhi); }
 __host__ __device__ inline unsigned long long shared_key(unsigned cost_bits, int d) { return ((unsigned long long)cost_bits << 32) | (unsigned)d; }
-// right-view chunks that are still computed (set not empty): e = 0 is chunk 0, e >= 1 is chunk tail + e - 1
-__host__ __device__ inline int shared_right_tail(int W, int D) { const int b = (shared_id_hi(W, D) + 1) >> 6; return b < 1 ? 1 : b; }
-__host__ __device__ inline int shared_right_chunks(int nbx, int W, int D) { return 1 + nbx - shared_right_tail(W, D); }
-__host__ __device__ inline int shared_right_chunk(int e, int W, int D) { return e == 0 ? 0 : shared_right_tail(W, D) + e - 1; }
 // A lane publishes its C hypotheses d = dl .. dl+C-1 of left pixel j to the right columns t - k, t = j - dl: ring slot
 // base + (C-1-k) with base = (t - (C-1)) mod 512, one address computation per pixel.  A column c with c mod 512 < C-1
 // can therefore land in slot c mod 512 or in the spill slot 512 + c mod 512; the flush takes the minimum of the two.
 __host__ __device__ inline int shared_ring_base(int t, int C) { return (int)((unsigned)(t - (C - 1)) & (unsigned)(SH_RING - 1)); }
-// Columns flushed after left chunk bx of a run: those no later chunk of the run reaches, (64bx - D, 64bx + 64 - D], or
-// at the run's end everything still in the ring, (64bx - D, 64bx + 63]; both cut to the published columns [3, pubhi].
-// The chunk-wise walk (SMT_SHARED_WALK=chunk) has at most D + 127 <= 383 columns live between two flushes (D <= 256);
-// the run walk publishes a whole run of at most SH_RUN = 4 chunks before its one flush (shared_run_flush_range), so at
-// most 256 + D - 1 <= 511 columns are live.  Either way no two live columns share a slot of the ring of 512.
-__host__ __device__ inline void shared_flush_range(int bx, int D, bool end, int pubhi, int &lo, int &hi)
-{
-    lo = 64 * bx - D + 1; hi = end ? 64 * bx + 63 : 64 * bx + 64 - D;
-    lo = lo < 3 ? 3 : lo; hi = hi > pubhi ? pubhi : hi;
-}
+// A whole run of at most SH_RUN = 4 chunks is published before its one flush (shared_run_flush_range), so at most
+// 256 + D - 1 <= 511 columns are live (D <= 256): no two live columns share a slot of the ring of 512.
 // Run walk.  A workgroup's chunks (chunk_decode over the left view alone, t = 0 .. K-1) are consecutive in the linear
 // (row, chunk-in-row) space, so its first chunk (i, bx) and their number describe them: shared_wg_chunks, one division
 // per workgroup.  Consecutive chunks of one row form a run; a run longer than SH_RUN chunks is cut into sub-runs of
@@ -517,21 +502,13 @@ template <int MODE> struct MapsCfg {
 // unused) and use the LDS of k_cost_maps2p (`ml`: staged operands in set `buf`, written by MapsStage, and the table the
 // kernel has filled: MODE 1 the 320-float LUT, MODE 2 the 256 x 64 rank table, Tables::rank).  MODE 2 stages the image values x64, so that v_sad_u16(va, vx, hd) is the rank
 // index 64*AD + hd, and its WTA key is rank << 16 | d: one wave min, no tie-break.
-// SHR (MODE_MAPS_FLOAT).  VIEW 0 (k_cost_maps_shared_chunks, the SMT_SHARED_WALK=chunk hook): every hypothesis that shared_publishes() also sends its key to
-// `ring` with an LDS 64-bit atomic min.  VIEW 1 (k_shared_right_edges): the map columns [skip_lo, skip_hi] are not
-// written, and a wave whose pixels all lie inside does nothing.
-// TWIN: shared_run_walk (below, the default left pass of the shared form) repeats this body's VIEW 0 MODE_MAPS_FLOAT
-// publishing path -- window rotation, WTA tie-break, publish -- over a staged run; only p0, npx and the staged base
-// differ.  A change to that path here belongs there too (tests/test_adcensus_shared_runs_gpu.py compares the two walks
-// map for map).  The copy goes when the chunk-wise kernel, kept as an A/B hook, is retired.
-template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME, bool SHR = false>
+// The left pass of the shared form (shared_run_walk, below) has a walk of its own over a staged run of chunks: the same
+// window, arithmetic and WTA, plus the publishes.
+template <int C, int VIEW, bool FULL, bool NTS = true, int MODE = MODE_VOLUME>
 __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tables &T, float *__restrict__ vol,
                                                float *__restrict__ disp, int i, int bx,
-                                               MapsLds<C, MapsCfg<MODE>::TABN, MapsCfg<MODE>::NBUF> *ml = nullptr, int buf = 0,
-                                               unsigned long long *ring = nullptr, int pubhi = 0, int skip_lo = 1, int skip_hi = 0)
+                                               MapsLds<C, MapsCfg<MODE>::TABN, MapsCfg<MODE>::NBUF> *ml = nullptr, int buf = 0)
 {
-    static_assert(!SHR || MODE == MODE_MAPS_FLOAT, "");
-    constexpr bool PUB = SHR && VIEW == 0, SKIP = SHR && VIEW == 1;
     constexpr bool STORE = MODE == MODE_VOLUME;
     constexpr unsigned VSCALE = MODE == MODE_MAPS_RANK ? 64u : 4u;
     constexpr int DM = 64 * C;                               // largest D this instantiation serves
@@ -615,8 +592,7 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
     const unsigned ooff = (unsigned)dlr * 4u;
     unsigned osoff = 0;                                      // scalar byte offset of the current pixel in the wave's run
     int res = 0;
-    int npx = min(FPW, W - (j0 + p0));                       // uniform; may be <= 0
-    if (SKIP && j0 + p0 >= skip_lo && j0 + p0 + FPW - 1 <= skip_hi) npx = 0;
+    const int npx = min(FPW, W - (j0 + p0));                 // uniform; may be <= 0
     __amdgpu_buffer_rsrc_t orsrc;
     if (STORE)
         orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(vol + ((size_t)i * W + j0 + p0) * D), 0,
@@ -625,14 +601,8 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
     // all ones and the two ANDs per hypothesis can be dropped (bit 63 is 0 in every table entry)
     const bool interior = (i >= 4) && (i < H - 4) && (j0 + p0 >= 3) && (j0 + p0 + npx - 1 <= W - 4);
 
-    // every (pixel, hypothesis) of this wave publishes (pubhi <= W-4): no per-hypothesis column test
-    const bool allin = PUB && (j0 + p0) - (D - 1) >= 3 && j0 + p0 + npx - 1 <= pubhi;
-    typedef __attribute__((address_space(3))) unsigned long long *lds_key_p;
-    const lds_key_p ring3 = (lds_key_p)ring;
-
-    auto run = [&](auto masked_tag, auto allin_tag) {
+    auto run = [&](auto masked_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
-        constexpr bool ALLIN = decltype(allin_tag)::value;
         // The anchor entries are read at wave-uniform LDS addresses.  The two addresses live in VGPRs that advance
         // once per group of C pixels (the pixels of a group use immediate offsets); left to itself the compiler keeps
         // them in SGPRs and spends two v_mov per pixel to feed the ds_read.
@@ -713,15 +683,6 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
                         const int wd = first * C + kk;       // wave-uniform
                         res = (lane == q) ? wd : res;
                     }
-                    if constexpr (PUB && SMT_SHARED_KNOCKOUT != 1) {
-                        const int tcol = (j0 + p0 + q) - dl;                 // right column of hypothesis k = 0
-                        const lds_key_p rp = ring3 + shared_ring_base(tcol, C);
-#pragma unroll
-                        for (int k = 0; k < C; k++)
-                            if (ok[k] && (ALLIN || shared_publishes(j0 + p0 + q, tcol - k, W, pubhi)))
-                                (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
-                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
                     // the new entry replaces the one that just left the window
                     const int ns = (VIEW == 0) ? (u + 1) % C : u % C;
                     rc[ns] = nc; rv[ns] = nv;
@@ -731,15 +692,10 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
             nx_a += 8u * C; nv_a += 2u * C;
         }
     };
-    if constexpr (PUB) {
-        if (allin) { if (interior) run(std::false_type{}, std::true_type{}); else run(std::true_type{}, std::true_type{}); }
-        else { if (interior) run(std::false_type{}, std::false_type{}); else run(std::true_type{}, std::false_type{}); }
-    } else {
-        if (interior) run(std::false_type{}, std::false_type{});
-        else run(std::true_type{}, std::false_type{});
-    }
+    if (interior) run(std::false_type{});
+    else run(std::true_type{});
     const int jw = j0 + p0 + lane;
-    if (disp && lane < npx && !(SKIP && jw >= skip_lo && jw <= skip_hi)) disp[(size_t)i * W + jw] = (float)res;
+    if (disp && lane < npx) disp[(size_t)i * W + jw] = (float)res;
 }
 
 // Workgroup -> 64-pixel chunk.  The chunks of a launch form one linear space (view, row, chunk-in-row)
@@ -999,7 +955,7 @@ __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables 
     }
 }
 
-// One flush of the key ring (shared_flush_range's columns lo .. hi of row i, run [S, E]): complete keys go to the map,
+// One flush of the key ring (shared_run_flush_range's columns lo .. hi of row i, run [S, E]): complete keys go to the map,
 // partial ones to the handle's key map with one agent-scope atomic min each; the slots are reset.
 template <int C>
 __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, int W, int D, int lo, int hi, int S, int E,
@@ -1016,86 +972,7 @@ __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, in
     }
 }
 
-// Shared maps-only form, chunk-wise walk (SMT_SHARED_WALK=chunk; the default is k_cost_maps_shared below, which walks a
-// run in one pass): both maps of a pair from one cost evaluation per shareable hypothesis.  The cost workgroups
-// run the VIEW 0 body over runs of K consecutive chunks (chunk_decode over the left view alone) and publish the keys of
-// the columns [3, pubhi] to a per-workgroup ring; a chunk's finished columns are flushed after the next chunk's
-// barrier, beside that chunk's arithmetic (their slots are disjoint, shared_flush_range), a run's last columns between
-// two barriers when the row or the workgroup ends.  k_shared_finish turns the merged partial keys into map entries and
-// adds the edge hypotheses; with SMT_SHARED_EDGES=wg k_shared_right_edges writes the columns outside the identity set
-// instead.  Table workgroups, LUT and staging are those of k_cost_maps2p.
-#ifndef SMT_SHARED_MIN_WAVES
-#define SMT_SHARED_MIN_WAVES 7     // waves per SIMD the register allocation must allow; measured 1 / 7 / 8: DESIGN.md section 4
-#endif
-template <int C, bool FULL>
-__global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared_chunks(int H, int W, int D, Tables T, float *__restrict__ disp0,
-                                                         float *__restrict__ disp1, unsigned long long *__restrict__ keys,
-                                                         int nbx, int K, int pubhi, int ncost, int nprep,
-                                                         const float *__restrict__ nL, const float *__restrict__ nR,
-                                                         Tables Tn, int ptx)
-{
-    static_assert(PNT == NT, "");
-    constexpr int MODE = MODE_MAPS_FLOAT;
-    constexpr int TABN = MapsCfg<MODE>::TABN, NBUF = MapsCfg<MODE>::NBUF;
-    __shared__ MapsLds<C, TABN, NBUF> lds;
-    __shared__ unsigned long long ring[SH_RING_N];
-    uint16_t *s_tab = lds.tab;
-    long b = blockIdx.x;
-    if (nprep > 0) {
-        const FusedGrid f = fused_grid(ncost, nprep);
-        int idx;
-        const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
-        b = idx * 8 + (int)(blockIdx.x & 7);
-        if (table) {
-            uint32_t (*sw)[PSW] = (uint32_t (*)[PSW])s_tab;
-            if (b < nprep) prep_tile(nL, nR, H, W, Tn, (int)b % ptx, (int)b / ptx, ptx, sw, sw + PSR);
-            return;
-        }
-    }
-    const int tid = threadIdx.x;
-    for (int e = tid; e < 320; e += NT) ((float *)s_tab)[e] = T.lut[e];
-    const int Dd = FULL ? 64 * C : D;
-    const int idhi = shared_id_hi(W, Dd);
-    for (int e = tid; e < SH_RING_N; e += NT) ring[e] = SH_NOKEY;
-    auto next = [&](int t, int &i, int &bx) {
-        int view;
-        if (t >= K || !chunk_decode(nbx, H, 1, K, b, t, view, i, bx)) return K;
-        return t;
-    };
-    MapsStage<C, FULL> st;
-    int i = 0, bx = 0;
-    int t = next(0, i, bx);
-    if (t < K) st.load(0, i, bx, W, D, T);
-    int buf = 0;
-    // pending flush: the previous chunk's columns (all workgroup-uniform)
-    bool pend = false, pend_end = false;
-    int pi = 0, plo = 0, phi = -1, pS = 0, pE = 0;
-    int S = -1;                                                            // first left column of the current run
-    while (t < K) {
-        st.template store<4u>(lds, buf, D);
-        __syncthreads();                                                   // every wave has published the previous chunk
-        if (pend) {
-            shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, idhi, disp1, keys);
-            if (pend_end) __syncthreads();                                 // the next run may use any slot
-        }
-        const int ci = i, cbx = bx;
-        t = next(t + 1, i, bx);
-        if (t < K) st.load(0, i, bx, W, D, T);
-        if (S < 0) S = 64 * cbx;
-        cost_fast_body<C, 0, FULL, true, MODE, true>(H, W, D, T, nullptr, disp0, ci, cbx, &lds, buf, ring, pubhi);
-        pend = true; pend_end = t >= K || i != ci;                         // consecutive chunks: same row <=> same run
-        pi = ci; pS = S; pE = 64 * cbx + 63;
-        shared_flush_range(cbx, Dd, pend_end, pubhi, plo, phi);
-        if (pend_end) S = -1;
-        buf ^= 1;
-    }
-    if (pend) {
-        __syncthreads();
-        shared_flush<C>(ring, pi, W, Dd, plo, phi, pS, pE, idhi, disp1, keys);
-    }
-}
-
-// ---- the shared form with runs walked in one pass -----------------------------------------------------------------
+// ---- the shared form: runs walked in one pass ----------------------------------------------------------------------
 // LDS of k_cost_maps_shared: the table area of MapsLds (the LUT; a table workgroup's tile) and ONE staging set that holds
 // a whole run of up to SH_RUN chunks: its anchors and the ext entries S-(D-1)-XPAD .. E+XPAD.
 template <int C> struct RunLds {
@@ -1159,11 +1036,16 @@ struct RunStage {
     }
 };
 
-// TWIN of the VIEW 0 publishing body of cost_fast_body (MODE_MAPS_FLOAT), see the note there, over a staged run of n
-// chunks from left column S of row i: wave w walks the 16 n consecutive pixels from S + 16 n w in one pass.  The register window and the four LDS address
-// registers carry through the walk; the interior and all-in tests are taken per wave (per 16-pixel segment inside one
-// loop, the four variants' loop invariants are all live at once and the kernel spills).  Same arithmetic, same keys,
-// same winners as cost_fast_body.
+// The left pass of the shared form over a staged run of n chunks from left column S of row i: the left map, and every
+// shareable cost published as a key to the ring slot of its right column.  Wave w walks the 16 n consecutive pixels
+// from S + 16 n w in one pass; lane l owns the hypotheses d = l*C .. l*C+C-1 of each.  Per pixel: the C costs
+// lut[4 AD] + lut[256 + census] from the anchor entry (read at a wave-uniform LDS address) and the lane's register
+// window of C ext entries, which takes in one new entry per pixel; the WTA, a wave minimum over the cost bit patterns
+// (costs are >= +0, so unsigned order is float order), the first lane that holds it and that lane's first such
+// hypothesis, i.e. the first strict minimum; then one LDS 64-bit atomic min per hypothesis that shared_publishes().
+// The window and the four LDS address registers carry through the walk; the interior and all-in tests are taken per
+// wave (per 16-pixel segment inside one loop, the four variants' loop invariants are all live at once and the kernel
+// spills).  cost_fast_body computes the same costs and winners chunk by chunk for the kernels that do not share.
 template <int C, bool FULL>
 __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__restrict__ disp, int i, int S, int n,
                                                 const RunLds<C> *ml, unsigned long long *ring, int pubhi)
@@ -1188,7 +1070,9 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
     bool ok[C];
 #pragma unroll
     for (int k = 0; k < C; k++) ok[k] = FULL || (dlr + k < D);
-    // ext entry of (pixel p, hypothesis dl+k): p + (D-1) - dl - k; the register ring of cost_fast_body, VIEW 0
+    // ext entry of (pixel p, hypothesis dl+k): p + (D-1) - dl - k.  With E(n) = staged entry e0 + n, pixel q needs
+    // E(q-k), k = 0..C-1: the C live entries sit in a register ring R[n mod C] = E(n), and the pixel loop is unrolled by
+    // C so that every ring index is a compile-time constant.  It starts with E(0), E(-1), ..., E(-(C-1)).
     const int e0 = p0 + (D - 1) - dl;
     uint64_t rc[C];
     unsigned rv[C];
@@ -1301,8 +1185,9 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
             nx_a += 8u * C; nv_a += 2u * C;
         }
     };
-    // per wave, as in cost_fast_body.  interior: every pixel has all 63 taps inside the image, the tap mask is all ones;
-    // all-in: every (pixel, hypothesis) publishes (pubhi <= W-4), no per-hypothesis column test
+    // per wave.  interior: every pixel has all 63 taps inside the image, so the tap mask is all ones and the AND per
+    // hypothesis is dropped (bit 63 is 0 in every table entry); all-in: every (pixel, hypothesis) publishes
+    // (pubhi <= W-4), no per-hypothesis column test
     const bool interior = (i >= 4) && (i < H - 4) && jw0 >= 3 && jw0 + npx - 1 <= W - 4;
     const bool allin = jw0 - (D - 1) >= 3 && jw0 + npx - 1 <= pubhi;
     if (allin) { if (interior) walk(std::false_type{}, std::true_type{}); else walk(std::true_type{}, std::true_type{}); }
@@ -1310,13 +1195,17 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
     if (lane < npx) disp[(size_t)i * W + jw0 + lane] = (float)res;
 }
 
-// Shared maps-only form, runs walked in one pass (the default; SMT_SHARED_WALK=chunk keeps k_cost_maps_shared_chunks).
-// Workgroup -> chunks, the fused table grid, the publishes and the key merges are those of the chunk-wise kernel.  Per
-// run (shared_run_len) of n <= SH_RUN chunks: stage once, barrier, every wave walks its quarter of the run and publishes
-// to the ring, barrier, flush every column the run published to (shared_run_flush_range) as an end flush -- complete
-// keys to the map, partial ones to the key map, slots reset.  The next run's staging store follows the flush and the
-// barrier behind it frees the ring and shows the staged set.  Every column still yields one key per run and the merges
-// are minima, so the maps and the final key-map state are the chunk-wise kernel's, bit for bit.
+// Shared maps-only form: both maps of a pair from one cost evaluation per shareable hypothesis.  A cost workgroup takes
+// K consecutive chunks of the left view alone (shared_wg_chunks: chunk_decode's, in its XCD's eighth) and publishes the
+// keys of the right columns [3, pubhi] to its ring.  Per run (shared_run_len) of n <= SH_RUN chunks: stage once,
+// barrier, every wave walks its quarter of the run and publishes, barrier, flush every column the run published to
+// (shared_run_flush_range) -- complete keys to the map, partial ones to the key map, slots reset.  The next run's
+// staging store follows the flush, and the barrier behind it frees the ring and shows the staged set.  A column yields
+// one key per run and the merges are minima, so their order does not matter.  k_shared_finish then turns the merged
+// partial keys into map entries and adds the edge hypotheses.  Table workgroups and LUT are those of k_cost_maps2p.
+#ifndef SMT_SHARED_MIN_WAVES
+#define SMT_SHARED_MIN_WAVES 7     // waves per SIMD the register allocation must allow; measured 1 / 7 / 8: DESIGN.md section 4
+#endif
 template <int C, bool FULL>
 __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(int H, int W, int D, Tables T, float *__restrict__ disp0,
                                                          float *__restrict__ disp1, unsigned long long *__restrict__ keys,
@@ -1372,42 +1261,6 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
     }
 }
 
-// SMT_SHARED_EDGES=wg: the VIEW 1 body over the right view's edge chunks (shared_right_chunk), K per workgroup; writes
-// the right map's columns outside the identity set.  A launch of its own behind k_cost_maps_shared.
-template <int C, bool FULL>
-__global__ void __launch_bounds__(NT) k_shared_right_edges(int H, int W, int D, Tables T, float *__restrict__ disp1, int nbx, int K)
-{
-    constexpr int MODE = MODE_MAPS_FLOAT;
-    constexpr int TABN = MapsCfg<MODE>::TABN, NBUF = MapsCfg<MODE>::NBUF;
-    __shared__ MapsLds<C, TABN, NBUF> lds;
-    const int tid = threadIdx.x;
-    for (int e = tid; e < 320; e += NT) ((float *)lds.tab)[e] = T.lut[e];
-    const int Dd = FULL ? 64 * C : D;
-    const int idhi = shared_id_hi(W, Dd);
-    const int nch = shared_right_chunks(nbx, W, Dd);
-    const long b = blockIdx.x;
-    auto next = [&](int t, int &i, int &bx) {
-        int view;
-        if (t >= K || !chunk_decode(nch, H, 1, K, b, t, view, i, bx)) return K;
-        bx = shared_right_chunk(bx, W, Dd);
-        return t;
-    };
-    MapsStage<C, FULL> st;
-    int i = 0, bx = 0;
-    int t = next(0, i, bx);
-    if (t < K) st.load(1, i, bx, W, D, T);
-    int buf = 0;
-    while (t < K) {
-        st.template store<4u>(lds, buf, D);
-        __syncthreads();
-        const int ci = i, cbx = bx;
-        t = next(t + 1, i, bx);
-        if (t < K) st.load(1, i, bx, W, D, T);
-        cost_fast_body<C, 1, FULL, true, MODE, true>(H, W, D, T, nullptr, disp1, ci, cbx, &lds, buf, nullptr, idhi, 3, idhi);
-        buf ^= 1;
-    }
-}
-
 // Right-view cost of (i, j', d) straight from the tables, with the arithmetic of cost_fast_body's VIEW 1: the census
 // index clamped to W+3, the value index to W-1, the anchor's tap mask, lut[ad] + lut[256 + hd].  j' + d >= 0.
 __device__ __forceinline__ unsigned long long shared_edge_key(const Tables &T, int i, int W, uint64_t acen, uint64_t amask,
@@ -1421,13 +1274,12 @@ __device__ __forceinline__ unsigned long long shared_edge_key(const Tables &T, i
     return shared_key(__float_as_uint(c), d);
 }
 
-// Partial keys of the shared form -> map entries; the consumed keys are reset for the next pair.  edges == 0
-// (SMT_SHARED_EDGES=wg): one thread per pixel of the identity set.  edges != 0: one thread per pixel of the columns
-// 3 .. W-1, which past the identity set merges the column's edge hypotheses (shared_edge_range, at most 7) into the key
-// and always writes; the blocks from nb1 on take the columns 0..2, one wave per pixel, every hypothesis an edge one.
-// T: the tables of the pair just computed (the launch before this one wrote the other set).
+// Partial keys of the shared form -> map entries; the consumed keys are reset for the next pair.  One thread per pixel
+// of the columns 3 .. W-1, which past the identity set merges the column's edge hypotheses (shared_edge_range, at most
+// 7) into the key and always writes; the blocks from nb1 on take the columns 0..2, one wave per pixel, every hypothesis
+// an edge one.  T: the tables of the pair just computed (the launch before this one wrote the other set).
 __global__ void __launch_bounds__(256) k_shared_finish(unsigned long long *__restrict__ keys, int H, int W, int D, int idhi,
-                                                       float *__restrict__ dispR, int edges, unsigned nb1, Tables T)
+                                                       float *__restrict__ dispR, unsigned nb1, Tables T)
 {
     if (blockIdx.x >= nb1) {                                               // columns 0..2
         const size_t w = (size_t)(blockIdx.x - nb1) * 4 + (threadIdx.x >> 6);
@@ -1445,7 +1297,7 @@ __global__ void __launch_bounds__(256) k_shared_finish(unsigned long long *__res
         if (lane == 0) dispR[p] = (float)(unsigned)k;
         return;
     }
-    const int n = edges ? W - 3 : idhi - 2;                                // columns 3 .. W-1 or 3 .. idhi
+    const int n = W - 3;                                                   // columns 3 .. W-1
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= (size_t)H * n) return;
     const int i = (int)(q / n), c = 3 + (int)(q % n);
@@ -1676,9 +1528,9 @@ static int place_volumes(smt_adcensus *h, bool allow_search)
     return SMT_OK;
 }
 
-template <int C, bool FULL>
-static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL = nullptr, const float *nR = nullptr,
-                        bool maps = false);
+// launch_fast<C, FULL> (below) by runtime C = 1..4 hypotheses per lane and full: D == 64 C; false for any other C
+static bool launch_fast_as(int C, bool full, smt_adcensus *h, int views, float *dL, float *dR, const float *nL = nullptr,
+                           const float *nR = nullptr, bool maps = false);
 
 // Streaming (non-temporal) or ordinary stores for the volumes?  Streaming stores were worth 8-19 % on the
 // devices of round 1; on another device the store-only twin is 5 % FASTER with ordinary stores (DESIGN.md
@@ -1712,14 +1564,7 @@ static void calibrate_store_mode(smt_adcensus *h, bool allow)
         for (int mode = 0; mode < 2; mode++) {
             h->plain_stores = mode == 1;
             const int reps = 4;
-            auto launch = [&]() {
-                switch (h->D / 64) {
-                case 1: launch_fast<1, true>(h, SMT_VIEW_BOTH, nullptr, nullptr); break;
-                case 2: launch_fast<2, true>(h, SMT_VIEW_BOTH, nullptr, nullptr); break;
-                case 3: launch_fast<3, true>(h, SMT_VIEW_BOTH, nullptr, nullptr); break;
-                default: launch_fast<4, true>(h, SMT_VIEW_BOTH, nullptr, nullptr); break;
-                }
-            };
+            auto launch = [&]() { (void)launch_fast_as(std::min(h->D / 64, 4), true, h, SMT_VIEW_BOTH, nullptr, nullptr); };
             launch();
             (void)hipEventRecord(e0, nullptr);
             for (int k = 0; k < reps; k++) launch();
@@ -1952,23 +1797,6 @@ static bool maps_shared()
     const char *env = getenv("SMT_MAPS_SHARED");
     return !(env && env[0] == '0' && env[1] == 0);
 }
-// SMT_SHARED_EDGES=wg in the environment (read at every call) keeps the right view's edge chunks in VIEW 1 workgroups
-// (k_shared_right_edges) and publishes the identity set alone, where by default every shareable column is published and
-// k_shared_finish adds the edge hypotheses: tests and same-process A/Bs.  The edge chunks then run in a launch of their
-// own behind the shared one, not as extra workgroups of its grid: the hook's timing is not the earlier form's.
-static bool shared_edges_finish()
-{
-    const char *env = getenv("SMT_SHARED_EDGES");
-    return !(env && env[0] == 'w' && env[1] == 'g' && env[2] == 0);
-}
-// SMT_SHARED_WALK=chunk in the environment (read at every call) keeps the chunk-wise kernel (k_cost_maps_shared_chunks:
-// one staging, one prologue and one flush per 64-pixel chunk) where by default a run of up to SH_RUN chunks is staged
-// once and walked in one pass (k_cost_maps_shared): tests and same-process A/Bs, same maps.
-static bool shared_walk_runs()
-{
-    const char *env = getenv("SMT_SHARED_WALK");
-    return !(env && strcmp(env, "chunk") == 0);
-}
 // The shapes the shared form serves: an identity set that is not empty, and D <= 192.  With four hypotheses per lane
 // (192 < D <= 256) the lanes' publishes are 32 bytes apart, a 4-way bank conflict, the kernel needs 93 VGPRs and the
 // identity set is a smaller part of the row; measured at 1242 x 375 D = 256 it loses 7 % to the two-view kernel
@@ -2001,24 +1829,16 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
         const char *env = getenv("SMT_MAPS_KERNEL");
         const int idhi = shared_id_hi(h->W, h->D);
         if (!(env && env[0] == 'r') && dL && dR && maps_shared_shape(h->W, h->D) && maps_shared()) {
-            // the left-view runs, then the finishing launch (or the VIEW 1 edge chunks and it), all on the caller's stream
-            const bool edges = shared_edges_finish();
+            // the left-view runs, then the finishing launch, both on the caller's stream
             const int ncs = maps_groups(nbx, h->H, 1, K);
             const unsigned gs = nL ? 8u * (unsigned)fused_grid(ncs, nprep).groups : (unsigned)ncs;
-            if (shared_walk_runs())
-                hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
-                                   h->skeys, nbx, K, shared_pub_hi(h->W, h->D, edges), ncs, nprep, nL, nR, Tn, ptx);
-            else
-                hipLaunchKernelGGL((k_cost_maps_shared_chunks<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
-                                   h->skeys, nbx, K, shared_pub_hi(h->W, h->D, edges), ncs, nprep, nL, nR, Tn, ptx);
-            if (!edges)
-                hipLaunchKernelGGL((k_shared_right_edges<C, FULL>), dim3((unsigned)maps_groups(shared_right_chunks(nbx, h->W, h->D), h->H, 1, K)),
-                                   dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dR, nbx, K);
-            const size_t nf = (size_t)h->H * (edges ? h->W - 3 : idhi - 2);
-            const unsigned nb1 = (unsigned)((nf + 255) / 256), nb0 = edges ? (unsigned)(((size_t)h->H * 3 + 3) / 4) : 0u;
+            hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
+                               h->skeys, nbx, K, shared_pub_hi(h->W), ncs, nprep, nL, nR, Tn, ptx);
+            const size_t nf = (size_t)h->H * (h->W - 3);                   // one thread per pixel of columns 3 .. W-1
+            const unsigned nb1 = (unsigned)((nf + 255) / 256), nb0 = (unsigned)(((size_t)h->H * 3 + 3) / 4);
             if (SMT_SHARED_KNOCKOUT != 2)
                 hipLaunchKernelGGL(k_shared_finish, dim3(nb1 + nb0), dim3(256), 0, h->stream, h->skeys, h->H, h->W, h->D, idhi,
-                                   dR, edges ? 1 : 0, nb1, h->T);
+                                   dR, nb1, h->T);
             return;
         }
         if (env && env[0] == 'r')
@@ -2060,6 +1880,23 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
     if (views & SMT_VIEW_RIGHT)
         hipLaunchKernelGGL((k_cost_fast<C, 1, FULL>), blocks(1), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T,
                            h->vol[1], dR, nbx);
+}
+
+static bool launch_fast_as(int C, bool full, smt_adcensus *h, int views, float *dL, float *dR, const float *nL,
+                           const float *nR, bool maps)
+{
+    switch (C * 2 + (full ? 1 : 0)) {
+    case 3: launch_fast<1, true>(h, views, dL, dR, nL, nR, maps); break;
+    case 5: launch_fast<2, true>(h, views, dL, dR, nL, nR, maps); break;
+    case 7: launch_fast<3, true>(h, views, dL, dR, nL, nR, maps); break;
+    case 9: launch_fast<4, true>(h, views, dL, dR, nL, nR, maps); break;
+    case 2: launch_fast<1, false>(h, views, dL, dR, nL, nR, maps); break;
+    case 4: launch_fast<2, false>(h, views, dL, dR, nL, nR, maps); break;
+    case 6: launch_fast<3, false>(h, views, dL, dR, nL, nR, maps); break;
+    case 8: launch_fast<4, false>(h, views, dL, dR, nL, nR, maps); break;
+    default: return false;
+    }
+    return true;
 }
 
 // One pair into table set (n & 1).  Three schedules for the pairs of a batch:
@@ -2126,19 +1963,7 @@ static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int vi
         case 7: launch_cost<7, false>(h, view0, nviews, dL, dR); break;
         default: launch_cost<8, false>(h, view0, nviews, dL, dR); break;
         }
-    } else {
-        switch (C * 2 + (full ? 1 : 0)) {
-        case 3: launch_fast<1, true>(h, views, dL, dR, nL, nR, maps); break;
-        case 5: launch_fast<2, true>(h, views, dL, dR, nL, nR, maps); break;
-        case 7: launch_fast<3, true>(h, views, dL, dR, nL, nR, maps); break;
-        case 9: launch_fast<4, true>(h, views, dL, dR, nL, nR, maps); break;
-        case 2: launch_fast<1, false>(h, views, dL, dR, nL, nR, maps); break;
-        case 4: launch_fast<2, false>(h, views, dL, dR, nL, nR, maps); break;
-        case 6: launch_fast<3, false>(h, views, dL, dR, nL, nR, maps); break;
-        case 8: launch_fast<4, false>(h, views, dL, dR, nL, nR, maps); break;
-        default: return SMT_ERR_ARG;
-        }
-    }
+    } else if (!launch_fast_as(C, full, h, views, dL, dR, nL, nR, maps)) return SMT_ERR_ARG;
     if (timed) { (void)hipEventRecord(ev[3], h->stream); h->n_timed++; }
     // the two-stream schedule waits on this before it reuses the table set; the fused one is ordered by its stream
     if (!prepped && !nL) SMT_HIP(hipEventRecord(h->cost_done[set], h->stream));
@@ -2199,17 +2024,8 @@ static int materialise_volumes(smt_adcensus *h)
     const long slot = h->n_timed % SMT_TIMING_SLOTS;
     hipEvent_t *ev = h->timing ? h->ev + 4 * slot : nullptr;
     if (ev) { (void)hipEventRecord(ev[0], h->stream); (void)hipEventRecord(ev[1], h->stream); h->ev_merged[slot] = true; }
-    switch ((h->D + 63) / 64 * 2 + (h->D % 64 == 0 ? 1 : 0)) {
-    case 3: launch_fast<1, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 5: launch_fast<2, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 7: launch_fast<3, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 9: launch_fast<4, true>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 2: launch_fast<1, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 4: launch_fast<2, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 6: launch_fast<3, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    case 8: launch_fast<4, false>(h, SMT_VIEW_BOTH, nullptr, nullptr, nullptr, nullptr, false); break;
-    default: return SMT_ERR_STATE;                           // only fast_both_views pairs are deferred
-    }
+    if (!launch_fast_as((h->D + 63) / 64, h->D % 64 == 0, h, SMT_VIEW_BOTH, nullptr, nullptr))
+        return SMT_ERR_STATE;                                // only fast_both_views pairs are deferred
     if (ev) { (void)hipEventRecord(ev[3], h->stream); h->n_timed++; }
     h->vol_pending = false;
     SMT_LAUNCH_CHECK();
@@ -2331,26 +2147,20 @@ SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
 }
 
 // Host-side walk of the shared maps-only form (k_cost_maps_shared + k_shared_finish) over pseudo-random costs with many
-// exact ties, through the kernel's own index functions.  The left pass follows the walk the environment selects:
-//   run walk (default): shared_wg_chunks / shared_run_len give a workgroup's sub-runs of at most SH_RUN chunks
-//     (checked against chunk_decode); a whole run is published, which must not put two columns into one ring slot,
-//     then flushed once as an end flush over shared_run_flush_range.
-//   chunk-wise walk (SMT_SHARED_WALK=chunk): chunk_decode / maps_groups give the runs; a chunk's flush over
-//     shared_flush_range is applied after the next chunk's publishes, as on the device, and must not meet a slot those
-//     touched.
-// Both use the lane -> hypothesis split, shared_publishes and shared_ring_base for the publishes, shared_complete and
-// the key map for the partial keys.  Then the finishing launch's edge hypotheses over shared_edge_range; with
-// SMT_SHARED_EDGES=wg in the environment, shared_right_chunk(s) for the VIEW 1 chunks instead.
+// exact ties, through the kernel's own index functions.  The left pass: shared_wg_chunks / shared_run_len give a
+// workgroup's sub-runs of at most SH_RUN chunks (checked against chunk_decode); a whole run is published -- the lane ->
+// hypothesis split, shared_publishes and shared_ring_base -- which must not put two columns into one ring slot, then
+// flushed once over shared_run_flush_range, shared_complete sending a key to the map or to the key map.  Then the
+// finishing launch's edge hypotheses over shared_edge_range.
 // The right view's pseudo-cost of (i, j', d) is the left one of (i, j' + d, d) where the identity holds and a cost of
 // its own elsewhere, constant in d from W+3-j' on as the staging clamps make it.  SMT_OK iff every right pixel is
-// written exactly once, with the first minimum over all its D hypotheses where the walk computes it (every column by
-// default, the identity set with wg), every ring ends empty and the key map is reset.  Needs no GPU.
+// written exactly once, with the first minimum over all its D hypotheses, every ring ends empty and the key map is
+// reset.  Needs no GPU.
 SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed)
 {
     if (H <= 0 || W <= 0 || D <= 0 || D > 256 || K < 1 || K > 64 || (long)H * W > (1L << 24)) return SMT_ERR_ARG;
     const int C = (D + 63) / 64, nbx = (W + FTJ - 1) / FTJ, idhi = shared_id_hi(W, D);
-    const bool edges = shared_edges_finish(), runs = shared_walk_runs();
-    const int pubhi = shared_pub_hi(W, D, edges);
+    const int pubhi = shared_pub_hi(W);
     const size_t N = (size_t)H * W;
     // costs: a small palette of floats >= +0 (ties), every cost equal (seed % 3 == 1), or mostly distinct
     static const float pal[] = {0.0f, 0.0f, 0.25f, 0.25f, 1.5f, 0.7265625f, 0.7265625f, 1.9999999f, 0.25f, 1e-30f};
@@ -2369,20 +2179,41 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
     };
     unsigned long long *keys = new (std::nothrow) unsigned long long[N];
     unsigned *val = new (std::nothrow) unsigned[N]();
-    unsigned char *nw = new (std::nothrow) unsigned char[N]();           // writers of each right pixel: shared path
-    unsigned char *nv = new (std::nothrow) unsigned char[N]();           //                              VIEW 1 path
-    int rc = (keys && val && nw && nv) ? SMT_OK : SMT_ERR_ALLOC;
+    unsigned char *nw = new (std::nothrow) unsigned char[N]();           // writers of each right pixel
+    int rc = (keys && val && nw) ? SMT_OK : SMT_ERR_ALLOC;
     for (size_t p = 0; rc == SMT_OK && p < N; p++) keys[p] = SH_NOKEY;
     if (rc == SMT_OK && idhi >= 3) {
         const int nleft = maps_groups(nbx, H, 1, K);
         unsigned long long ring[SH_RING_N];
-        long stamp[SH_RING_N];                                            // serial of the last chunk that published to a slot
+        int owner[SH_RING_N];                                             // right column that holds a slot in this run
         for (long b = 0; b < nleft && rc == SMT_OK; b++) {
-            for (int e = 0; e < SH_RING_N; e++) { ring[e] = SH_NOKEY; stamp[e] = -1; }
-            auto flush = [&](int i, int lo, int hi, int S, int E, long serial, bool end) {
+            for (int e = 0; e < SH_RING_N; e++) ring[e] = SH_NOKEY;
+            int view, i, bx, ni, nbxn;
+            int left = shared_wg_chunks(nbx, H, K, b, i, bx);
+            for (int t = 0; t < K; t++)                                   // the chunks are chunk_decode's
+                if (chunk_decode(nbx, H, 1, K, b, t, view, ni, nbxn) != (t < left)) rc = SMT_ERR_STATE;
+            // sub-runs of SH_RUN: the publishes of the whole run, then its one flush
+            for (int t = 0; left > 0 && rc == SMT_OK;) {
+                const int n = shared_run_len(nbx, bx, left);
+                if (n < 1 || n > SH_RUN) { rc = SMT_ERR_STATE; break; }
+                for (int u = 0; u < n; u++)
+                    if (!chunk_decode(nbx, H, 1, K, b, t + u, view, ni, nbxn) || ni != i || nbxn != bx + u) rc = SMT_ERR_STATE;
+                const int S = 64 * bx, E = S + 64 * n - 1;
+                for (int e = 0; e < SH_RING_N; e++) owner[e] = -1;
+                for (int j = S; j <= E && j < W; j++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int k = 0; k < C; k++) {
+                            const int dl = lane * C, d = dl + k, tcol = j - dl;
+                            if (d >= D || !shared_publishes(j, tcol - k, W, pubhi)) continue;
+                            const int s = shared_ring_base(tcol, C) + (C - 1 - k);
+                            if (owner[s] != -1 && owner[s] != tcol - k) rc = SMT_ERR_STATE;   // two live columns in a slot
+                            owner[s] = tcol - k;
+                            ring[s] = std::min(ring[s], shared_key(cost_bits(i, j, d), d));
+                        }
+                int lo, hi;
+                shared_run_flush_range(S, E, D, pubhi, lo, hi);
                 for (int c = lo; c <= hi; c++) {
                     const int s = c & (SH_RING - 1);
-                    if (!end && (stamp[s] > serial || (s < C - 1 && stamp[SH_RING + s] > serial))) rc = SMT_ERR_STATE;
                     unsigned long long k = ring[s];
                     ring[s] = SH_NOKEY;
                     if (s < C - 1) { k = std::min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
@@ -2392,71 +2223,14 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                         val[p] = (unsigned)k; nw[p]++;
                     } else if (k != SH_NOKEY) keys[p] = std::min(keys[p], k);
                 }
-            };
-            int view, i, bx, ni, nbxn;
-            if (runs) {
-                // run walk: sub-runs of SH_RUN, the publishes of the whole run, then its one end flush
-                int left = shared_wg_chunks(nbx, H, K, b, i, bx);
-                for (int t = 0; t < K; t++)                                   // the chunks are chunk_decode's
-                    if (chunk_decode(nbx, H, 1, K, b, t, view, ni, nbxn) != (t < left)) rc = SMT_ERR_STATE;
-                int owner[SH_RING_N];                                         // right column that holds a slot in this run
-                for (int t = 0; left > 0 && rc == SMT_OK;) {
-                    const int n = shared_run_len(nbx, bx, left);
-                    if (n < 1 || n > SH_RUN) { rc = SMT_ERR_STATE; break; }
-                    for (int u = 0; u < n; u++)
-                        if (!chunk_decode(nbx, H, 1, K, b, t + u, view, ni, nbxn) || ni != i || nbxn != bx + u) rc = SMT_ERR_STATE;
-                    const int S = 64 * bx, E = S + 64 * n - 1;
-                    for (int e = 0; e < SH_RING_N; e++) owner[e] = -1;
-                    for (int j = S; j <= E && j < W; j++)
-                        for (int lane = 0; lane < 64; lane++)
-                            for (int k = 0; k < C; k++) {
-                                const int dl = lane * C, d = dl + k, tcol = j - dl;
-                                if (d >= D || !shared_publishes(j, tcol - k, W, pubhi)) continue;
-                                const int s = shared_ring_base(tcol, C) + (C - 1 - k);
-                                if (owner[s] != -1 && owner[s] != tcol - k) rc = SMT_ERR_STATE;   // two live columns in a slot
-                                owner[s] = tcol - k;
-                                ring[s] = std::min(ring[s], shared_key(cost_bits(i, j, d), d));
-                            }
-                    int lo, hi;
-                    shared_run_flush_range(S, E, D, pubhi, lo, hi);
-                    flush(i, lo, hi, S, E, 0, true);
-                    for (int e = 0; e < SH_RING_N; e++) if (ring[e] != SH_NOKEY) rc = SMT_ERR_STATE;   // free for the next run
-                    left -= n; t += n; bx += n;
-                    if (bx == nbx) { bx = 0; i++; }
-                }
-                continue;
+                for (int e = 0; e < SH_RING_N; e++) if (ring[e] != SH_NOKEY) rc = SMT_ERR_STATE;   // free for the next run
+                left -= n; t += n; bx += n;
+                if (bx == nbx) { bx = 0; i++; }
             }
-            bool pend = false, pend_end = false;
-            int pi = 0, plo = 0, phi = -1, pS = 0, pE = 0, S = -1;
-            long serial = 0;
-            bool have = chunk_decode(nbx, H, 1, K, b, 0, view, i, bx);
-            for (int t = 0; have && rc == SMT_OK; t++, serial++) {
-                if (pend && pend_end) { flush(pi, plo, phi, pS, pE, serial - 1, true); pend = false; }
-                const bool more = t + 1 < K && chunk_decode(nbx, H, 1, K, b, t + 1, view, ni, nbxn);
-                if (S < 0) S = 64 * bx;
-                for (int q = 0; q < FTJ && 64 * bx + q < W; q++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int k = 0; k < C; k++) {
-                            const int dl = lane * C, d = dl + k, tcol = 64 * bx + q - dl;
-                            if (d >= D || !shared_publishes(64 * bx + q, tcol - k, W, pubhi)) continue;
-                            const int s = shared_ring_base(tcol, C) + (C - 1 - k);
-                            ring[s] = std::min(ring[s], shared_key(cost_bits(i, 64 * bx + q, d), d));
-                            stamp[s] = serial;
-                        }
-                if (pend) flush(pi, plo, phi, pS, pE, serial - 1, false);     // beside this chunk's publishes on the device
-                pend = true; pend_end = !more || ni != i;
-                if (more && ni == i && nbxn != bx + 1) rc = SMT_ERR_STATE;
-                pi = i; pS = S; pE = 64 * bx + 63;
-                shared_flush_range(bx, D, pend_end, pubhi, plo, phi);
-                if (pend_end) S = -1;
-                have = more; i = ni; bx = nbxn;
-            }
-            if (pend && rc == SMT_OK) flush(pi, plo, phi, pS, pE, serial - 1, true);
-            for (int e = 0; e < SH_RING_N; e++) if (ring[e] != SH_NOKEY) rc = SMT_ERR_STATE;   // nothing left behind
         }
         // the finishing launch
         for (int i = 0; i < H; i++)
-            for (int c = edges ? 0 : 3; c <= (edges ? W - 1 : idhi); c++) {
+            for (int c = 0; c < W; c++) {
                 const size_t p = (size_t)i * W + c;
                 if (shared_in_set(c, idhi)) {
                     if (keys[p] != SH_NOKEY) { val[p] = (unsigned)keys[p]; nw[p]++; keys[p] = SH_NOKEY; }
@@ -2470,24 +2244,12 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                 if (k == SH_NOKEY) rc = SMT_ERR_STATE;
                 val[p] = (unsigned)k; nw[p]++;
             }
-        // the VIEW 1 workgroups
-        const int nre = shared_right_chunks(nbx, W, D), nright = edges ? 0 : maps_groups(nre, H, 1, K);
-        for (long b = 0; b < nright; b++)
-            for (int t = 0; t < K; t++) {
-                int view, i, e;
-                if (!chunk_decode(nre, H, 1, K, b, t, view, i, e)) break;
-                const int bx = shared_right_chunk(e, W, D);
-                if (bx < 0 || bx >= nbx) { rc = SMT_ERR_STATE; break; }
-                for (int q = 0; q < FTJ && 64 * bx + q < W; q++)
-                    if (!(64 * bx + q >= 3 && 64 * bx + q <= idhi)) nv[(size_t)i * W + 64 * bx + q]++;
-            }
     }
     for (int i = 0; i < H && rc == SMT_OK; i++)
         for (int c = 0; c < W && rc == SMT_OK; c++) {
             const size_t p = (size_t)i * W + c;
-            if (idhi < 3) { if (nw[p] || nv[p]) rc = SMT_ERR_STATE; continue; }   // the two-view kernel serves this shape
+            if (idhi < 3) { if (nw[p]) rc = SMT_ERR_STATE; continue; }   // the two-view kernel serves this shape
             if (keys[p] != SH_NOKEY) rc = SMT_ERR_STATE;
-            if (!edges && !shared_in_set(c, idhi)) { if (nw[p] != 0 || nv[p] != 1) rc = SMT_ERR_STATE; continue; }
             float mn = 0.0f;
             int want = 0;
             for (int d = 0; d < D; d++) {
@@ -2496,9 +2258,9 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                 memcpy(&f, &bits, 4);
                 if (d == 0 || f < mn) { mn = f; want = d; }
             }
-            if (nw[p] != 1 || nv[p] != 0 || val[p] != (unsigned)want) rc = SMT_ERR_STATE;
+            if (nw[p] != 1 || val[p] != (unsigned)want) rc = SMT_ERR_STATE;
         }
-    delete[] keys; delete[] val; delete[] nw; delete[] nv;
+    delete[] keys; delete[] val; delete[] nw;
     return rc;
 }
 

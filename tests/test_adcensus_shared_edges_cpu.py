@@ -89,15 +89,6 @@ def test_walk_shapes_reach_the_rules():
 
 @pytest.mark.parametrize("K", [1, 3, 4, 64])
 @pytest.mark.parametrize("H,W,D", WALK_SHAPES)
-def test_shared_keys_walk_with_edges(selftest, monkeypatch, H, W, D, K):
-    monkeypatch.delenv("SMT_SHARED_EDGES", raising=False)
+def test_shared_keys_walk_with_edges(selftest, H, W, D, K):
     for seed in (0, 1, 2, 7):
         assert selftest(H, W, D, K, seed) == 0, seed
-
-
-@pytest.mark.parametrize("H,W,D", [(3, 70, 64), (2, 259, 192), (2, 323, 256), (5, 211, 33)])
-def test_shared_keys_walk_with_edge_workgroups(selftest, monkeypatch, H, W, D):
-    monkeypatch.setenv("SMT_SHARED_EDGES", "wg")
-    for K in (1, 3, 4, 64):
-        for seed in (0, 1, 2, 7):
-            assert selftest(H, W, D, K, seed) == 0, (K, seed)

@@ -2,9 +2,8 @@
 k_cost_maps_shared + k_shared_finish): the left pass publishes every shareable cost, the finishing launch evaluates the
 edge hypotheses W-3 <= j' + d <= W+3 of the columns j' > W-3-D and every hypothesis of the columns 0..2 and merges them
 with the column's key.  Every map of every pair, NaN-prefilled, against the oracle's WTA and against the same call under
-SMT_SHARED_EDGES=wg (edge chunks in right-view workgroups) and SMT_MAPS_SHARED=0 (the two-view kernel), at the smallest
-shapes that reach each rule and every run length; ties; edge hypotheses that win and that tie; the census edge fix; one
-map requested; the deferred volumes."""
+SMT_MAPS_SHARED=0 (the two-view kernel), at the smallest shapes that reach each rule and every run length; ties; edge
+hypotheses that win and that tie; the census edge fix; one map requested; the deferred volumes."""
 import ctypes as C
 import functools
 
@@ -26,7 +25,7 @@ SHAPES = [(3, 70, 64, 2, None),        # one identity column (W-3-D == 3), one c
           (4, 262, 256, 2, "force"),   # C = 4, one identity column
           (5, 450, 256, 2, "force")]
 CHUNKS = [None, "1", "3", "64"]        # SMT_MAPS_CHUNKS
-ENV = ("SMT_MAPS_SHARED", "SMT_SHARED_EDGES", "SMT_MAPS_KERNEL", "SMT_BATCH_VOLUMES", "SMT_OVERLAP", "SMT_MAPS_CHUNKS")
+ENV = ("SMT_MAPS_SHARED", "SMT_MAPS_KERNEL", "SMT_BATCH_VOLUMES", "SMT_OVERLAP", "SMT_MAPS_CHUNKS")
 _ORACLE = None
 
 
@@ -98,14 +97,10 @@ def test_batch_against_the_oracle_and_the_other_forms(smt, H, W, D, B, form, mon
         _env(monkeypatch, "SMT_MAPS_CHUNKS", K)
         dl, dr = _batch(adc, Lb, Rb)
         _check(dl, dr, maps, (K, "finish"))
-        monkeypatch.setenv("SMT_SHARED_EDGES", "wg")
-        dlw, drw = _batch(adc, Lb, Rb)
-        monkeypatch.delenv("SMT_SHARED_EDGES")
-        _check(dlw, drw, maps, (K, "wg"))
         monkeypatch.setenv("SMT_MAPS_SHARED", "0")
         dl0, dr0 = _batch(adc, Lb, Rb)
         _env(monkeypatch, "SMT_MAPS_SHARED", form)
-        for a, b in ((dl, dlw), (dr, drw), (dl, dl0), (dr, dr0)):
+        for a, b in ((dl, dl0), (dr, dr0)):
             assert np.array_equal(a.cpu().numpy(), b.cpu().numpy()), K
         # the key map was left reset: the same call again gives the same maps
         dl2, dr2 = _batch(adc, Lb, Rb)
@@ -188,13 +183,10 @@ def test_census_right_edge_fix(smt, O, fix, monkeypatch):
     Rb = _dev(rs.randint(0, 256, (3, H, W)))
     adc = _handle(smt, Lb, Rb, D, quirks=QUIRK_FIX_CENSUS_RIGHT_EDGE if fix else 0)
     dl, dr = _batch(adc, Lb, Rb)
-    monkeypatch.setenv("SMT_SHARED_EDGES", "wg")
-    dlw, drw = _batch(adc, Lb, Rb)
-    monkeypatch.delenv("SMT_SHARED_EDGES")
     monkeypatch.setenv("SMT_MAPS_SHARED", "0")
     dl0, dr0 = _batch(adc, Lb, Rb)
     monkeypatch.delenv("SMT_MAPS_SHARED")
-    for a, b in ((dl, dlw), (dr, drw), (dl, dl0), (dr, dr0)):
+    for a, b in ((dl, dl0), (dr, dr0)):
         assert np.array_equal(a.cpu().numpy(), b.cpu().numpy())
     if fix:
         # the right map is the mirrored, swapped pair's left map

@@ -1,11 +1,10 @@
 """The shared maps-only form with runs walked in one pass (adcensus.hip, k_cost_maps_shared) without a GPU: the host walk
 of the form's rules (smt_adcensus_selftest_shared_keys) over the shapes and chunk counts of
 test_adcensus_shared_runs_gpu.py.  A workgroup's consecutive chunks of one row form a run, cut into sub-runs of SH_RUN = 4
-chunks; a run is published as a whole and flushed once.  The walk follows SMT_SHARED_WALK (run walk by default, `chunk`
-the chunk-wise kernel) and SMT_SHARED_EDGES; every right pixel must be written exactly once with its first minimum, no
-two live columns may meet in a ring slot, rings end empty and the key map is reset.  That the shapes reach a 4-chunk run,
-a sub-run, a row change inside a workgroup, a walk cut by W and the ring's bound of 511 live columns is asserted on a
-Python recomputation of the run structure (adcensus_shared_runs_cases.py)."""
+chunks; a run is published as a whole and flushed once.  Every right pixel must be written exactly once with its first
+minimum, no two live columns may meet in a ring slot, rings end empty and the key map is reset.  That the shapes reach a
+4-chunk run, a sub-run, a row change inside a workgroup, a walk cut by W and the ring's bound of 511 live columns is
+asserted on a Python recomputation of the run structure (adcensus_shared_runs_cases.py)."""
 import ctypes as C
 import os
 import sys
@@ -56,23 +55,9 @@ def test_no_run_has_more_live_columns_than_the_ring():
     assert max(features(H, W, D, K)["live"] for H, W, D, _ in SHAPES for K in KS) == 511
 
 
-def _walk(selftest, monkeypatch, H, W, D, walk, edges):
-    if edges is None: monkeypatch.delenv("SMT_SHARED_EDGES", raising=False)
-    else: monkeypatch.setenv("SMT_SHARED_EDGES", edges)
-    if walk is None: monkeypatch.delenv("SMT_SHARED_WALK", raising=False)
-    else: monkeypatch.setenv("SMT_SHARED_WALK", walk)
+# the ids the cases had while a second parameter chose between two walks: they keep their names
+@pytest.mark.parametrize("H,W,D,form", SHAPES, ids=["%d-%d-%d-%s-None" % s for s in SHAPES])
+def test_shared_keys_walk(selftest, H, W, D, form):
     for K in KS:
         for seed in (0, 1, 2):
             assert selftest(H, W, D, K, seed) == 0, (K, seed)
-
-
-@pytest.mark.parametrize("walk", [None, "chunk"])
-@pytest.mark.parametrize("H,W,D,form", SHAPES)
-def test_shared_keys_walk(selftest, monkeypatch, H, W, D, form, walk):
-    _walk(selftest, monkeypatch, H, W, D, walk, None)
-
-
-@pytest.mark.parametrize("walk", [None, "chunk"])
-@pytest.mark.parametrize("H,W,D,form", SHAPES)
-def test_shared_keys_walk_with_edge_workgroups(selftest, monkeypatch, H, W, D, form, walk):
-    _walk(selftest, monkeypatch, H, W, D, walk, "wg")

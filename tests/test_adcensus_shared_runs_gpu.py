@@ -1,8 +1,8 @@
 """The shared maps-only form of smt_adcensus_compute_batch with runs walked in one pass (adcensus.hip, k_cost_maps_shared):
 a workgroup stages a run of up to SH_RUN = 4 consecutive chunks of one row once, every wave walks a contiguous quarter of
 it, and the run's columns are flushed once.  Every map of every pair, NaN-prefilled, against the oracle's WTA and against
-the same call under SMT_MAPS_SHARED=0 (the two-view kernel) and SMT_SHARED_WALK=chunk (the chunk-wise kernel), and a
-second identical call (the key map was left reset), at the shapes of adcensus_shared_runs_cases.py: short ones, and the
+the same call under SMT_MAPS_SHARED=0 (the two-view kernel), and a second identical call (the key map was left reset),
+at the shapes of adcensus_shared_runs_cases.py: short ones, and the
 smallest that reach a 4-chunk run (64 pixels per wave), a row change inside a workgroup, sub-runs, a walk cut by W, every
 C and 511 live columns, the ring's bound (test_adcensus_shared_runs_cpu.py asserts that they do); ties everywhere; one
 map requested (the two-view kernel serves those calls, as test_adcensus_shared_edges_gpu.py establishes)."""
@@ -22,8 +22,7 @@ from adcensus_shared_runs_cases import CHUNKS, SHAPES  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 B = 2
-ENV = ("SMT_MAPS_SHARED", "SMT_SHARED_EDGES", "SMT_SHARED_WALK", "SMT_MAPS_KERNEL", "SMT_BATCH_VOLUMES", "SMT_OVERLAP",
-       "SMT_MAPS_CHUNKS")
+ENV = ("SMT_MAPS_SHARED", "SMT_MAPS_KERNEL", "SMT_BATCH_VOLUMES", "SMT_OVERLAP", "SMT_MAPS_CHUNKS")
 _ORACLE = None
 
 
@@ -92,14 +91,10 @@ def test_batch_against_the_oracle_and_the_other_forms(smt, H, W, D, form, monkey
         _env(monkeypatch, "SMT_MAPS_CHUNKS", K)
         dl, dr = _batch(adc, Lb, Rb)
         _check(dl, dr, maps, (K, "runs"))
-        monkeypatch.setenv("SMT_SHARED_WALK", "chunk")
-        dlc, drc = _batch(adc, Lb, Rb)
-        monkeypatch.delenv("SMT_SHARED_WALK")
-        _check(dlc, drc, maps, (K, "chunk"))
         monkeypatch.setenv("SMT_MAPS_SHARED", "0")
         dl0, dr0 = _batch(adc, Lb, Rb)
         _env(monkeypatch, "SMT_MAPS_SHARED", form)
-        for a, b in ((dl, dlc), (dr, drc), (dl, dl0), (dr, dr0)):
+        for a, b in ((dl, dl0), (dr, dr0)):
             assert np.array_equal(a, b), K
         # the key map was left reset: the same call again gives the same maps
         dl2, dr2 = _batch(adc, Lb, Rb)
