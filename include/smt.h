@@ -15,7 +15,10 @@
  *   - images  [H][W] row-major; volumes [H][W][D], d fastest, float32 -- the reference
  *     layout (AD-CensusV1/AD-Census.h:87).
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls are
- *     asynchronous on that stream unless documented as synchronising.
+ *     asynchronous on that stream unless documented as synchronising.  tests/test_stream_order_gpu.py holds every entry
+ *     point that takes device buffers to this sentence: called on a busy stream with inputs that arrive behind the work
+ *     in front of them, it computes what it computes on an idle one, and returns before the stream has drained unless
+ *     its comment ends with "Synchronising." (the decisions: tests/stream_order_cases.py).
  *   - every function returns SMT_OK (0) or a negative smt_status.  The reference
  *     validates nothing (void functions, UB on bad sizes); this ABI rejects bad
  *     arguments instead.

@@ -24,6 +24,16 @@ Rules
   * check() asserts, on the device for torch, that every byte outside the outputs -- guards, gaps and inputs -- is
     what it was before the call, names the first region that is not, and returns the outputs as numpy arrays.
     In-place tensors (inout) are outputs: their gaps and guards are still held.
+  * Deferred inputs (tests/test_stream_order_gpu.py).  build(deferred=True) makes two images of the buffer.  `buf`
+    holds the DECOY image when build returns: the pattern everywhere, and in every in / inout tensor a decoy of its
+    data that stays inside the tensor's domain -- uint8 and floating data reversed in flat order (the same multiset of
+    values), int32 data (arm maps, arm volumes, integer disparities: upper bounds of walks) all equal to the tensor's
+    own minimum; a name in `keep` keeps its data, one in `decoys` gets the array given there.  The TRUE image, what
+    build() makes otherwise, waits in a second tensor of the same kind; arrive() copies it over the whole of buf --
+    outputs and guards included -- with
+    buf.copy_(true, non_blocking=True): on a device, one device-to-device copy on torch's current stream.  A call
+    that reads before arrive() computes from decoys, one that writes before it has its output overwritten by the
+    prefill; check() and initial() refer to the true image.  decoyed() names the tensors whose decoy differs.
 """
 import ctypes as C
 
@@ -97,7 +107,33 @@ class Arena:
         inner = int(np.prod(t.shape[1:])) * t.dtype.itemsize
         return [(t.off + b * t.stride * t.dtype.itemsize, inner) for b in range(t.shape[0])]
 
-    def build(self):
+    def _decoy(self, t):
+        """the decoy of t's data: same shape and dtype, inside the tensor's domain"""
+        if t.name in self._own_decoy:
+            d = np.ascontiguousarray(self._own_decoy[t.name], t.dtype)
+            assert d.shape == t.shape, (t.name, d.shape, t.shape)
+            return d
+        if t.dtype == np.int32:
+            return np.full_like(t.data, t.data.min())
+        assert t.dtype == np.uint8 or t.dtype.kind == "f", (t.name, t.dtype)
+        return np.ascontiguousarray(t.data.reshape(-1)[::-1]).reshape(t.shape)
+
+    def _fill(self, host, decoy):
+        for t in self._t.values():
+            if t.data is None:
+                continue
+            data = self._decoy(t) if decoy and t.name not in self._keep_true else t.data
+            for b, (off, nb) in enumerate(self._maps(t)):
+                src = data[b] if t.stride else data
+                host[off:off + nb] = np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+
+    def build(self, deferred=False, keep=(), decoys=None):
+        """deferred: buf holds the decoy image until arrive(); keep: inputs that keep their data in the decoy image;
+        decoys: {name: array} for inputs whose decoy the caller states instead of the rule (the caller answers for its
+        domain)"""
+        self.deferred, self._keep_true, self._own_decoy = bool(deferred), frozenset(keep), dict(decoys or {})
+        assert set(self._own_decoy) <= set(self._t), sorted(set(self._own_decoy) - set(self._t))
+        assert self._keep_true <= set(self._t), sorted(self._keep_true - set(self._t))
         cur = 0
         for k, name in enumerate(self._order):
             t = self._t[name]
@@ -117,24 +153,44 @@ class Arena:
         host[:] = pattern(cur, self.seed)
         written = np.zeros(cur, bool)              # bytes the call may change
         for t in self._t.values():
-            for b, (off, nb) in enumerate(self._maps(t)):
-                if t.data is not None:
-                    src = t.data[b] if t.stride else t.data
-                    host[off:off + nb] = np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+            for off, nb in self._maps(t):
                 if t.role != "in":
                     written[off:off + nb] = True
+        true = None
+        if deferred:
+            true = host.copy()
+            self._fill(true, decoy=False)
+        self._fill(host, decoy=deferred)           # what buf holds when build returns
         if self.device is None:
             self.buf, self._keep = host, raw
-            self._init, self._held = host.copy(), ~written
+            self._init, self._held = (true if deferred else host.copy()), ~written
             self.base = host.ctypes.data
         else:
             import torch
             self.buf = torch.from_numpy(host.copy()).to(self.device)
-            self._init = self.buf.clone()
+            self._init = torch.from_numpy(true).to(self.device) if deferred else self.buf.clone()
             self._held = torch.from_numpy(~written).to(self.device)
             self.base = self.buf.data_ptr()
+            if deferred:
+                torch.cuda.synchronize(self.device)
         assert self.base % BASE_ALIGN == 0
         return self
+
+    def arrive(self):
+        """the true image over the whole of buf, outputs and guards included; on a device asynchronously, on torch's
+        current stream"""
+        assert self.deferred
+        if self.device is None:
+            self.buf[:] = self._init
+        else:
+            self.buf.copy_(self._init, non_blocking=True)
+
+    def decoyed(self):
+        """the in / inout tensors whose decoy differs from their data (a one-element or constant tensor does not)"""
+        if not self.deferred:
+            return []
+        return [t.name for t in self._t.values() if t.data is not None and t.name not in self._keep_true
+                and not np.array_equal(self._decoy(t).view(np.uint8), t.data.view(np.uint8))]
 
     def addr(self, name):
         return self.base + self._t[name].off
@@ -171,34 +227,37 @@ class Arena:
             parts.append(piece)
         return np.concatenate(parts).view(t.dtype).reshape(t.shape)
 
-    def check(self):
-        """-> {name: numpy array} of the outputs and in-place tensors.  AssertionError names the first held byte that
-        changed."""
+    def check(self, buf=None):
+        """-> {name: numpy array} of the outputs and in-place tensors, read from `buf` (default: the arena's buffer; a
+        snapshot of it otherwise).  AssertionError names the first held byte that changed."""
+        buf = self.buf if buf is None else buf
+        assert buf.shape == self.buf.shape
         if self.device is None:
-            bad = (self.buf != self._init) & self._held
+            bad = (buf != self._init) & self._held
             n = int(bad.sum())
             first = int(np.flatnonzero(bad)[0]) if n else -1
         else:
             import torch
-            bad = (self.buf != self._init) & self._held          # on the device
+            bad = (buf != self._init) & self._held          # on the device
             n = int(bad.sum().item())
             first = int(torch.nonzero(bad)[0].item()) if n else -1
         assert n == 0, f"{n} bytes outside the outputs changed; first: {self._where(first)}"
-        return {name: self._read(name, self.buf) for name, t in self._t.items() if t.role != "in"}
+        return {name: self._read(name, buf) for name, t in self._t.items() if t.role != "in"}
 
 
 def same_bytes(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
-def run_two_seeds(make, device=None, sync=None):
+def run_two_seeds(make, device=None, sync=None, deferred=False):
     """make(arena) declares the tensors of one call and returns call(arena) -> status.  Runs it under both seeds,
-    check()s each, asserts the status is 0 and the outputs are bit-identical; -> (outputs, arena of the last seed)."""
+    check()s each, asserts the status is 0 and the outputs are bit-identical; -> (outputs, arena of the last seed).
+    deferred: the arena holds decoys until call(arena) itself lets the inputs arrive()."""
     outs = []
     for seed in SEEDS:
         A = Arena(seed, device)
         call = make(A)
-        A.build()
+        A.build(deferred=deferred)
         rc = call(A)
         if sync is not None:
             sync()
