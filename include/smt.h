@@ -280,8 +280,8 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  * write maps only (both maps requested, D <= 256, W >= D + 6) the right map of the columns 3 <= j' <= W-3-D is taken
  * from keys (cost bits << 32 | d) that the left pass publishes.  The columns j' > W-3-D get the keys of their
  * hypotheses with j' + d <= W-4 the same way; what is left to them are the edge hypotheses W-3 <= j' + d <= W+3 (the
- * cost is constant in d past W+3-j', so later ones cannot be a first minimum), which the finishing launch evaluates
- * with the right view's arithmetic and merges into the key, as it evaluates every hypothesis of the columns 0..2.
+ * cost is constant in d past W+3-j', so later ones cannot be a first minimum), which the launch's edge items evaluate
+ * with the right view's arithmetic and merge into the key, as they evaluate every hypothesis of the columns 0..2.
  * Maps are those of the two-view kernel, bit for bit.  The host takes this form for D <= 192 and keeps the two-view
  * kernel for 192 < D <= 256, where it measured slower.
  *   SMT_MAPS_SHARED=0 in the environment (read at every call, like SMT_MAPS_CHUNKS / SMT_MAPS_KERNEL / SMT_OVERLAP)
@@ -295,8 +295,26 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  * kernel's own index functions over pseudo-random costs with many exact ties (seed % 3: 0 a palette with ties, 1 every
  * cost equal, 2 mostly distinct; the right view's edge hypotheses have pseudo-costs of their own).  SMT_OK iff every
  * right pixel is written exactly once, with the first minimum over its shared and its edge hypotheses, every ring ends
- * empty and the key map is reset;
- * SMT_ERR_STATE otherwise; SMT_ERR_ARG unless H, W >= 1, 1 <= D <= 256, 1 <= K <= 64. */
+ * empty and the key map is reset; and that the split finish below (edge merges in front of or behind the publishes'
+ * merges, by seed & 4, then the conversion) gives the single pass's result;
+ * SMT_ERR_STATE otherwise; SMT_ERR_ARG unless H, W >= 1, 1 <= D <= 256, 1 <= K <= 64.
+ * Finishing a pair.  The launch of a shared pair carries three kinds of auxiliary workgroups beside its cost
+ * workgroups: the table tiles of the NEXT pair, the edge items of ITS OWN pair (the edge hypotheses above, merged into
+ * the key map with atomic minima for the columns <= W-4 and written to the map for the columns W-3 .. W-1 and 0..2) and
+ * the conversion items of the PREVIOUS shared pair (key -> map entry, key reset; they need no tables).  A handle has
+ * two key maps, pair n merges into map n & 1.  The last shared pair of a call, and a shared pair followed by anything
+ * but another shared pair, is converted by a small launch of its own on the handle's stream before anything else is
+ * issued there: no conversion is pending when an entry point returns.
+ *   SMT_SHARED_FINISH=apart in the environment (read at every call) converts every pair with that launch of its own
+ *   right behind the pair's launch (two launches per pair): same-process A/Bs and tests.  Maps are the same.
+ * Test hooks, host only (no GPU), exported and declared in csrc/adcensus_internal.h:
+ *   int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
+ * every cost workgroup (ncost > 0, a multiple of 8) and every table, edge and conversion item of such a launch is
+ * decoded exactly once;
+ *   int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
+ * the same for the counts of an H x W x D pair (first: nothing to convert, last: no tables to build), and the items'
+ * pixel arithmetic covers each key, each pixel of the columns W-2-D .. W-1 and each of the columns 0..2 exactly once,
+ * and no column W-3-D < j' <= W-4 has an empty edge range.  SMT_OK, SMT_ERR_STATE, or SMT_ERR_ARG (also for W < D + 6). */
 
 /* Synchronises the stream and returns SMT_ERR_DOMAIN if any pixel seen since the previous
  * smt_adcensus_status call (or since create) was not an integer in 0..255 (then those pairs' volumes

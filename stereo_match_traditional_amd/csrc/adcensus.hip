@@ -412,8 +412,8 @@ __device__ __forceinline__ void st_stream(__amdgpu_buffer_rsrc_t r, unsigned vof
 // (shared_pub_hi): every shareable cost is published.  The columns of the IDENTITY SET 3 <= j' <= W-3-D get all their D
 // hypotheses that way.  A column j' > W-3-D lacks the EDGE HYPOTHESES with j' + d >= W-3; the VIEW 1 staging clamps the
 // census index to W+3 and the value index to W-1, so the cost is constant in d from W+3-j' on and only d <= W+3-j' can
-// be a first minimum: at most 7 per column (shared_edge_range).  Columns 0..2 share nothing.  k_shared_finish evaluates
-// the edge hypotheses from the tables and merges them with the column's key.
+// be a first minimum: at most 7 per column (shared_edge_range).  Columns 0..2 share nothing.  The launch's edge items evaluate
+// the edge hypotheses from the tables and merge them with the column's key (shared_edge_item).
 // Runs of chunks are those of chunk_decode (below).
 #ifndef SMT_SHARED_KNOCKOUT
 #define SMT_SHARED_KNOCKOUT 0      // measurement builds only (wrong maps): 1 no LDS publishes, 2 no key-map merges
@@ -464,11 +464,68 @@ __host__ __device__ inline void shared_run_flush_range(int S, int E, int D, int 
 // key map: with the other runs' keys, and past the identity set with the edge hypotheses (never complete).
 __host__ __device__ inline bool shared_complete(int c, int S, int E, int D) { return c >= S && c + D - 1 <= E; }
 __host__ __device__ inline bool shared_complete(int c, int S, int E, int D, int idhi) { return c <= idhi && shared_complete(c, S, E, D); }
-// Edge hypotheses of right column c, evaluated by k_shared_finish: d in [lo, hi] (columns 0..2: every d that can win).
+// Edge hypotheses of right column c, evaluated by the edge items: d in [lo, hi] (columns 0..2: every d that can win).
 __host__ __device__ inline void shared_edge_range(int c, int W, int D, int &lo, int &hi)
 {
     lo = c >= 3 && W - 3 - c > 0 ? W - 3 - c : 0;
     hi = W + 3 - c < D - 1 ? W + 3 - c : D - 1;
+}
+// Auxiliary work items of a shared launch.  The workgroups of the fused grid's "table" class (fused_grid / fused_decode)
+// take the items b = 0 .. naux-1 of one list: nprep table tiles of the NEXT pair, then nconv conversion items of the
+// PREVIOUS pair, then nedge edge items of THIS pair (shared_aux_decode).
+//   conversion item: SH_CONV_PX consecutive entries of the previous pair's key map, taken as a flat array of H*W keys,
+//     two per 16-byte load: k != SH_NOKEY -> map entry (float)d, key reset.  Needs no tables.
+//   edge item < shared_edge_col_items(): SH_EDGE_PX pixels of the columns idhi+1 .. W-1 in row-major order, one thread
+//     per pixel at a time.  Columns <= W-4 merge their minimum over shared_edge_range into the key map with an atomic
+//     min (minima commute with the cost workgroups' merges); the columns W-3 .. W-1 get no publishes and write the map.
+//   the other edge items: SH_EDGE0_PX pixels of the columns 0..2, one wave per pixel, every hypothesis an edge one,
+//     written to the map.
+// INVARIANT: the key map holds keys only at the columns 3 .. W-4; the entries of the columns 0..2 and W-3 .. W-1 stay
+// SH_NOKEY for ever, so a conversion over the whole flat array never touches the map entries the edge items wrote.
+constexpr int SH_CONV_PX = 16 * 256;                         // 16 keys per thread (NT threads)
+constexpr int SH_EDGE_PX = 4 * 256;
+constexpr int SH_EDGE0_PX = 16 * 4;                          // 16 pixels per wave
+__host__ __device__ inline int shared_conv_items(int H, int W) { return (int)(((long)H * W + SH_CONV_PX - 1) / SH_CONV_PX); }
+__host__ __device__ inline int shared_edge_cols(int W, int D) { return W - 1 - shared_id_hi(W, D); }   // idhi+1 .. W-1
+__host__ __device__ inline int shared_edge_col_items(int H, int W, int D)
+{
+    return (int)(((long)H * shared_edge_cols(W, D) + SH_EDGE_PX - 1) / SH_EDGE_PX);
+}
+__host__ __device__ inline int shared_edge_items(int H, int W, int D)
+{
+    return shared_edge_col_items(H, W, D) + (3 * H + SH_EDGE0_PX - 1) / SH_EDGE0_PX;
+}
+constexpr int AUX_PREP = 0, AUX_CONV = 1, AUX_EDGE = 2, AUX_NONE = 3;
+__host__ __device__ inline int shared_aux_decode(int b, int nprep, int nconv, int nedge, int &item)
+{
+    item = b;
+    if (item < nprep) return AUX_PREP;
+    item -= nprep;
+    if (item < nconv) return AUX_CONV;
+    item -= nconv;
+    return item < nedge ? AUX_EDGE : AUX_NONE;
+}
+// Pixel arithmetic of the items, step `it` of thread `tid` (wave `wv`): false past the end of the item's set.
+__host__ __device__ inline bool shared_conv_px(int item, int it, int tid, long N, long &p)    // the keys p and p + 1
+{
+    p = (long)item * SH_CONV_PX + 2 * ((long)it * 256 + tid);
+    return p < N;
+}
+__host__ __device__ inline bool shared_edge_px(int item, int it, int tid, int H, int W, int D, int &i, int &c)
+{
+    const int nc = shared_edge_cols(W, D);
+    const long q = (long)item * SH_EDGE_PX + (long)it * 256 + tid;
+    if (q >= (long)H * nc) return false;
+    i = (int)(q / nc);
+    c = shared_id_hi(W, D) + 1 + (int)(q - (long)i * nc);
+    return true;
+}
+__host__ __device__ inline bool shared_edge0_px(int item, int it, int wv, int H, int &i, int &c)
+{
+    const int w = item * SH_EDGE0_PX + it * 4 + wv;
+    if (w >= 3 * H) return false;
+    i = w / 3; c = w - 3 * i;
+    return true;
 }
 
 struct __attribute__((aligned(16))) Anchor { uint64_t cen, mask; };
@@ -1195,14 +1252,99 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
     if (lane < npx) disp[(size_t)i * W + jw0 + lane] = (float)res;
 }
 
+// Right-view cost of (i, j', d) straight from the tables, with the arithmetic of cost_fast_body's VIEW 1: the census
+// index clamped to W+3, the value index to W-1, the anchor's tap mask, lut[ad] + lut[256 + hd].  j' + d >= 0.
+__device__ __forceinline__ unsigned long long shared_edge_key(const Tables &T, int i, int W, uint64_t acen, uint64_t amask,
+                                                              int va, int x, int d)
+{
+    const int xc = x > W + 3 ? W + 3 : x, xv = x > W - 1 ? W - 1 : x;
+    const int hd = __popcll((acen ^ T.cenX[1][(size_t)i * T.WX + xc]) & amask);
+    const int vx = T.u8[0][(size_t)i * W + xv];
+    const int ad = va > vx ? va - vx : vx - va;
+    const float c = T.lut[ad] + T.lut[256 + hd];
+    return shared_key(__float_as_uint(c), d);
+}
+
+// The auxiliary items of a shared launch (rules: shared_aux_decode and the functions next to it).  None uses LDS.
+// Conversion: partial keys -> map entries, the consumed keys reset for the pair after the next.  All 8 loads of a
+// thread are issued before the first store.
+__device__ __forceinline__ void shared_conv_item(unsigned long long *__restrict__ keys, float *__restrict__ dispR, long N,
+                                                 int item)
+{
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+    constexpr int NI = SH_CONV_PX / (2 * NT);
+    u64x2 k[NI];
+    // step `it` takes the keys p0 + 512 it and the one behind it (shared_conv_px is linear in `it`)
+    long p0;
+    (void)shared_conv_px(item, 0, (int)threadIdx.x, N, p0);
+    const long left = N - p0;                                              // <= 0: nothing for this thread
+    unsigned long long *__restrict__ kp = keys + p0;
+    float *__restrict__ dp = dispR + p0;
+#pragma unroll
+    for (int it = 0; it < NI; it++) {
+        constexpr int ST = 2 * NT;
+        k[it].x = k[it].y = SH_NOKEY;
+        if (it * ST + 1 < left) k[it] = *reinterpret_cast<const u64x2 *>(kp + it * ST);   // p is even: 16-byte aligned
+        else if (it * ST < left) k[it].x = kp[it * ST];
+    }
+#pragma unroll
+    for (int it = 0; it < NI; it++) {
+        constexpr int ST = 2 * NT;
+        if (k[it].x != SH_NOKEY) { dp[it * ST] = (float)(unsigned)k[it].x; kp[it * ST] = SH_NOKEY; }
+        if (k[it].y != SH_NOKEY) { dp[it * ST + 1] = (float)(unsigned)k[it].y; kp[it * ST + 1] = SH_NOKEY; }
+    }
+}
+
+// Edge hypotheses of this pair from its tables T (read-only in this launch: the table workgroups write the other set).
+__device__ __forceinline__ void shared_edge_item(const Tables &T, int H, int W, int D, float *__restrict__ dispR,
+                                                 unsigned long long *__restrict__ keys, int item)
+{
+    const int ncol = shared_edge_col_items(H, W, D);
+    if (item < ncol) {
+#pragma unroll 1
+        for (int it = 0; it < SH_EDGE_PX / NT; it++) {
+            int i, c;
+            if (!shared_edge_px(item, it, (int)threadIdx.x, H, W, D, i, c)) return;
+            const size_t p = (size_t)i * W + c;
+            const uint64_t acen = T.cenA[1][p], amask = T.mask[p];
+            const int va = T.u8[1][p];
+            int lo, hi;
+            shared_edge_range(c, W, D, lo, hi);
+            unsigned long long k = SH_NOKEY;
+            for (int d = lo; d <= hi; d++) k = min(k, shared_edge_key(T, i, W, acen, amask, va, c + d, d));
+            if (c > W - 4) dispR[p] = (float)(unsigned)k;                  // nothing is published to the last three
+            else if (k != SH_NOKEY && SMT_SHARED_KNOCKOUT != 2) atomicMin(&keys[p], k);
+        }
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (int it = 0; it < SH_EDGE0_PX / 4; it++) {                         // columns 0..2
+        int i, c;
+        if (!shared_edge0_px(item - ncol, it, (int)(threadIdx.x >> 6), H, i, c)) return;
+        const size_t p = (size_t)i * W + c;
+        const uint64_t acen = T.cenA[1][p], amask = T.mask[p];
+        const int va = T.u8[1][p];
+        int lo, hi;
+        shared_edge_range(c, W, D, lo, hi);
+        unsigned long long k = SH_NOKEY;
+        for (int d = lo + lane; d <= hi; d += 64) k = min(k, shared_edge_key(T, i, W, acen, amask, va, c + d, d));
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) k = min(k, (unsigned long long)__shfl_xor((long long)k, s));
+        if (lane == 0) dispR[p] = (float)(unsigned)k;
+    }
+}
+
 // Shared maps-only form: both maps of a pair from one cost evaluation per shareable hypothesis.  A cost workgroup takes
 // K consecutive chunks of the left view alone (shared_wg_chunks: chunk_decode's, in its XCD's eighth) and publishes the
 // keys of the right columns [3, pubhi] to its ring.  Per run (shared_run_len) of n <= SH_RUN chunks: stage once,
 // barrier, every wave walks its quarter of the run and publishes, barrier, flush every column the run published to
 // (shared_run_flush_range) -- complete keys to the map, partial ones to the key map, slots reset.  The next run's
 // staging store follows the flush, and the barrier behind it frees the ring and shows the staged set.  A column yields
-// one key per run and the merges are minima, so their order does not matter.  k_shared_finish then turns the merged
-// partial keys into map entries and adds the edge hypotheses.  Table workgroups and LUT are those of k_cost_maps2p.
+// one key per run and the merges are minima, so their order does not matter.  The launch's edge items merge the edge
+// hypotheses into the same key map; the conversion items of the NEXT shared launch (or k_shared_convert) turn the merged
+// keys into map entries.  The workgroups of the fused grid's table class take the auxiliary items (shared_aux_decode):
+// table tiles as in k_cost_maps2p, conversion items of the previous pair (ckeys -> cdisp), edge items of this pair.
 #ifndef SMT_SHARED_MIN_WAVES
 #define SMT_SHARED_MIN_WAVES 7     // waves per SIMD the register allocation must allow; measured 1 / 7 / 8: DESIGN.md section 4
 #endif
@@ -1211,21 +1353,27 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
                                                          float *__restrict__ disp1, unsigned long long *__restrict__ keys,
                                                          int nbx, int K, int pubhi, int ncost, int nprep,
                                                          const float *__restrict__ nL, const float *__restrict__ nR,
-                                                         Tables Tn, int ptx)
+                                                         Tables Tn, int ptx, int nconv, int nedge,
+                                                         unsigned long long *__restrict__ ckeys, float *__restrict__ cdisp)
 {
-    static_assert(PNT == NT, "");
+    static_assert(PNT == NT && NT == 256, "");
     static_assert(2 * PSR * PSW * 4 <= PREP_LDS_U16 * 2 && 320 * 4 <= PREP_LDS_U16 * 2, "");
     __shared__ RunLds<C> lds;
     __shared__ unsigned long long ring[SH_RING_N];
-    long b = blockIdx.x;
-    if (nprep > 0) {
-        const FusedGrid f = fused_grid(ncost, nprep);
+    long b;
+    {
+        const FusedGrid f = fused_grid(ncost, nprep + nconv + nedge);
         int idx;
         const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
         b = idx * 8 + (int)(blockIdx.x & 7);
-        if (table) {
-            uint32_t (*sw)[PSW] = (uint32_t (*)[PSW])lds.tab;
-            if (b < nprep) prep_tile(nL, nR, H, W, Tn, (int)b % ptx, (int)b / ptx, ptx, sw, sw + PSR);
+        if (table) {                                                       // an auxiliary item, or none
+            int item;
+            const int kind = shared_aux_decode((int)b, nprep, nconv, nedge, item);
+            if (kind == AUX_PREP) {
+                uint32_t (*sw)[PSW] = (uint32_t (*)[PSW])lds.tab;
+                prep_tile(nL, nR, H, W, Tn, item % ptx, item / ptx, ptx, sw, sw + PSR);
+            } else if (kind == AUX_CONV) shared_conv_item(ckeys, cdisp, (long)H * W, item);
+            else if (kind == AUX_EDGE) shared_edge_item(T, H, W, FULL ? 64 * C : D, disp1, keys, item);
             return;
         }
     }
@@ -1261,59 +1409,11 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
     }
 }
 
-// Right-view cost of (i, j', d) straight from the tables, with the arithmetic of cost_fast_body's VIEW 1: the census
-// index clamped to W+3, the value index to W-1, the anchor's tap mask, lut[ad] + lut[256 + hd].  j' + d >= 0.
-__device__ __forceinline__ unsigned long long shared_edge_key(const Tables &T, int i, int W, uint64_t acen, uint64_t amask,
-                                                              int va, int x, int d)
+// The conversion items of a pair that no later shared launch carries (the last shared pair of a batch loop, or every
+// pair under SMT_SHARED_FINISH=apart): shared_conv_items() workgroups.
+__global__ void __launch_bounds__(NT) k_shared_convert(unsigned long long *__restrict__ keys, float *__restrict__ dispR, long N)
 {
-    const int xc = x > W + 3 ? W + 3 : x, xv = x > W - 1 ? W - 1 : x;
-    const int hd = __popcll((acen ^ T.cenX[1][(size_t)i * T.WX + xc]) & amask);
-    const int vx = T.u8[0][(size_t)i * W + xv];
-    const int ad = va > vx ? va - vx : vx - va;
-    const float c = T.lut[ad] + T.lut[256 + hd];
-    return shared_key(__float_as_uint(c), d);
-}
-
-// Partial keys of the shared form -> map entries; the consumed keys are reset for the next pair.  One thread per pixel
-// of the columns 3 .. W-1, which past the identity set merges the column's edge hypotheses (shared_edge_range, at most
-// 7) into the key and always writes; the blocks from nb1 on take the columns 0..2, one wave per pixel, every hypothesis
-// an edge one.  T: the tables of the pair just computed (the launch before this one wrote the other set).
-__global__ void __launch_bounds__(256) k_shared_finish(unsigned long long *__restrict__ keys, int H, int W, int D, int idhi,
-                                                       float *__restrict__ dispR, unsigned nb1, Tables T)
-{
-    if (blockIdx.x >= nb1) {                                               // columns 0..2
-        const size_t w = (size_t)(blockIdx.x - nb1) * 4 + (threadIdx.x >> 6);
-        if (w >= (size_t)H * 3) return;
-        const int i = (int)(w / 3), c = (int)(w % 3), lane = threadIdx.x & 63;
-        const size_t p = (size_t)i * W + c;
-        const uint64_t acen = T.cenA[1][p], amask = T.mask[p];
-        const int va = T.u8[1][p];
-        int lo, hi;
-        shared_edge_range(c, W, D, lo, hi);
-        unsigned long long k = SH_NOKEY;
-        for (int d = lo + lane; d <= hi; d += 64) k = min(k, shared_edge_key(T, i, W, acen, amask, va, c + d, d));
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) k = min(k, (unsigned long long)__shfl_xor((long long)k, s));
-        if (lane == 0) dispR[p] = (float)(unsigned)k;
-        return;
-    }
-    const int n = W - 3;                                                   // columns 3 .. W-1
-    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= (size_t)H * n) return;
-    const int i = (int)(q / n), c = 3 + (int)(q % n);
-    const size_t p = (size_t)i * W + c;
-    unsigned long long k = c <= W - 4 ? keys[p] : SH_NOKEY;                // nothing is published to the last three
-    if (c <= idhi) {
-        if (k != SH_NOKEY) { dispR[p] = (float)(unsigned)k; keys[p] = SH_NOKEY; }
-        return;
-    }
-    if (k != SH_NOKEY) keys[p] = SH_NOKEY;
-    const uint64_t acen = T.cenA[1][p], amask = T.mask[p];
-    const int va = T.u8[1][p];
-    int lo, hi;
-    shared_edge_range(c, W, D, lo, hi);
-    for (int d = lo; d <= hi; d++) k = min(k, shared_edge_key(T, i, W, acen, amask, va, c + d, d));
-    dispR[p] = (float)(unsigned)k;
+    shared_conv_item(keys, dispR, N, (int)blockIdx.x);
 }
 
 // Store-only twin of k_cost_fast2<C, true>: the same grid, workgroup -> chunk order and streaming stores
@@ -1395,7 +1495,14 @@ struct smt_adcensus {
     float store_mode_ms[2];   // calibration: kernel ms with streaming / plain stores (0: not calibrated)
     int place_tries;     // candidate volume pairs tried by place_volumes
     float place_ms;      // store-only time of the pair that was kept (0: no search)
-    unsigned long long *skeys;   // [H][W] key map of the shared maps-only form: SH_NOKEY between launches
+    // Two [H][W] key maps of the shared maps-only form; pair n merges into map n_pairs & 1.  Both are all SH_NOKEY after
+    // create and whenever no conversion is pending.  conv_pending: the shared pair issued last has its partial keys in
+    // skeys[conv_map], still to be converted into its right map conv_dR -- by the next pair's shared launch, or by
+    // flush_conversion().  Never true when an entry point returns (the caller may free its maps).
+    unsigned long long *skeys[2];
+    bool conv_pending;
+    int conv_map;
+    float *conv_dR;
     // Deferred volumes of a batch's last pair (smt_adcensus_compute_batch, smt_adcensus_volume).  vol_lent: a caller
     // has been given a volume pointer, so every batch from then on writes its last pair's volumes itself.
     // vol_pending: the last pair took the maps-only path and its volumes are still to be written, by the both-views
@@ -1636,6 +1743,17 @@ static bool build_rank(const float *lut, uint16_t *rank)
     return true;
 }
 
+// The pending conversion of the shared form, if any, as a launch of its own on the handle's stream.  Every path that
+// is not the next pair's shared launch calls this before it does anything else on the stream.
+static void flush_conversion(smt_adcensus *h)
+{
+    if (!h->conv_pending) return;
+    const long N = (long)h->H * h->W;
+    hipLaunchKernelGGL(k_shared_convert, dim3((unsigned)shared_conv_items(h->H, h->W)), dim3(NT), 0, h->stream,
+                       h->skeys[h->conv_map], h->conv_dR, N);
+    h->conv_pending = false;
+}
+
 static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsigned flags, smt_adcensus **out)
 {
     if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || !(sigmaC > 0.0f) || !(sigmaS > 0.0f))
@@ -1666,7 +1784,7 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
         }
         alloc((void **)&h->TS[t].mask, N * 8);
     }
-    alloc((void **)&h->skeys, N * 8);
+    for (int t = 0; t < 2; t++) alloc((void **)&h->skeys[t], N * 8);
     h->T = h->TS[0];
     if (rc != SMT_OK) { smt_adcensus_destroy(h); return rc; }
     if (hipStreamCreateWithFlags(&h->prep_stream, hipStreamNonBlocking) != hipSuccess ||
@@ -1690,7 +1808,8 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
     // GetPtrLeft/Right before the first Compute* reads zeros
     if (!rank_ok || hipMemcpy(h->TS[0].lut, lut, sizeof(lut), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(h->vol[0], 0, V * 4) != hipSuccess || hipMemset(h->vol[1], 0, V * 4) != hipSuccess ||
-        hipMemset(h->TS[0].flag, 0, 4) != hipSuccess || hipMemset(h->skeys, 0xFF, N * 8) != hipSuccess) {
+        hipMemset(h->TS[0].flag, 0, 4) != hipSuccess || hipMemset(h->skeys[0], 0xFF, N * 8) != hipSuccess ||
+        hipMemset(h->skeys[1], 0xFF, N * 8) != hipSuccess) {
         smt_adcensus_destroy(h);
         return SMT_ERR_HIP;
     }
@@ -1726,6 +1845,7 @@ SMT_API int smt_adcensus_destroy(smt_adcensus *h)
 {
     if (!h) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
+    if (h->conv_pending) { flush_conversion(h); (void)hipStreamSynchronize(h->stream); }
     if (h->prep_stream) { (void)hipStreamSynchronize(h->prep_stream); (void)hipStreamDestroy(h->prep_stream); }
     if (h->in_ready) (void)hipEventDestroy(h->in_ready);
     for (int t = 0; t < 2; t++) {
@@ -1740,7 +1860,7 @@ SMT_API int smt_adcensus_destroy(smt_adcensus *h)
         (void)hipFree(h->TS[t].mask);
     }
     (void)hipFree(h->TS[0].lut); (void)hipFree(h->TS[0].rank); (void)hipFree(h->TS[0].flag);
-    (void)hipFree(h->skeys);
+    (void)hipFree(h->skeys[0]); (void)hipFree(h->skeys[1]);
     if (h->ev) {
         for (int k = 0; k < SMT_TIMING_SLOTS * 4; k++) (void)hipEventDestroy(h->ev[k]);
         delete[] h->ev_merged;
@@ -1808,6 +1928,30 @@ static bool maps_shared_shape(int W, int D)
     return D <= 192 || (env && env[0] == 'f');
 }
 
+// SMT_SHARED_FINISH=apart in the environment (read at every call) converts every shared pair's keys with a launch of
+// its own right behind the pair's launch, instead of inside the next pair's: same-process A/Bs and tests.
+static bool shared_finish_apart()
+{
+    const char *env = getenv("SMT_SHARED_FINISH");
+    return env && strcmp(env, "apart") == 0;
+}
+
+// The pair takes the shared form (k_cost_maps_shared); every other pair flushes a pending conversion first.
+static bool pair_takes_shared(const smt_adcensus *h, int views, const float *dL, const float *dR, bool maps)
+{
+    if (!(views == SMT_VIEW_BOTH && maps) || h->force_generic || (h->D + 63) / 64 > 4) return false;
+    const char *env = getenv("SMT_MAPS_KERNEL");
+    return !(env && env[0] == 'r') && dL && dR && maps_shared_shape(h->W, h->D) && maps_shared();
+}
+
+// Table workgroups of one pair: the tiles and the workgroups of the 13 border columns (16 rows each).
+static int prep_items(int H, int W, int &ptx)
+{
+    ptx = (W + PTW - 1) / PTW;
+    const int pty = (H + PTH - 1) / PTH, eb = (H + PNT / 16 - 1) / (PNT / 16);
+    return ptx * (pty + (eb + ptx - 1) / ptx);
+}
+
 template <int C, bool FULL>
 static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const float *nL, const float *nR, bool maps)
 {
@@ -1820,25 +1964,26 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
         int nprep = 0, ptx = 1;
         unsigned grid = (unsigned)ncost;
         if (nL) {
-            ptx = (h->W + PTW - 1) / PTW;
-            const int pty = (h->H + PTH - 1) / PTH, eb = (h->H + PNT / 16 - 1) / (PNT / 16);
-            nprep = ptx * (pty + (eb + ptx - 1) / ptx);
+            nprep = prep_items(h->H, h->W, ptx);
             grid = 8u * (unsigned)fused_grid(ncost, nprep).groups;
         }
         const Tables &Tn = h->TS[(h->n_pairs + 1) & 1];
         const char *env = getenv("SMT_MAPS_KERNEL");
-        const int idhi = shared_id_hi(h->W, h->D);
-        if (!(env && env[0] == 'r') && dL && dR && maps_shared_shape(h->W, h->D) && maps_shared()) {
-            // the left-view runs, then the finishing launch, both on the caller's stream
-            const int ncs = maps_groups(nbx, h->H, 1, K);
-            const unsigned gs = nL ? 8u * (unsigned)fused_grid(ncs, nprep).groups : (unsigned)ncs;
+        if (pair_takes_shared(h, views, dL, dR, maps)) {
+            // One launch on the caller's stream: the left-view runs, this pair's edge items, the next pair's table tiles
+            // and the previous shared pair's conversion.  This pair's own conversion stays pending.
+            const int km = (int)(h->n_pairs & 1);
+            if (h->conv_pending && h->conv_map == km) flush_conversion(h);   // cannot happen: shared pairs in a row alternate
+            const bool carried = h->conv_pending;
+            const int ncs = maps_groups(nbx, h->H, 1, K), Dd = FULL ? 64 * C : h->D;
+            const int nconv = carried ? shared_conv_items(h->H, h->W) : 0, nedge = shared_edge_items(h->H, h->W, Dd);
+            const unsigned gs = 8u * (unsigned)fused_grid(ncs, nprep + nconv + nedge).groups;
             hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
-                               h->skeys, nbx, K, shared_pub_hi(h->W), ncs, nprep, nL, nR, Tn, ptx);
-            const size_t nf = (size_t)h->H * (h->W - 3);                   // one thread per pixel of columns 3 .. W-1
-            const unsigned nb1 = (unsigned)((nf + 255) / 256), nb0 = (unsigned)(((size_t)h->H * 3 + 3) / 4);
-            if (SMT_SHARED_KNOCKOUT != 2)
-                hipLaunchKernelGGL(k_shared_finish, dim3(nb1 + nb0), dim3(256), 0, h->stream, h->skeys, h->H, h->W, h->D, idhi,
-                                   dR, nb1, h->T);
+                               h->skeys[km], nbx, K, shared_pub_hi(h->W), ncs, nprep, nL, nR, Tn, ptx, nconv, nedge,
+                               carried ? h->skeys[h->conv_map] : nullptr, carried ? h->conv_dR : nullptr);
+            if (SMT_SHARED_KNOCKOUT != 2) { h->conv_pending = true; h->conv_map = km; h->conv_dR = dR; }
+            else h->conv_pending = false;
+            if (shared_finish_apart()) flush_conversion(h);
             return;
         }
         if (env && env[0] == 'r')
@@ -1926,6 +2071,7 @@ static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int vi
     const int set = (int)(h->n_pairs & 1);
     h->T = h->TS[set];
     h->vol_pending = false;                                  // never observable: dropped with the tables they would come from
+    if (!pair_takes_shared(h, views, dL, dR, maps)) flush_conversion(h);
     const bool timed = h->timing && (h->n_seen++ % h->timing_stride) == 0;
     const long slot = h->n_timed % SMT_TIMING_SLOTS;
     hipEvent_t *ev = timed ? h->ev + 4 * slot : nullptr;
@@ -2007,8 +2153,11 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
         int rc = adcensus_pair(h, L + b * N, R + b * N, views, dispL ? dispL + b * N : nullptr,
                                dispR ? dispR + b * N : nullptr, sched == 1 && b > 0, b > 0 ? sched == 2 : prepped,
                                bl, br, maps_ok && (!last || !last_volumes));
-        if (rc != SMT_OK) return rc;
+        if (rc != SMT_OK) { flush_conversion(h); return rc; }
     }
+    // the last shared pair has no next launch; the caller may read or free its maps behind this call
+    flush_conversion(h);
+    SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
 
@@ -2020,6 +2169,7 @@ bool adcensus_fused_both_views(const smt_adcensus *h) { return fast_both_views(h
 // what it would have.  With timing on, the launch is recorded like a pair whose tables were already built.
 static int materialise_volumes(smt_adcensus *h)
 {
+    flush_conversion(h);
     if (!h->vol_pending) return SMT_OK;
     const long slot = h->n_timed % SMT_TIMING_SLOTS;
     hipEvent_t *ev = h->timing ? h->ev + 4 * slot : nullptr;
@@ -2146,12 +2296,13 @@ SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
     return rc;
 }
 
-// Host-side walk of the shared maps-only form (k_cost_maps_shared + k_shared_finish) over pseudo-random costs with many
+// Host-side walk of the shared maps-only form (k_cost_maps_shared's cost, edge and conversion items) over pseudo-random costs with many
 // exact ties, through the kernel's own index functions.  The left pass: shared_wg_chunks / shared_run_len give a
 // workgroup's sub-runs of at most SH_RUN chunks (checked against chunk_decode); a whole run is published -- the lane ->
 // hypothesis split, shared_publishes and shared_ring_base -- which must not put two columns into one ring slot, then
 // flushed once over shared_run_flush_range, shared_complete sending a key to the map or to the key map.  Then the
-// finishing launch's edge hypotheses over shared_edge_range.
+// edge hypotheses over shared_edge_range and the conversion: as one pass over the pixels, and split into the launch's
+// edge items and the next launch's conversion items, which must agree.
 // The right view's pseudo-cost of (i, j', d) is the left one of (i, j' + d, d) where the identity holds and a cost of
 // its own elsewhere, constant in d from W+3-j' on as the staging clamps make it.  SMT_OK iff every right pixel is
 // written exactly once, with the first minimum over all its D hypotheses, every ring ends empty and the key map is
@@ -2228,7 +2379,63 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                 if (bx == nbx) { bx = 0; i++; }
             }
         }
-        // the finishing launch
+        // The split finish on copies of the state behind the left pass: the edge items' merges (seed & 4: in front of
+        // the publishes' merges instead of behind them -- minima commute) and direct writes, then the conversion over
+        // the flat key map.  Its result must be the single pass's below.
+        unsigned long long *keys2 = new (std::nothrow) unsigned long long[N];
+        unsigned *val2 = new (std::nothrow) unsigned[N];
+        unsigned char *nw2 = new (std::nothrow) unsigned char[N];
+        if (!keys2 || !val2 || !nw2) rc = SMT_ERR_ALLOC;
+        if (rc == SMT_OK) {
+            memcpy(val2, val, N * sizeof(unsigned));
+            memcpy(nw2, nw, N);
+            const bool edges_first = (seed & 4u) != 0;
+            for (size_t p = 0; p < N; p++) keys2[p] = edges_first ? SH_NOKEY : keys[p];
+            const int nedge = shared_edge_items(H, W, D), ncol = shared_edge_col_items(H, W, D);
+            for (int item = 0; item < nedge; item++) {
+                if (item < ncol) {
+                    for (int it = 0; it < SH_EDGE_PX / 256; it++)
+                        for (int tid = 0; tid < 256; tid++) {
+                            int i, c;
+                            if (!shared_edge_px(item, it, tid, H, W, D, i, c)) continue;
+                            const size_t p = (size_t)i * W + c;
+                            int lo, hi;
+                            shared_edge_range(c, W, D, lo, hi);
+                            unsigned long long k = SH_NOKEY;
+                            for (int d = lo; d <= hi; d++) k = std::min(k, shared_key(right_bits(i, c, d), d));
+                            if (k == SH_NOKEY) rc = SMT_ERR_STATE;                      // an empty edge range
+                            if (c > W - 4) { val2[p] = (unsigned)k; nw2[p]++; }
+                            else keys2[p] = std::min(keys2[p], k);
+                        }
+                } else {
+                    for (int it = 0; it < SH_EDGE0_PX / 4; it++)
+                        for (int wv = 0; wv < 4; wv++) {
+                            int i, c;
+                            if (!shared_edge0_px(item - ncol, it, wv, H, i, c)) continue;
+                            const size_t p = (size_t)i * W + c;
+                            int lo, hi;
+                            shared_edge_range(c, W, D, lo, hi);
+                            unsigned long long k = SH_NOKEY;
+                            for (int d = lo; d <= hi; d++) k = std::min(k, shared_key(right_bits(i, c, d), d));
+                            val2[p] = (unsigned)k; nw2[p]++;
+                        }
+                }
+            }
+            if (edges_first) for (size_t p = 0; p < N; p++) keys2[p] = std::min(keys2[p], keys[p]);
+            for (int i = 0; i < H; i++)                                                 // the invariant of the key map
+                for (int c = 0; c < W; c++)
+                    if ((c < 3 || c > W - 4) && keys2[(size_t)i * W + c] != SH_NOKEY) rc = SMT_ERR_STATE;
+            const int nconv = shared_conv_items(H, W);
+            for (int item = 0; item < nconv; item++)
+                for (int it = 0; it < SH_CONV_PX / 512; it++)
+                    for (int tid = 0; tid < 256; tid++) {
+                        long p;
+                        if (!shared_conv_px(item, it, tid, (long)N, p)) continue;
+                        for (long e = p; e < p + 2 && e < (long)N; e++)
+                            if (keys2[e] != SH_NOKEY) { val2[e] = (unsigned)keys2[e]; nw2[e]++; keys2[e] = SH_NOKEY; }
+                    }
+        }
+        // the single pass
         for (int i = 0; i < H; i++)
             for (int c = 0; c < W; c++) {
                 const size_t p = (size_t)i * W + c;
@@ -2244,6 +2451,9 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                 if (k == SH_NOKEY) rc = SMT_ERR_STATE;
                 val[p] = (unsigned)k; nw[p]++;
             }
+        for (size_t p = 0; p < N && rc == SMT_OK; p++)
+            if (val2[p] != val[p] || nw2[p] != nw[p] || keys2[p] != keys[p]) rc = SMT_ERR_STATE;
+        delete[] keys2; delete[] val2; delete[] nw2;
     }
     for (int i = 0; i < H && rc == SMT_OK; i++)
         for (int c = 0; c < W && rc == SMT_OK; c++) {
@@ -2261,6 +2471,94 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
             if (nw[p] != 1 || val[p] != (unsigned)want) rc = SMT_ERR_STATE;
         }
     delete[] keys; delete[] val; delete[] nw;
+    return rc;
+}
+
+// Host-side check of a shared launch's auxiliary list (fused_grid / fused_decode over ncost cost workgroups and
+// nprep + nconv + nedge auxiliary items, shared_aux_decode): every cost workgroup and every table, conversion and edge
+// item is decoded exactly once.  Needs no GPU.
+SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv)
+{
+    if (ncost <= 0 || (ncost & 7) || nprep < 0 || nedge < 0 || nconv < 0) return SMT_ERR_ARG;
+    const int naux = nprep + nconv + nedge;
+    const FusedGrid f = fused_grid(ncost, naux);
+    if (8L * f.groups < (long)ncost + naux) return SMT_ERR_STATE;
+    unsigned char *cost = new (std::nothrow) unsigned char[(size_t)ncost]();
+    unsigned char *aux = new (std::nothrow) unsigned char[(size_t)naux + 1]();
+    int rc = (cost && aux) ? SMT_OK : SMT_ERR_ALLOC;
+    for (long blk = 0; blk < 8L * f.groups && rc == SMT_OK; blk++) {
+        int idx = -1;
+        const bool table = fused_decode(f, (int)(blk >> 3), idx);
+        if (idx < 0) { rc = SMT_ERR_STATE; break; }
+        const long b = (long)idx * 8 + (blk & 7);
+        if (!table) {
+            if (b >= ncost || cost[b]++) rc = SMT_ERR_STATE;
+            continue;
+        }
+        int item = -1;
+        const int kind = shared_aux_decode((int)b, nprep, nconv, nedge, item);
+        if (kind == AUX_NONE) { if (b < naux) rc = SMT_ERR_STATE; continue; }
+        const int n = kind == AUX_PREP ? nprep : kind == AUX_CONV ? nconv : nedge;
+        const int base = kind == AUX_PREP ? 0 : kind == AUX_CONV ? nprep : nprep + nconv;
+        if (item < 0 || item >= n || base + item != b || aux[b]++) rc = SMT_ERR_STATE;
+    }
+    for (int c = 0; c < ncost && rc == SMT_OK; c++) if (cost[c] != 1) rc = SMT_ERR_STATE;
+    for (int a = 0; a < naux && rc == SMT_OK; a++) if (aux[a] != 1) rc = SMT_ERR_STATE;
+    delete[] cost; delete[] aux;
+    return rc;
+}
+
+// Host-side check of the shared launch of an H x W x D pair with K chunks per cost workgroup, through the functions the
+// kernel runs: the launch's counts as launch_fast computes them (first: no conversion carried; last: no table tiles)
+// pass smt_adcensus_selftest_shared_aux_grid; the conversion items cover each of the H*W keys exactly once; the edge
+// items cover each pixel of the columns idhi+1 .. W-1 and 0..2 exactly once and no other; the edge range of every
+// column idhi < c <= W-4 is not empty.  Needs no GPU.
+SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last)
+{
+    if (H <= 0 || W <= 0 || D <= 0 || D > 256 || K < 1 || K > 64 || (long)H * W > (1L << 24)) return SMT_ERR_ARG;
+    const int idhi = shared_id_hi(W, D), nbx = (W + FTJ - 1) / FTJ;
+    if (idhi < 3) return SMT_ERR_ARG;                                     // the two-view kernel serves this shape
+    int ptx;
+    const int ncost = maps_groups(nbx, H, 1, K), nprep = last ? 0 : prep_items(H, W, ptx);
+    const int nconv = first ? 0 : shared_conv_items(H, W), nedge = shared_edge_items(H, W, D);
+    int rc = smt_adcensus_selftest_shared_aux_grid(ncost, nprep, nedge, nconv);
+    if (rc != SMT_OK) return rc;
+    const long N = (long)H * W;
+    unsigned char *seen = new (std::nothrow) unsigned char[(size_t)N]();
+    if (!seen) return SMT_ERR_ALLOC;
+    for (int item = 0; item < shared_conv_items(H, W); item++)
+        for (int it = 0; it < SH_CONV_PX / 512; it++)
+            for (int tid = 0; tid < 256; tid++) {
+                long p;
+                long p0;
+                (void)shared_conv_px(item, 0, tid, N, p0);
+                const bool in = shared_conv_px(item, it, tid, N, p);
+                if (p != p0 + 512L * it) rc = SMT_ERR_STATE;              // the kernel steps one pointer by 512 keys
+                if (!in) continue;
+                if (p < 0 || (p & 1)) { rc = SMT_ERR_STATE; continue; }
+                for (long e = p; e < p + 2 && e < N; e++) if (seen[e]++) rc = SMT_ERR_STATE;
+            }
+    for (long p = 0; p < N; p++) { if (seen[p] != 1) rc = SMT_ERR_STATE; seen[p] = 0; }
+    const int ncol = shared_edge_col_items(H, W, D);
+    for (int item = 0; item < nedge; item++)
+        for (int it = 0; it < (item < ncol ? SH_EDGE_PX / 256 : SH_EDGE0_PX / 4); it++)
+            for (int t = 0; t < (item < ncol ? 256 : 4); t++) {
+                int i = -1, c = -1;
+                if (!(item < ncol ? shared_edge_px(item, it, t, H, W, D, i, c) : shared_edge0_px(item - ncol, it, t, H, i, c)))
+                    continue;
+                const bool in = i >= 0 && i < H && (item < ncol ? c > idhi && c < W : c >= 0 && c < 3);
+                if (!in || seen[(long)i * W + c]++) rc = SMT_ERR_STATE;
+            }
+    for (int i = 0; i < H; i++)
+        for (int c = 0; c < W; c++) {
+            const bool edge = c < 3 || c > idhi;
+            if (seen[(long)i * W + c] != (edge ? 1 : 0)) rc = SMT_ERR_STATE;
+            int lo, hi;
+            shared_edge_range(c, W, D, lo, hi);
+            if (c > idhi && c <= W - 4 && (lo > hi || lo < 1 || c + lo != W - 3)) rc = SMT_ERR_STATE;
+            if (edge && (lo < 0 || hi > D - 1 || lo > hi)) rc = SMT_ERR_STATE;
+        }
+    delete[] seen;
     return rc;
 }
 

@@ -17,3 +17,6 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
 bool adcensus_fused_both_views(const smt_adcensus *h);
 // Host-only selftest of the shared maps-only form's run / ring / flush / merge arithmetic (documented in include/smt.h).
 SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
+// Host-only selftests of the shared form's auxiliary work items (documented in include/smt.h).
+SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
+SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);

@@ -1,0 +1,42 @@
+// Stand-alone driver of the host-only selftests of csrc/adcensus.hip, for sanitizer builds of the host code (no GPU, no
+// Python):
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-sanitize-recover=undefined stereo_match_traditional_amd/csrc/adcensus.hip \
+//         tools/adcensus_selftest_main.cpp -fsanitize=address,undefined -o adcensus_selftest && ./adcensus_selftest
+// Exit status 0 iff every selftest returned SMT_OK on every shape (and the sanitizers stayed silent).
+#include <cstdio>
+
+extern "C" {
+int smt_adcensus_selftest_fused_grid(int ncost, int nprep);
+int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep);
+int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
+int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
+int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
+}
+
+int main()
+{
+    static const int shapes[][3] = {{1, 70, 64}, {1, 500, 192}, {3, 70, 64}, {5, 198, 192}, {4, 262, 256}, {7, 133, 64},
+                                    {6, 261, 192}, {32, 128, 64}, {16, 128, 62}, {64, 140, 100}, {65, 330, 192},
+                                    {6, 259, 192}, {7, 129, 33}, {40, 700, 192}, {128, 96, 20}, {3, 1030, 192},
+                                    {3, 69, 64}, {9, 70, 256}};
+    static const int grids[][4] = {{8, 5, 3, 2}, {8, 0, 3, 2}, {8, 5, 0, 2}, {8, 5, 3, 0}, {8, 0, 0, 0}, {8, 40, 30, 20},
+                                   {8104, 1110, 256, 507}, {8104, 0, 256, 0}, {1000, 17, 5, 333}};
+    static const int Ks[] = {1, 3, 4, 64};
+    int bad = 0;
+    for (const auto &g : grids) {
+        if (smt_adcensus_selftest_shared_aux_grid(g[0], g[1], g[2], g[3]) != 0) { printf("aux_grid %d %d %d %d\n", g[0], g[1], g[2], g[3]); bad++; }
+        if (g[1] > 0 && smt_adcensus_selftest_fused_grid(g[0], g[1]) != 0) { printf("fused_grid %d %d\n", g[0], g[1]); bad++; }
+    }
+    for (const auto &s : shapes)
+        for (int K : Ks) {
+            const bool served = s[1] - 3 - s[2] >= 3;        // the identity set is not empty
+            for (unsigned seed = 0; seed < 8; seed++)
+                if (smt_adcensus_selftest_shared_keys(s[0], s[1], s[2], K, seed) != 0) { printf("shared_keys %d %d %d K=%d seed=%u\n", s[0], s[1], s[2], K, seed); bad++; }
+            for (int fl = 0; served && fl < 4; fl++)
+                if (smt_adcensus_selftest_shared_aux(s[0], s[1], s[2], K, fl & 1, fl >> 1) != 0) { printf("shared_aux %d %d %d K=%d %d\n", s[0], s[1], s[2], K, fl); bad++; }
+            if (smt_adcensus_selftest_maps_grid((s[1] + 63) / 64, s[0], K, 5) != 0) { printf("maps_grid %d %d K=%d\n", s[0], s[1], K); bad++; }
+        }
+    printf("%s: %d failures\n", bad ? "FAILED" : "ok", bad);
+    return bad ? 1 : 0;
+}
