@@ -104,7 +104,11 @@ int smt_set_device(int device);
  * have no cap of their own (one thread per pixel and hypothesis).  ASW window side
  * 2*(winSize+1)+1 <= 64 (winSize <= 30; one window row per wavefront pass); MedianFilter wnd_size <= 7;
  * volumes of 4 GiB or more take the plain one-pixel-per-wave aggregation kernel (32-bit tap offsets in
- * the shared-tap kernels). */
+ * the shared-tap kernels).  Image size: H * W < 2^31 everywhere (pixel indices are int: smt_adcensus_create*,
+ * smt_crossarm_create*, smt_scanline_create*, smt_wta, smt_ncc and the batch and post-processing entry points reject
+ * more); hypothesis addresses are 64-bit, so a volume of H * W * D elements may pass 2^31 elements and 2^32 bytes
+ * (tests/test_large_volume_gpu.py runs every volume stage at 4 GiB to 8 GiB; DESIGN.md section 2, "Large volumes").
+ * The one-thread-per-hypothesis CBLSM helpers take up to 2^39 hypotheses (the grid size). */
 
 #define SMT_MAX_DISPARITY 512
 

@@ -1756,7 +1756,8 @@ static void flush_conversion(smt_adcensus *h)
 
 static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsigned flags, smt_adcensus **out)
 {
-    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || !(sigmaC > 0.0f) || !(sigmaS > 0.0f))
+    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || !(sigmaC > 0.0f) || !(sigmaS > 0.0f) ||
+        (long long)H * W >= (1ll << 31))                 // pixel counts and key-map items are int
         return SMT_ERR_ARG;
     smt_adcensus *h = new (std::nothrow) smt_adcensus();
     if (!h) return SMT_ERR_ALLOC;
@@ -2747,7 +2748,8 @@ SMT_API int smt_adcensus_diag(smt_adcensus *h, int reps, float *sclk_mhz, float 
 
 SMT_API int smt_wta(const float *vol, int H, int W, int D, float *disp, void *stream)
 {
-    if (!vol || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;
+    if (!vol || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || (size_t)H * W >= ((size_t)1 << 31))
+        return SMT_ERR_ARG;                              // pixel indices are int; hypothesis addresses are (size_t)p * D
     const int N = H * W;
     dim3 grid((N + 3) / 4);
     const int C = (D + 63) / 64;

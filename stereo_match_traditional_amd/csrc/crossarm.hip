@@ -488,7 +488,7 @@ __global__ void __launch_bounds__(NT) k_aggregate_pipe(const float *__restrict__
     float acc[C];
 #pragma unroll
     for (int k = 0; k < C; k++) acc[k] = 0.0f;
-    const char *base = (const char *)(vin + dl);         // + tap byte offset (< 2^32: V*4 bytes <= 1.6e9... checked by host)
+    const char *base = (const char *)(vin + dl);         // + tap byte offset, unsigned 32-bit: V * 4 bytes < 2^32 (smt_crossarm_aggregate takes the plain walk from 4 GiB on)
 
     auto ld = [&](unsigned off, float (&x)[C]) {
         const float *src = (const float *)(base + off);
@@ -1469,7 +1469,7 @@ SMT_API void smt_crossarm_cblsm_params(smt_crossarm_params *p)
 
 SMT_API int smt_crossarm_create(int H, int W, int D, const smt_crossarm_params *p, smt_crossarm **out)
 {
-    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;
+    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || (long long)H * W >= (1ll << 31)) return SMT_ERR_ARG;   // pixel indices are int
     smt_crossarm *h = new (std::nothrow) smt_crossarm();
     if (!h) return SMT_ERR_ALLOC;
     h->device = smt_current_device();
@@ -1972,6 +1972,7 @@ SMT_API int smt_cblsm_ad(const uint8_t *L, const uint8_t *R, int H, int W, int D
     if (!L || !R || !vol || H <= 0 || W <= 0 || D <= 0 || (view != SMT_VIEW_LEFT && view != SMT_VIEW_RIGHT))
         return SMT_ERR_ARG;
     const size_t V = (size_t)H * W * D;
+    if ((V + NT - 1) / NT > (size_t)INT_MAX) return SMT_ERR_ARG;        // one thread per hypothesis: the grid size
     hipLaunchKernelGGL(k_cblsm_ad, dim3((unsigned)((V + NT - 1) / NT)), dim3(NT), 0, smt_stream(stream), L, R,
                        H, W, D, view == SMT_VIEW_LEFT ? 0 : 1, vol);
     SMT_LAUNCH_CHECK();
@@ -1986,6 +1987,7 @@ SMT_API int smt_cblsm_choose_arm_length(int dir, const int *own_arm, const int *
         (dir >= 2 && !other_vertical_arm))
         return SMT_ERR_ARG;
     const size_t V = (size_t)H * W * D;
+    if ((V + NT - 1) / NT > (size_t)INT_MAX) return SMT_ERR_ARG;        // the grid size
     hipLaunchKernelGGL(k_choose_arm, dim3((unsigned)((V + NT - 1) / NT)), dim3(NT), 0, smt_stream(stream), dir, own_arm,
                        other_vertical_arm, armRL, armRR, H, W, D, arm_volume);
     SMT_LAUNCH_CHECK();
@@ -2001,6 +2003,7 @@ SMT_API int smt_cblsm_cost_aggregation_new(const uint8_t *Lp, const uint8_t *Rp,
         return SMT_ERR_ARG;
     const int w = winSize + 1;
     const size_t V = (size_t)H * W * D;
+    if ((V + NT - 1) / NT > (size_t)INT_MAX) return SMT_ERR_ARG;        // the grid size
     hipLaunchKernelGGL(k_cblsm_cost_agg_new, dim3((unsigned)((V + NT - 1) / NT)), dim3(NT), 0, smt_stream(stream), Lp, Rp,
                        H + 2 * w, W + 2 * w, w, armvolL, armvolR, armvolUp, armvolDown, D, cost);
     SMT_LAUNCH_CHECK();

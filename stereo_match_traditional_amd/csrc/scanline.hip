@@ -307,7 +307,7 @@ struct smt_scanline {
 
 SMT_API int smt_scanline_create(int H, int W, int D, int p1, int p2, smt_scanline **out)
 {
-    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY) return SMT_ERR_ARG;
+    if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || (long long)H * W >= (1ll << 31)) return SMT_ERR_ARG;   // as the other stages; addresses are long
     smt_scanline *h = new (std::nothrow) smt_scanline();
     if (!h) return SMT_ERR_ALLOC;
     h->device = smt_current_device();

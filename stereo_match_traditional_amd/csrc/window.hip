@@ -1299,7 +1299,9 @@ int smt_ncc_loop_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, i
 SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int winSize, int32_t *disp,
                     double *cost, void *stream)
 {
-    if (!L || !R || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winSize < 0) return SMT_ERR_ARG;
+    if (!L || !R || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winSize < 0 ||
+        (size_t)H * W >= ((size_t)1 << 31))
+        return SMT_ERR_ARG;                              // pixel indices are int; cost addresses are (size_t)p * D
     const int N = H * W;
     hipStream_t st = smt_stream(stream);
     const long long side = 2LL * winSize + 1;
