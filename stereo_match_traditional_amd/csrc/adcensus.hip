@@ -419,7 +419,7 @@ __device__ __forceinline__ void st_stream(__amdgpu_buffer_rsrc_t r, unsigned vof
 #define SMT_SHARED_KNOCKOUT 0      // measurement builds only (wrong maps): 1 no LDS publishes, 2 no key-map merges
 #endif
 constexpr int SH_RING = 512;                                 // key ring, indexed by right column mod 512
-constexpr int SH_RING_N = SH_RING + 4;                       // + the spill slots of shared_ring_base()
+constexpr int SH_RING_N = SH_RING + 4;                       // + the spill slots of shared_ring_base() / shared_ring_slot()
 constexpr unsigned long long SH_NOKEY = ~0ull;
 __host__ __device__ inline int shared_id_hi(int W, int D) { return W - 3 - D; }           // the set is [3, hi]; empty when hi < 3
 __host__ __device__ inline int shared_pub_hi(int W) { return W - 4; }                     // last published right column
@@ -431,6 +431,23 @@ __host__ __device__ inline unsigned long long shared_key(unsigned cost_bits, int
 // base + (C-1-k) with base = (t - (C-1)) mod 512, one address computation per pixel.  A column c with c mod 512 < C-1
 // can therefore land in slot c mod 512 or in the spill slot 512 + c mod 512; the flush takes the minimum of the two.
 __host__ __device__ inline int shared_ring_base(int t, int C) { return (int)((unsigned)(t - (C - 1)) & (unsigned)(SH_RING - 1)); }
+// The GROUPED form (shared_ring_grouped: the D = 192 kernel) computes the base once per group of C pixels, for the
+// group's first pixel, column t0 = j0 - dl: pixel j0 + u publishes hypothesis k to slot base(t0) + u + (C-1-k), the
+// offset a compile-time constant in [0, 2 (C-1)].  That is the slot ((c - o) mod 512) + o of column c = t0 + u - k
+// with o = u + C-1-k, so a column c with c mod 512 < 2 (C-1) can land in c mod 512 or in the spill slot 512 + c mod
+// 512: SH_SPILL = 4 spill slots at C <= 3 (C = 4 would need 6).  The flush takes the minimum of the two for every s
+// below shared_ring_spill(): the slots the form can reach.
+// A wave's groups start at its first pixel: pixel q of wave w of a run of n chunks is pixel 16 n w + q of the run.
+constexpr int SH_SPILL = SH_RING_N - SH_RING;
+// shared_walk_groups: the walk takes whole groups of C pixels without a per-pixel exit, then the pixels left over.
+// Both are switched per instantiation (Dfull: 64 C, or 0 when D != 64 C); measured at D = 192 and D = 128, DESIGN.md
+// section 4.  The grouped ring needs the group loop.
+__host__ __device__ constexpr bool shared_walk_groups(int C, int Dfull) { return C == 3 && Dfull == 192; }
+__host__ __device__ constexpr bool shared_ring_grouped(int C, int Dfull) { return C == 3 && Dfull == 192; }
+static_assert(!shared_ring_grouped(3, 192) || shared_walk_groups(3, 192), "");
+__host__ __device__ inline int shared_ring_slot(int t0, int u, int k, int C) { return shared_ring_base(t0, C) + u + (C - 1 - k); }
+__host__ __device__ constexpr int shared_ring_spill(int C, bool grouped) { return grouped ? 2 * (C - 1) : C - 1; }
+static_assert(shared_ring_spill(3, true) <= SH_SPILL && shared_ring_spill(4, false) <= SH_SPILL, "");
 // A whole run of at most SH_RUN = 4 chunks is published before its one flush (shared_run_flush_range), so at most
 // 256 + D - 1 <= 511 columns are live (D <= 256): no two live columns share a slot of the ring of 512.
 // Run walk.  A workgroup's chunks (chunk_decode over the left view alone, t = 0 .. K-1) are consecutive in the linear
@@ -1014,7 +1031,7 @@ __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables 
 
 // One flush of the key ring (shared_run_flush_range's columns lo .. hi of row i, run [S, E]): complete keys go to the map,
 // partial ones to the handle's key map with one agent-scope atomic min each; the slots are reset.
-template <int C>
+template <int C, bool GROUPED>
 __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, int W, int D, int lo, int hi, int S, int E,
                                              int idhi, float *__restrict__ dispR, unsigned long long *__restrict__ keys)
 {
@@ -1022,7 +1039,7 @@ __device__ __forceinline__ void shared_flush(unsigned long long *ring, int i, in
         const int s = c & (SH_RING - 1);
         unsigned long long k = ring[s];
         ring[s] = SH_NOKEY;
-        if (s < C - 1) { k = min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
+        if (s < shared_ring_spill(C, GROUPED)) { k = min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
         const size_t p = (size_t)i * W + c;
         if (shared_complete(c, S, E, D, idhi)) dispR[p] = (float)(unsigned)k;
         else if (k != SH_NOKEY && SMT_SHARED_KNOCKOUT != 2) atomicMin(&keys[p], k);
@@ -1112,7 +1129,9 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
     // stepped ring address) are taken by the D = 192 kernel only: it is the form they were measured to pay in.  At
     // C = 2 the same four measured slower at 720p x 128 in every run, with the stepped address (64 -> 70 VGPRs, 8 -> 7
     // waves per SIMD) and without it, and the other forms gain scratch with the stepped address; those compile to the
-    // code they had.
+    // code they had.  The stepped address has since become one base per group of C pixels
+    // (GROUPED, below) in a group loop without per-pixel exits (GROUP_LOOP), again in the D = 192 kernel only: at C = 2
+    // the two together gained 4x the run-to-run spread at 720p x 128 and cost a wave per SIMD.
     constexpr bool TRIM = C == 3 && FULL;
     const Anchor *s_anc = ml->anc;
     const uint16_t *s_vala = ml->vala;
@@ -1156,90 +1175,112 @@ __device__ __forceinline__ void shared_run_walk(int H, int W, int Drt, float *__
     uint32_t nx_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint64_t *)(s_cenx + e0);
     uint32_t nv_a = (uint32_t)(size_t)(const __attribute__((address_space(3))) uint16_t *)(s_valx + e0);
     asm volatile("" : "+v"(anc_a), "+v"(val_a), "+v"(nx_a), "+v"(nv_a));
-    // byte offset in the ring of slot shared_ring_base(t, C) of the pixel at hand, t = j - dl: advanced by one slot per
-    // pixel and wrapped, where computing it from the column takes two more vector instructions per pixel, at the price of
-    // one more live register
-    constexpr bool RING_STEP = TRIM;
+    // byte offset in the ring of slot shared_ring_base(t, C) of the group's first pixel, t = j - dl: advanced by C slots
+    // per group and wrapped, the group's other pixels at immediate offsets from it (shared_ring_slot), where computing it
+    // from the column takes two vector instructions per pixel, at the price of one more live register
+    constexpr bool GROUPED = shared_ring_grouped(C, FULL ? 64 * C : 0);
+    constexpr bool GROUP_LOOP = shared_walk_groups(C, FULL ? 64 * C : 0);
+    static_assert(GROUP_LOOP || !GROUPED, "");
     const uint32_t ring_b = (uint32_t)(size_t)ring3;
     uint32_t ra = 8u * (uint32_t)shared_ring_base(jw0 - dl, C);
 
     auto walk = [&](auto masked_tag, auto allin_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
         constexpr bool ALLIN = decltype(allin_tag)::value;
-#pragma unroll 1
-        for (int g = 0; g < npx; g += C) {
-#pragma unroll
-            for (int u = 0; u < C; u++) {
-                const int q = g + u;
-                if (q < npx) {
-                    Anchor a;
-                    if (MASKED) {                                            // one ds_read_b128
-                        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-                        const u64x2 v = *(const __attribute__((address_space(3))) u64x2 *)(size_t)(anc_a + 16u * u);
-                        a.cen = v.x; a.mask = v.y;
-                    }
-                    else { a.cen = *(lds_u64_p)(size_t)(anc_a + 16u * u); a.mask = 0; }
-                    const unsigned va = *(lds_u16_p)(size_t)(val_a + 2u * u);
-                    // entry that joins the ring for the next pixel (always inside the staged range)
-                    const uint64_t nc = *(lds_u64_p)(size_t)(nx_a + 8u * (unsigned)(u + 1));
-                    const unsigned nv = *(lds_u16_p)(size_t)(nv_a + 2u * (unsigned)(u + 1));
-                    float c[C];
-                    unsigned key[C];
-#pragma unroll
-                    for (int k = 0; k < C; k++) {
-                        const int slot = (((u - k) % C) + C) % C;            // E(q-k) with q = u (mod C)
-                        uint64_t x = a.cen ^ rc[slot];
-                        if (MASKED) x &= a.mask;
-                        const int hd = __popcll(x);
-                        const unsigned ad4 = __builtin_amdgcn_sad_u16(va, rv[slot], 0u);   // 4*|va - vx|
-                        c[k] = *(const float *)(lutA + ad4) + lutC[hd];
-                        key[k] = ok[k] ? __float_as_uint(c[k]) : 0xFFFFFFFFu;
-                    }
-                    unsigned ml0 = key[0];
-#pragma unroll
-                    for (int k = 1; k < C; k++) ml0 = min(ml0, key[k]);
-                    // ml0 is compared against the minimum below, so the untied form saves its copy per pixel
-                    unsigned m;
-                    if constexpr (TRIM) m = wave_min_u32_untied(ml0);
-                    else m = wave_min_u32(ml0);
-                    const unsigned long long b = __ballot(ml0 == m);
-                    const int first = __builtin_ctzll(b);
-                    int kk = C - 1;
-#pragma unroll
-                    for (int k = C - 2; k >= 0; k--)
-                        if ((unsigned)__builtin_amdgcn_readlane((int)key[k], first) == m) kk = k;
-                    const int wd = first * C + kk;           // wave-uniform
-                    // lane q keeps pixel q's winner (q <= 63): one v_writelane where (lane == q) ? wd : res took a
-                    // compare and a move under a saved exec mask.  This compiler has no writelane builtin, hence the
-                    // statement.  Both sources are scalar and gfx9 reads one SGPR per vector instruction, so the lane
-                    // goes in m0.  No wait states are needed: on gfx9 only a lane select in an SGPR that a vector
-                    // instruction wrote has a hazard, and m0 is written by the s_mov.  The compiler warns about the m0
-                    // clobber (-Winline-asm) at each instantiation; the kernel uses m0 nowhere else.
-                    if constexpr (TRIM)
-                        asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(res) : "s"(__builtin_amdgcn_readfirstlane(wd)), "s"(q) : "m0");
-                    else res = (lane == q) ? wd : res;
-                    if constexpr (SMT_SHARED_KNOCKOUT != 1) {
-                        const int tcol = (jw0 + q) - dl;                     // right column of hypothesis k = 0
-                        lds_key_p rp;
-                        if constexpr (RING_STEP) rp = (lds_key_p)(size_t)(ring_b + ra);
-                        else rp = ring3 + shared_ring_base(tcol, C);
-#pragma unroll
-                        for (int k = 0; k < C; k++)
-                            if (ok[k] && (ALLIN || shared_publishes(jw0 + q, tcol - k, W, pubhi)))
-                                (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
-                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                    if constexpr (RING_STEP) ra = (ra + 8u) & (8u * SH_RING - 1u);
-                    // the new entry replaces the one that just left the window.  The value is made a 32-bit one here:
-                    // carried round the loop as the 16 bits it was loaded as, it is zero-extended again at every use
-                    // (one v_and per pixel), though ds_read_u16 already returned it so
-                    unsigned nv32 = nv;
-                    if constexpr (TRIM) asm("" : "+v"(nv32));
-                    rc[(u + 1) % C] = nc; rv[(u + 1) % C] = nv32;
-                }
+        // pixel q = g + u of the walk; u = q mod C is a constant once the group is unrolled (the register window's
+        // indices and the immediate offsets from the group's addresses depend on it)
+        auto pixel = [&](const int u, const int q) __attribute__((always_inline)) {
+            Anchor a;
+            if (MASKED) {                                            // one ds_read_b128
+                typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+                const u64x2 v = *(const __attribute__((address_space(3))) u64x2 *)(size_t)(anc_a + 16u * u);
+                a.cen = v.x; a.mask = v.y;
             }
-            anc_a += 16u * C; val_a += 2u * C;
-            nx_a += 8u * C; nv_a += 2u * C;
+            else { a.cen = *(lds_u64_p)(size_t)(anc_a + 16u * u); a.mask = 0; }
+            const unsigned va = *(lds_u16_p)(size_t)(val_a + 2u * u);
+            // entry that joins the ring for the next pixel (always inside the staged range)
+            const uint64_t nc = *(lds_u64_p)(size_t)(nx_a + 8u * (unsigned)(u + 1));
+            const unsigned nv = *(lds_u16_p)(size_t)(nv_a + 2u * (unsigned)(u + 1));
+            float c[C];
+            unsigned key[C];
+#pragma unroll
+            for (int k = 0; k < C; k++) {
+                const int slot = (((u - k) % C) + C) % C;            // E(q-k) with q = u (mod C)
+                uint64_t x = a.cen ^ rc[slot];
+                if (MASKED) x &= a.mask;
+                const int hd = __popcll(x);
+                const unsigned ad4 = __builtin_amdgcn_sad_u16(va, rv[slot], 0u);   // 4*|va - vx|
+                c[k] = *(const float *)(lutA + ad4) + lutC[hd];
+                key[k] = ok[k] ? __float_as_uint(c[k]) : 0xFFFFFFFFu;
+            }
+            unsigned ml0 = key[0];
+#pragma unroll
+            for (int k = 1; k < C; k++) ml0 = min(ml0, key[k]);
+            // ml0 is compared against the minimum below, so the untied form saves its copy per pixel
+            unsigned m;
+            if constexpr (TRIM) m = wave_min_u32_untied(ml0);
+            else m = wave_min_u32(ml0);
+            const unsigned long long b = __ballot(ml0 == m);
+            const int first = __builtin_ctzll(b);
+            int kk = C - 1;
+#pragma unroll
+            for (int k = C - 2; k >= 0; k--)
+                if ((unsigned)__builtin_amdgcn_readlane((int)key[k], first) == m) kk = k;
+            const int wd = first * C + kk;           // wave-uniform
+            // lane q keeps pixel q's winner (q <= 63): one v_writelane where (lane == q) ? wd : res took a
+            // compare and a move under a saved exec mask.  This compiler has no writelane builtin, hence the
+            // statement.  Both sources are scalar and gfx9 reads one SGPR per vector instruction, so the lane
+            // goes in m0.  No wait states are needed: on gfx9 only a lane select in an SGPR that a vector
+            // instruction wrote has a hazard, and m0 is written by the s_mov.  The compiler warns about the m0
+            // clobber (-Winline-asm) at each instantiation; the kernel uses m0 nowhere else.
+            if constexpr (TRIM)
+                asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(res) : "s"(__builtin_amdgcn_readfirstlane(wd)), "s"(q) : "m0");
+            else res = (lane == q) ? wd : res;
+            if constexpr (SMT_SHARED_KNOCKOUT != 1) {
+                const int tcol = (jw0 + q) - dl;                     // right column of hypothesis k = 0
+                lds_key_p rp;
+                if constexpr (GROUPED) rp = (lds_key_p)(size_t)(ring_b + ra) + u;   // the group's base: immediate offsets
+                else rp = ring3 + shared_ring_base(tcol, C);
+#pragma unroll
+                for (int k = 0; k < C; k++)
+                    if (ok[k] && (ALLIN || shared_publishes(jw0 + q, tcol - k, W, pubhi)))
+                        (void)__hip_atomic_fetch_min(rp + (C - 1 - k), shared_key(__float_as_uint(c[k]), dl + k),
+                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            // the new entry replaces the one that just left the window.  The value is made a 32-bit one here:
+            // carried round the loop as the 16 bits it was loaded as, it is zero-extended again at every use
+            // (one v_and per pixel), though ds_read_u16 already returned it so
+            unsigned nv32 = nv;
+            if constexpr (TRIM) asm("" : "+v"(nv32));
+            rc[(u + 1) % C] = nc; rv[(u + 1) % C] = nv32;
+        };
+        if constexpr (GROUP_LOOP) {
+            // whole groups without a per-pixel exit -- one basic block, so the group's addresses are advanced once and a
+            // pixel's arithmetic can fill the wait states of its neighbour's DPP chain -- then the at most C-1 pixels left
+            // over, from the same base
+            int g = 0;
+#pragma unroll 1
+            for (; g + C <= npx; g += C) {
+#pragma unroll
+                for (int u = 0; u < C; u++) pixel(u, g + u);
+                anc_a += 16u * C; val_a += 2u * C;
+                nx_a += 8u * C; nv_a += 2u * C;
+                if constexpr (GROUPED) ra = (ra + 8u * C) & (8u * SH_RING - 1u);
+            }
+#pragma unroll
+            for (int u = 0; u < C - 1; u++)
+                if (g + u < npx) pixel(u, g + u);
+        } else {
+#pragma unroll 1
+            for (int g = 0; g < npx; g += C) {
+#pragma unroll
+                for (int u = 0; u < C; u++) {
+                    const int q = g + u;
+                    if (q < npx) pixel(u, q);
+                }
+                anc_a += 16u * C; val_a += 2u * C;
+                nx_a += 8u * C; nv_a += 2u * C;
+            }
         }
     };
     // per wave.  interior: every pixel has all 63 taps inside the image, so the tap mask is all ones and the AND per
@@ -1404,7 +1445,7 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
         const int cE = cS + FTJ * cn - 1;
         int lo, hi;
         shared_run_flush_range(cS, cE, Dd, pubhi, lo, hi);
-        shared_flush<C>(ring, ci, W, Dd, lo, hi, cS, cE, idhi, disp1, keys);
+        shared_flush<C, shared_ring_grouped(C, FULL ? 64 * C : 0)>(ring, ci, W, Dd, lo, hi, cS, cE, idhi, disp1, keys);
         if (n <= 0) break;
     }
 }
@@ -2300,7 +2341,7 @@ SMT_API int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep)
 // Host-side walk of the shared maps-only form (k_cost_maps_shared's cost, edge and conversion items) over pseudo-random costs with many
 // exact ties, through the kernel's own index functions.  The left pass: shared_wg_chunks / shared_run_len give a
 // workgroup's sub-runs of at most SH_RUN chunks (checked against chunk_decode); a whole run is published -- the lane ->
-// hypothesis split, shared_publishes and shared_ring_base -- which must not put two columns into one ring slot, then
+// hypothesis split, shared_publishes and shared_ring_slot -- which must not put two columns into one ring slot, then
 // flushed once over shared_run_flush_range, shared_complete sending a key to the map or to the key map.  Then the
 // edge hypotheses over shared_edge_range and the conversion: as one pass over the pixels, and split into the launch's
 // edge items and the next launch's conversion items, which must agree.
@@ -2313,6 +2354,7 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
     if (H <= 0 || W <= 0 || D <= 0 || D > 256 || K < 1 || K > 64 || (long)H * W > (1L << 24)) return SMT_ERR_ARG;
     const int C = (D + 63) / 64, nbx = (W + FTJ - 1) / FTJ, idhi = shared_id_hi(W, D);
     const int pubhi = shared_pub_hi(W);
+    const bool grouped = shared_ring_grouped(C, D == 64 * C ? D : 0);
     const size_t N = (size_t)H * W;
     // costs: a small palette of floats >= +0 (ties), every cost equal (seed % 3 == 1), or mostly distinct
     static const float pal[] = {0.0f, 0.0f, 0.25f, 0.25f, 1.5f, 0.7265625f, 0.7265625f, 1.9999999f, 0.25f, 1e-30f};
@@ -2357,7 +2399,10 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                         for (int k = 0; k < C; k++) {
                             const int dl = lane * C, d = dl + k, tcol = j - dl;
                             if (d >= D || !shared_publishes(j, tcol - k, W, pubhi)) continue;
-                            const int s = shared_ring_base(tcol, C) + (C - 1 - k);
+                            // the kernel's slot: per pixel, or from the base of the pixel's group in its wave's walk
+                            const int u = grouped ? ((j - S) % (FPW * n)) % C : 0;
+                            const int s = shared_ring_slot(tcol - u, u, k, C);
+                            if (s < 0 || s >= SH_RING_N) { rc = SMT_ERR_STATE; continue; }
                             if (owner[s] != -1 && owner[s] != tcol - k) rc = SMT_ERR_STATE;   // two live columns in a slot
                             owner[s] = tcol - k;
                             ring[s] = std::min(ring[s], shared_key(cost_bits(i, j, d), d));
@@ -2368,7 +2413,7 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
                     const int s = c & (SH_RING - 1);
                     unsigned long long k = ring[s];
                     ring[s] = SH_NOKEY;
-                    if (s < C - 1) { k = std::min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
+                    if (s < shared_ring_spill(C, grouped)) { k = std::min(k, ring[SH_RING + s]); ring[SH_RING + s] = SH_NOKEY; }
                     const size_t p = (size_t)i * W + c;
                     if (shared_complete(c, S, E, D, idhi)) {
                         if (k == SH_NOKEY) rc = SMT_ERR_STATE;

@@ -19,7 +19,8 @@ int main()
     static const int shapes[][3] = {{1, 70, 64}, {1, 500, 192}, {3, 70, 64}, {5, 198, 192}, {4, 262, 256}, {7, 133, 64},
                                     {6, 261, 192}, {32, 128, 64}, {16, 128, 62}, {64, 140, 100}, {65, 330, 192},
                                     {6, 259, 192}, {7, 129, 33}, {40, 700, 192}, {128, 96, 20}, {3, 1030, 192},
-                                    {3, 69, 64}, {9, 70, 256}};
+                                    {3, 69, 64}, {9, 70, 256}, {3, 257, 192}, {3, 258, 192}, {3, 304, 192}, {4, 1030, 192},
+                                    {6, 530, 128}, {2, 1536, 192}, {2, 1920, 192}};
     static const int grids[][4] = {{8, 5, 3, 2}, {8, 0, 3, 2}, {8, 5, 0, 2}, {8, 5, 3, 0}, {8, 0, 0, 0}, {8, 40, 30, 20},
                                    {8104, 1110, 256, 507}, {8104, 0, 256, 0}, {1000, 17, 5, 333}};
     static const int Ks[] = {1, 3, 4, 64};
