@@ -888,6 +888,50 @@ int smt_ncc_flow_set_form(smt_ncc_flow *h, int form);
 int smt_ncc_flow_run_batch(smt_ncc_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int32_t *disp,
                            double *cost);
 
+/* Both views of NCC from one pass over the costs.  The reference has no NCC right view; this one mirrors NCC.h:69-95 as
+ * GetPointDepthRight mirrors GetPointDepthLeft.  For winSize <= i < H-winSize, winSize <= x < W-winSize:
+ *   costR[i][x][d] = ComputeCost(R window centred (i, x), L window centred (i, x+d)) while x + winSize + d <= W-1, else the
+ *                    `invalid` sentinel 255.0 (the mirror of j-winSize-d >= 0, NCC.h:81-89);
+ *   dispR[i][x]    = WinTakeAll(costR[i][x][:]) (NCC.h:53-67: float-narrowed running maximum, the last hypothesis that
+ *                    beats it wins, a NaN never wins, a NaN at d = 0 gives 0); border pixels: map 0, cost 0.0.
+ * Equivalently dispR = fliplr(NCC_algorithem(fliplr(R), fliplr(L))).  dispL and costL are exactly what smt_ncc writes under
+ * the impl in force (smt_ncc_set_impl); costL and costR are optional float64 [H][W][D].  Accepts and rejects what smt_ncc
+ * does (both maps are required).  Scratch comes from the arena; asynchronous on `stream`.
+ * Forms (smt_lrncc_set_impl: 0 = the dispatch rule, 1 = COMPOSED, 2 = KEYS wherever it exists; smt_lrncc_last_form reports
+ * what the last successful call with a non-empty interior ran):
+ *   KEYS      on the integer forms (impl 2 up to 31x31, impl 3 up to 181x181) the cost expression is symmetric in its two
+ *             windows, so costR[i][x][d] == costL[i][x+d][d] bit for bit: the left cost kernel offers every real, non-NaN
+ *             cost to right pixel x-d as a 64-bit rank key, combined per workgroup in LDS and then by one device-wide
+ *             maximum per touched pixel in an [H][W] uint64 scratch map; a finishing launch names the winner (a NaN at
+ *             d = 0 gives 0; a pixel with sentinel hypotheses gets the first of them, W - winSize - x).  costR is a
+ *             diagonal gather of costL (held in scratch when the caller takes none).  8*H*W bytes of scratch more.
+ *   COMPOSED  both images flipped on the device, the single-view path on the swapped pair, map and costs flipped back.
+ *             The loop nest (impl 1, sides beyond the integer forms, no scratch) always takes it: its float64 sums are not
+ *             symmetric.  Also the fallback when the key map cannot be had.
+ * Both forms give identical bits on the integer kernels. */
+#define SMT_LRNCC_FORM_COMPOSED 1
+#define SMT_LRNCC_FORM_KEYS     2
+int smt_lrncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int winSize, int32_t *dispL, int32_t *dispR,
+              double *costL, double *costR, void *stream);
+/* Test hooks (process-wide, plain unsynchronised globals): see smt_lrncc.  SMT_ERR_ARG outside 0..2. */
+int smt_lrncc_set_impl(int impl);
+int smt_lrncc_last_form(void);
+/* Test hook, host only (no GPU): left costs [W - 2 winSize][D] of one row from a hostile palette chosen by seed % 4
+ * (exact ties; doubles that round down and up to one float; NaN at d = 0 and d > 0; a mix) -- for every right pixel the
+ * hypothesis the largest rank key names, with the NaN-at-0 and first-sentinel rules, equals the sequential WinTakeAll
+ * of its row.  SMT_OK or SMT_ERR_STATE; SMT_ERR_ARG for non-positive sizes, winSize < 0, D > SMT_MAX_DISPARITY, W > 65536. */
+int smt_lrncc_selftest_keys(int W, int D, int winSize, unsigned seed);
+
+/* smt_lrncc for `pairs` gray pairs on the handle of smt_ncc_flow_run_batch, then per pair the int-map cross-check of
+ * Sad.h:184-222 (NCC.h has none of its own; its maps are int like SAD's): dispL, dispR int32 [pairs][H][W], lastdisp and
+ * cls exactly smt_sad_crosscheck of the call's own two maps.  Any output may be NULL (maps nobody takes live in arena
+ * scratch; with every output NULL the call does nothing).  The left view is what smt_ncc_flow_run_batch writes under the
+ * same smt_ncc_flow_set_form; one statistics launch serves both views under KEYS.  The handle's tables grow as in
+ * smt_ncc_flow_run_batch: a warm call neither allocates nor synchronises.  Same limits: at most 32767 pairs, calls on one
+ * handle ordered on one stream, pairs == 0 is a no-op, SMT_ERR_ARG for a NULL handle or image or pairs < 0. */
+int smt_lrncc_flow_run_batch(smt_ncc_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int32_t *dispL,
+                             int32_t *dispR, int32_t *lastdisp, uint8_t *cls);
+
 /* getGausssianMask (ASW.h:16-35) and getColorMask (:41-47), computed on the HOST in
  * float64 exactly as the reference does.  space: (2*winSize+3)^2 doubles, color: 256. */
 int smt_asw_masks(int winSize, double sigma_space, double sigma_color, double *space_host,

@@ -23,6 +23,7 @@ QUIRK_FIX_CENSUS_RIGHT_EDGE = 0x8
 QUIRK_FIX_ALL = 0xF
 SAD_FORM_COMPOSED, SAD_FORM_BOX_KEYS, SAD_FORM_BOX_VOLUME = 1, 2, 3
 NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX = 1, 2, 3
+LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS = 1, 2
 
 
 class SmtError(RuntimeError):
@@ -108,6 +109,12 @@ def _declare_ncc_flow(l):
     l.smt_ncc_flow_set_stream.argtypes = [vp, vp]
     l.smt_ncc_flow_set_form.argtypes = [vp, i]
     l.smt_ncc_flow_run_batch.argtypes = [vp, vp, vp, i, vp, vp]
+    if hasattr(l, "smt_lrncc"):                                # both views (csrc/ncc_both.hip)
+        l.smt_lrncc.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp]
+        l.smt_lrncc_set_impl.argtypes = [i]
+        l.smt_lrncc_last_form.argtypes = []
+        l.smt_lrncc_selftest_keys.argtypes = [i, i, i, C.c_uint]
+        l.smt_lrncc_flow_run_batch.argtypes = [vp, vp, vp, i, vp, vp, vp, vp]
 
 
 def lib():

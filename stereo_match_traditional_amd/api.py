@@ -13,6 +13,7 @@ from ._lib import check, lib, VIEW_LEFT, VIEW_RIGHT, VIEW_BOTH, SMT_FILL_UB_LIST
 from ._lib import (QUIRK_FIX_RIGHT_ARM_STRIDE, QUIRK_FIX_STICKY_TAU, QUIRK_FIX_SCAN_VERTICAL,  # noqa: F401
                    QUIRK_FIX_CENSUS_RIGHT_EDGE, QUIRK_FIX_ALL)
 from ._lib import NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX  # noqa: F401
+from ._lib import LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
@@ -21,7 +22,8 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "to_float", "MedianFilter", "RemoveSpeckles", "MedianFilterBatch", "RemoveSpecklesBatch", "imread", "imwrite", "ADCensusOption", "adcensus_option_aggregate", "Pipeline", "scratch_trim", "scratch_info", "scratch_poison",
            "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow",
            "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow",
-           "CrossAggFlow", "ncc_box_set_band", "ncc_last_form", "NCCFlow", "NCC_FORM_LOOP", "NCC_FORM_DOT4", "NCC_FORM_BOX"]
+           "CrossAggFlow", "ncc_box_set_band", "ncc_last_form", "NCCFlow", "NCC_FORM_LOOP", "NCC_FORM_DOT4", "NCC_FORM_BOX",
+           "NCC_both", "lrncc_set_impl", "lrncc_last_form", "LRNCC_FORM_COMPOSED", "LRNCC_FORM_KEYS"]
 
 
 def current_stream_ptr(device=None):
@@ -800,6 +802,34 @@ def NCC_algorithem(leftImage, rigthImage, winSize, dispRange, want_cost=False):
     check(lib().smt_ncc(_ptr(leftImage), _ptr(rigthImage), H, W, dispRange, winSize, _ptr(disp), _ptr(cost),
                         current_stream_ptr()), "smt_ncc")
     return (disp, cost) if want_cost else disp
+
+
+@_on_tensor_device
+def NCC_both(leftImage, rigthImage, winSize, dispRange, want_cost=False):
+    """smt_lrncc: NCC.h:69-95 and its mirror from one pass over the costs.  uint8 [H][W] unpadded images -> (dispL, dispR)
+    int32, or (dispL, dispR, costL, costR) with float64 [H][W][dispRange] costs.  dispR equals
+    fliplr(NCC_algorithem(fliplr(R), fliplr(L)))."""
+    H, W = leftImage.shape
+    _dev(leftImage, torch.uint8, (H, W), "leftImage")
+    _dev(rigthImage, torch.uint8, (H, W), "rigthImage")
+    dl = torch.empty((H, W), dtype=torch.int32, device=leftImage.device)
+    dr = torch.empty_like(dl)
+    cl = torch.full((H, W, dispRange), float("nan"), dtype=torch.float64, device=leftImage.device) if want_cost else None
+    cr = torch.full_like(cl, float("nan")) if want_cost else None
+    check(lib().smt_lrncc(_ptr(leftImage), _ptr(rigthImage), H, W, dispRange, winSize, _ptr(dl), _ptr(dr), _ptr(cl), _ptr(cr),
+                          current_stream_ptr()), "smt_lrncc")
+    return (dl, dr, cl, cr) if want_cost else (dl, dr)
+
+
+def lrncc_set_impl(impl):
+    """Which form smt_lrncc and NCCFlow.run_both take: 0 = the dispatch rule (default), 1 = LRNCC_FORM_COMPOSED (mirrored
+    single-view calls), 2 = LRNCC_FORM_KEYS wherever it exists (test hook)."""
+    check(lib().smt_lrncc_set_impl(int(impl)), "smt_lrncc_set_impl")
+
+
+def lrncc_last_form():
+    """Which form the last both-view NCC call ran: LRNCC_FORM_COMPOSED or LRNCC_FORM_KEYS (0: none yet)."""
+    return int(lib().smt_lrncc_last_form())
 
 
 def sad_set_impl(impl):
@@ -1582,6 +1612,28 @@ class NCCFlow:
         check(lib().smt_ncc_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_ncc_flow_set_stream")
         check(lib().smt_ncc_flow_run_batch(self._h, _ptr(L8), _ptr(R8), P, _ptr(disp), _ptr(cost)), "smt_ncc_flow_run_batch")
         return (disp, cost) if want_cost else disp
+
+    def run_both(self, L8, R8, want=("dispL", "dispR", "lastdisp", "cls")):
+        """smt_lrncc_flow_run_batch: uint8 [pairs][row][col] (or [row][col]) -> (dispL, dispR, lastdisp, cls), int32, int32,
+        int32 and uint8 [pairs][row][col]; an output not named in `want` is not computed for the caller and comes back as
+        None.  lastdisp and cls are sad_CrossCheckDiaparity of the two maps.  On torch's current stream of the handle's
+        device; nothing synchronises."""
+        if L8.dim() == 2:
+            L8, R8 = L8[None], R8[None]
+        P = L8.shape[0]
+        if _dev_index(L8.device) != _dev_index(self.device) or R8.device != L8.device:
+            raise ValueError(f"NCC handle lives on {self.device}, images on {L8.device} / {R8.device}")
+        _dev(L8, torch.uint8, (P, self.row, self.col), "L8")
+        _dev(R8, torch.uint8, (P, self.row, self.col), "R8")
+        unknown = set(want) - {"dispL", "dispR", "lastdisp", "cls"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        shape = (P, self.row, self.col)
+        outs = [torch.empty(shape, dtype=torch.uint8 if n == "cls" else torch.int32, device=L8.device) if n in want else None
+                for n in ("dispL", "dispR", "lastdisp", "cls")]
+        check(lib().smt_ncc_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_ncc_flow_set_stream")
+        check(lib().smt_lrncc_flow_run_batch(self._h, _ptr(L8), _ptr(R8), P, *[_ptr(o) for o in outs]), "smt_lrncc_flow_run_batch")
+        return tuple(outs)
 
     def close(self):
         if getattr(self, "_h", None) is not None:

@@ -37,12 +37,18 @@ __host__ __device__ inline int nbox_rwe(int side, int KT) { return (64 * KT + NB
 // i0 brings in image row i0 + t, takes out image row i0 + t - side (once there is one) and, from t = side - 1 on, emits
 // window row i0 + t - side + 1, i.e. image row i0 + t - side + 1 + win.  The two rows of step t + 1 are fetched into
 // registers before step t computes and written to the other half of the LDS row buffer after it; one barrier per step.
-template <int KT>
+//
+// PUB (the both-view call, csrc/ncc_both.hip): every real, non-NaN cost of (x, d) is also offered to right pixel x - d as
+// a rank key (csrc/ncc_keys.h).  The workgroup's 64 columns times 64 KT hypotheses reach 64 KT + 64 right pixels of a
+// row; the offers of one step are combined by 64-bit LDS maxima in one of two key rows, and the step after it sends one
+// agent-scope maximum per touched pixel to rkeys ([pairs][H][W], zero before the launch) and clears the row -- behind
+// the step's own barrier, so no barrier is added.
+template <int KT, bool PUB>
 __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R, int H, int W,
                                                  int D, int win, int band, const int *__restrict__ sumL,
                                                  const double *__restrict__ rootL, const int *__restrict__ sumR,
                                                  const double *__restrict__ rootR, int32_t *__restrict__ disp,
-                                                 double *__restrict__ cost_out)
+                                                 double *__restrict__ cost_out, unsigned long long *__restrict__ rkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned s_nbox[];
     const int side = 2 * win + 1, Hi = H - 2 * win, Wi = W - 2 * win;
@@ -50,6 +56,7 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
         const size_t po = (size_t)blockIdx.z * H * W;
         L += po; R += po; sumL += po; rootL += po; sumR += po; rootR += po; disp += po;
         if (cost_out) cost_out += po * D;
+        if constexpr (PUB) rkeys += po;
     }
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -92,6 +99,20 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
                         __builtin_amdgcn_alignbyte(shi[q], slo[q], 3)};
         }
     };
+    // PUB: [2][NKE] keys behind the staged rows; entry e of a row is right window column x0 - 64 KT + e
+    constexpr int NKE = 64 * KT + NBSW;
+    unsigned long long *s_keys = reinterpret_cast<unsigned long long *>(s_nbox + 4 * ROWE);
+    auto flush = [&](int half, int io) {                       // the keys of window row io go out, the row is cleared
+        for (int e = threadIdx.x; e < NKE; e += NBT) {
+            const unsigned long long v = s_keys[half * NKE + e];
+            if (v) {
+                atomicMax(rkeys + (size_t)(io + win) * W + win + (x0 - 64 * KT + e), v);
+                s_keys[half * NKE + e] = 0ull;
+            }
+        }
+    };
+    if constexpr (PUB)
+        for (int e = threadIdx.x; e < 2 * NKE; e += NBT) s_keys[e] = 0ull;
     fetch(0);
     commit(0);
     __syncthreads();
@@ -156,6 +177,8 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
         const int io = i0 + t - side + 1;                      // window row of this step (>= i0: there is one)
         const bool leaving = t >= side;
         if (t + 1 < nsteps) fetch(t + 1);
+        if constexpr (PUB)
+            if (io > i0) flush(half ^ 1, io - 1);              // what step t - 1 emitted
         if (live) {
             const unsigned *rows = s_rows + (size_t)half * 2 * ROWE;
             row_pass(rows, rows + LWE, std::false_type());
@@ -179,6 +202,9 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
                             c[k] = ncc_int_cost(n, C[j][k], sa, rta, sumR[q], rootR[q]);
                         } else c[k] = 255.0;                   // `invalid` 0xff, NCC.h:88
                         if (cost_out && act) cost_out[p * D + d] = c[k];
+                        if constexpr (PUB)
+                            if (act && x - d >= 0 && c[k] == c[k])
+                                atomicMax(s_keys + half * NKE + (x - d - (x0 - 64 * KT)), ncc_rank_key(c[k], d));
                         if (k == 0) poison = __ballot(c[0] != c[0] && lane == 0) != 0;   // d = 0 is slot 0 of lane 0
                         v[k] = ncc_wta_term(c[k], act);
                     }
@@ -204,6 +230,7 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
         if (t + 1 < nsteps) commit(half ^ 1);
         __syncthreads();
     }
+    if constexpr (PUB) flush((nsteps - 1) & 1, i1 - 1);        // the last step's row (i1 > i0: it emitted)
 }
 
 int g_ncc_box_band = 0;        // test hook: window rows per band, 0 = box_band's choice
@@ -215,13 +242,19 @@ int nbox_band(int Hi, int Wi, int side)
 
 template <int KT>
 int launch_nbox(hipStream_t st, const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int win, const int *sumL,
-                const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost)
+                const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost,
+                unsigned long long *rkeys)
 {
     const int side = 2 * win + 1, Hi = H - 2 * win, Wi = W - 2 * win, band = nbox_band(Hi, Wi, side);
     const size_t shm = (size_t)4 * (nbox_lwe(side) + nbox_rwe(side, KT)) * 4;   // <= 16 KiB; two staging items per thread suffice
     static_assert(2 * (((NBSW + NCC_INT_MAX_SIDE + 3) & ~3) + ((64 * KT + NBSW + NCC_INT_MAX_SIDE + 3) & ~3)) / 4 <= 2 * NBT, "staging items");
     const dim3 grid((Wi + NBSW - 1) / NBSW, (Hi + band - 1) / band, pairs);
-    hipLaunchKernelGGL(k_ncc_box<KT>, grid, dim3(NBT), shm, st, L, R, H, W, D, win, band, sumL, rootL, sumR, rootR, disp, cost);
+    if (rkeys)                                                 // + the two key rows, at most 9 KiB
+        hipLaunchKernelGGL((k_ncc_box<KT, true>), grid, dim3(NBT), shm + (size_t)2 * (64 * KT + NBSW) * 8, st, L, R, H, W, D, win, band,
+                           sumL, rootL, sumR, rootR, disp, cost, rkeys);
+    else
+        hipLaunchKernelGGL((k_ncc_box<KT, false>), grid, dim3(NBT), shm, st, L, R, H, W, D, win, band, sumL, rootL, sumR, rootR, disp,
+                           cost, rkeys);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -246,18 +279,28 @@ int ncc_flow_rule(long long side, int D)
 
 }  // namespace
 
-// side <= 181, interior not empty, tables from ncc_stats_launch (declared in csrc/smt_common.h)
+// side <= 181, interior not empty, tables from ncc_stats_launch (declared in csrc/smt_common.h); rkeys: NULL, or the
+// zeroed [pairs][H][W] key map of the both-view call
 int smt_ncc_box_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int winSize, const int *sumL,
-                        const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st)
+                        const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st,
+                        unsigned long long *rkeys)
 {
     const int K = (D + 63) / 64;
     int rc;
-    if (K <= 1) rc = launch_nbox<1>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost);
-    else if (K <= 2) rc = launch_nbox<2>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost);
-    else if (K <= 4) rc = launch_nbox<4>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost);
-    else rc = launch_nbox<8>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost);
+    if (K <= 1) rc = launch_nbox<1>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
+    else if (K <= 2) rc = launch_nbox<2>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
+    else if (K <= 4) rc = launch_nbox<4>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
+    else rc = launch_nbox<8>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
     if (rc == SMT_OK) g_smt_ncc_last_form = SMT_NCC_FORM_BOX;
     return rc;
+}
+
+// the statistics pass and the flow's dispatch rule for csrc/ncc_both.hip (this translation unit's copy of k_ncc_stats)
+bool smt_ncc_stats_ready(int winSize) { return ncc_stats_ready(winSize); }
+int smt_ncc_stats_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int winSize, int *sumL, double *rootL,
+                          int *sumR, double *rootR, hipStream_t st)
+{
+    return ncc_stats_launch(st, L, R, pairs, H, W, winSize, sumL, rootL, sumR, rootR);
 }
 
 SMT_API int smt_ncc_box_set_band(int band)
@@ -398,6 +441,21 @@ struct smt_ncc_flow {
     double *roots;              // [2][cap][H][W]
 };
 
+// cold: the tables grow to `pairs` (the old ones may still be read, so the stream is waited for)
+static int ncc_flow_grow(smt_ncc_flow *h, int pairs)
+{
+    if (pairs <= h->cap) return SMT_OK;
+    const size_t N = (size_t)h->H * h->W;
+    SMT_HIP(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->sums); (void)hipFree(h->roots);
+    h->sums = nullptr; h->roots = nullptr; h->cap = 0;
+    int rc = smt_malloc((void **)&h->sums, (size_t)2 * pairs * N * 4);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->roots, (size_t)2 * pairs * N * 8);
+    if (rc != SMT_OK) { (void)hipFree(h->sums); h->sums = nullptr; return rc; }
+    h->cap = pairs;
+    return SMT_OK;
+}
+
 SMT_API void smt_ncc_default_params(smt_ncc_params *p)
 {
     if (!p) return;
@@ -465,19 +523,57 @@ SMT_API int smt_ncc_flow_run_batch(smt_ncc_flow *h, const uint8_t *grayL, const 
     if (form != SMT_NCC_FORM_LOOP || Hi <= 0 || Wi <= 0) SMT_HIP(hipMemsetAsync(disp, 0, (size_t)pairs * N * 4, st));
     if (Hi <= 0 || Wi <= 0) return SMT_OK;
     if (form == SMT_NCC_FORM_LOOP) return smt_ncc_loop_enqueue(grayL, grayR, pairs, H, W, D, win, disp, cost, st);
-    if (pairs > h->cap) {                                      // cold: the tables grow (the old ones may still be read)
-        SMT_HIP(hipStreamSynchronize(st));
-        (void)hipFree(h->sums); (void)hipFree(h->roots);
-        h->sums = nullptr; h->roots = nullptr; h->cap = 0;
-        int rc = smt_malloc((void **)&h->sums, (size_t)2 * pairs * N * 4);
-        if (rc == SMT_OK) rc = smt_malloc((void **)&h->roots, (size_t)2 * pairs * N * 8);
-        if (rc != SMT_OK) { (void)hipFree(h->sums); h->sums = nullptr; return rc; }
-        h->cap = pairs;
-    }
+    int rc = ncc_flow_grow(h, pairs);
+    if (rc != SMT_OK) return rc;
     int *sumL = h->sums, *sumR = h->sums + (size_t)h->cap * N;
     double *rootL = h->roots, *rootR = h->roots + (size_t)h->cap * N;
-    int rc = ncc_stats_launch(st, grayL, grayR, pairs, H, W, win, sumL, rootL, sumR, rootR);
+    rc = ncc_stats_launch(st, grayL, grayR, pairs, H, W, win, sumL, rootL, sumR, rootR);
     if (rc != SMT_OK) return rc;
     return form == SMT_NCC_FORM_DOT4 ? smt_ncc_dot4_enqueue(grayL, grayR, pairs, H, W, D, win, sumL, rootL, sumR, rootR, disp, cost, st)
                                      : smt_ncc_box_enqueue(grayL, grayR, pairs, H, W, D, win, sumL, rootL, sumR, rootR, disp, cost, st);
+}
+
+// Both views and the int-map cross-check for a batch, on the handle of smt_ncc_flow_run_batch: the form is chosen as
+// there, the tables grow as there, and smt_lrncc_enqueue (csrc/ncc_both.hip) does the rest for the whole batch.  Maps
+// the caller does not take live in arena scratch for the call.
+SMT_API int smt_lrncc_flow_run_batch(smt_ncc_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int32_t *dispL,
+                                     int32_t *dispR, int32_t *lastdisp, uint8_t *cls)
+{
+    if (!h || pairs < 0 || pairs > 32767) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!grayL || !grayR) return SMT_ERR_ARG;
+    if (!dispL && !dispR && !lastdisp && !cls) return SMT_OK;
+    smt_dev_guard dev_guard(h->device);
+    const int H = h->H, W = h->W, D = h->D, win = h->P.winSize;
+    const size_t N = (size_t)H * W;
+    hipStream_t st = h->stream;
+    const long long Hi = (long long)H - 2LL * win, Wi = (long long)W - 2LL * win;
+    int form = h->form ? h->form : ncc_flow_rule(2LL * win + 1, D);
+    if (form != SMT_NCC_FORM_LOOP && Hi > 0 && Wi > 0 && !ncc_stats_ready(win)) form = SMT_NCC_FORM_LOOP;
+    int *sumL = nullptr, *sumR = nullptr;
+    double *rootL = nullptr, *rootR = nullptr;
+    if (form != SMT_NCC_FORM_LOOP && Hi > 0 && Wi > 0) {
+        const int rc = ncc_flow_grow(h, pairs);
+        if (rc != SMT_OK) return rc;
+        sumL = h->sums; sumR = h->sums + (size_t)h->cap * N;
+        rootL = h->roots; rootR = h->roots + (size_t)h->cap * N;
+    }
+    int32_t *dl = dispL, *dr = dispR, *last1 = nullptr;
+    uint8_t *cls1 = nullptr;
+    int rc = SMT_OK;
+    if (!dl && smt_scratch_alloc((void **)&dl, (size_t)pairs * N * 4, st) != hipSuccess) { dl = nullptr; rc = SMT_ERR_ALLOC; }
+    if (rc == SMT_OK && !dr && smt_scratch_alloc((void **)&dr, (size_t)pairs * N * 4, st) != hipSuccess) { dr = nullptr; rc = SMT_ERR_ALLOC; }
+    if (rc == SMT_OK && cls && !lastdisp && smt_scratch_alloc((void **)&last1, N * 4, st) != hipSuccess) { last1 = nullptr; rc = SMT_ERR_ALLOC; }
+    if (rc == SMT_OK && lastdisp && !cls && smt_scratch_alloc((void **)&cls1, N, st) != hipSuccess) { cls1 = nullptr; rc = SMT_ERR_ALLOC; }
+    if (rc == SMT_OK)
+        rc = smt_lrncc_enqueue(form, grayL, grayR, pairs, H, W, D, win, sumL, rootL, sumR, rootR, dl, dr, nullptr, nullptr, st);
+    if (rc == SMT_OK && (lastdisp || cls))
+        for (int b = 0; b < pairs && rc == SMT_OK; b++)                       // Sad.h:184-222 on the call's own maps
+            rc = smt_sad_crosscheck(dl + b * N, dr + b * N, H, W, lastdisp ? lastdisp + b * N : last1, cls ? cls + b * N : cls1,
+                                    (void *)st);
+    if (cls1) smt_scratch_free(cls1, st);
+    if (last1) smt_scratch_free(last1, st);
+    if (!dispR && dr) smt_scratch_free(dr, st);
+    if (!dispL && dl) smt_scratch_free(dl, st);
+    return rc;
 }

@@ -4,6 +4,7 @@
 // bit for bit wherever both exist.
 #pragma once
 #include "smt_common.h"
+#include "ncc_keys.h"
 
 namespace {
 

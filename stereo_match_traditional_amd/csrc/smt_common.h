@@ -70,10 +70,25 @@ int smt_cblsm_v4_box_enqueue(const uint32_t *S, int *const armL[4], int *const a
 extern int g_smt_ncc_last_form;
 int smt_ncc_loop_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int winSize, int32_t *disp,
                          double *cost, hipStream_t st);
+// rkeys (dot4 and box): NULL, or a zeroed [pairs][H][W] map into which the launch also publishes, under an agent-scope
+// maximum, the rank key (csrc/ncc_keys.h) of every real, non-NaN cost of (x, d) at right pixel x - d.
 int smt_ncc_dot4_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int winSize, const int *sumL,
-                         const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st);
+                         const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st,
+                         unsigned long long *rkeys = nullptr);
 int smt_ncc_box_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int winSize, const int *sumL,
-                        const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st);
+                        const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st,
+                        unsigned long long *rkeys = nullptr);
+// The statistics pass of csrc/ncc_common.h as csrc/ncc_box.hip holds it, and the impl smt_ncc would run now (1, 2, 3).
+bool smt_ncc_stats_ready(int winSize);
+int smt_ncc_stats_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int winSize, int *sumL, double *rootL,
+                          int *sumR, double *rootR, hipStream_t st);
+int smt_ncc_current_impl(void);
+// Both NCC views of `pairs` dense pairs (csrc/ncc_both.hip), arguments already checked: `form` is the SMT_NCC_FORM_* of the
+// left view; the four tables hold room for the batch unless the form is the loop nest (they are filled here); dispL and
+// dispR are required, costL and costR optional.  Records SMT_LRNCC_FORM_* for smt_lrncc_last_form.
+int smt_lrncc_enqueue(int form, const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int winSize, int *sumL,
+                      double *rootL, int *sumR, double *rootR, int32_t *dispL, int32_t *dispR, double *costL, double *costR,
+                      hipStream_t st);
 
 // The SMT_QUIRK_* flags of a cross-arm handle after create (csrc/crossarm.hip), for smt_pipeline_set_quirks: they take
 // effect from the next arms call.  SMT_ERR_ARG for an unknown bit.

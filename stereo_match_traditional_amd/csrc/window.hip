@@ -334,12 +334,17 @@ __device__ __forceinline__ int ncc_copy_off(int s, int CS)
 
 // ncc_int_cost, ncc_wta_term, wave_prefix_max_f32, ncc_wta_last: csrc/ncc_common.h
 
-template <int K, int G>
+// PUB (the both-view call, csrc/ncc_both.hip): every real, non-NaN cost of (j, d) is also offered to right pixel j - d as
+// a rank key (csrc/ncc_keys.h).  The workgroup's 16 pixels times 64 K hypotheses reach 64 K + 15 right pixels of the row:
+// the offers are combined by 64-bit LDS maxima in a key row behind the left windows, and after a barrier one agent-scope
+// maximum per touched pixel goes to rkeys ([pairs][H][W], zero before the launch).
+template <int K, int G, bool PUB>
 __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R, int H, int W,
                                                    int D, int win, const int *__restrict__ sumL,
                                                    const double *__restrict__ rootL, const int *__restrict__ sumR,
                                                    const double *__restrict__ rootR, int RW, int CS,
-                                                   int32_t *__restrict__ disp, double *__restrict__ cost_out)
+                                                   int32_t *__restrict__ disp, double *__restrict__ cost_out,
+                                                   unsigned long long *__restrict__ rkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int side = 2 * win + 1;
@@ -347,6 +352,7 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
         const size_t po = (size_t)blockIdx.z * H * W;
         L += po; R += po; sumL += po; rootL += po; sumR += po; rootR += po; disp += po;
         if (cost_out) cost_out += po * D;
+        if constexpr (PUB) rkeys += po;
     }
     // LDS: the right image's rows under the workgroup as 4 byte-shifted dword copies (copy s, dword w = bytes
     // xlo + 4w + s .. + 3: any unaligned dword of a row is an aligned dword of one copy), the raw rows they are
@@ -358,6 +364,11 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = win + blockIdx.y, j0 = win + blockIdx.x * NCP;
     const int xlo = ((j0 - win - (64 * K - 1)) >> 2) << 2;               // first staged column (multiple of 4, may be < 0)
+    // PUB: [NKE] keys, 8-byte aligned behind s_A; entry e is image column j0 - 64 K + e
+    constexpr int NKE = 64 * K + NCP;
+    unsigned long long *s_keys = (unsigned long long *)(smem + (((size_t)(4 * CS + side * (RW + 1) + NCP * side * G) * 4 + 7) & ~(size_t)7));
+    if constexpr (PUB)
+        for (int e = threadIdx.x; e < NKE; e += NCP * 64) s_keys[e] = 0ull;   // ordered before the offers by the barriers below
     for (int e = threadIdx.x; e < side * (RW + 1); e += NCP * 64) {
         const int r = e / (RW + 1), w = e - r * (RW + 1);
         const uint8_t *row = R + (size_t)(i - win + r) * W;
@@ -404,7 +415,8 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
         }
     }
     __syncthreads();
-    if (!live) return;
+    do {                                                  // once; a wave past the last pixel leaves (and, PUB, waits below)
+    if (!live) break;
     const int p = i * W + j;
     // Hypotheses of a lane: d = 4K * (lane / 4) + 4k + lane % 4, k = 0..K-1.  Slot k at tap group g then needs the
     // dword 4k bytes before slot 0's, i.e. the dword slot 0 needs at group g - k: one LDS read per row position
@@ -451,6 +463,8 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
         } else c[k] = 255.0;                              // `invalid` 0xff, NCC.h:88
         if (cost_out && act) cost_out[(size_t)p * D + d] = c[k];
         const bool isn = c[k] != c[k];
+        if constexpr (PUB)
+            if (act && j - win - d >= 0 && !isn) atomicMax(s_keys + (j - d - (j0 - 64 * K)), ncc_rank_key(c[k], d));
         if (k == 0) poison = __ballot(isn && d == 0) != 0;   // d = 0 sits in slot 0 of one of the first four lanes
         v[k] = ncc_wta_term(c[k], act);
     }
@@ -482,6 +496,14 @@ __global__ void __launch_bounds__(NCP * 64) k_ncc2(const uint8_t *__restrict__ L
     }
     const int out = ncc_wta_last(key, poison);
     if (lane == 0) disp[p] = out;
+    } while (0);
+    if constexpr (PUB) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < NKE; e += NCP * 64) {
+            const unsigned long long v = s_keys[e];
+            if (v) atomicMax(rkeys + (size_t)i * W + (j0 - 64 * K + e), v);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------- ASW
@@ -1242,12 +1264,17 @@ SMT_API int smt_ncc_last_form(void) { return g_smt_ncc_last_form; }
 template <int K>
 static int launch_ncc2(int G, dim3 grid, size_t shm, hipStream_t st, const uint8_t *L, const uint8_t *R, int H, int W, int D,
                        int win, const int *sumL, const double *rootL, const int *sumR, const double *rootR, int RW, int CS,
-                       int32_t *disp, double *cost)
+                       int32_t *disp, double *cost, unsigned long long *rkeys)
 {
 #define SMT_NCC2(GG)                                                                                          \
     case GG:                                                                                                  \
-        SMT_HIP(hipFuncSetAttribute((const void *)k_ncc2<K, GG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
-        hipLaunchKernelGGL((k_ncc2<K, GG>), grid, dim3(NCP * 64), shm, st, L, R, H, W, D, win, sumL, rootL, sumR, rootR, RW, CS, disp, cost); \
+        if (rkeys) {                                                                                          \
+            SMT_HIP(hipFuncSetAttribute((const void *)k_ncc2<K, GG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+            hipLaunchKernelGGL((k_ncc2<K, GG, true>), grid, dim3(NCP * 64), shm, st, L, R, H, W, D, win, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); \
+        } else {                                                                                              \
+            SMT_HIP(hipFuncSetAttribute((const void *)k_ncc2<K, GG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+            hipLaunchKernelGGL((k_ncc2<K, GG, false>), grid, dim3(NCP * 64), shm, st, L, R, H, W, D, win, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); \
+        }                                                                                                     \
         break
     switch (G) {
         SMT_NCC2(1); SMT_NCC2(2); SMT_NCC2(3); SMT_NCC2(4); SMT_NCC2(5); SMT_NCC2(6); SMT_NCC2(7); SMT_NCC2(8);
@@ -1260,23 +1287,25 @@ static int launch_ncc2(int G, dim3 grid, size_t shm, hipStream_t st, const uint8
 // k_ncc2 over the interiors of `pairs` dense pairs (one launch, the pair on grid.z); side <= 31, interior not empty,
 // the tables from ncc_stats_launch.  The border of disp / cost is the caller's.
 int smt_ncc_dot4_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int winSize, const int *sumL,
-                         const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st)
+                         const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st,
+                         unsigned long long *rkeys)
 {
     const int side = 2 * winSize + 1, Hi = H - 2 * winSize, Wi = W - 2 * winSize;
     const int K = (D + 63) / 64, G = (side + 3) / 4;
     const int RW = 16 * K + G + 5, CS = (side * RW + 31) / 32 * 32 + 32;   // + 32: room for the copies' bank offsets
-    const size_t shm2 = ((size_t)4 * CS + (size_t)side * (RW + 1) + (size_t)NCP * side * G) * 4;
+    const size_t shm2 = ((size_t)4 * CS + (size_t)side * (RW + 1) + (size_t)NCP * side * G) * 4 +
+                        (rkeys ? 8 + (size_t)(64 * K + NCP) * 8 : 0);      // + the key row of the both-view call
     const dim3 grid((Wi + NCP - 1) / NCP, Hi, pairs);
     int rc;
     switch (K) {
-    case 1: rc = launch_ncc2<1>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    case 2: rc = launch_ncc2<2>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    case 3: rc = launch_ncc2<3>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    case 4: rc = launch_ncc2<4>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    case 5: rc = launch_ncc2<5>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    case 6: rc = launch_ncc2<6>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    case 7: rc = launch_ncc2<7>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
-    default: rc = launch_ncc2<8>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost); break;
+    case 1: rc = launch_ncc2<1>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    case 2: rc = launch_ncc2<2>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    case 3: rc = launch_ncc2<3>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    case 4: rc = launch_ncc2<4>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    case 5: rc = launch_ncc2<5>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    case 6: rc = launch_ncc2<6>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    case 7: rc = launch_ncc2<7>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
+    default: rc = launch_ncc2<8>(G, grid, shm2, st, L, R, H, W, D, winSize, sumL, rootL, sumR, rootR, RW, CS, disp, cost, rkeys); break;
     }
     if (rc != SMT_OK) return rc;
     SMT_LAUNCH_CHECK();
@@ -1296,6 +1325,14 @@ int smt_ncc_loop_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, i
     return SMT_OK;
 }
 
+static int ncc_env_impl()
+{
+    static const int env_impl = [] { const char *e = getenv("SMT_NCC_IMPL"); return e ? atoi(e) : 0; }();   // debugging aid: overrides smt_ncc_set_impl
+    return env_impl;
+}
+
+int smt_ncc_current_impl(void) { return ncc_env_impl() ? ncc_env_impl() : g_ncc_impl; }
+
 SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int winSize, int32_t *disp,
                     double *cost, void *stream)
 {
@@ -1306,8 +1343,7 @@ SMT_API int smt_ncc(const uint8_t *L, const uint8_t *R, int H, int W, int D, int
     hipStream_t st = smt_stream(stream);
     const long long side = 2LL * winSize + 1;
     const int Hi = H - 2 * winSize, Wi = W - 2 * winSize;
-    static const int env_impl = [] { const char *e = getenv("SMT_NCC_IMPL"); return e ? atoi(e) : 0; }();   // debugging aid: overrides smt_ncc_set_impl
-    const int impl = env_impl ? env_impl : g_ncc_impl;
+    const int impl = smt_ncc_current_impl();
     // the kernels write the costs of interior pixels only: the border's are 0.0, like the border of the map (an output
     // the caller can read is defined everywhere; `cost` is a checking aid, the extra pass over it is not on a hot path)
     if (cost && winSize > 0) SMT_HIP(hipMemsetAsync(cost, 0, (size_t)N * D * 8, st));

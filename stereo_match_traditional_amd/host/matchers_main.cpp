@@ -67,6 +67,11 @@ int main(int argc, char **argv)
             std::vector<int> d(n, 0);
             smt::NCC_algorithem(L.data(), R.data(), W, H, d.data(), 3, D);
             printf("ncc %016llx\n", (unsigned long long)fnv(d.data(), n * 4));
+            std::vector<unsigned char> cls(n);
+            smt::NCCFlow(H, W, D, 3).runBoth(L.data(), R.data(), 1, nullptr, nullptr, nullptr, cls.data());
+            size_t cnt[3] = {0, 0, 0};
+            for (unsigned char c : cls) cnt[c < 3 ? c : 2]++;
+            printf("ncc_lr_kept/occluded/mismatched %zu/%zu/%zu\n", cnt[0], cnt[1], cnt[2]);   // the LR check of both views
         }
         {   // ASWeight.cpp:43-66
             const int winSize = 3, w = winSize + 1, T = 40;

@@ -501,6 +501,21 @@ public:
         check(smt_ncc_flow_run_batch(h_, L.get(), R.get(), pairs, d.get(), nullptr), "smt_ncc_flow_run_batch");
         d.download(disp);
     }
+    // both views and the int-map cross-check (smt_lrncc_flow_run_batch): dispLeft, dispRight, lastdisp int
+    // [pairs][rows][cols], cls uchar [pairs][rows][cols] (0 kept / 1 occlusion / 2 mismatch); any may be null
+    void runBoth(const unsigned char *leftImages, const unsigned char *rigthImages, int pairs, int *dispLeft, int *dispRight,
+                 int *lastdisp, unsigned char *cls)
+    {
+        const size_t n = n_ * (size_t)pairs;
+        DevBuf<unsigned char> L(n), R(n), c(n);
+        DevBuf<int> dl(n), dr(n), last(n);
+        L.upload(leftImages); R.upload(rigthImages);
+        check(smt_lrncc_flow_run_batch(h_, L.get(), R.get(), pairs, dl.get(), dr.get(), last.get(), c.get()), "smt_lrncc_flow_run_batch");
+        if (dispLeft) dl.download(dispLeft);
+        if (dispRight) dr.download(dispRight);
+        if (lastdisp) last.download(lastdisp);
+        if (cls) c.download(cls);
+    }
 private:
     smt_ncc_flow *h_ = nullptr;
     size_t n_;

@@ -207,3 +207,17 @@ def ncc_batch(L8, R8, D, **params):
     dl = flow.run(L8.contiguous(), R8.contiguous())
     flow.close()
     return dl, dl
+
+
+def ncc_both_batch(L8, R8, D, **params):
+    """`compute` for run_sharded on both NCC views (smt_lrncc_flow_run_batch) for a [count, H, W] uint8 shard on this
+    rank's GPU -> (left maps, right maps), int32.  Keywords as api.NCCFlow."""
+    from .api import NCCFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.int32, device=L8.device)
+        return z, z.clone()
+    flow = NCCFlow(H, W, D, L8.device, **params)
+    dl, dr, _, _ = flow.run_both(L8.contiguous(), R8.contiguous(), want=("dispL", "dispR"))
+    flow.close()
+    return dl, dr
