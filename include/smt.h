@@ -1017,8 +1017,9 @@ int smt_asw_crosscheck(const float *dispL, const float *dispR, int H, int W, uin
 
 /* The active lines of ASW/ASWeight.cpp for a batch of gray pairs (uint8 [pairs][H][W], unpadded), per pair in the file's
  * order: copyMakeBorder of both images by winSize + 1 (:54-55), both views (:60-61, through smt_asw_both),
- * CrossCheckDiaparity (:66) into lastDisp, uint8 [pairs][H][W].  The flow stops at :66 (normalize, filterSpeckles,
- * medianBlur and FillImageNew are OpenCV / scan-order fillers).  The handle owns the two masks (smt_asw_masks, built and
+ * CrossCheckDiaparity (:66) into lastDisp, uint8 [pairs][H][W].  smt_asw_flow_run_batch stops at :66;
+ * smt_asw_flow_run_batch_post (below) goes on through :67-78 (normalize, filterSpeckles, medianBlur, FillImageNew) and
+ * reaches the end of the file.  The handle owns the two masks (smt_asw_masks, built and
  * uploaded once at create), the padded images and one pair of maps: a warm call allocates nothing beyond the scratch
  * arena.  Asynchronous on the handle's stream; pairs == 0 is a no-op; any of the three outputs may be NULL.
  * SMT_ERR_ARG for non-positive sizes, NULL inputs, winSize outside 1..30, D outside 1..SMT_MAX_DISPARITY and
@@ -1209,6 +1210,100 @@ int smt_crossagg_flow_status(smt_crossagg_flow *h);
  * of smt_remove_speckles_batch is examined by exactly one thread of its border-merge kernel.  SMT_OK or SMT_ERR_STATE
  * (SMT_ERR_ARG unless 0 < H*W < 2^28). */
 int smt_speckle_selftest_tiles(int H, int W);
+
+/* =====================================================================================
+ * The tail of ASW/ASWeight.cpp (:67-78) on the device (csrc/asw_tail.hip)
+ * =====================================================================================
+ *   :67-72  normalize(.., 0, 255, NORM_MINMAX) of dispLeft, dispRight, lastDisp and convertTo(CV_8UC1)
+ *   :73     filterSpeckles(lastDisp, 0, 40, 2)
+ *   :74     medianBlur(lastDisp, lastDisp, 5)            -> speckle.png
+ *   :76     FillImageNew(lastDisp) (ASW/ASW.h:434-511)   -> filled.png
+ *   :78     medianBlur(lastDisp, lastDisp, 3)            -> medain.png
+ * Batch conventions, all entry points below, as smt_median_filter_batch: `pairs` maps `stride` ELEMENTS apart (0 =
+ * dense, otherwise >= H*W), asynchronous on `stream`, a fixed number of launches whatever the data and the pair count,
+ * no host synchronisation, no allocation once the scratch arena is warm.  SMT_ERR_ARG, before any device work, for NULL
+ * maps, pairs <= 0, non-positive sizes, strides below H*W and H*W >= 2^28.
+ *
+ * The three OpenCV steps are "parity unpinned", like smt_bgr2gray: OpenCV's source is in neither tree, so the rules
+ * below are this library's DEFINITION of the steps, restated from a reading of OpenCV 3.1 that no test could hold
+ * against OpenCV itself.
+ *
+ * normalize(src, dst, 0, 255, NORM_MINMAX) + convertTo(CV_8UC1)  (3 launches; 8 * pairs bytes of scratch):
+ *   smin, smax over the map; in double  scale = 255.0 * (smax - smin > DBL_EPSILON ? 1.0 / (smax - smin) : 0.0)  (the
+ *   division correctly rounded) and  shift = 0.0 - smin * scale;  per pixel convertTo's  t = (float)v * (float)scale
+ *   rounded to float, then  t + (float)shift  rounded to float (no fused multiply-add);  a uint8 destination takes
+ *   saturate_cast<uchar>(t): round half to even, clamp to 0..255.  A constant map gives all zeros.
+ *   smt_minmax_normalize_u8_batch: uint8 -> uint8, once, as :69 + :72 treat lastDisp.  in == out is allowed.
+ *   smt_minmax_normalize_f32_u8_batch: float -> uint8, as :67-68 + :70-71 treat dispLeft / dispRight: the float result
+ *     above is the normalised float map, the same rounding makes it uint8.  Every input must be finite (with a NaN or
+ *     an infinity the result is unspecified). */
+int smt_minmax_normalize_u8_batch(const uint8_t *in, uint8_t *out, int pairs, size_t stride, int H, int W, void *stream);
+int smt_minmax_normalize_f32_u8_batch(const float *in, uint8_t *out, int pairs, size_t stride, int H, int W, void *stream);
+/* filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on CV_8UC1, in place (parity unpinned): the connected components
+ * of the 4-NEIGHBOUR graph whose edges join neighbours a, b with |a - b| <= maxDiff and neither equal to newVal; every
+ * pixel of a component of AT MOST maxSpeckleSize pixels becomes newVal (its low byte).  The relation is symmetric, so
+ * the order of traversal does not matter: this is smt_remove_speckles_batch's tiled union-find (four launches,
+ * 10 * pairs * H * W bytes of scratch) instantiated for uint8 pixels, 4 neighbours and `<=`.  err_dev as
+ * smt_remove_speckles_batch. */
+int smt_filter_speckles_u8_batch(uint8_t *maps, int pairs, size_t stride, int W, int H, int newVal, int maxSpeckleSize,
+                                 int maxDiff, int *err_dev, void *stream);
+/* medianBlur(src, dst, ksize), uint8, ksize 3 or 5 (else SMT_ERR_ARG) (parity unpinned): the true median of the
+ * ksize x ksize window under BORDER_REPLICATE; any H, W >= 1 (a window wider than the image is all border).  OpenCV
+ * copies when src == dst, so "in place" means out of place: in != out here (SMT_ERR_ARG), smt_asw_tail_batch brings the
+ * copy.  One launch, no scratch: a tile and its halo in LDS, four adjacent outputs per thread, selection by a min/max
+ * network on packed 16-bit lanes (csrc/median_net.h; smt_median_blur_selftest_nets, host only, checks both networks on
+ * every input of zeros and ones: SMT_OK or SMT_ERR_STATE). */
+int smt_median_blur_u8_batch(const uint8_t *in, uint8_t *out, int pairs, size_t stride, int W, int H, int ksize,
+                             void *stream);
+int smt_median_blur_selftest_nets(void);
+/* FillImageNew(disp) (ASW/ASW.h:434-511), uint8, in place, W <= 65535 (:480's 0xffff must end the right walk; wider:
+ * SMT_ERR_ARG), as the reference's code behaves, not as it may have been meant.  A pixel is a hole when it is 0; the
+ * holes are listed in raster order; every read is of the unmodified map.  With T(k) = k (k + 1) / 2, hole i at (r, c):
+ *   1. left walk: probes columns c - T(k), k = 0, 1, ..; the first nonzero value is pushed to a list and the hole is
+ *      done; a probe below column 0 abandons the walk;
+ *   2. right walk: probes columns c + T(k): a column > W pushes 0; a nonzero value is pushed; column == W IS READ -- the
+ *      first pixel of row r + 1 -- and if that byte is 0 the walk ends with NOTHING pushed;
+ *   3. hole i receives list[i], not its own value: after one hole that pushed nothing, every later hole of the map
+ *      receives the value found for a later pushing hole, and the last holes index past the list's end.
+ * Two reads are undefined in the reference and defined here: the byte at (H - 1, W), one past the buffer, reads as 0;
+ * a hole whose index is at or past the list's length keeps 0.
+ * fix: 0, or SMT_ASW_FIX_FILL_ROW_END: column == W counts as outside and pushes 0 like every column past it.  Every
+ * hole then pushes exactly once, nothing shifts and no row reads its neighbour.  Unknown bits: SMT_ERR_ARG.
+ * counts: int32 [pairs][2], may be NULL: the holes that pushed nothing, and the holes left 0 for want of a list entry
+ * (the two are equal by construction: the list is short by one entry per missing push).  (0, 0) means the reference's
+ * own run was defined.
+ * Three launches (per row the search and the row's counts; per map the scan of the row counts; per row the gather);
+ * pairs * (H * W + 16 * H) bytes of scratch or so.
+ * smt_fill_image_new_host: the same rules on HOST memory through csrc/fill_image_rules.h, no GPU. */
+#define SMT_ASW_FIX_FILL_ROW_END 0x1u
+int smt_fill_image_new_batch(uint8_t *maps, int pairs, size_t stride, int H, int W, unsigned fix, int *counts,
+                             void *stream);
+int smt_fill_image_new_host(uint8_t *maps, int pairs, size_t stride, int H, int W, unsigned fix, int *counts);
+/* ASWeight.cpp:73-78's arguments.  fix: SMT_ASW_FIX_* (a field of its own: the bits of SMT_QUIRK_FIX_* belong to other
+ * handles). */
+typedef struct smt_asw_post_params {
+    int speckle_newval, speckle_max_size, speckle_max_diff;     /* 0, 40, 2   :73 */
+    int median_first, median_last;                              /* 5, 3       :74, :78; each 3 or 5 */
+    unsigned fix;                                               /* 0 */
+} smt_asw_post_params;
+void smt_asw_post_default_params(smt_asw_post_params *p);
+/* :69 + :72 and :73-78 in place on `pairs` uint8 DEVICE maps (lastDisp as smt_asw_crosscheck wrote it), each step once
+ * over the batch.  after_median / after_fill: optional uint8 copies, `stride` apart like lastDisp, of the states the
+ * driver writes as speckle.png and filled.png.  fill_counts as smt_fill_image_new_batch's counts, err_dev as
+ * smt_remove_speckles_batch's; post == NULL: the defaults.  pairs == 0 is a no-op.  SMT_ERR_ARG also for W > 65535,
+ * medians other than 3 or 5 and unknown fix bits.  14 launches with both copies. */
+int smt_asw_tail_batch(uint8_t *lastDisp, int pairs, size_t stride, int H, int W, const smt_asw_post_params *post,
+                       uint8_t *after_median, uint8_t *after_fill, int *fill_counts, int *err_dev, void *stream);
+/* smt_asw_flow_run_batch for all pairs, then :67-68 + :70-71 into dispL8 / dispR8 (uint8 [pairs][H][W], each optional
+ * and then needing its float map: dispL8 without dispL is SMT_ERR_ARG), then smt_asw_tail_batch ONCE over the batch on
+ * lastDisp (required, dense).  dispL / dispR stay the un-normalised float maps run_batch writes.  On the handle's
+ * stream, with run_batch's asynchrony contract; pairs == 0 is a no-op.  A speckle kernel that hit its loop cap (never
+ * expected) makes smt_asw_flow_status return SMT_ERR_STATE (synchronising, read-and-clear). */
+int smt_asw_flow_run_batch_post(smt_asw_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
+                                float *dispR, uint8_t *lastDisp, uint8_t *dispL8, uint8_t *dispR8,
+                                const smt_asw_post_params *post, uint8_t *after_median, uint8_t *after_fill,
+                                int *fill_counts);
+int smt_asw_flow_status(smt_asw_flow *h);
 
 #ifdef __cplusplus
 }

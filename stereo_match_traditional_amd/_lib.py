@@ -24,6 +24,7 @@ QUIRK_FIX_ALL = 0xF
 SAD_FORM_COMPOSED, SAD_FORM_BOX_KEYS, SAD_FORM_BOX_VOLUME = 1, 2, 3
 NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX = 1, 2, 3
 LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS = 1, 2
+ASW_FIX_FILL_ROW_END = 0x1   # SMT_ASW_FIX_FILL_ROW_END (smt_fill_image_new_batch, smt_asw_post_params.fix)
 
 
 class SmtError(RuntimeError):
@@ -81,6 +82,12 @@ class CBLSMPostParams(C.Structure):
                 ("speckle_invalid", C.c_int), ("median_wnd", C.c_int)]
 
 
+class ASWPostParams(C.Structure):
+    """smt_asw_post_params: ASWeight.cpp:73-78's filterSpeckles / medianBlur arguments and the SMT_ASW_FIX_* flags."""
+    _fields_ = [("speckle_newval", C.c_int), ("speckle_max_size", C.c_int), ("speckle_max_diff", C.c_int),
+                ("median_first", C.c_int), ("median_last", C.c_int), ("fix", C.c_uint)]
+
+
 class ADCensusOption(C.Structure):
     """struct ADCensusOption (CBLSM/adcensus_types.h:45-75)."""
     _fields_ = [("min_disparity", C.c_int32), ("max_disparity", C.c_int32), ("lambda_ad", C.c_int32),
@@ -117,6 +124,25 @@ def _declare_ncc_flow(l):
         l.smt_lrncc_flow_run_batch.argtypes = [vp, vp, vp, i, vp, vp, vp, vp]
 
 
+def _declare_asw_tail(l):
+    """The signatures of ASWeight.cpp's tail (include/smt.h); an older build loaded through SMT_HIP_LIB is left as it is."""
+    if not hasattr(l, "smt_asw_tail_batch"):
+        return
+    vp, i, z = C.c_void_p, C.c_int, C.c_size_t
+    l.smt_minmax_normalize_u8_batch.argtypes = [vp, vp, i, z, i, i, vp]
+    l.smt_minmax_normalize_f32_u8_batch.argtypes = [vp, vp, i, z, i, i, vp]
+    l.smt_filter_speckles_u8_batch.argtypes = [vp, i, z, i, i, i, i, i, vp, vp]
+    l.smt_median_blur_u8_batch.argtypes = [vp, vp, i, z, i, i, i, vp]
+    l.smt_median_blur_selftest_nets.argtypes = []
+    l.smt_fill_image_new_batch.argtypes = [vp, i, z, i, i, C.c_uint, vp, vp]
+    l.smt_fill_image_new_host.argtypes = [vp, i, z, i, i, C.c_uint, vp]
+    l.smt_asw_post_default_params.argtypes = [C.POINTER(ASWPostParams)]
+    l.smt_asw_post_default_params.restype = None
+    l.smt_asw_tail_batch.argtypes = [vp, i, z, i, i, C.POINTER(ASWPostParams), vp, vp, vp, vp, vp]
+    l.smt_asw_flow_run_batch_post.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, C.POINTER(ASWPostParams), vp, vp, vp]
+    l.smt_asw_flow_status.argtypes = [vp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -127,6 +153,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.smt_strerror.restype = C.c_char_p
         _declare_ncc_flow(_lib)
+        _declare_asw_tail(_lib)
     return _lib
 
 

@@ -14,6 +14,7 @@ from ._lib import (QUIRK_FIX_RIGHT_ARM_STRIDE, QUIRK_FIX_STICKY_TAU, QUIRK_FIX_S
                    QUIRK_FIX_CENSUS_RIGHT_EDGE, QUIRK_FIX_ALL)
 from ._lib import NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX  # noqa: F401
 from ._lib import LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS  # noqa: F401
+from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
@@ -23,7 +24,8 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "ADCensusHostBatch", "CBLSMFlow", "AdaptiveSupportWeightBoth", "asw_both_set_impl", "ASWFlow",
            "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow",
            "CrossAggFlow", "ncc_box_set_band", "ncc_last_form", "NCCFlow", "NCC_FORM_LOOP", "NCC_FORM_DOT4", "NCC_FORM_BOX",
-           "NCC_both", "lrncc_set_impl", "lrncc_last_form", "LRNCC_FORM_COMPOSED", "LRNCC_FORM_KEYS"]
+           "NCC_both", "lrncc_set_impl", "lrncc_last_form", "LRNCC_FORM_COMPOSED", "LRNCC_FORM_KEYS",
+           "ASW_FIX_FILL_ROW_END", "MinMaxNormalizeU8", "FilterSpecklesU8", "MedianBlurU8", "FillImageNew", "ASWTail"]
 
 
 def current_stream_ptr(device=None):
@@ -1066,6 +1068,104 @@ def median_inplace_set_impl(impl):
     check(lib().smt_median_inplace_set_impl(int(impl)), "smt_median_inplace_set_impl")
 
 
+def _u8_batch(maps, name, dtype=torch.uint8):
+    """[P][H][W] (or [H][W]) maps on the GPU, each map dense, consecutive maps stride(0) >= H*W elements apart."""
+    m3 = maps[None] if isinstance(maps, torch.Tensor) and maps.dim() == 2 else maps
+    if not isinstance(m3, torch.Tensor) or not m3.is_cuda or m3.dtype != dtype or m3.dim() != 3:
+        raise TypeError(f"{name} must be a {dtype} [pairs][H][W] tensor on the GPU")
+    P, H, W = m3.shape
+    if m3.stride(2) != 1 or (H > 1 and m3.stride(1) != W) or (P > 1 and m3.stride(0) < H * W):
+        raise TypeError(f"{name}: every map must be dense and the maps must not overlap (strides {m3.stride()})")
+    return m3, P, H, W, (m3.stride(0) if P > 1 else H * W)
+
+
+def _asw_post(post):
+    q = _lib.ASWPostParams()
+    lib().smt_asw_post_default_params(C.byref(q))
+    for k, v in post.items():
+        if not hasattr(q, k):
+            raise AttributeError(k)
+        setattr(q, k, v)
+    return q
+
+
+@_on_tensor_device
+def MinMaxNormalizeU8(maps, out=None):
+    """normalize(m, m, 0, 255, NORM_MINMAX) + convertTo(CV_8UC1) (ASWeight.cpp:67-72) per map of [pairs][H][W] (or
+    [H][W]): uint8 maps (smt_minmax_normalize_u8_batch) or finite float32 maps (smt_minmax_normalize_f32_u8_batch) ->
+    uint8 maps of the same layout (`out`: default a new tensor; for uint8 maps it may be `maps` itself).  The library's
+    restatement of OpenCV 3.1, parity unpinned.  Asynchronous on the current stream."""
+    if isinstance(maps, torch.Tensor) and maps.dtype == torch.float32:
+        m3, P, H, W, stride = _u8_batch(maps, "maps", torch.float32)
+        fn, what = lib().smt_minmax_normalize_f32_u8_batch, "smt_minmax_normalize_f32_u8_batch"
+    else:
+        m3, P, H, W, stride = _u8_batch(maps, "maps")
+        fn, what = lib().smt_minmax_normalize_u8_batch, "smt_minmax_normalize_u8_batch"
+    if out is None:
+        out = torch.empty_strided(tuple(maps.shape), tuple(maps.stride()), dtype=torch.uint8, device=maps.device)
+    o3, Po, Ho, Wo, ostride = _u8_batch(out, "out")
+    if (Po, Ho, Wo, ostride) != (P, H, W, stride):
+        raise ValueError("out must have the shape and strides of maps")
+    check(fn(_ptr(m3), _ptr(o3), P, stride, H, W, current_stream_ptr()), what)
+    return out
+
+
+@_on_tensor_device
+def FilterSpecklesU8(maps, newVal, maxSpeckleSize, maxDiff, err=None):
+    """filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on CV_8UC1 (ASWeight.cpp:73), in place on [pairs][H][W] (or
+    [H][W]) uint8 maps: 4-neighbour components of at most maxSpeckleSize pixels become newVal.  The library's restatement
+    of OpenCV 3.1, parity unpinned.  err: optional int32 [1] device flag (loop cap, never expected).  Asynchronous."""
+    m3, P, H, W, stride = _u8_batch(maps, "maps")
+    check(lib().smt_filter_speckles_u8_batch(_ptr(m3), P, stride, W, H, int(newVal), int(maxSpeckleSize), int(maxDiff),
+                                             _ptr(err), current_stream_ptr()), "smt_filter_speckles_u8_batch")
+    return maps
+
+
+@_on_tensor_device
+def MedianBlurU8(maps, ksize):
+    """medianBlur(src, dst, ksize) (ASWeight.cpp:74, :78), ksize 3 or 5, uint8, BORDER_REPLICATE, on every map of
+    [pairs][H][W] (or [H][W]) -> a new tensor of the same layout (OpenCV's in-place call copies, so this is it).  The
+    library's restatement of OpenCV 3.1, parity unpinned.  One launch, asynchronous."""
+    m3, P, H, W, stride = _u8_batch(maps, "maps")
+    out = torch.empty_strided(tuple(maps.shape), tuple(maps.stride()), dtype=torch.uint8, device=maps.device)
+    o3 = out[None] if out.dim() == 2 else out
+    check(lib().smt_median_blur_u8_batch(_ptr(m3), _ptr(o3), P, stride, W, H, int(ksize), current_stream_ptr()),
+          "smt_median_blur_u8_batch")
+    return out
+
+
+@_on_tensor_device
+def FillImageNew(maps, fix=0, counts=False):
+    """FillImageNew (ASW/ASW.h:434-511) in place on [pairs][H][W] (or [H][W]) uint8 maps, with the reference's defects
+    (include/smt.h); fix=ASW_FIX_FILL_ROW_END makes column W count as outside.  counts=True: also returns int32
+    [pairs][2] (holes that pushed nothing, holes left 0 for want of a list entry).  Three launches, asynchronous."""
+    m3, P, H, W, stride = _u8_batch(maps, "maps")
+    cnt = torch.zeros((P, 2), dtype=torch.int32, device=maps.device) if counts else None
+    check(lib().smt_fill_image_new_batch(_ptr(m3), P, stride, H, W, C.c_uint(int(fix)), _ptr(cnt), current_stream_ptr()),
+          "smt_fill_image_new_batch")
+    return (maps, cnt) if counts else maps
+
+
+@_on_tensor_device
+def ASWTail(lastDisp, stages=False, err=None, **post):
+    """ASWeight.cpp:69 + :72-78 in place on [pairs][H][W] (or [H][W]) uint8 maps (smt_asw_tail_batch): normalize,
+    filterSpeckles, medianBlur 5, FillImageNew, medianBlur 3, each once over the batch.  Keywords override
+    smt_asw_post_default_params.  -> (lastDisp, fill counts [pairs][2]); stages=True: (lastDisp, after_median,
+    after_fill, counts), the driver's speckle.png and filled.png states.  Asynchronous on the current stream."""
+    m3, P, H, W, stride = _u8_batch(lastDisp, "lastDisp")
+    q = _asw_post(post)
+    cnt = torch.zeros((P, 2), dtype=torch.int32, device=lastDisp.device)
+    am = torch.empty_strided(tuple(m3.shape), tuple(m3.stride()), dtype=torch.uint8, device=m3.device) if stages else None
+    af = torch.empty_strided(tuple(m3.shape), tuple(m3.stride()), dtype=torch.uint8, device=m3.device) if stages else None
+    check(lib().smt_asw_tail_batch(_ptr(m3), P, stride, H, W, C.byref(q), _ptr(am), _ptr(af), _ptr(cnt), _ptr(err),
+                                   current_stream_ptr()), "smt_asw_tail_batch")
+    if stages:
+        if lastDisp.dim() == 2:
+            am, af = am[0], af[0]
+        return lastDisp, am, af, cnt
+    return lastDisp, cnt
+
+
 def _cblsm_post(post):
     q = _lib.CBLSMPostParams()
     lib().smt_cblsm_post_default_params(C.byref(q))
@@ -1511,6 +1611,35 @@ class ASWFlow:
         check(lib().smt_asw_flow_run_batch(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(last)),
               "smt_asw_flow_run_batch")
         return dl, dr, last
+
+    def run_post(self, grayL, grayR, **post):
+        """run(), then the file's tail (:67-78, smt_asw_flow_run_batch_post) once over the batch -> dict: dispL, dispR
+        (the un-normalised float maps of run()), dispL8, dispR8 (:67-68 + :70-71), lastDisp (the finished map, medain.png),
+        after_median, after_fill (speckle.png, filled.png), fill_counts int32 [pairs][2].  Keywords override
+        smt_asw_post_default_params."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"ASW handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        q = _asw_post(post)
+        shp = (P, self.row, self.col)
+        dl = torch.empty(shp, dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        u8 = [torch.empty(shp, dtype=torch.uint8, device=grayL.device) for _ in range(5)]
+        last, dl8, dr8, am, af = u8
+        cnt = torch.zeros((P, 2), dtype=torch.int32, device=grayL.device)
+        check(lib().smt_asw_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_asw_flow_set_stream")
+        check(lib().smt_asw_flow_run_batch_post(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(last),
+                                                _ptr(dl8), _ptr(dr8), C.byref(q), _ptr(am), _ptr(af), _ptr(cnt)),
+              "smt_asw_flow_run_batch_post")
+        return {"dispL": dl, "dispR": dr, "dispL8": dl8, "dispR8": dr8, "lastDisp": last, "after_median": am,
+                "after_fill": af, "fill_counts": cnt}
+
+    def status(self):
+        check(lib().smt_asw_flow_status(self._h), "smt_asw_flow_status")
 
     def close(self):
         if getattr(self, "_h", None) is not None:

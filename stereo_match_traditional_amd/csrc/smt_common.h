@@ -55,6 +55,11 @@ size_t smt_speckle_scratch_bytes(int pairs, int W, int H);
 int smt_speckle_enqueue(float *disp, int pairs, size_t stride, int W, int H, int diff_insame, unsigned min_speckle_area,
                         int invalid_val, void *scratch, int *err_dev, hipStream_t st);
 
+// filterSpeckles on uint8 maps (csrc/speckle.hip: the same kernels for uint8 pixels, 4 neighbours, `<=`), on the same
+// scratch size, arguments already checked.  Four launches on `st` (three when maxSpeckleSize < 0).
+int smt_speckle_u8_enqueue(uint8_t *maps, int pairs, size_t stride, int W, int H, int newVal, int maxSpeckleSize,
+                           int maxDiff, void *scratch, int *err_dev, hipStream_t st);
+
 // The fused costAggregationV4 of smt_cblsm_flow_run_batch_v4 (csrc/cblsm_v4.hip): S = the uint32 summed-area table of
 // the left view's AD volume, armL / armR = the four [H][W] arm maps (left, right, up, down) of the left / right image.
 // Writes the WTA map to `disp` and, unless NULL, the aggregated volume to `vol`; ORs 1 into *err_dev when a rectangle

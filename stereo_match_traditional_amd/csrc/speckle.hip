@@ -28,6 +28,11 @@ __device__ __forceinline__ bool sp_linked(float a, float b, float inv, float dif
 {
     return a != inv && b != inv && fabsf(b - a) <= diff;                  // :290-292
 }
+// filterSpeckles on CV_8UC1 (smt_filter_speckles_u8_batch): the pixels, newVal and maxDiff as ints
+__device__ __forceinline__ bool sp_linked(int a, int b, int inv, int diff)
+{
+    return a != inv && b != inv && abs(b - a) <= diff;
+}
 
 // Union-find on `lab` with parent <= child.  SCOPE: __HIP_MEMORY_SCOPE_WORKGROUP for the LDS forest,
 // __HIP_MEMORY_SCOPE_AGENT for the global one.  find halves the path it walks (atomic min: a slot only ever goes
@@ -84,11 +89,14 @@ __host__ __device__ static inline int sp_fwd_dx(int k) { return k == 0 ? 1 : k -
 
 namespace {
 
-__global__ void __launch_bounds__(NT_TILE) k_sp_tile(const float *__restrict__ d, int pairs, size_t stride, int W, int H,
-                                                     int ntx, float inv, float diff, int *__restrict__ par,
+// T = the pixel type, V = the type it is compared in (float / float for RemoveSpeckles, uint8_t / int for filterSpeckles),
+// NB = 8 or 4 neighbours.
+template <class T, class V, int NB>
+__global__ void __launch_bounds__(NT_TILE) k_sp_tile(const T *__restrict__ d, int pairs, size_t stride, int W, int H,
+                                                     int ntx, V inv, V diff, int *__restrict__ par,
                                                      int *__restrict__ cnt, short *__restrict__ loc, int *err)
 {
-    __shared__ float v[TN];
+    __shared__ V v[TN];
     __shared__ int lab[TN];
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
     const int y0 = ty * TS, x0 = tx * TS;
@@ -96,13 +104,13 @@ __global__ void __launch_bounds__(NT_TILE) k_sp_tile(const float *__restrict__ d
     const size_t n = (size_t)H * W;
     bool bad = false;
     for (int b = blockIdx.y; b < pairs; b += gridDim.y) {
-        const float *db = d + (size_t)b * stride;
+        const T *db = d + (size_t)b * stride;
         bool valid[TN / NT_TILE];
 #pragma unroll
         for (int i = 0; i < TN / NT_TILE; i++) {
             const int k = threadIdx.x + i * NT_TILE, r = k / TS, c = k % TS;
             const bool in = r < th && c < tw;
-            const float x = in ? db[(size_t)(y0 + r) * W + x0 + c] : 0.0f;
+            const V x = in ? (V)db[(size_t)(y0 + r) * W + x0 + c] : (V)0;
             valid[i] = in && x != inv;
             v[k] = x;
             lab[k] = valid[i] ? k : -1;
@@ -112,13 +120,13 @@ __global__ void __launch_bounds__(NT_TILE) k_sp_tile(const float *__restrict__ d
         for (int i = 0; i < TN / NT_TILE; i++) {
             if (!valid[i]) continue;
             const int k = threadIdx.x + i * NT_TILE, r = k / TS, c = k % TS;
-            const float x = v[k];
-            // backward neighbours: left, above-left, above, above-right (each in-tile link once)
+            const V x = v[k];
+            // backward neighbours: left, above-left, above, above-right (each in-tile link once; NB == 4: no diagonals)
             if (c > 0 && sp_linked(x, v[k - 1], inv, diff)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, k, k - 1, TN + 1, bad);
             if (r > 0) {
-                if (c > 0 && sp_linked(x, v[k - TS - 1], inv, diff)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, k, k - TS - 1, TN + 1, bad);
+                if (NB == 8 && c > 0 && sp_linked(x, v[k - TS - 1], inv, diff)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, k, k - TS - 1, TN + 1, bad);
                 if (sp_linked(x, v[k - TS], inv, diff)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, k, k - TS, TN + 1, bad);
-                if (c + 1 < tw && sp_linked(x, v[k - TS + 1], inv, diff)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, k, k - TS + 1, TN + 1, bad);
+                if (NB == 8 && c + 1 < tw && sp_linked(x, v[k - TS + 1], inv, diff)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, k, k - TS + 1, TN + 1, bad);
             }
         }
         __syncthreads();
@@ -138,8 +146,9 @@ __global__ void __launch_bounds__(NT_TILE) k_sp_tile(const float *__restrict__ d
     if (bad && err) *err = 1;
 }
 
-__global__ void __launch_bounds__(NT_MERGE) k_sp_merge(const float *__restrict__ d, int pairs, size_t stride, int W,
-                                                       int H, int ntx, float inv, float diff, int *par,
+template <class T, class V, int NB>
+__global__ void __launch_bounds__(NT_MERGE) k_sp_merge(const T *__restrict__ d, int pairs, size_t stride, int W,
+                                                       int H, int ntx, V inv, V diff, int *par,
                                                        const short *__restrict__ loc, int *err)
 {
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
@@ -152,19 +161,20 @@ __global__ void __launch_bounds__(NT_MERGE) k_sp_merge(const float *__restrict__
     const int y = y0 + r, x = x0 + c, p = y * W + x;
     bool bad = false;
     for (int b = blockIdx.y; b < pairs && !bad; b += gridDim.y) {
-        const float *db = d + (size_t)b * stride;
+        const T *db = d + (size_t)b * stride;
         const short *lb = loc + (size_t)b * n;
         int *pb = par + (size_t)b * n;
-        const float dp = db[p];
+        const V dp = (V)db[p];
         if (dp == inv) continue;
         const int rp = (y0 + lb[p] / TS) * W + x0 + lb[p] % TS;             // p's local root
         for (int k = 0; k < 4; k++) {
+            if (NB == 4 && (k & 1)) continue;                               // the two diagonals
             const int rr = r + sp_fwd_dy(k), cc = c + sp_fwd_dx(k);
             if (rr < th && cc >= 0 && cc < tw) continue;                    // same tile: k_sp_tile's link
             const int yy = y + sp_fwd_dy(k), xx = x + sp_fwd_dx(k);
             if (yy >= H || xx < 0 || xx >= W) continue;
             const int q = yy * W + xx;
-            if (!sp_linked(dp, db[q], inv, diff)) continue;
+            if (!sp_linked(dp, (V)db[q], inv, diff)) continue;
             const int lq = lb[q];
             const int qy0 = yy & ~(TS - 1), qx0 = xx & ~(TS - 1);
             uf_union<__HIP_MEMORY_SCOPE_AGENT>(pb, rp, (qy0 + lq / TS) * W + qx0 + lq % TS, cap, bad);
@@ -212,8 +222,10 @@ __global__ void __launch_bounds__(NT_TILE) k_sp_count(int pairs, int W, int H, i
     if (bad && err) *err = 1;
 }
 
-__global__ void __launch_bounds__(NT_TILE) k_sp_apply(float *d, int pairs, size_t stride, int W, int H, int ntx,
-                                                      float inv, unsigned min_area, const int *__restrict__ par,
+// LE: a component of at most min_area pixels goes (filterSpeckles' maxSpeckleSize), not one of fewer than min_area
+template <class T, bool LE>
+__global__ void __launch_bounds__(NT_TILE) k_sp_apply(T *d, int pairs, size_t stride, int W, int H, int ntx,
+                                                      T inv, unsigned min_area, const int *__restrict__ par,
                                                       const int *__restrict__ cnt, const short *__restrict__ loc)
 {
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
@@ -221,7 +233,7 @@ __global__ void __launch_bounds__(NT_TILE) k_sp_apply(float *d, int pairs, size_
     const int th = min(TS, H - y0), tw = min(TS, W - x0);
     const size_t n = (size_t)H * W;
     for (int b = blockIdx.y; b < pairs; b += gridDim.y) {
-        float *db = d + (size_t)b * stride;
+        T *db = d + (size_t)b * stride;
         const short *lb = loc + (size_t)b * n;
         const int *pb = par + (size_t)b * n, *cb = cnt + (size_t)b * n;
 #pragma unroll
@@ -231,12 +243,12 @@ __global__ void __launch_bounds__(NT_TILE) k_sp_apply(float *d, int pairs, size_
             const int g = (y0 + r) * W + x0 + c, l = lb[g];
             if (l < 0) continue;
             const int root = pb[(y0 + l / TS) * W + x0 + l % TS];
-            if ((unsigned)cb[root] < min_area) db[g] = inv;                 // :304-308
+            if (LE ? (unsigned)cb[root] <= min_area : (unsigned)cb[root] < min_area) db[g] = inv;   // :304-308
         }
     }
 }
 
-int speckle_check(const float *disp, int pairs, size_t stride, int W, int H)
+int speckle_check(const void *disp, int pairs, size_t stride, int W, int H)
 {
     if (!disp || pairs <= 0 || W <= 0 || H <= 0) return SMT_ERR_ARG;
     if ((long long)H * W >= (1ll << 31)) return SMT_ERR_ARG;
@@ -261,13 +273,54 @@ int smt_speckle_enqueue(float *disp, int pairs, size_t stride, int W, int H, int
     const float inv = (float)invalid_val, diff = (float)diff_insame;
     const int ntx = (W + TS - 1) / TS, nty = (H + TS - 1) / TS;
     const dim3 grid((unsigned)ntx * nty, pairs < MAX_GRID_Y ? pairs : MAX_GRID_Y);
-    hipLaunchKernelGGL(k_sp_tile, grid, dim3(NT_TILE), 0, st, disp, pairs, stride, W, H, ntx, inv, diff, par, cnt, loc, err_dev);
-    hipLaunchKernelGGL(k_sp_merge, grid, dim3(NT_MERGE), 0, st, disp, pairs, stride, W, H, ntx, inv, diff, par, loc, err_dev);
+    hipLaunchKernelGGL((k_sp_tile<float, float, 8>), grid, dim3(NT_TILE), 0, st, (const float *)disp, pairs, stride, W, H, ntx,
+                       inv, diff, par, cnt, loc, err_dev);
+    hipLaunchKernelGGL((k_sp_merge<float, float, 8>), grid, dim3(NT_MERGE), 0, st, (const float *)disp, pairs, stride, W, H,
+                       ntx, inv, diff, par, loc, err_dev);
     hipLaunchKernelGGL(k_sp_count, grid, dim3(NT_TILE), 0, st, pairs, W, H, ntx, par, cnt, loc, err_dev);
-    hipLaunchKernelGGL(k_sp_apply, grid, dim3(NT_TILE), 0, st, disp, pairs, stride, W, H, ntx, inv, min_speckle_area, par,
-                       cnt, loc);
+    hipLaunchKernelGGL((k_sp_apply<float, false>), grid, dim3(NT_TILE), 0, st, disp, pairs, stride, W, H, ntx, inv,
+                       min_speckle_area, par, cnt, loc);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
+}
+
+// filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on CV_8UC1 maps: the same four launches over the 4-neighbour
+// graph, `<=` as the size test.  A newVal outside 0..255 equals no pixel; the pixels that go receive its low byte.
+// A negative maxDiff links nothing, a negative maxSpeckleSize removes nothing.
+int smt_speckle_u8_enqueue(uint8_t *maps, int pairs, size_t stride, int W, int H, int newVal, int maxSpeckleSize,
+                           int maxDiff, void *scratch, int *err_dev, hipStream_t st)
+{
+    const size_t n = (size_t)H * W;
+    if (stride == 0) stride = n;
+    int *par = (int *)scratch, *cnt = par + (size_t)pairs * n;
+    short *loc = (short *)(cnt + (size_t)pairs * n);
+    const int ntx = (W + TS - 1) / TS, nty = (H + TS - 1) / TS;
+    const dim3 grid((unsigned)ntx * nty, pairs < MAX_GRID_Y ? pairs : MAX_GRID_Y);
+    hipLaunchKernelGGL((k_sp_tile<uint8_t, int, 4>), grid, dim3(NT_TILE), 0, st, (const uint8_t *)maps, pairs, stride, W, H,
+                       ntx, newVal, maxDiff, par, cnt, loc, err_dev);
+    hipLaunchKernelGGL((k_sp_merge<uint8_t, int, 4>), grid, dim3(NT_MERGE), 0, st, (const uint8_t *)maps, pairs, stride, W, H,
+                       ntx, newVal, maxDiff, par, loc, err_dev);
+    hipLaunchKernelGGL(k_sp_count, grid, dim3(NT_TILE), 0, st, pairs, W, H, ntx, par, cnt, loc, err_dev);
+    if (maxSpeckleSize >= 0)
+        hipLaunchKernelGGL((k_sp_apply<uint8_t, true>), grid, dim3(NT_TILE), 0, st, maps, pairs, stride, W, H, ntx,
+                           (uint8_t)newVal, (unsigned)maxSpeckleSize, par, cnt, loc);
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+SMT_API int smt_filter_speckles_u8_batch(uint8_t *maps, int pairs, size_t stride, int W, int H, int newVal,
+                                         int maxSpeckleSize, int maxDiff, int *err_dev, void *stream)
+{
+    int rc = speckle_check(maps, pairs, stride, W, H);
+    if (rc != SMT_OK) return rc;
+    if ((long long)H * W >= (1ll << 28)) return SMT_ERR_ARG;
+    hipStream_t st = smt_stream(stream);
+    void *scratch = nullptr;
+    const hipError_t e = smt_scratch_alloc(&scratch, smt_speckle_scratch_bytes(pairs, W, H), st);
+    if (e != hipSuccess) { g_smt_last_hip = (int)e; return SMT_ERR_ALLOC; }
+    rc = smt_speckle_u8_enqueue(maps, pairs, stride, W, H, newVal, maxSpeckleSize, maxDiff, scratch, err_dev, st);
+    smt_scratch_free(scratch, st);
+    return rc;
 }
 
 SMT_API int smt_remove_speckles_batch(float *disp, int pairs, size_t disp_stride, int W, int H, int diff_insame,

@@ -1,6 +1,8 @@
 // Counterpart of SAD/SADmain.cpp, NCC/NCC_main.cpp and ASW/ASWeight.cpp on a synthetic pair: host
 // buffers in, host maps out, everything computed by libsmt_hip.so through smt_host.hpp.  Prints
-// FNV-1a hashes for tests/test_cpp_host_gpu.py.   usage: matchers_main H W D seed
+// FNV-1a hashes for tests/test_cpp_host_gpu.py.   usage: matchers_main [--asw-post] H W D seed
+// --asw-post: also ASWeight.cpp:69-79 on the cross-checked map (smt::ASWTail); writes speckle.png, filled.png and
+// medain.png into the working directory and prints their hashes.
 #include <cstdio>
 #include <cstdlib>
 #include "smt_host.hpp"
@@ -48,6 +50,13 @@ static std::vector<unsigned char> pad(const std::vector<unsigned char> &a, int H
 
 int main(int argc, char **argv)
 {
+    bool asw_post = false;                                 // --asw-post (anywhere): also ASWeight.cpp's tail and its files
+    for (int k = 1; k < argc; k++)
+        if (std::string(argv[k]) == "--asw-post") {
+            asw_post = true;
+            for (int j = k; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc--; k--;
+        }
     const int H = argc > 1 ? atoi(argv[1]) : 40, W = argc > 2 ? atoi(argv[2]) : 90, D = argc > 3 ? atoi(argv[3]) : 32;
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 5;
     try {
@@ -89,6 +98,17 @@ int main(int argc, char **argv)
             printf("median %016llx\n", (unsigned long long)fnv(med.data(), n * 4));
             smt::RemoveSpeckles(dl.data(), W, H, 1, 30, -2147483647 - 1);   // main.cpp:93 with int(+inf) on x86
             printf("speckles %016llx\n", (unsigned long long)fnv(dl.data(), n * 4));
+            if (asw_post) {   // ASWeight.cpp:69, :72-79: the three maps the driver writes, into the working directory
+                std::vector<unsigned char> speckle(n), filled(n);
+                int counts[2] = {0, 0};
+                smt::ASWTail(last.data(), H, W, speckle.data(), filled.data(), nullptr, counts);
+                smt::imwrite("speckle.png", speckle.data(), H, W, 1);      // :75
+                smt::imwrite("filled.png", filled.data(), H, W, 1);        // :77
+                smt::imwrite("medain.png", last.data(), H, W, 1);          // :79
+                printf("asw_speckle %016llx\nasw_filled %016llx\nasw_medain %016llx\nasw_fill_no_push %d\n",
+                       (unsigned long long)fnv(speckle.data(), n), (unsigned long long)fnv(filled.data(), n),
+                       (unsigned long long)fnv(last.data(), n), counts[0]);
+            }
         }
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());

@@ -596,6 +596,41 @@ inline void RemoveSpeckles(float *disparity_map, const int &width, const int &he
     a.download(disparity_map);
 }
 
+// FillImageNew(disp) (ASW/ASW.h:434-511) on a host map uchar [rows][cols], in place, with the reference's defects
+// (include/smt.h: smt_fill_image_new_batch); fix = SMT_ASW_FIX_FILL_ROW_END makes column `cols` count as outside.
+// counts (may be null): int[2], the holes that pushed nothing and the holes left 0 for want of a list entry.
+inline void FillImageNew(unsigned char *disp, int rows, int cols, unsigned fix = 0, int *counts = nullptr)
+{
+    const size_t n = (size_t)rows * cols;
+    DevBuf<unsigned char> a(n);
+    DevBuf<int> c(2);
+    a.upload(disp);
+    check(smt_fill_image_new_batch(a.get(), 1, 0, rows, cols, fix, c.get(), nullptr), "smt_fill_image_new_batch");
+    a.download(disp);
+    if (counts) c.download(counts);
+}
+// ASWeight.cpp:69 + :72-78 on the host map CrossCheckDiaparity wrote (uchar [rows][cols]), in place: normalize,
+// filterSpeckles, medianBlur 5, FillImageNew, medianBlur 3 (smt_asw_tail_batch).  afterMedian / afterFill (may be null):
+// the states the driver writes as speckle.png and filled.png.  post == nullptr: the driver's arguments.
+inline void ASWTail(unsigned char *lastDisp, int rows, int cols, unsigned char *afterMedian = nullptr,
+                    unsigned char *afterFill = nullptr, const smt_asw_post_params *post = nullptr, int *fillCounts = nullptr)
+{
+    const size_t n = (size_t)rows * cols;
+    DevBuf<unsigned char> a(n), am(n), af(n);
+    DevBuf<int> c(2), err(1);
+    const int zero = 0;
+    a.upload(lastDisp); err.upload(&zero);
+    check(smt_asw_tail_batch(a.get(), 1, 0, rows, cols, post, am.get(), af.get(), c.get(), err.get(), nullptr),
+          "smt_asw_tail_batch");
+    a.download(lastDisp);
+    if (afterMedian) am.download(afterMedian);
+    if (afterFill) af.download(afterFill);
+    if (fillCounts) c.download(fillCounts);
+    int e = 0;
+    err.download(&e);
+    if (e) throw std::runtime_error("smt_asw_tail_batch: a speckle kernel hit its loop cap");
+}
+
 // ------------------------------------------------------------------ drivers' image handling
 // imread(path) (AD-CensusV1/main.cpp:16-17): 3-channel B, G, R;  cvtColor(.., CV_BGR2GRAY) (:19-20);
 // imwrite(path, img) (:115-117).  Host-side decoding / encoding is libsmt_hip.so's own (PNG, PGM, PPM).

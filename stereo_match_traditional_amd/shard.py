@@ -180,6 +180,22 @@ def asw_batch(L8, R8, D, **params):
     return dl, dr
 
 
+def asw_post_batch(L8, R8, D, post=None, **params):
+    """`compute` for run_sharded on ASWeight.cpp's flow with its tail (smt_asw_flow_run_batch_post) for a [count, H, W]
+    uint8 shard on this rank's GPU -> (finished lastDisp maps, normalised left maps), uint8.  `post`: dict of
+    smt_asw_post_params overrides; other keywords as api.ASWFlow."""
+    from .api import ASWFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.uint8, device=L8.device)
+        return z, z.clone()
+    flow = ASWFlow(H, W, D, L8.device, **params)
+    r = flow.run_post(L8.contiguous(), R8.contiguous(), **(post or {}))
+    flow.status()
+    flow.close()
+    return r["lastDisp"], r["dispL8"]
+
+
 def sad_batch(L8, R8, D, **params):
     """`compute` for run_sharded on SADmain.cpp's flow (smt_sad_flow_run_batch) for a [count, H, W] uint8 shard on this
     rank's GPU -> (left maps, right maps), int32.  Keywords as api.SADFlow."""
