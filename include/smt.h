@@ -642,6 +642,76 @@ int smt_cblsm_selftest_box(int H, int W, int D, int max_arm, int fill, unsigned 
 int smt_cblsm_selftest_v4(int H, int W, int D, int max_arm, unsigned seed);
 
 /* =====================================================================================
+ * CBLSM's window cost volumes      ComputeDispLeft / ComputeDispRight / ComputeDispV4
+ *                                  (CBLSM/CBLSM.h:451-489, :409-447, :494-532; call site CBLSM.cpp:132)
+ * =====================================================================================
+ * With w = winSize + 1, side = 2 w + 1, n = side^2 and images replicate-padded by w (CBLSM.cpp:124-125), entry
+ * vol[y][x][d] over the UNPADDED pixels is the mean absolute difference of two side x side windows of row y:
+ *   S(y, xa, xb) = the integer sum of |Lp - Rp| over the windows centred at left column xa and right column xb;
+ *   cost         = the float nearest to S / n (sadvalueMean, :17-22: cv::mean narrowed to float).
+ *   LEFT   d <= x: cost of S(y, x, x - d); d > x repeats the entry at d = x (the `cost = last` chain, :476-481).
+ *   RIGHT  x + d <= W-1-w: cost of S(y, x + d, x).  The guard of :434 stops the view w columns before its data does,
+ *          and that is reproduced: for x <= W-1-w < x + d the entry repeats the one at d = W-1-w-x; for x > W-1-w even
+ *          d = 0 copies, from the element before the pixel's vector, so all D entries of the last w columns of a row
+ *          equal the cost at (y, W-1-w, 0).  W <= w makes the reference read before its buffer: SMT_ERR_REF_UB,
+ *          nothing is written.
+ *   V4     3-channel padded images [H+2w][W+2w][3]; per tap the smallest of the three channel differences (minValue
+ *          ignores its T), added into a uchar, divided by n as an integer:
+ *          (float)(((sum of min_c |L_c - R_c|) mod 256) / n); LEFT's edge rule; there is no right counterpart.
+ * These functions call cv::mean and absdiff, whose source is in neither tree: they are "parity unpinned", held to a
+ * loop-for-loop restatement (tests/cblsm_window_cases.py) and to the exactness of the quotient: for every integer
+ * S <= 255 n and every odd side up to 65, 101 and 181, (float)((double)S / n), (float)((double)S * (1.0 / n)) and the
+ * IEEE float quotient (float)S / (float)n are the same float (S < 2^24, so (float)S is exact).
+ *
+ * smt_cblsm_window_cost_batch: `pairs` padded pairs -> `pairs` volumes.  form: SMT_CBLSM_COST_*.  Strides in elements
+ * (bytes of an image, floats of a volume) between consecutive pairs, 0 = dense; gaps between pairs are never written.
+ * Asynchronous on `stream`, no allocation.  pairs == 0 is a no-op.  SMT_ERR_ARG for NULL pointers, non-positive sizes,
+ * pairs < 0 or > 65535, D > SMT_MAX_DISPARITY, winSize < 0 or > 89 (side > 181), an unknown form and strides below a
+ * map's size; SMT_ERR_REF_UB as above, before any launch. */
+#define SMT_CBLSM_COST_LEFT  1
+#define SMT_CBLSM_COST_RIGHT 2
+#define SMT_CBLSM_COST_V4    3
+int smt_cblsm_window_cost_batch(const uint8_t *Lp, const uint8_t *Rp, int pairs, size_t img_stride, int H, int W, int D,
+                                int winSize, int form, float *vol, size_t vol_stride, void *stream);
+/* smt_cblsm_window_cost_batch on host memory, through the same inline rule functions (csrc/cblsm_window_rules.h: the
+ * edge rule per form, the quotient, V4's minimum and wrap).  The same arguments without the stream, the same statuses. */
+int smt_cblsm_window_cost_host(const uint8_t *Lp, const uint8_t *Rp, int pairs, size_t img_stride, int H, int W, int D,
+                               int winSize, int form, float *vol, size_t vol_stride);
+/* Test hooks (process-wide, plain unsynchronised globals).  set_impl: 0 (default) = the dispatch rule in
+ * csrc/cblsm_window.hip, 1 = the tap loop (one thread per pixel and hypothesis: the independent formulation), 2 = the box
+ * kernel (row sums sliding along a row, a box sum moving down a row, lanes along d); V4 always runs the tap loop.
+ * set_band: rows per band of the box kernel's grid, 0 = its own choice.  set_store: 0 = the default, 1 = plain,
+ * 2 = non-temporal stores of the box kernel.  SMT_ERR_ARG outside those values.  last_form: 1 or 2, what the last
+ * successful call ran (0 before the first). */
+int smt_cblsm_window_set_impl(int impl);
+int smt_cblsm_window_set_band(int band);
+int smt_cblsm_window_set_store(int mode);
+int smt_cblsm_window_last_form(void);
+/* Test hook: out_dev[k] = the box kernel's own __device__ quotient of S_dev[k] by n (1 <= n <= 181^2, every
+ * S_dev[k] < 2^24), so that the instruction sequence the kernel uses can be swept over every sum.  Asynchronous on
+ * `stream`.  SMT_ERR_ARG for NULL pointers, n outside that range or count > 2^31. */
+int smt_cblsm_window_quotient(const uint32_t *S_dev, size_t count, int n, float *out_dev, void *stream);
+/* Test hook, host only (no GPU): on random bytes and on an all-0 against an all-255 pair of the shape, the box
+ * arithmetic (row sums sliding along a row, a box sum moving down a row, in uint32) against direct window sums, and the
+ * chain rules against a literal per-pixel walk over a flat buffer (a guarded entry copies the element before it).  V4:
+ * the walk only.  SMT_OK or SMT_ERR_STATE; SMT_ERR_ARG for non-positive sizes, winSize outside 0..89, an unknown form,
+ * D > SMT_MAX_DISPARITY or more than 2^22 hypotheses; SMT_ERR_REF_UB for RIGHT with W <= winSize + 1. */
+int smt_cblsm_selftest_window(int H, int W, int D, int winSize, int form, unsigned seed);
+/* CBLSM.cpp with :132 enabled (and its right-view counterpart) for `pairs` gray pairs [pairs][H][W], per pair: the
+ * arms of both images as smt_cblsm_flow_run_batch computes them; the padding of :124-125 into buffers the handle owns;
+ * the LEFT window volume into the handle's scratch and its first costAggregationV5 pass on the left arms; the RIGHT
+ * window volume and its first pass on the right arms; the two second passes on the LEFT arms (:149-150) with the WTA
+ * (:152-153), exactly as smt_cblsm_flow_run_batch.  Window costs are non-integer floats whose sums round, so both
+ * passes are the in-order walk (smt_crossarm_aggregate, order 1), never a summed-area table.
+ *   dispL, dispR   float32 [pairs][H][W], integer-valued
+ * smt_cblsm_flow_volumes lends the last pair's first-pass volumes.  The handle's three volumes suffice and a handle may
+ * be called with different winSize in turn, and with the other run_batch entries in between.  pairs == 0 is a no-op.
+ * Asynchronous on the handle's stream only; errors through smt_cblsm_flow_status.  SMT_ERR_ARG for NULL arguments,
+ * pairs < 0 and winSize outside 0..89; SMT_ERR_REF_UB for W <= winSize + 1, before any device work. */
+int smt_cblsm_flow_run_batch_window(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int winSize,
+                                    float *dispL, float *dispR);
+
+/* =====================================================================================
  * Left-right consistency              replaces LeftRightConsistency
  *                                     (AD-CensusV1/PostProcessing.h:72-135)
  * ===================================================================================== */

@@ -24,6 +24,8 @@ QUIRK_FIX_ALL = 0xF
 SAD_FORM_COMPOSED, SAD_FORM_BOX_KEYS, SAD_FORM_BOX_VOLUME = 1, 2, 3
 NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX = 1, 2, 3
 LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS = 1, 2
+CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4 = 1, 2, 3   # SMT_CBLSM_COST_* (smt_cblsm_window_cost_batch)
+CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX = 1, 2          # smt_cblsm_window_last_form
 ASW_FIX_FILL_ROW_END = 0x1   # SMT_ASW_FIX_FILL_ROW_END (smt_fill_image_new_batch, smt_asw_post_params.fix)
 
 
@@ -143,6 +145,23 @@ def _declare_asw_tail(l):
     l.smt_asw_flow_status.argtypes = [vp]
 
 
+def _declare_cblsm_window(l):
+    """The signatures of CBLSM's window cost volumes (include/smt.h); an older build loaded through SMT_HIP_LIB is left
+    as it is."""
+    if not hasattr(l, "smt_cblsm_window_cost_batch"):
+        return
+    vp, i, z = C.c_void_p, C.c_int, C.c_size_t
+    l.smt_cblsm_window_cost_batch.argtypes = [vp, vp, i, z, i, i, i, i, i, vp, z, vp]
+    l.smt_cblsm_window_cost_host.argtypes = [vp, vp, i, z, i, i, i, i, i, vp, z]
+    l.smt_cblsm_window_set_impl.argtypes = [i]
+    l.smt_cblsm_window_set_band.argtypes = [i]
+    l.smt_cblsm_window_set_store.argtypes = [i]
+    l.smt_cblsm_window_last_form.argtypes = []
+    l.smt_cblsm_window_quotient.argtypes = [vp, z, i, vp, vp]
+    l.smt_cblsm_selftest_window.argtypes = [i, i, i, i, i, C.c_uint]
+    l.smt_cblsm_flow_run_batch_window.argtypes = [vp, vp, vp, i, i, vp, vp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -154,6 +173,7 @@ def lib():
         _lib.smt_strerror.restype = C.c_char_p
         _declare_ncc_flow(_lib)
         _declare_asw_tail(_lib)
+        _declare_cblsm_window(_lib)
     return _lib
 
 

@@ -15,6 +15,7 @@ from ._lib import (QUIRK_FIX_RIGHT_ARM_STRIDE, QUIRK_FIX_STICKY_TAU, QUIRK_FIX_S
 from ._lib import NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX  # noqa: F401
 from ._lib import LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS  # noqa: F401
 from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
+from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
@@ -25,6 +26,8 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "GetPointDepthBoth", "sad_both_set_impl", "sad_both_set_dispatch", "sad_both_set_band", "sad_both_last_form", "SADFlow",
            "CrossAggFlow", "ncc_box_set_band", "ncc_last_form", "NCCFlow", "NCC_FORM_LOOP", "NCC_FORM_DOT4", "NCC_FORM_BOX",
            "NCC_both", "lrncc_set_impl", "lrncc_last_form", "LRNCC_FORM_COMPOSED", "LRNCC_FORM_KEYS",
+           "ComputeDispLeft", "ComputeDispRight", "ComputeDispV4", "cblsm_window_set_impl", "cblsm_window_set_band",
+           "cblsm_window_set_store", "cblsm_window_last_form", "CBLSM_WINDOW_FORM_TAP", "CBLSM_WINDOW_FORM_BOX",
            "ASW_FIX_FILL_ROW_END", "MinMaxNormalizeU8", "FilterSpecklesU8", "MedianBlurU8", "FillImageNew", "ASWTail"]
 
 
@@ -494,6 +497,64 @@ def costAggregationV4(dispvolume, CostVolume, ArmvolumeL, ArmvolumeR, ArmvolumeU
                                               _ptr(ub_flag) if ub_flag is not None else None, current_stream_ptr()),
           "smt_cblsm_cost_aggregation_v4")
     return CostVolume
+
+
+@_on_tensor_device
+def _window_cost(form, leftimg, rightimg, winsize, dispRange, out):
+    w = int(winsize) + 1
+    batched = leftimg.dim() == (4 if form == CBLSM_COST_V4 else 3)
+    L, R = (leftimg, rightimg) if batched else (leftimg[None], rightimg[None])
+    P, Hp, Wp = L.shape[0], L.shape[1], L.shape[2]
+    H, W, D = Hp - 2 * w, Wp - 2 * w, int(dispRange)
+    shp = (P, Hp, Wp, 3) if form == CBLSM_COST_V4 else (P, Hp, Wp)
+    _dev(L, torch.uint8, shp, "leftimg")
+    _dev(R, torch.uint8, shp, "rightimg")
+    if H <= 0 or W <= 0:
+        raise ValueError(f"padded images of {Hp} x {Wp} hold no pixel for winsize {winsize}")
+    if out is None:
+        out = torch.empty((P, H, W, D) if batched else (H, W, D), dtype=torch.float32, device=L.device)
+    _dev(out, torch.float32, (P, H, W, D) if batched else (H, W, D), "dispVolume")
+    check(lib().smt_cblsm_window_cost_batch(_ptr(L), _ptr(R), P, 0, H, W, D, int(winsize), form, _ptr(out), 0,
+                                            current_stream_ptr()), "smt_cblsm_window_cost_batch")
+    return out
+
+
+def ComputeDispLeft(leftimg, rightimg, winsize, dispRange, out=None):
+    """CBLSM.h:451-489: uint8 images replicate-padded by winsize + 1, [row + 2w][col + 2w] (or a batch of them) ->
+    float32 window cost volume [row][col][dispRange] over the unpadded pixels (`out=` to fill a caller's)."""
+    return _window_cost(CBLSM_COST_LEFT, leftimg, rightimg, winsize, dispRange, out)
+
+
+def ComputeDispRight(leftimg, rightimg, winsize, dispRange, out=None):
+    """CBLSM.h:409-447, with its early stop: the view ends winsize + 1 columns before its data does and the last
+    columns of a row repeat one cost.  Raises (SMT_ERR_REF_UB) when col <= winsize + 1."""
+    return _window_cost(CBLSM_COST_RIGHT, leftimg, rightimg, winsize, dispRange, out)
+
+
+def ComputeDispV4(leftimg, rightimg, winsize, dispRange, out=None):
+    """CBLSM.h:494-532: 3-channel padded images [row + 2w][col + 2w][3]; per tap the smallest channel difference, summed
+    in a uchar, divided as an integer."""
+    return _window_cost(CBLSM_COST_V4, leftimg, rightimg, winsize, dispRange, out)
+
+
+def cblsm_window_set_impl(impl):
+    """Test hook: 0 = the dispatch rule, 1 = the tap loop, 2 = the box kernel (gray forms)."""
+    check(lib().smt_cblsm_window_set_impl(int(impl)), "smt_cblsm_window_set_impl")
+
+
+def cblsm_window_set_band(band):
+    """Test hook: rows per band of the box kernel's grid, 0 = its own choice."""
+    check(lib().smt_cblsm_window_set_band(int(band)), "smt_cblsm_window_set_band")
+
+
+def cblsm_window_set_store(mode):
+    """Timing hook: 0 = the default, 1 = plain, 2 = non-temporal stores of the box kernel."""
+    check(lib().smt_cblsm_window_set_store(int(mode)), "smt_cblsm_window_set_store")
+
+
+def cblsm_window_last_form():
+    """CBLSM_WINDOW_FORM_TAP or CBLSM_WINDOW_FORM_BOX: what the last window cost call ran."""
+    return int(lib().smt_cblsm_window_last_form())
 
 
 # ======================================================================================
@@ -1421,6 +1482,24 @@ class CBLSMFlow:
         check(lib().smt_cblsm_flow_run_batch_post(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
                                                   _ptr(counts), C.byref(q)), "smt_cblsm_flow_run_batch_post")
         return dl, dr, cls, counts
+
+    def run_window(self, grayL, grayR, winSize=1):
+        """CBLSM.cpp with :132 enabled (smt_cblsm_flow_run_batch_window): the window costs of ComputeDispLeft /
+        ComputeDispRight in place of the absolute differences, then the same two aggregation passes and WTA as run().
+        uint8 [pairs][row][col] (or [row][col]) -> (dispL, dispR), float32 [pairs][row][col]."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"CBLSM handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        check(lib().smt_cblsm_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_cblsm_flow_set_stream")
+        check(lib().smt_cblsm_flow_run_batch_window(self._h, _ptr(grayL), _ptr(grayR), P, int(winSize), _ptr(dl), _ptr(dr)),
+              "smt_cblsm_flow_run_batch_window")
+        return dl, dr
 
     def run_v4(self, grayL, grayR):
         """The per-hypothesis-arm flow (chooseArmLength*, ComputeAD, costAggregationV4, ComputeDispOringin;

@@ -62,6 +62,7 @@ static inline bool cblsm_sat_exact(const smt_cblsm_params &p) { return cblsm_arm
 namespace {
 
 constexpr int NT = 256;   // four waves per workgroup
+constexpr int CBLSM_WINDOW_MAX_W = 90;   // winSize + 1 of the widest window smt_cblsm_window_cost_batch takes (side 181)
 constexpr int SU = 8;     // rows / columns whose loads are issued before their adds
 
 // Column prefix of the AD volume of one view, AD evaluated from the two images: view 0 |L[i][j] - R[i][max(j-d, 0)]|
@@ -159,6 +160,7 @@ struct smt_cblsm_flow {
     int *err;                 // nonzero when k_sat_box (or the costAggregationV4 kernels) clipped a rectangle to the plane
     int *post_err;            // nonzero when a speckle kernel of run_batch_post hit its loop cap
     int *v4_arms;             // run_batch_v4 past the summed-area bound only: three [H][W][D] arm volumes, allocated on first use
+    uint8_t *padL, *padR;     // run_batch_window: the images of CBLSM.cpp:124-125, room for the widest border (90)
 };
 
 SMT_API void smt_cblsm_default_params(smt_cblsm_params *p)
@@ -176,6 +178,7 @@ SMT_API int smt_cblsm_flow_destroy(smt_cblsm_flow *h)
     if (h->caR) smt_crossarm_destroy(h->caR);
     (void)hipFree(h->pass1[0]); (void)hipFree(h->pass1[1]);
     (void)hipFree(h->scratch); (void)hipFree(h->err); (void)hipFree(h->post_err); (void)hipFree(h->v4_arms);
+    (void)hipFree(h->padL); (void)hipFree(h->padR);
     delete h;
     return SMT_OK;
 }
@@ -205,6 +208,10 @@ static int cblsm_create(int H, int W, int D, const smt_cblsm_params *p, smt_cbls
     if (rc == SMT_OK) rc = smt_malloc(&h->scratch, V);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->err, 4);
     if (rc == SMT_OK) rc = smt_malloc((void **)&h->post_err, 4);
+    // a few hundred KiB beside the volumes, so that run_batch_window never allocates whatever winSize it is given
+    const size_t padded = ((size_t)H + 2 * CBLSM_WINDOW_MAX_W) * ((size_t)W + 2 * CBLSM_WINDOW_MAX_W);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->padL, padded);
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->padR, padded);
     if (rc == SMT_OK && (hipMemset(h->err, 0, 4) != hipSuccess || hipMemset(h->post_err, 0, 4) != hipSuccess)) rc = SMT_ERR_HIP;
     if (rc != SMT_OK) { smt_cblsm_flow_destroy(h); return rc; }
     *out = h;
@@ -278,6 +285,40 @@ SMT_API int smt_cblsm_flow_run_batch(smt_cblsm_flow *h, const uint8_t *grayL, co
         if (rc == SMT_OK) rc = cblsm_first_pass(h, h->caR, L8, R8, 1);               // :134, :146
         if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, h->pass1[0], vol2, 1, dispL + b * N);   // :149, :152
         if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, h->pass1[1], vol2, 1, dispR + b * N);   // :150 (LEFT arms), :153
+        if (rc != SMT_OK) return rc;
+    }
+    return SMT_OK;
+}
+
+// CBLSM.cpp with :132 enabled: the window costs of ComputeDispLeft, and ComputeDispRight as the right view's counterpart,
+// in place of ComputeAD / ComputeADRight.  No summed-area shortcut here: a window cost is the float nearest to S / n, not
+// an integer, so the partial sums of costAggregationV5's float loop round and their order matters -- both passes of both
+// views are crossarm.hip's in-order walk (order 1), which adds in the reference's order.  The scratch holds each window
+// volume and then each second-pass output, so the handle's three volumes suffice.
+SMT_API int smt_cblsm_flow_run_batch_window(smt_cblsm_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int winSize,
+                                            float *dispL, float *dispR)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!grayL || !grayR || !dispL || !dispR || winSize < 0 || winSize + 1 > CBLSM_WINDOW_MAX_W) return SMT_ERR_ARG;
+    const int H = h->H, W = h->W, D = h->D, w = winSize + 1;
+    if (W <= w) return SMT_ERR_REF_UB;                                               // ComputeDispRight reads before its buffer
+    smt_dev_guard dev_guard(h->device);
+    const size_t N = (size_t)H * W;
+    float *vol = (float *)h->scratch;
+    void *st = (void *)h->stream;
+    for (int b = 0; b < pairs; b++) {
+        const uint8_t *L8 = grayL + b * N, *R8 = grayR + b * N;
+        int rc = smt_crossarm_arms(h->caL, L8, 1);                                   // CBLSM.cpp:64-67
+        if (rc == SMT_OK) rc = smt_crossarm_arms(h->caR, R8, 1);                     // :101-104
+        if (rc == SMT_OK) rc = smt_pad_replicate(L8, H, W, w, h->padL, st);          // :124
+        if (rc == SMT_OK) rc = smt_pad_replicate(R8, H, W, w, h->padR, st);          // :125
+        if (rc == SMT_OK) rc = smt_cblsm_window_cost_batch(h->padL, h->padR, 1, 0, H, W, D, winSize, SMT_CBLSM_COST_LEFT, vol, 0, st);   // :132
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, vol, h->pass1[0], 1, nullptr);             // :147
+        if (rc == SMT_OK) rc = smt_cblsm_window_cost_batch(h->padL, h->padR, 1, 0, H, W, D, winSize, SMT_CBLSM_COST_RIGHT, vol, 0, st);
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caR, vol, h->pass1[1], 1, nullptr);             // :146
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, h->pass1[0], vol, 1, dispL + b * N);       // :149, :152
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, h->pass1[1], vol, 1, dispR + b * N);       // :150 (LEFT arms), :153
         if (rc != SMT_OK) return rc;
     }
     return SMT_OK;

@@ -13,7 +13,11 @@
 //   :155, :160  LeftRightConsistency(col, row, gate = 5, dispLeft, dispRight, occlusion, mismatches)
 //   :161        RemoveSpeckles(dispLeft, col, row, 1, 50, Invalid_Float)       int(+inf): INT_MIN on x86
 //   :162        MedianFilter(dispLeft, dispLeft, col, row, 3)                  in == out
-//   usage: cblsm_main H W D seed [--post]
+// With --window[=winSize] (default 1, :28) the flow runs once more with :132 enabled -- ComputeDispLeft, and ComputeDispRight as
+// its right-view counterpart, on the images padded as :124-125 pad them, in place of ComputeAD / ComputeADRight -- through
+// smt::CBLSMFlow::runWindow, and the two maps are hashed (disp_left_window, disp_right_window); the two window volumes are hashed too, computed by
+// smt::ComputeDispLeft / smt::ComputeDispRight on host-padded images (window_left, window_right).
+//   usage: cblsm_main H W D seed [--post] [--window[=winSize]]
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -54,7 +58,12 @@ int main(int argc, char **argv)
     const int dispRange = argc > 3 ? atoi(argv[3]) : 60;                       // CBLSM.cpp:29
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 6;
     bool post = false;
-    for (int k = 1; k < argc; k++) post = post || strcmp(argv[k], "--post") == 0;
+    int window = -1;
+    for (int k = 1; k < argc; k++) {
+        post = post || strcmp(argv[k], "--post") == 0;
+        if (strcmp(argv[k], "--window") == 0) window = 1;
+        else if (strncmp(argv[k], "--window=", 9) == 0) window = atoi(argv[k] + 9);
+    }
     try {
         using namespace smt;
         Image imageL, imageR;
@@ -103,6 +112,28 @@ int main(int argc, char **argv)
             MedianFilter(dispLeft.data(), dispLeft.data(), col, row, 3);        // :162
             printf("occlusion %zu\nmismatches %zu\ndisp_left_post %016llx\n", occlusion.size(), mismatches.size(),
                    (unsigned long long)fnv(dispLeft.data(), n * 4));
+        }
+        if (window >= 0) {
+            // :124-125 copyMakeBorder(BORDER_REPLICATE) by window + 1, then :132 and its right-view counterpart on their own
+            const int w = window + 1;
+            Image padL, padR;
+            padL.rows = padR.rows = row + 2 * w; padL.cols = padR.cols = col + 2 * w; padL.channels = padR.channels = 1;
+            padL.data.resize((size_t)padL.rows * padL.cols); padR.data.resize(padL.data.size());
+            for (int i = 0; i < padL.rows; i++)
+                for (int j = 0; j < padL.cols; j++) {
+                    const int si = i < w ? 0 : (i - w > row - 1 ? row - 1 : i - w), sj = j < w ? 0 : (j - w > col - 1 ? col - 1 : j - w);
+                    padL.data[(size_t)i * padL.cols + j] = leftPtr[(size_t)si * col + sj];
+                    padR.data[(size_t)i * padL.cols + j] = rightPtr[(size_t)si * col + sj];
+                }
+            ComputeDispLeft(dispVolumLeft.data(), padL, padR, window, dispRange, row, col);     // :132
+            ComputeDispRight(dispVolumRight.data(), padL, padR, window, dispRange, row, col);
+            printf("window_left %016llx\nwindow_right %016llx\n", (unsigned long long)fnv(dispVolumLeft.data(), V * 4),
+                   (unsigned long long)fnv(dispVolumRight.data(), V * 4));
+            std::vector<float> wl(n), wr(n);
+            CBLSMFlow flow(row, col, dispRange);
+            flow.runWindow(leftPtr, rightPtr, 1, window, wl.data(), wr.data());   // :132 enabled
+            printf("disp_left_window %016llx\ndisp_right_window %016llx\n", (unsigned long long)fnv(wl.data(), n * 4),
+                   (unsigned long long)fnv(wr.data(), n * 4));
         }
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());

@@ -707,6 +707,65 @@ inline void ComputeAD(int col, int row, int dispRange, unsigned char *leftImage,
 inline void ComputeADRight(int col, int row, int dispRange, unsigned char *leftImage, unsigned char *rightImage, float *ADcostVolum)
 { compute_ad_(col, row, dispRange, leftImage, rightImage, ADcostVolum, SMT_VIEW_RIGHT); }
 
+// ComputeDispLeft / ComputeDispRight / ComputeDispV4 (CBLSM.h:451-489, :409-447, :494-532), the reference's argument
+// order: the images are the PADDED ones (copyMakeBorder by winsize + 1, CBLSM.cpp:124-125; three channels for V4), _row_
+// and _col_ the unpadded sizes, dispVolume float [_row_][_col_][dispRange].  Throws where ComputeDispRight reads before
+// its buffer (_col_ <= winsize + 1).
+inline void compute_disp_(float *dispVolume, const Image &leftimg, const Image &rightimg, int winsize, int dispRange, int _row_,
+                          int _col_, int form)
+{
+    const int w = winsize + 1, ch = form == SMT_CBLSM_COST_V4 ? 3 : 1;
+    if (leftimg.rows != _row_ + 2 * w || leftimg.cols != _col_ + 2 * w || leftimg.channels != ch ||
+        rightimg.rows != leftimg.rows || rightimg.cols != leftimg.cols || rightimg.channels != ch)
+        check(SMT_ERR_ARG, "ComputeDisp: images must be padded by winsize + 1");
+    DevBuf<unsigned char> L(leftimg.data.size()), R(rightimg.data.size());
+    DevBuf<float> vol((size_t)_row_ * _col_ * dispRange);
+    L.upload(leftimg.data.data()); R.upload(rightimg.data.data());
+    check(smt_cblsm_window_cost_batch(L.get(), R.get(), 1, 0, _row_, _col_, dispRange, winsize, form, vol.get(), 0, nullptr),
+          "smt_cblsm_window_cost_batch");
+    vol.download(dispVolume);
+}
+inline void ComputeDispLeft(float *dispVolume, const Image &leftimg, const Image &rightimg, int winsize, int dispRange, int _row_, int _col_)
+{ compute_disp_(dispVolume, leftimg, rightimg, winsize, dispRange, _row_, _col_, SMT_CBLSM_COST_LEFT); }
+inline void ComputeDispRight(float *dispVolume, const Image &leftimg, const Image &rightimg, int winsize, int dispRange, int _row_, int _col_)
+{ compute_disp_(dispVolume, leftimg, rightimg, winsize, dispRange, _row_, _col_, SMT_CBLSM_COST_RIGHT); }
+inline void ComputeDispV4(float *dispVolume, const Image &leftimg, const Image &rightimg, int winsize, int dispRange, int _row_, int _col_)
+{ compute_disp_(dispVolume, leftimg, rightimg, winsize, dispRange, _row_, _col_, SMT_CBLSM_COST_V4); }
+
+// CBLSM.cpp's flow for batches of gray pairs (smt_cblsm_flow_*): host buffers in and out
+class CBLSMFlow {
+public:
+    CBLSMFlow(int rows, int cols, int dispRange, int device = 0) : n_((size_t)rows * cols)
+    {
+        check(smt_cblsm_flow_create_on(device, rows, cols, dispRange, nullptr, &h_), "smt_cblsm_flow_create_on");
+    }
+    ~CBLSMFlow() { if (h_) smt_cblsm_flow_destroy(h_); }
+    CBLSMFlow(const CBLSMFlow &) = delete;
+    CBLSMFlow &operator=(const CBLSMFlow &) = delete;
+    // grayL, grayR: uchar [pairs][rows][cols]; dispLeft, dispRight: float [pairs][rows][cols].  CBLSM.cpp as it is run:
+    // the first passes aggregate ComputeAD / ComputeADRight
+    void run(const unsigned char *grayL, const unsigned char *grayR, int pairs, float *dispLeft, float *dispRight)
+    { run_(grayL, grayR, pairs, -1, dispLeft, dispRight); }
+    // the same with :132 enabled: the first passes aggregate ComputeDispLeft / ComputeDispRight of the padded images
+    void runWindow(const unsigned char *grayL, const unsigned char *grayR, int pairs, int winSize, float *dispLeft, float *dispRight)
+    { run_(grayL, grayR, pairs, winSize, dispLeft, dispRight); }
+private:
+    void run_(const unsigned char *grayL, const unsigned char *grayR, int pairs, int winSize, float *dispLeft, float *dispRight)
+    {
+        const size_t n = n_ * (size_t)pairs;
+        DevBuf<unsigned char> L(n), R(n);
+        DevBuf<float> dl(n), dr(n);
+        L.upload(grayL); R.upload(grayR);
+        if (winSize < 0) check(smt_cblsm_flow_run_batch(h_, L.get(), R.get(), pairs, dl.get(), dr.get()), "smt_cblsm_flow_run_batch");
+        else check(smt_cblsm_flow_run_batch_window(h_, L.get(), R.get(), pairs, winSize, dl.get(), dr.get()), "smt_cblsm_flow_run_batch_window");
+        check(smt_cblsm_flow_status(h_), "smt_cblsm_flow_status");
+        if (dispLeft) dl.download(dispLeft);
+        if (dispRight) dr.download(dispRight);
+    }
+    smt_cblsm_flow *h_ = nullptr;
+    size_t n_;
+};
+
 // costAggregationV5 (CBLSM.h:1179-1224): rectangle mean, rows outer / columns inner, with the four arm arrays the
 // caller passes -- whichever image they were computed on (CBLSM.cpp:150 aggregates the right volume with the left
 // image's arms).  winSize is unused by the reference too.

@@ -120,6 +120,22 @@ def cblsm_v4_batch(L8, R8, D, **params):
     return dl, dl
 
 
+def cblsm_window_batch(L8, R8, D, winSize=1, **params):
+    """`compute` for run_sharded on CBLSM.cpp's flow with :132 enabled (smt_cblsm_flow_run_batch_window: window costs in
+    place of absolute differences) for a [count, H, W] uint8 shard on this rank's GPU -> (left maps, right maps).
+    Keywords as api.CBLSMFlow."""
+    from .api import CBLSMFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = CBLSMFlow(H, W, D, L8.device, **params)
+    dl, dr = flow.run_window(L8.contiguous(), R8.contiguous(), winSize)
+    flow.status()
+    flow.close()
+    return dl, dr
+
+
 def crossagg_batch(L8, R8, D, **params):
     """`compute` for run_sharded on the CrossAggregator flow of CBLSM.cpp:133-143, 152 (smt_crossagg_flow_run_batch) for
     a [count, H, W, 3] uint8 BGR shard on this rank's GPU -> (left maps, right maps).  Keywords as api.CrossAggFlow."""
