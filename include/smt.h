@@ -1002,6 +1002,94 @@ int smt_lrncc_selftest_keys(int W, int D, int winSize, unsigned seed);
 int smt_lrncc_flow_run_batch(smt_ncc_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, int32_t *dispL,
                              int32_t *dispR, int32_t *lastdisp, uint8_t *cls);
 
+/* ncc() (NCC.h:117-272), the whole-image matcher NCC_main.cpp:24 calls in a commented line.  A different function from
+ * NCC_algorithem: every pixel is written, and the reference has a right view of it.  L, R uint8 [H][W], k = kernel_size,
+ * O = max_offset.  For pixel (y, x): rows sy = max(0, y-k) .. ey = min(H-1, y+k), columns sx .. ex likewise (:186-189);
+ * the loops visit N = (ey-sy+1)(ex-sx+1) taps, the reference's count is n = (ey-sy)(ex-sx) (:190), one short per axis.
+ * For o = 1 .. O the window holds two byte images:
+ *   SMT_VIEW_LEFT  ("left")   a = L,  b = T:  T[y][c]  = R[y][c] for c < o, R[y][c-o] otherwise          (:147-158)
+ *   SMT_VIEW_RIGHT ("right")  a = T', b = R:  T'[y][c] = L[y][c+o] for c < W-o, L[y][c] otherwise        (:162-173)
+ * ma = sum a / n, mb = sum b / n (not the means: n != N); A = sum (a-ma)^2, B = sum (b-mb)^2, C = sum (a-ma)(b-mb), three
+ * sequential float64 sums over the N taps, rows outer, each divided by n; res = C / (sqrt(A) sqrt(B)) / n (:224).  A running
+ * maximum starts at -2.0 and o wins when res > max (:261-266): a NaN never wins and the first of equal costs stays.
+ * depth uint8 [H][W] = (uchar)(3 o) of the winner, which wraps from o = 86 on; offset (optional, may be NULL) int32 [H][W]
+ * = the winning o, 0 where no offset won; cost (optional, may be NULL) float64 [H][W][max_offset], index o-1 (a diagnostic
+ * output: the INT form stores it with a stride of max_offset doubles across lanes, 1.5 to 1.7 times the maps-only call at 450x375).
+ * Exact form: with the integer window sums and q = 2n - N, res = Ci / (n sqrt(Ai) sqrt(Bi)), Ai = n^2 Saa - q Sa^2,
+ * Bi = n^2 Sbb - q Sb^2, Ci = n^2 Sab - q Sa Sb, evaluated as (double)Ci / ((double)n * (sqrt((double)Ai) * sqrt((double)Bi))).
+ * Ai >= 0, and 0 only for an all-zero window; res is NaN exactly where Ai Bi = 0; |res| <= 1/n.  Every integer stays below
+ * 2^53 for kernel_size <= 35 (the tight terms at k = 35: q Sa^2 <= 4759 * 255^2 * 71^4 = 7.864e15 and n^2 Saa <= 4900^2 *
+ * 255^2 * 71^2 = 7.870e15, against 2^53 = 9.007e15; both pass it at k = 36; csrc/ncc_whole_rules.h has the arithmetic).
+ * The expression is symmetric in a and b, so the left type's cost at (y, x, o) equals the right type's at (y, x-o, o) word
+ * for word wherever x-k >= o and x+k <= W-1.
+ * Forms (smt_whole_ncc_set_impl: 0 = the dispatch rule, 1 = LOOP, 2 = INT wherever it exists; smt_whole_ncc_last_form
+ * reports what the last successful call ran; process-wide unsynchronised globals like smt_ncc_set_impl's):
+ *   LOOP  :181-267 loop for loop, one lane per pixel: the independent formulation, and the only one for kernel_size > 35.
+ *         The reference squares with pow(x, 2), this form with x * x: the same double wherever pow is correctly rounded
+ *         for the exponent 2 (the recorded fixture pins the maps, not the costs).
+ *   INT   the exact form: per-row prefix sums of the clamped vertical window sums of v and v^2 give Sa, Saa and the shifted
+ *         image's Sb, Sbb as two or four loads per range; Sab is a running sum down the rows and a sum over the clamped
+ *         columns, in uint32.
+ * The two forms give the same NaN pattern and costs within their rounding bounds (tests/ncc_whole_cases.py derives them).
+ * Decided defects.  (1) `Mat depth(height, width, 0)` is uninitialised in OpenCV: a pixel at which every offset is NaN
+ * keeps garbage in the reference; here it is 0.  (2) For o > W the shift loops write outside tmp (:149, :169):
+ * max_offset > W returns SMT_ERR_REF_UB before any launch; max_offset == W is defined (every column is fill).  (3) n = 0
+ * needs a one-row or one-column window: H < 2, W < 2 or kernel_size < 1 is SMT_ERR_ARG.  (4) add_constant (:127-130) is
+ * OpenCV's saturating `right += 10` and the reference applies it to the CALLER's image (`Mat right = in2` shares the data);
+ * here min(R + 10, 255) goes to a scratch copy, for both views, and the caller's buffer stays as it is (parity unpinned,
+ * like the other OpenCV restatements).
+ * SMT_ERR_ARG also for NULL images or depth, a view other than SMT_VIEW_LEFT / SMT_VIEW_RIGHT, max_offset outside
+ * 1 .. SMT_MAX_DISPARITY, H > 65535 or H * W >= 2^31.  params == NULL means the defaults (5, 79, 0: NCC.h:121-122).  Scratch
+ * comes from the arena; asynchronous on `stream`.  (The entry points are named smt_whole_ncc*: the names that begin with
+ * smt_ncc are NCC_algorithem's family, a closed list.) */
+#define SMT_NCC_WHOLE_FORM_LOOP 1
+#define SMT_NCC_WHOLE_FORM_INT  2
+typedef struct smt_whole_ncc_params { int kernel_size, max_offset, add_constant; } smt_whole_ncc_params;
+void smt_whole_ncc_default_params(smt_whole_ncc_params *p);
+int smt_whole_ncc(const uint8_t *L, const uint8_t *R, int H, int W, const smt_whole_ncc_params *params, int view,
+                  uint8_t *depth_u8, int32_t *offset_i32, double *cost_f64, void *stream);
+/* Test hooks (process-wide, plain unsynchronised globals): see smt_whole_ncc.  SMT_ERR_ARG outside 0..2. */
+int smt_whole_ncc_set_impl(int impl);
+int smt_whole_ncc_last_form(void);
+/* Test hook (process-wide, a plain unsynchronised global): into how many consecutive runs a cost launch splits the offsets
+ * 1 .. max_offset (each workgroup keeps the winner of one run; a finishing launch combines the runs in their order), capped
+ * at max_offset; 0 (default) = chosen from the size of the grid.  Every value gives the same maps and costs.  SMT_ERR_ARG
+ * below 0.  smt_whole_ncc_last_groups: the number of runs of the last successful call (0 before the first). */
+int smt_whole_ncc_set_groups(int groups);
+int smt_whole_ncc_last_groups(void);
+/* Test hook, host only (no GPU): on four pairs of the shape (pseudo-random, 255 against 255, opposed checkerboards, a
+ * shifted copy) the INT kernel's recurrences restated on the host with the kernel's own index helpers
+ * (csrc/ncc_whole_rules.h) -- tiles, row strips, halo lanes, entering and leaving rows, clamped column sums, the shifted
+ * image's two ranges in the prefix tables -- equal the direct double loop over the shifted copy for Sab, Sb and Sbb at
+ * every (y, x, o), fill columns and all four clamps included; and on hostile cost rows (exact ties, NaN first and later, all
+ * NaN) the kernels' split of the offsets into G runs (nw_group) tiles 1 .. max_offset once and in order and the run-wise
+ * winner (nw_offer) names the sequential loop's offset, for every G.  SMT_OK or SMT_ERR_STATE; rejects what smt_whole_ncc
+ * rejects, and SMT_ERR_ARG for kernel_size > 35 or more than 2^22 hypotheses. */
+int smt_whole_ncc_selftest_box(int H, int W, int kernel_size, int max_offset, int view, unsigned seed);
+/* bgr_to_grey (NCC.h:97-115) for n images: BGR uint8 [n][H][W][3] -> uint8 [n][H][W].  Each channel is uchar(0.333 v),
+ * truncated, from a 256-entry table made on the host with the reference's expression; the three are added (at most
+ * 3 * 84: no wrap).  Not the rule of smt_bgr2gray.  n == 0 is a no-op; SMT_ERR_ARG for n < 0, non-positive sizes or NULL
+ * buffers.  Asynchronous on `stream`. */
+int smt_bgr_to_grey_batch(const uint8_t *bgr, int n, int H, int W, uint8_t *grey, void *stream);
+
+/* NCC_main.cpp with :24 enabled, for both types and for `pairs` gray pairs uint8 [pairs][H][W]: depthL / depthR uint8 and
+ * offL / offR int32 [pairs][H][W] are per pair bit for bit what smt_whole_ncc writes for SMT_VIEW_LEFT / SMT_VIEW_RIGHT under
+ * the matching impl; then per pair the int-map cross-check of Sad.h:184-222 on the two OFFSET maps: lastdisp int32 and cls
+ * uint8 [pairs][H][W] are exactly smt_sad_crosscheck of the call's own offL and offR.  Any output may be NULL (maps nobody
+ * takes live in arena scratch; with every output NULL the call does nothing); pairs == 0 is a no-op.  One statistics launch
+ * and one cost launch serve both views of the whole batch (the view and the pair on a grid axis); the right type's costs
+ * are computed, not taken from the left pass.  The handle owns no device memory: every table comes from the arena, and the
+ * call is asynchronous on the handle's stream.  create_on rejects what smt_whole_ncc rejects (SMT_ERR_REF_UB for
+ * max_offset > W); set_form: 0 (default) = as smt_whole_ncc chooses, else SMT_NCC_WHOLE_FORM_*, SMT_ERR_ARG for INT with
+ * kernel_size > 35.  At most 32767 pairs per call; SMT_ERR_ARG for a NULL handle or image or pairs < 0. */
+typedef struct smt_whole_ncc_flow smt_whole_ncc_flow;
+int smt_whole_ncc_flow_create_on(int device, int H, int W, const smt_whole_ncc_params *p, smt_whole_ncc_flow **out);
+int smt_whole_ncc_flow_destroy(smt_whole_ncc_flow *h);
+int smt_whole_ncc_flow_set_stream(smt_whole_ncc_flow *h, void *stream);
+int smt_whole_ncc_flow_set_form(smt_whole_ncc_flow *h, int form);
+int smt_whole_ncc_flow_run_batch(smt_whole_ncc_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, uint8_t *depthL,
+                                 uint8_t *depthR, int32_t *offL, int32_t *offR, int32_t *lastdisp, uint8_t *cls);
+
 /* getGausssianMask (ASW.h:16-35) and getColorMask (:41-47), computed on the HOST in
  * float64 exactly as the reference does.  space: (2*winSize+3)^2 doubles, color: 256. */
 int smt_asw_masks(int winSize, double sigma_space, double sigma_color, double *space_host,

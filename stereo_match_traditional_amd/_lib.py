@@ -26,6 +26,7 @@ NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX = 1, 2, 3
 LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS = 1, 2
 CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4 = 1, 2, 3   # SMT_CBLSM_COST_* (smt_cblsm_window_cost_batch)
 CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX = 1, 2          # smt_cblsm_window_last_form
+NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT = 1, 2               # smt_whole_ncc_last_form
 ASW_FIX_FILL_ROW_END = 0x1   # SMT_ASW_FIX_FILL_ROW_END (smt_fill_image_new_batch, smt_asw_post_params.fix)
 
 
@@ -70,6 +71,11 @@ class SADParams(C.Structure):
 class NCCParams(C.Structure):
     """smt_ncc_params: NCC_main.cpp:17's winSize."""
     _fields_ = [("winSize", C.c_int)]
+
+
+class NCCWholeParams(C.Structure):
+    """smt_whole_ncc_params: NCC.h:121-122's kernel_size and max_offset, :117's add_constant."""
+    _fields_ = [("kernel_size", C.c_int), ("max_offset", C.c_int), ("add_constant", C.c_int)]
 
 
 class PostParams(C.Structure):
@@ -162,6 +168,29 @@ def _declare_cblsm_window(l):
     l.smt_cblsm_flow_run_batch_window.argtypes = [vp, vp, vp, i, i, vp, vp]
 
 
+def _declare_ncc_whole(l):
+    """The signatures of NCC.h's whole-image ncc() (include/smt.h); an older build loaded through SMT_HIP_LIB is left as
+    it is."""
+    if not hasattr(l, "smt_whole_ncc"):
+        return
+    vp, i = C.c_void_p, C.c_int
+    pp = C.POINTER(NCCWholeParams)
+    l.smt_whole_ncc_default_params.argtypes = [pp]
+    l.smt_whole_ncc_default_params.restype = None
+    l.smt_whole_ncc.argtypes = [vp, vp, i, i, pp, i, vp, vp, vp, vp]
+    l.smt_whole_ncc_set_impl.argtypes = [i]
+    l.smt_whole_ncc_last_form.argtypes = []
+    l.smt_whole_ncc_set_groups.argtypes = [i]
+    l.smt_whole_ncc_last_groups.argtypes = []
+    l.smt_whole_ncc_selftest_box.argtypes = [i, i, i, i, i, C.c_uint]
+    l.smt_bgr_to_grey_batch.argtypes = [vp, i, i, i, vp, vp]
+    l.smt_whole_ncc_flow_create_on.argtypes = [i, i, i, pp, C.POINTER(vp)]
+    l.smt_whole_ncc_flow_destroy.argtypes = [vp]
+    l.smt_whole_ncc_flow_set_stream.argtypes = [vp, vp]
+    l.smt_whole_ncc_flow_set_form.argtypes = [vp, i]
+    l.smt_whole_ncc_flow_run_batch.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -174,6 +203,7 @@ def lib():
         _declare_ncc_flow(_lib)
         _declare_asw_tail(_lib)
         _declare_cblsm_window(_lib)
+        _declare_ncc_whole(_lib)
     return _lib
 
 

@@ -15,6 +15,7 @@ from ._lib import (QUIRK_FIX_RIGHT_ARM_STRIDE, QUIRK_FIX_STICKY_TAU, QUIRK_FIX_S
 from ._lib import NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX  # noqa: F401
 from ._lib import LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS  # noqa: F401
 from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
+from ._lib import NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT  # noqa: F401
 from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
@@ -28,6 +29,8 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "NCC_both", "lrncc_set_impl", "lrncc_last_form", "LRNCC_FORM_COMPOSED", "LRNCC_FORM_KEYS",
            "ComputeDispLeft", "ComputeDispRight", "ComputeDispV4", "cblsm_window_set_impl", "cblsm_window_set_band",
            "cblsm_window_set_store", "cblsm_window_last_form", "CBLSM_WINDOW_FORM_TAP", "CBLSM_WINDOW_FORM_BOX",
+           "ncc", "bgr_to_grey", "ncc_whole_set_impl", "ncc_whole_last_form", "ncc_whole_set_groups", "ncc_whole_last_groups", "NCCWholeFlow", "NCC_WHOLE_FORM_LOOP",
+           "NCC_WHOLE_FORM_INT",
            "ASW_FIX_FILL_ROW_END", "MinMaxNormalizeU8", "FilterSpecklesU8", "MedianBlurU8", "FillImageNew", "ASWTail"]
 
 
@@ -893,6 +896,70 @@ def lrncc_set_impl(impl):
 def lrncc_last_form():
     """Which form the last both-view NCC call ran: LRNCC_FORM_COMPOSED or LRNCC_FORM_KEYS (0: none yet)."""
     return int(lib().smt_lrncc_last_form())
+
+
+def _ncc_whole_params(kernel_size, max_offset, add_constant):
+    p = _lib.NCCWholeParams()
+    p.kernel_size, p.max_offset, p.add_constant = int(kernel_size), int(max_offset), int(bool(add_constant))
+    return p
+
+
+@_on_tensor_device
+def ncc(in1, in2, type, add_constant=False, kernel_size=5, max_offset=79, want_offset=False, want_cost=False):
+    """ncc() (NCC.h:117-272): uint8 [H][W] gray images, type "left" or "right" -> depth uint8 [H][W] = (uchar)(3 * offset) of
+    the winner, every pixel written (0 where every offset's cost is NaN).  kernel_size and max_offset are the two values the
+    reference fixes at 5 and 79.  want_offset adds the winning offset int32 [H][W] (0: none won), want_cost the costs
+    float64 [H][W][max_offset], index offset - 1; the return value is depth, or a tuple in the order depth, offset, cost.
+    add_constant works on a copy: in2 stays as it is.  want_cost is a diagnostic: the integer form stores the volume with a
+    stride of max_offset doubles across lanes, 1.5 to 1.7 times the maps-only call at 450x375."""
+    if type not in ("left", "right"):
+        raise ValueError(f"type must be 'left' or 'right', not {type!r}")   # the reference returns an empty Mat
+    H, W = in1.shape
+    _dev(in1, torch.uint8, (H, W), "in1")
+    _dev(in2, torch.uint8, (H, W), "in2")
+    depth = torch.empty((H, W), dtype=torch.uint8, device=in1.device)
+    off = torch.empty((H, W), dtype=torch.int32, device=in1.device) if want_offset else None
+    cost = torch.full((H, W, int(max_offset)), float("nan"), dtype=torch.float64, device=in1.device) if want_cost else None
+    p = _ncc_whole_params(kernel_size, max_offset, add_constant)
+    check(lib().smt_whole_ncc(_ptr(in1), _ptr(in2), H, W, C.byref(p), VIEW_LEFT if type == "left" else VIEW_RIGHT, _ptr(depth),
+                              _ptr(off), _ptr(cost), current_stream_ptr()), "smt_whole_ncc")
+    out = (depth,) + ((off,) if want_offset else ()) + ((cost,) if want_cost else ())
+    return out if len(out) > 1 else depth
+
+
+@_on_tensor_device
+def bgr_to_grey(bgr):
+    """bgr_to_grey (NCC.h:97-115): uint8 [H][W][3] or [n][H][W][3] -> uint8 [H][W] or [n][H][W]; each channel is
+    uchar(0.333 * v), truncated, then the three are added.  Not cvtColor_BGR2GRAY's rule."""
+    single = bgr.dim() == 3
+    b = bgr[None] if single else bgr
+    n, H, W, ch = b.shape
+    _dev(b, torch.uint8, (n, H, W, 3), "bgr")
+    grey = torch.empty((n, H, W), dtype=torch.uint8, device=bgr.device)
+    check(lib().smt_bgr_to_grey_batch(_ptr(b), n, H, W, _ptr(grey), current_stream_ptr()), "smt_bgr_to_grey_batch")
+    return grey[0] if single else grey
+
+
+def ncc_whole_set_impl(impl):
+    """Which form ncc() and NCCWholeFlow take: 0 = the dispatch rule (default), 1 = NCC_WHOLE_FORM_LOOP (the reference's loop
+    nest), 2 = NCC_WHOLE_FORM_INT wherever it exists, kernel_size <= 35 (test hook)."""
+    check(lib().smt_whole_ncc_set_impl(int(impl)), "smt_whole_ncc_set_impl")
+
+
+def ncc_whole_set_groups(groups):
+    """Into how many runs a cost launch of ncc() / NCCWholeFlow splits the offsets; 0 = chosen from the grid (test hook: every
+    value gives the same results)."""
+    check(lib().smt_whole_ncc_set_groups(int(groups)), "smt_whole_ncc_set_groups")
+
+
+def ncc_whole_last_groups():
+    """Into how many runs the last ncc() / NCCWholeFlow call split the offsets (0: none yet)."""
+    return int(lib().smt_whole_ncc_last_groups())
+
+
+def ncc_whole_last_form():
+    """Which form the last ncc() / NCCWholeFlow call ran: NCC_WHOLE_FORM_LOOP or NCC_WHOLE_FORM_INT (0: none yet)."""
+    return int(lib().smt_whole_ncc_last_form())
 
 
 def sad_set_impl(impl):
@@ -1846,6 +1913,61 @@ class NCCFlow:
     def close(self):
         if getattr(self, "_h", None) is not None:
             lib().smt_ncc_flow_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NCCWholeFlow:
+    """NCC_main.cpp with :24 enabled, both types, for batches of gray pairs (smt_whole_ncc_flow_*), followed by the int-map
+    cross-check of Sad.h:184-222 on the two offset maps.  Keywords: kernel_size, max_offset, add_constant (defaults 5, 79,
+    False).  The sharding unit of shard.ncc_whole_batch."""
+    OUTS = ("depthL", "depthR", "offL", "offR", "lastdisp", "cls")
+
+    def __init__(self, row, col, device=None, kernel_size=5, max_offset=79, add_constant=False):
+        self.row, self.col = int(row), int(col)
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        p = _ncc_whole_params(kernel_size, max_offset, add_constant)
+        h = C.c_void_p()
+        check(lib().smt_whole_ncc_flow_create_on(_dev_index(self.device), self.row, self.col, C.byref(p), C.byref(h)),
+              "smt_whole_ncc_flow_create_on")
+        self._h = h
+
+    def set_form(self, form):
+        """0 = as ncc() chooses (default), else NCC_WHOLE_FORM_LOOP / NCC_WHOLE_FORM_INT."""
+        check(lib().smt_whole_ncc_flow_set_form(self._h, int(form)), "smt_whole_ncc_flow_set_form")
+        return self
+
+    def run(self, L8, R8, want=OUTS):
+        """uint8 [pairs][row][col] (or [row][col]) -> (depthL, depthR, offL, offR, lastdisp, cls): uint8, uint8, int32, int32,
+        int32 and uint8 [pairs][row][col]; an output not named in `want` comes back as None.  lastdisp and cls are
+        sad_CrossCheckDiaparity of the two offset maps.  On torch's current stream of the handle's device; nothing
+        synchronises."""
+        if L8.dim() == 2:
+            L8, R8 = L8[None], R8[None]
+        P = L8.shape[0]
+        if _dev_index(L8.device) != _dev_index(self.device) or R8.device != L8.device:
+            raise ValueError(f"NCC handle lives on {self.device}, images on {L8.device} / {R8.device}")
+        _dev(L8, torch.uint8, (P, self.row, self.col), "L8")
+        _dev(R8, torch.uint8, (P, self.row, self.col), "R8")
+        unknown = set(want) - set(self.OUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        shape = (P, self.row, self.col)
+        outs = [torch.empty(shape, dtype=torch.int32 if n in ("offL", "offR", "lastdisp") else torch.uint8, device=L8.device)
+                if n in want else None for n in self.OUTS]
+        check(lib().smt_whole_ncc_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_whole_ncc_flow_set_stream")
+        check(lib().smt_whole_ncc_flow_run_batch(self._h, _ptr(L8), _ptr(R8), P, *[_ptr(o) for o in outs]),
+              "smt_whole_ncc_flow_run_batch")
+        return tuple(outs)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().smt_whole_ncc_flow_destroy(self._h)
             self._h = None
 
     def __del__(self):

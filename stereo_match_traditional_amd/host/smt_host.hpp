@@ -521,6 +521,70 @@ private:
     size_t n_;
 };
 
+// ncc(in1, in2, type, add_constant) (NCC.h:117-272): gray uchar [rows][cols] -> depth uchar [rows][cols] = (uchar)(3 * offset)
+// of the winner; type "left" or "right".  kernel_size and max_offset are the values the reference fixes at 5 and 79.
+// in2 stays as it is under add_constant (the reference adds 10 to the caller's image).
+inline void ncc(const unsigned char *in1, const unsigned char *in2, int rows, int cols, const std::string &type,
+                unsigned char *depth, bool add_constant = false, int kernel_size = 5, int max_offset = 79, int *offset = nullptr)
+{
+    if (type != "left" && type != "right") throw std::runtime_error("ncc: type must be \"left\" or \"right\"");
+    const size_t n = (size_t)rows * cols;
+    DevBuf<unsigned char> L(n), R(n), d(n);
+    DevBuf<int> o(n);
+    L.upload(in1); R.upload(in2);
+    smt_whole_ncc_params p = {kernel_size, max_offset, add_constant ? 1 : 0};
+    check(smt_whole_ncc(L.get(), R.get(), rows, cols, &p, type == "left" ? SMT_VIEW_LEFT : SMT_VIEW_RIGHT, d.get(), o.get(), nullptr,
+                        nullptr), "smt_whole_ncc");
+    d.download(depth);
+    if (offset) o.download(offset);
+}
+
+// bgr_to_grey (NCC.h:97-115): B, G, R uchar [rows][cols][3] -> uchar [rows][cols], each channel uchar(0.333 v), then added
+inline void bgr_to_grey(const unsigned char *bgr, int rows, int cols, unsigned char *grey)
+{
+    const size_t n = (size_t)rows * cols;
+    DevBuf<unsigned char> b(3 * n), g(n);
+    b.upload(bgr);
+    check(smt_bgr_to_grey_batch(b.get(), 1, rows, cols, g.get(), nullptr), "smt_bgr_to_grey_batch");
+    g.download(grey);
+}
+
+// NCC_main.cpp with :24 enabled, both types, for batches of gray pairs (smt_whole_ncc_flow_*): host buffers in and out
+class NCCWholeFlow {
+public:
+    NCCWholeFlow(int rows, int cols, int kernel_size = 5, int max_offset = 79, bool add_constant = false, int device = 0)
+        : n_((size_t)rows * cols)
+    {
+        smt_whole_ncc_params p = {kernel_size, max_offset, add_constant ? 1 : 0};
+        check(smt_whole_ncc_flow_create_on(device, rows, cols, &p, &h_), "smt_whole_ncc_flow_create_on");
+    }
+    ~NCCWholeFlow() { if (h_) smt_whole_ncc_flow_destroy(h_); }
+    NCCWholeFlow(const NCCWholeFlow &) = delete;
+    NCCWholeFlow &operator=(const NCCWholeFlow &) = delete;
+    // 0 = as ncc() chooses, else SMT_NCC_WHOLE_FORM_*
+    void set_form(int form) { check(smt_whole_ncc_flow_set_form(h_, form), "smt_whole_ncc_flow_set_form"); }
+    // in1, in2: uchar [pairs][rows][cols]; depthLeft, depthRight uchar, offLeft, offRight, lastdisp int [pairs][rows][cols]
+    // (lastdisp: the cross-check of Sad.h:184-222 on the two offset maps); any output may be null
+    void run(const unsigned char *in1, const unsigned char *in2, int pairs, unsigned char *depthLeft, unsigned char *depthRight,
+             int *offLeft, int *offRight, int *lastdisp)
+    {
+        const size_t n = n_ * (size_t)pairs;
+        DevBuf<unsigned char> L(n), R(n), dl(n), dr(n), c(n);
+        DevBuf<int> ol(n), orr(n), last(n);
+        L.upload(in1); R.upload(in2);
+        check(smt_whole_ncc_flow_run_batch(h_, L.get(), R.get(), pairs, dl.get(), dr.get(), ol.get(), orr.get(), last.get(), c.get()),
+              "smt_whole_ncc_flow_run_batch");
+        if (depthLeft) dl.download(depthLeft);
+        if (depthRight) dr.download(depthRight);
+        if (offLeft) ol.download(offLeft);
+        if (offRight) orr.download(offRight);
+        if (lastdisp) last.download(lastdisp);
+    }
+private:
+    smt_whole_ncc_flow *h_ = nullptr;
+    size_t n_;
+};
+
 // getGausssianMask + getColorMask (ASW.h:16-47)
 inline void getMasks(std::vector<double> &spaceMask, std::vector<double> &colorMask, int winSize, double spaceSigma,
                      double colorSigma)

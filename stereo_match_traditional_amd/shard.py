@@ -253,3 +253,20 @@ def ncc_both_batch(L8, R8, D, **params):
     dl, dr, _, _ = flow.run_both(L8.contiguous(), R8.contiguous(), want=("dispL", "dispR"))
     flow.close()
     return dl, dr
+
+
+def ncc_whole_batch(L8, R8, D=None, **params):
+    """`compute` for run_sharded on NCC.h's whole-image ncc(), both types (smt_whole_ncc_flow_run_batch), for a
+    [count, H, W] uint8 shard on this rank's GPU -> (left offset maps, right offset maps), int32.  D, when given, is
+    max_offset; keywords as api.NCCWholeFlow."""
+    from .api import NCCWholeFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.int32, device=L8.device)
+        return z, z.clone()
+    if D is not None:
+        params = dict(params, max_offset=D)
+    flow = NCCWholeFlow(H, W, L8.device, **params)
+    _, _, ol, orr, _, _ = flow.run(L8.contiguous(), R8.contiguous(), want=("offL", "offR"))
+    flow.close()
+    return ol, orr
