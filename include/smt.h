@@ -333,6 +333,22 @@ int smt_adcensus_status(smt_adcensus *h);
  * twice, AD_Census::WTA. */
 int smt_wta(const float *vol, int H, int W, int D, float *disp, void *stream);
 
+/* Sub-pixel disparities: the parabola through the winner and its two neighbours that SAD/Sad.h:76-81 and
+ * CBLSM/CBLSM.h:285-290 compute and then drop (they return best_disp).  One rule everywhere
+ * (csrc/subpixel_rule.h), for a cost row c[0..D) in float32, one rounding per operation:
+ *   w = the winner by smt_wta's rule;  if w == 0 or w == D - 1 the result is (float)w;  otherwise
+ *   s = (c[w-1] + c[w+1]) - 2 c[w];  den = min_den < s ? s : min_den  (std::max(min_den, s): a NaN s gives min_den);
+ *   off = (c[w-1] - c[w+1]) / (2 den);  result = isfinite(off) ? (float)w + off : (float)w.
+ * min_den is the reference's literal 1 (Sad.h:80); it must be finite and > 0, else SMT_ERR_ARG.  Volumes of
+ * AD-Census magnitude (costs in [0, 2]) almost always sit under that clamp: pass a small value for the true parabola. */
+typedef struct smt_subpixel_params { float min_den; } smt_subpixel_params;   /* 1: Sad.h:80 */
+void smt_subpixel_default_params(smt_subpixel_params *p);
+/* smt_wta with the rule above: vol float32 [H][W][D] (4-byte aligned, D <= SMT_MAX_DISPARITY), disp float32 [H][W].
+ * p == NULL means the defaults.  Argument checks as smt_wta, plus min_den.  Asynchronous on `stream`. */
+int smt_wta_subpixel(const float *vol, int H, int W, int D, const smt_subpixel_params *p, float *disp, void *stream);
+/* The same on host buffers with the same rule header, no GPU. */
+int smt_wta_subpixel_host(const float *vol, int H, int W, int D, const smt_subpixel_params *p, float *disp);
+
 /* =====================================================================================
  * Cross-arm rectangle aggregation     replaces class CrossArmAggregation
  *                                     (AD-CensusV1/CrossArm.{h,cpp}) and the active
@@ -439,6 +455,11 @@ int smt_crossarm_set_occupancy(smt_crossarm *h, int waves_per_simd);
 /* Tuning hook (variants 3 .. 13, the default included; 0 .. 2 ignore it): 0 = column strips interleaved over the 8 XCDs,
  * 1 = every XCD owns one contiguous band of rows and sweeps it strip by strip.  Placement only; results are identical. */
 int smt_crossarm_set_sweep(smt_crossarm *h, int sweep);
+/* Sub-pixel switch: with p != NULL, smt_crossarm_aggregate writes to `disp` the winner refined by the rule of
+ * smt_wta_subpixel with p->min_den; NULL = off, the integer map (the default).  From the next call on the handle,
+ * between runs.  Fused into the default variant (13) and the plain walk (1, also D > 256, volumes >= 4 GiB and order 2);
+ * every other variant aggregates into vol_out and smt_wta_subpixel reads it back.  vol_out is the same either way. */
+int smt_crossarm_set_subpixel(smt_crossarm *h, const smt_subpixel_params *p);
 /* Test hook, host only (no GPU, no handle): the workgroup-to-pixel map of aggregation variant `variant` on an H x W image
  * with smt_crossarm_set_strip_width(strip_width) (0 = the width smt_crossarm_set_variant selects) and
  * smt_crossarm_set_sweep(sweep), through the functions the kernels and the launchers run.  Every workgroup and wave of
@@ -509,6 +530,10 @@ int smt_scanline_destroy(smt_scanline *h);
 int smt_scanline_set_stream(smt_scanline *h, void *stream);
 /* SMT_QUIRK_FIX_SCAN_VERTICAL for the passes 2 and 3 of smt_scanline_pass / smt_scanline_run (0 = faithful, the default) */
 int smt_scanline_set_quirks(smt_scanline *h, unsigned quirks);
+/* Sub-pixel switch: with p != NULL, the fused WTA of smt_scanline_run writes the winner refined by the rule of
+ * smt_wta_subpixel with p->min_den, inside the last pass; NULL = off, the integer map (the default).  From the next
+ * call on the handle, between runs. */
+int smt_scanline_set_subpixel(smt_scanline *h, const smt_subpixel_params *p);
 
 /* ScanlineOptimizer::ScanLine (:104-128): the four passes and ((left+right)+up)+down,
  * written to vol_out (`_ProcessedVolume`).  gray: float32 [H][W] guidance image
@@ -540,6 +565,11 @@ int smt_pipeline_set_stream(smt_pipeline *h, void *stream);
  * default.  With SMT_QUIRK_FIX_RIGHT_ARM_STRIDE square and portrait pairs (H >= W) run too: arms then never leave
  * their row; without it H > W gives SMT_ERR_REF_UB as before. */
 int smt_pipeline_set_quirks(smt_pipeline *h, unsigned quirks);
+/* Sub-pixel switch of the scanline handle and of both views' aggregation handles, under every SMT_PIPE_SCHEDULE, between
+ * runs; NULL = off, the integer maps (the default).  With it smt_pipeline_run_batch and _post give dispL refined from
+ * the scanline sum and dispR refined from the aggregated right volume; the LR check (which rounds j - disp + 0.5),
+ * RemoveSpeckles and MedianFilter then run on those maps, unchanged. */
+int smt_pipeline_set_subpixel(smt_pipeline *h, const smt_subpixel_params *p);
 /* main.cpp:46-92 for `pairs` pairs of uint8 gray images [pairs][H][W] (the images after cvtColor, :19-20), in
  * main.cpp's order with lines 86-89 and 92 enabled: float copies, ComputeADcensus(+Right), CrossArm
  * Initialize + four arm passes + AggregationVertical + WTA on the left and on the right image,

@@ -191,6 +191,26 @@ def _declare_ncc_whole(l):
     l.smt_whole_ncc_flow_run_batch.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp]
 
 
+class SubpixelParams(C.Structure):
+    """smt_subpixel_params: the parabola rule's clamp (Sad.h:80's literal 1)."""
+    _fields_ = [("min_den", C.c_float)]
+
+
+def _declare_subpixel(l):
+    """The signatures of the sub-pixel entry points (include/smt.h); an older build loaded through SMT_HIP_LIB is left
+    as it is."""
+    if not hasattr(l, "smt_wta_subpixel"):
+        return
+    vp, i = C.c_void_p, C.c_int
+    pp = C.POINTER(SubpixelParams)
+    l.smt_subpixel_default_params.argtypes = [pp]
+    l.smt_subpixel_default_params.restype = None
+    l.smt_wta_subpixel.argtypes = [vp, i, i, i, pp, vp, vp]
+    l.smt_wta_subpixel_host.argtypes = [vp, i, i, i, pp, vp]
+    for name in ("smt_scanline_set_subpixel", "smt_crossarm_set_subpixel", "smt_pipeline_set_subpixel"):
+        getattr(l, name).argtypes = [vp, pp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -204,6 +224,7 @@ def lib():
         _declare_asw_tail(_lib)
         _declare_cblsm_window(_lib)
         _declare_ncc_whole(_lib)
+        _declare_subpixel(_lib)
     return _lib
 
 

@@ -18,7 +18,7 @@ from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
 from ._lib import NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT  # noqa: F401
 from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
-__all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
+__all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "wta_subpixel", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
@@ -253,6 +253,25 @@ def wta(vol, disp=None):
     return disp
 
 
+def _subpixel_arg(min_den):
+    """NULL (switch off) for None, else a pointer to smt_subpixel_params; the library checks the value"""
+    return None if min_den is None else C.byref(_lib.SubpixelParams(float(min_den)))
+
+
+@_on_tensor_device
+def wta_subpixel(vol, min_den=1.0, disp=None):
+    """wta() with the winner refined by the parabola through it and its two neighbours: the value Sad.h:76-81 and
+    CBLSM.h:285-290 compute and drop.  min_den is the clamp of the denominator (the reference's literal 1; pass a small
+    value for the true parabola on volumes of AD-Census magnitude).  A winner at either end of the range is kept."""
+    H, W, D = vol.shape
+    _dev(vol, torch.float32, name="vol")
+    if disp is None:
+        disp = torch.empty((H, W), dtype=torch.float32, device=vol.device)
+    _dev(disp, torch.float32, (H, W), "disp")
+    check(lib().smt_wta_subpixel(_ptr(vol), H, W, D, _subpixel_arg(min_den), _ptr(disp), current_stream_ptr()), "smt_wta_subpixel")
+    return disp
+
+
 # ======================================================================================
 # CrossArmAggregation  (AD-CensusV1/CrossArm.h:9-36) + CBLSM.h arms / costAggregationV5
 # ======================================================================================
@@ -288,6 +307,11 @@ class CrossArmAggregation:
 
     def _bind(self):
         check(lib().smt_crossarm_set_stream(self._h, current_stream_ptr(self.device)), "smt_crossarm_set_stream")
+
+    def set_subpixel(self, min_den=None):
+        """From the next aggregation on, the `disp` map carries the parabola's fraction (wta_subpixel's rule with this
+        min_den); None = integer maps, the default."""
+        check(lib().smt_crossarm_set_subpixel(self._h, _subpixel_arg(min_den)), "smt_crossarm_set_subpixel")
 
     def ComputeArmLengths(self, Image):
         """ComputeLeftArmLength, ComputeRightArmLength, ComputeTopArmLength,
@@ -585,6 +609,11 @@ class ScanlineOptimizer:
     def set_quirks(self, quirks):
         """QUIRK_FIX_* from the next ScanLine / ScanPass on."""
         check(lib().smt_scanline_set_quirks(self._h, C.c_uint(quirks)), "smt_scanline_set_quirks")
+
+    def set_subpixel(self, min_den=None):
+        """From the next ScanLine on, its `disp` map carries the parabola's fraction (wta_subpixel's rule with this
+        min_den); None = the integer map, the default."""
+        check(lib().smt_scanline_set_subpixel(self._h, _subpixel_arg(min_den)), "smt_scanline_set_subpixel")
 
     def ScanLine(self, costVolume, Image, out=None, disp=None):
         """:104-128; returns `_ProcessedVolume`.  Image = float32 gray guidance."""
@@ -1405,9 +1434,10 @@ def scratch_info(device=None):
 class Pipeline:
     """main.cpp:46-92 (scanline and LR check enabled) for batches of gray pairs; the sharding unit of config 3."""
 
-    def __init__(self, row, col, dispRange, device=None, quirks=0, **params):
+    def __init__(self, row, col, dispRange, device=None, quirks=0, subpixel=None, **params):
         """params: the fields of smt_pipeline_params.  quirks: QUIRK_FIX_* for every stage, 0 = the reference's
-        results; QUIRK_FIX_RIGHT_ARM_STRIDE also admits row > col."""
+        results; QUIRK_FIX_RIGHT_ARM_STRIDE also admits row > col.  subpixel: min_den of set_subpixel, None = integer
+        maps."""
         self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         p = _lib.PipelineParams()
@@ -1422,10 +1452,17 @@ class Pipeline:
         self._h = h
         if quirks:
             self.set_quirks(quirks)
+        if subpixel is not None:
+            self.set_subpixel(subpixel)
 
     def set_quirks(self, quirks):
         """QUIRK_FIX_* from the next run on (between runs)."""
         check(lib().smt_pipeline_set_quirks(self._h, C.c_uint(quirks)), "smt_pipeline_set_quirks")
+
+    def set_subpixel(self, min_den=None):
+        """From the next run on (between runs), dispL and dispR carry the parabola's fraction (wta_subpixel's rule with
+        this min_den), and the LR check, RemoveSpeckles and MedianFilter run on those maps; None = integer maps."""
+        check(lib().smt_pipeline_set_subpixel(self._h, _subpixel_arg(min_den)), "smt_pipeline_set_subpixel")
 
     def run(self, grayL, grayR):
         """uint8 [pairs][row][col] (or [row][col]) -> (dispL after LR check, dispR, cls, counts[pairs][2])."""

@@ -383,13 +383,14 @@ constexpr int AGG_MAX_STRIP_WIDTH = 4096;
 inline int agg_default_width(int variant) { return variant >= 7 ? 8 : 16; }
 inline bool agg_width_ok(int w) { return w >= 4 && !(w & 3) && w <= AGG_MAX_STRIP_WIDTH; }
 
-// one wave per pixel; lane owns d = lane*C .. lane*C+C-1 (masked when >= D)
-template <int C, int ORDER>
+// one wave per pixel; lane owns d = lane*C .. lane*C+C-1 (masked when >= D).  SUB (smt_crossarm_set_subpixel): the fused
+// WTA writes the winner refined by the sub-pixel rule with min_den (an unused argument otherwise).
+template <int C, int ORDER, bool SUB = false>
 __global__ void __launch_bounds__(NT) k_aggregate(const float *__restrict__ vin, float *__restrict__ vout,
                                                   int H, int W, int D, const int *__restrict__ armL,
                                                   const int *__restrict__ armR, const int *__restrict__ armT,
                                                   const int *__restrict__ armB, float *__restrict__ disp,
-                                                  int *ub_flag)
+                                                  int *ub_flag, float min_den)
 {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -442,8 +443,13 @@ __global__ void __launch_bounds__(NT) k_aggregate(const float *__restrict__ vin,
     }
     if (ub && lane == 0) atomicOr(ub_flag, 1);
     if (disp) {
-        const int wd = wave_wta<C, false>(acc, dl, D);
-        if (lane == 0) disp[p] = (float)wd;
+        if constexpr (SUB) {
+            const float wf = wave_wta_subpixel<C, false>(acc, dl, D, min_den);
+            if (lane == 0) disp[p] = wf;
+        } else {
+            const int wd = wave_wta<C, false>(acc, dl, D);
+            if (lane == 0) disp[p] = (float)wd;
+        }
     }
 }
 
@@ -771,13 +777,17 @@ __device__ __forceinline__ i4v buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned vo, un
 // q = r*8 + c).  Lane q keeps pixel q's rectangle (box coordinates relative to the block's top-left
 // pixel, 16-bit fields); the classification loop broadcasts them with v_readlane once per batch of 64
 // box positions, so no rectangle lives in SGPRs across the tap loop.
-template <int C, int ORDER, bool FULL, int QR, int SKIP, int TWS = 3>
+// SUB (smt_crossarm_set_subpixel; instantiated for the default form, SKIP == 7, only): the fused WTA writes the winner
+// refined by the sub-pixel rule with min_den, an argument the other instantiations do not read.
+template <int C, int ORDER, bool FULL, int QR, int SKIP, int TWS = 3, bool SUB = false>
 __global__ void __launch_bounds__(NT, (SKIP == 6 ? (C <= 2 ? 5 : C == 3 ? 4 : 3) : (SKIP == 4 || SKIP == 5) ? (C <= 3 ? 5 : 3) : (C <= 3 ? 6 : 4))) k_aggregate_multi(const float *__restrict__ vin, float *__restrict__ vout,
                                                         int H, int W, int D, const int *__restrict__ armL,
                                                         const int *__restrict__ armR, const int *__restrict__ armT,
                                                         const int *__restrict__ armB, float *__restrict__ disp,
-                                                        int *ub_flag, int SW, const float *__restrict__ member, int sweep)
+                                                        int *ub_flag, int SW, const float *__restrict__ member, int sweep,
+                                                        float min_den)
 {
+    static_assert(!SUB || SKIP == 7, "the refined WTA is fused into the default form only");
     // tile geometry: pixel q of the wave sits at row q >> TWS, column q & (QC - 1) of a TH x QC tile.  TWS = 3: QR x 8
     // (q's bit position in the membership mask and its place in the tile coincide); TWS = 2 with QR = 2: 4 x 4 pixels --
     // the most compact 16-pixel tile, 7-8 % fewer union taps on the benchmark pair (233 against 252 per tile) -- with
@@ -1209,8 +1219,13 @@ __global__ void __launch_bounds__(NT, (SKIP == 6 ? (C <= 2 ? 5 : C == 3 ? 4 : 3)
             if (FULL || dl + k < D) __builtin_nontemporal_store(mean[k], dst + k);
         }
         if (disp) {
-            const int wd = wave_wta<C, FULL>(mean, dl, D);
-            if (lane == 0) disp[p] = (float)wd;
+            if constexpr (SUB) {
+                const float wf = wave_wta_subpixel<C, FULL>(mean, dl, D, min_den);
+                if (lane == 0) disp[p] = wf;
+            } else {
+                const int wd = wave_wta<C, FULL>(mean, dl, D);
+                if (lane == 0) disp[p] = (float)wd;
+            }
         }
     };
     // accumulators are read with static register numbers; pixels that need the plain walk (reference UB,
@@ -1453,6 +1468,7 @@ struct smt_crossarm {
     uint16_t *cand;      // [4][H][W] arm candidates {threshold still tau, already tau_low} (mask-based arm kernels)
     bool arm_walk;       // test hook: use the neighbour-by-neighbour kernels even when the masks apply
     int occ_lds;         // dynamic LDS bytes per aggregation workgroup, used as an occupancy limiter (see smt_crossarm_set_occupancy)
+    float sub_min_den;   // smt_crossarm_set_subpixel: > 0 = the WTA of smt_crossarm_aggregate is refined; 0 = off
 };
 
 SMT_API void smt_crossarm_default_params(smt_crossarm_params *p)
@@ -1669,9 +1685,10 @@ static void launch_agg_quad(smt_crossarm *h, const float *vin, float *vout, floa
 #undef SMT_AGGQ
 }
 
-template <int ORDER, int QR, int SKIP, int TWS = 3>
+template <int ORDER, int QR, int SKIP, int TWS = 3, bool SUB = false>
 static void launch_agg_multi(smt_crossarm *h, const float *vin, float *vout, float *disp)
 {
+    const float min_den = SUB ? h->sub_min_den : 0.0f;
     constexpr int TH = (8 * QR) >> TWS;
     const int SW = agg_tile_width(h->strip_w8);
     dim3 grid((unsigned)agg_tile_grid(agg_tiles<TWS, TH>(h->H, SW), h->W, SW, h->sweep));
@@ -1679,8 +1696,8 @@ static void launch_agg_multi(smt_crossarm *h, const float *vin, float *vout, flo
     const bool full = (h->D == 64 * C);
     int *ub = h->flip + 4;
 #define SMT_AGGM(CC, FF)                                                                                  \
-    hipLaunchKernelGGL((k_aggregate_multi<CC, ORDER, FF, QR, SKIP, TWS>), grid, dim3(NT), (size_t)h->occ_lds, h->stream, vin, vout, h->H, h->W, \
-                       h->D, h->arm[0], h->arm[1], h->arm[2], h->arm[3], disp, ub, SW, h->member, h->sweep)
+    hipLaunchKernelGGL((k_aggregate_multi<CC, ORDER, FF, QR, SKIP, TWS, SUB>), grid, dim3(NT), (size_t)h->occ_lds, h->stream, vin, vout, h->H, h->W, \
+                       h->D, h->arm[0], h->arm[1], h->arm[2], h->arm[3], disp, ub, SW, h->member, h->sweep, min_den)
     if constexpr (SKIP == 6) {
         switch (C) {                                       // D is a multiple of 64 here (smt_crossarm_aggregate)
         case 1: SMT_AGGM(1, true); break;
@@ -1727,15 +1744,16 @@ static void launch_agg_pipe(smt_crossarm *h, const float *vin, float *vout, floa
 #undef SMT_AGGP
 }
 
-template <int ORDER>
+template <int ORDER, bool SUB = false>
 static void launch_agg(smt_crossarm *h, const float *vin, float *vout, float *disp)
 {
     dim3 grid((unsigned)agg_plain_grid(h->H * h->W));
     const int C = (h->D + 63) / 64;
     int *ub = h->flip + 4;
+    const float min_den = SUB ? h->sub_min_den : 0.0f;
 #define SMT_AGG(CC)                                                                                   \
-    hipLaunchKernelGGL((k_aggregate<CC, ORDER>), grid, dim3(NT), 0, h->stream, vin, vout, h->H, h->W, \
-                       h->D, h->arm[0], h->arm[1], h->arm[2], h->arm[3], disp, ub)
+    hipLaunchKernelGGL((k_aggregate<CC, ORDER, SUB>), grid, dim3(NT), 0, h->stream, vin, vout, h->H, h->W, \
+                       h->D, h->arm[0], h->arm[1], h->arm[2], h->arm[3], disp, ub, min_den)
     switch (C) {
     case 1: SMT_AGG(1); break;
     case 2: SMT_AGG(2); break;
@@ -1798,6 +1816,24 @@ SMT_API int smt_crossarm_aggregate(smt_crossarm *h, const float *vin, float *vou
     if (variant != 1 && (size_t)h->H * h->W * h->D * 4 >= ((size_t)1 << 32)) variant = 1;
     if (h->D > 256) variant = 1;                          // 5..8 hypotheses per lane: the plain walk only
     if (variant == 10 && (h->D % 64 != 0 || ((uintptr_t)vin & 15) != 0)) variant = 12;   // the four-taps form gathers whole 16-byte quads
+    // smt_crossarm_set_subpixel: the refined WTA is fused into the plain walk and into the default form; every other
+    // variant aggregates into vout without a map and smt_wta_subpixel reads vout back (the composed route)
+    if (disp && h->sub_min_den > 0.0f) {
+        if (order == 2) launch_agg<2, true>(h, vin, vout, disp);
+        else if (variant == 1) { if (order == 0) launch_agg<0, true>(h, vin, vout, disp); else launch_agg<1, true>(h, vin, vout, disp); }
+        else if (variant == 13) { if (order == 0) launch_agg_multi<0, 2, 7, 2, true>(h, vin, vout, disp); else launch_agg_multi<1, 2, 7, 2, true>(h, vin, vout, disp); }
+        else {
+            const float keep = h->sub_min_den;
+            h->sub_min_den = 0.0f;
+            const int rc = smt_crossarm_aggregate(h, vin, vout, order, nullptr);
+            h->sub_min_den = keep;
+            if (rc != SMT_OK) return rc;
+            const smt_subpixel_params sp{keep};
+            return smt_wta_subpixel(vout, h->H, h->W, h->D, &sp, disp, (void *)h->stream);
+        }
+        SMT_LAUNCH_CHECK();
+        return SMT_OK;
+    }
     if (order == 2) { launch_agg<2>(h, vin, vout, disp); SMT_LAUNCH_CHECK(); return SMT_OK; }   // inactive sibling: plain walk only
     if (variant == 0) { if (order == 0) launch_agg_quad<0, 4>(h, vin, vout, disp); else launch_agg_quad<1, 4>(h, vin, vout, disp); }
     else if (variant == 1) { if (order == 0) launch_agg<0>(h, vin, vout, disp); else launch_agg<1>(h, vin, vout, disp); }
@@ -1814,6 +1850,13 @@ SMT_API int smt_crossarm_aggregate(smt_crossarm *h, const float *vin, float *vou
     else if (variant == 13) { if (order == 0) launch_agg_multi<0, 2, 7, 2>(h, vin, vout, disp); else launch_agg_multi<1, 2, 7, 2>(h, vin, vout, disp); }
     else { if (order == 0) launch_agg_pipe<0>(h, vin, vout, disp); else launch_agg_pipe<1>(h, vin, vout, disp); }
     SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+SMT_API int smt_crossarm_set_subpixel(smt_crossarm *h, const smt_subpixel_params *p)
+{
+    if (!h || (p && !spx_min_den_ok(p->min_den))) return SMT_ERR_ARG;
+    h->sub_min_den = p ? p->min_den : 0.0f;
     return SMT_OK;
 }
 

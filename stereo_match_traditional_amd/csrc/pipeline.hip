@@ -181,6 +181,18 @@ SMT_API int smt_pipeline_set_quirks(smt_pipeline *h, unsigned quirks)
     return rc;
 }
 
+SMT_API int smt_pipeline_set_subpixel(smt_pipeline *h, const smt_subpixel_params *p)
+{
+    if (!h || (p && !spx_min_den_ok(p->min_den))) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    // the maps a run writes: dispL by the scanline handle, dispR by the right view's aggregation -- caR's where the
+    // schedule has one, else caL's, whose left-view call asks for no map
+    int rc = smt_scanline_set_subpixel(h->so, p);
+    if (rc == SMT_OK) rc = smt_crossarm_set_subpixel(h->caL, p);
+    if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_subpixel(h->caR, p);
+    return rc;
+}
+
 #define PIPE_HIP(call) do { if (rc == SMT_OK && (call) != hipSuccess) rc = SMT_ERR_HIP; } while (0)
 
 // main.cpp:93-94 for pair b, on M after its LR check

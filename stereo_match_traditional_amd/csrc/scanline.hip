@@ -67,6 +67,7 @@ struct ScanArgs {
     float *disp;         // fused WTA of the accumulated volume (last pass) or null
     int H, W, D;
     float p1, p2;
+    float min_den;       // MODE 4: the sub-pixel rule's parameter (subpixel_rule.h), else unused
 };
 
 template <int C> struct vecf { float v[C]; };          // C = 5..8 (D > 256)
@@ -122,7 +123,8 @@ __device__ __forceinline__ void st_row(float *p, int dl, int D, const float (&sr
 
 // PASS: 0 left->right, 1 right->left, 2 top->bottom, 3 bottom->top
 // MODE: 0 out = path ; 1 out = out + path ; 2 out = out + path and fused WTA of the sum ;
-//       3 out = (out + add2) + path
+//       3 out = (out + add2) + path ; 4 = 2 with the winner refined by the sub-pixel rule (smt_scanline_set_subpixel;
+//       the last pass only)
 // FIXV (PASS >= 2 only): the vertical pass is the horizontal recurrence along a column instead of the reference's
 template <int C, int PASS, int MODE, bool FULL, bool FIXV = false>
 __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int line)
@@ -131,7 +133,8 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
     constexpr int PF = (PASS < 2) ? PF_H : PF_V;
     constexpr bool ACC = (MODE >= 1);
     constexpr bool ACC2 = (MODE == 3);
-    constexpr bool WTA = (MODE == 2);
+    constexpr bool WTA = (MODE == 2 || MODE == 4);
+    constexpr bool SUB = (MODE == 4);
     const int lane = threadIdx.x & 63;
     constexpr bool HORIZ = (PASS < 2);
     const int H = a.H, W = a.W, D = a.D;
@@ -156,8 +159,13 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
     const float p1 = a.p1;
 
     auto wta_store = [&](const float (&res)[C], long pix) {
-        const int wd = wave_wta<C, FULL>(res, dl, D);
-        if (lane == 0) a.disp[pix] = (float)wd;
+        if constexpr (SUB) {
+            const float wf = wave_wta_subpixel<C, FULL>(res, dl, D, a.min_den);
+            if (lane == 0) a.disp[pix] = wf;
+        } else {
+            const int wd = wave_wta<C, FULL>(res, dl, D);
+            if (lane == 0) a.disp[pix] = (float)wd;
+        }
     };
 
     float last[C];
@@ -303,6 +311,7 @@ struct smt_scanline {
     hipStream_t stream;
     float *scratch;      // one [H][W][D] volume: the right path until the up pass consumes it
     bool fix_vertical;   // SMT_QUIRK_FIX_SCAN_VERTICAL
+    float sub_min_den;   // smt_scanline_set_subpixel: > 0 = the fused WTA of smt_scanline_run is refined; 0 = off
 };
 
 SMT_API int smt_scanline_create(int H, int W, int D, int p1, int p2, smt_scanline **out)
@@ -344,6 +353,22 @@ SMT_API int smt_scanline_set_quirks(smt_scanline *h, unsigned quirks)
     return SMT_OK;
 }
 
+SMT_API int smt_scanline_set_subpixel(smt_scanline *h, const smt_subpixel_params *p)
+{
+    if (!h || (p && !spx_min_den_ok(p->min_den))) return SMT_ERR_ARG;
+    h->sub_min_den = p ? p->min_den : 0.0f;
+    return SMT_OK;
+}
+
+// MODE 4 exists for the last pass only
+template <int C, bool FULL>
+static void launch_scan_sub(smt_scanline *h, const ScanArgs &a)
+{
+    dim3 grid((h->W + NTS / 64 - 1) / (NTS / 64));
+    if (h->fix_vertical) hipLaunchKernelGGL((k_scan<C, 3, 4, FULL, true>), grid, dim3(NTS), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_scan<C, 3, 4, FULL>), grid, dim3(NTS), 0, h->stream, a);
+}
+
 template <int C, int MODE, bool FULL>
 static void launch_scan2(smt_scanline *h, int pass, const ScanArgs &a)
 {
@@ -373,11 +398,13 @@ static void launch_scan(smt_scanline *h, int pass, const ScanArgs &a, int mode)
         if (mode == 0) launch_scan2<CF, 0, true>(h, pass, a);
         else if (mode == 1) launch_scan2<CF, 1, true>(h, pass, a);
         else if (mode == 2) launch_scan2<CF, 2, true>(h, pass, a);
+        else if (mode == 4) launch_scan_sub<CF, true>(h, a);
         else launch_scan2<CF, 3, true>(h, pass, a);
     } else {
         if (mode == 0) launch_scan2<C, 0, false>(h, pass, a);
         else if (mode == 1) launch_scan2<C, 1, false>(h, pass, a);
         else if (mode == 2) launch_scan2<C, 2, false>(h, pass, a);
+        else if (mode == 4) launch_scan_sub<C, false>(h, a);
         else launch_scan2<C, 3, false>(h, pass, a);
     }
 }
@@ -437,5 +464,6 @@ SMT_API int smt_scanline_run(smt_scanline *h, const float *vin, const float *gra
     int rc = scan_pass(h, a, 2, 3);                                        // vout = (left + right) + up
     if (rc != SMT_OK) return rc;
     a.disp = disp;
-    return scan_pass(h, a, 3, disp ? 2 : 1);                               // vout = (..) + down [+ WTA]
+    a.min_den = h->sub_min_den;
+    return scan_pass(h, a, 3, disp ? (h->sub_min_den > 0.0f ? 4 : 2) : 1);  // vout = (..) + down [+ WTA, refined or not]
 }

@@ -4,6 +4,7 @@
 #include <mutex>
 #include <stdint.h>
 #include "../../include/smt.h"
+#include "subpixel_rule.h"
 
 #define SMT_API extern "C" __attribute__((visibility("default")))
 
@@ -176,6 +177,30 @@ __device__ __forceinline__ int wave_wta(const float (&v)[C], int dl, int D)
     const int wd = __builtin_amdgcn_readlane(dl + bk, first);
     const int nan0 = __builtin_amdgcn_readlane((int)(v[0] != v[0]), 0);   // lane 0 owns d = 0
     return nan0 ? 0 : wd;
+}
+
+// wave_wta with the winner refined by the parabola through it and its two neighbours (spx_refine, subpixel_rule.h),
+// returned wave-uniform.  The neighbours d = w - 1 and w + 1 sit in lane d / C, register d % C: every register of that
+// lane is read with v_readlane at the wave-uniform lane and an unrolled scalar select on the wave-uniform d % C picks
+// one, so nothing goes through LDS and the row is not read again.  (Selecting the register first and reading one lane
+// is the same thing to the compiler as v[d % C], and it moves such an array to LDS.)  A winner at either end of the
+// range is returned as it is.
+template <int C, bool FULL>
+__device__ __forceinline__ float wave_wta_subpixel(const float (&v)[C], int dl, int D, float min_den)
+{
+    const int w = wave_wta<C, FULL>(v, dl, D);
+    if (w == 0 || w == D - 1) return (float)w;
+    auto at = [&](int d) {
+        const int l = d / C, r = d - l * C;
+        int x = __builtin_amdgcn_readlane(__float_as_int(v[0]), l);
+#pragma unroll
+        for (int k = 1; k < C; k++) {
+            const int xk = __builtin_amdgcn_readlane(__float_as_int(v[k]), l);
+            x = (r == k) ? xk : x;
+        }
+        return __int_as_float(x);
+    };
+    return spx_refine(w, D, at(w - 1), at(w), at(w + 1), min_den);
 }
 
 // Correctly rounded a[k] / b for a wave-uniform integer-valued divisor 1 <= b <= 65535 (a rectangle area, a support

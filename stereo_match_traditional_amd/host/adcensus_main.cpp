@@ -5,6 +5,9 @@
 //   usage: adcensus_main [--fix] H W D seed            (--fix anywhere: SMT_QUIRK_FIX_ALL on every stage of the two
 //                                                       single-pair forms -- the algorithm as it was meant, on any
 //                                                       image shape; without it every reference defect is reproduced)
+//          --subpixel [min_den] anywhere: the maps of the aggregation and of the scanline optimiser carry the parabola's
+//                                                      fraction (smt_wta_subpixel; min_den defaults to Sad.h:80's 1).  A
+//                                                      number right behind it is min_den: without one, put it last
 //          adcensus_main --images left.png right.png D [disparity_out.png]     (imread -> cvtColor -> pipeline
 //                                                     -> imwrite, the file path of main.cpp:16-20, :115-117)
 //          adcensus_main --batch pairs H W D             (config 5 on every visible GPU, one handle per device)
@@ -87,6 +90,16 @@ int main(int argc, char **argv)
             for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
             argc--; k--;
         }
+    float subpixel = 0.0f;                                // --subpixel [min_den]: 0 = integer maps
+    for (int k = 1; k < argc; k++)
+        if (!strcmp(argv[k], "--subpixel")) {
+            char *end = nullptr;
+            const float v = k + 1 < argc ? strtof(argv[k + 1], &end) : 0.0f;
+            const int take = (end && end != argv[k + 1] && !*end) ? 2 : 1;     // the next word, if it is a number
+            subpixel = take == 2 ? v : 1.0f;                                   // Sad.h:80
+            for (int m = k; m + take < argc; m++) argv[m] = argv[m + take];
+            argc -= take; k--;
+        }
     int row = argc > 1 ? atoi(argv[1]) : 72, col = argc > 2 ? atoi(argv[2]) : 160;
     int dispRange = argc > 3 ? atoi(argv[3]) : 64;
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 3;
@@ -129,6 +142,7 @@ int main(int argc, char **argv)
 
         smt::CrossArmAggregation CrossArm;
         CrossArm.setQuirks(quirks);
+        CrossArm.setSubpixel(subpixel);
         CrossArm.Initialize(row, col, leftptr.data(), rightptr.data(), tao, dispRange);
         CrossArm.ComputeArmLengths(leftGray.data(), 1);
         CrossArm.AggregationVertical(costVolumeLeftPtr, aggL.data());
@@ -142,6 +156,7 @@ int main(int argc, char **argv)
 
         smt::ScanlineOptimizer ScanlineOpt;               // main.cpp:86-89 (enabled)
         ScanlineOpt.setQuirks(quirks);
+        ScanlineOpt.setSubpixel(subpixel);
         ScanlineOpt.Initialize(row, col, dispRange, aggL.data(), p1, p2);
         ScanlineOpt.ScanLine(aggL.data(), leftptr.data());
         ScanlineOpt.WTA(leftDisp.data());

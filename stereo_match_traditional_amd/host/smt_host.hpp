@@ -136,7 +136,15 @@ public:
         p.tau = tao;
         p.quirks = quirks_;
         check(smt_crossarm_create(row, col, dispRange, &p, &h_), "smt_crossarm_create");
+        apply_subpixel();
         started_ = false;
+    }
+    // Sub-pixel switch (smt_crossarm_set_subpixel): min_den > 0 = WTA and the device map of AggregationVerticalDevice
+    // are refined by the parabola rule, 0 = integer maps (the default).  Kept across Initialize.
+    void setSubpixel(float min_den)
+    {
+        sub_ = min_den;
+        if (h_) apply_subpixel();
     }
     // SMT_QUIRK_* (SMT_QUIRK_FIX_RIGHT_ARM_STRIDE and SMT_QUIRK_FIX_STICKY_TAU act here); 0 = the reference's results.
     // They are parameters of the handle: call it before Initialize, which every use of the class starts with.
@@ -184,10 +192,17 @@ public:
         const size_t n = (size_t)row_ * col_;
         DevBuf<float> v(n * D_), d(n);
         v.upload(AggredCostVolume);
-        check(smt_wta(v.get(), row_, col_, D_, d.get(), nullptr), "wta");
+        if (sub_ != 0.0f) { const smt_subpixel_params sp{sub_}; check(smt_wta_subpixel(v.get(), row_, col_, D_, &sp, d.get(), nullptr), "wta_subpixel"); }
+        else check(smt_wta(v.get(), row_, col_, D_, d.get(), nullptr), "wta");
         d.download(disp);
     }
 private:
+    void apply_subpixel()
+    {
+        const smt_subpixel_params sp{sub_};
+        check(smt_crossarm_set_subpixel(h_, sub_ != 0.0f ? &sp : nullptr), "smt_crossarm_set_subpixel");
+    }
+    float sub_ = 0.0f;
     void arm_dir(const unsigned char *image, int channels, int dir)
     {
         DevBuf<unsigned char> img((size_t)row_ * col_ * channels);
@@ -213,7 +228,15 @@ public:
         if (h_) { smt_scanline_destroy(h_); h_ = nullptr; }
         check(smt_scanline_create(row, col, dispRange, p1, p2, &h_), "smt_scanline_create");
         if (quirks_) check(smt_scanline_set_quirks(h_, quirks_), "smt_scanline_set_quirks");
+        apply_subpixel();
         processed_.resize((size_t)row * col * dispRange);
+    }
+    // Sub-pixel switch (smt_scanline_set_subpixel): min_den > 0 = WTA gives the winner refined by the parabola rule,
+    // 0 = the integer map (the default).  Kept across Initialize.
+    void setSubpixel(float min_den)
+    {
+        sub_ = min_den;
+        if (h_) apply_subpixel();
     }
     // SMT_QUIRK_* (SMT_QUIRK_FIX_SCAN_VERTICAL acts here); 0 = the reference's results.  Kept across Initialize.
     void setQuirks(unsigned quirks)
@@ -232,11 +255,18 @@ public:
     void WTA(float *disp)
     {
         DevBuf<float> d((size_t)row_ * col_);
-        check(smt_wta(processed_.get(), row_, col_, D_, d.get(), nullptr), "wta");
+        if (sub_ != 0.0f) { const smt_subpixel_params sp{sub_}; check(smt_wta_subpixel(processed_.get(), row_, col_, D_, &sp, d.get(), nullptr), "wta_subpixel"); }
+        else check(smt_wta(processed_.get(), row_, col_, D_, d.get(), nullptr), "wta");
         d.download(disp);
     }
     float *DeviceProcessedVolume() { return processed_.get(); }
 private:
+    void apply_subpixel()
+    {
+        const smt_subpixel_params sp{sub_};
+        check(smt_scanline_set_subpixel(h_, sub_ != 0.0f ? &sp : nullptr), "smt_scanline_set_subpixel");
+    }
+    float sub_ = 0.0f;
     smt_scanline *h_ = nullptr;
     unsigned quirks_ = 0;
     int row_ = 0, col_ = 0, D_ = 0;
@@ -884,6 +914,51 @@ inline void ComputeDispOringin(float *costVolume, float *disp, int dispRange, in
     check(smt_wta(v.get(), row, col, dispRange, d.get(), nullptr), "smt_wta");
     d.download(disp);
 }
+
+// The winner of every row refined by the parabola through it and its two neighbours (smt_wta_subpixel: the value
+// Sad.h:76-81 and CBLSM.h:285-290 compute and drop).  min_den = the reference's literal 1.
+inline void WTASubpixel(float *costVolume, float *disp, int dispRange, int row, int col, float min_den = 1.0f)
+{
+    const size_t n = (size_t)row * col;
+    DevBuf<float> v(n * dispRange), d(n);
+    v.upload(costVolume);
+    const smt_subpixel_params sp{min_den};
+    check(smt_wta_subpixel(v.get(), row, col, dispRange, &sp, d.get(), nullptr), "smt_wta_subpixel");
+    d.download(disp);
+}
+
+// ------------------------------------------------------------------ the batched main.cpp pipeline (smt_pipeline_*)
+// Host buffers in and out: grayL / grayR uint8 [pairs][row][col]; dispL (after the LR check), dispR float and cls uint8
+// [pairs][row][col].  setSubpixel(min_den): both maps refined (smt_pipeline_set_subpixel), 0 = integer maps, the default.
+class Pipeline {
+public:
+    Pipeline(int row, int col, int dispRange, const smt_pipeline_params *p = nullptr) : row_(row), col_(col)
+    {
+        check(smt_pipeline_create(row, col, dispRange, p, &h_), "smt_pipeline_create");
+    }
+    ~Pipeline() { if (h_) smt_pipeline_destroy(h_); }
+    Pipeline(const Pipeline &) = delete;
+    Pipeline &operator=(const Pipeline &) = delete;
+    void setQuirks(unsigned quirks) { check(smt_pipeline_set_quirks(h_, quirks), "smt_pipeline_set_quirks"); }
+    void setSubpixel(float min_den)
+    {
+        const smt_subpixel_params sp{min_den};
+        check(smt_pipeline_set_subpixel(h_, min_den != 0.0f ? &sp : nullptr), "smt_pipeline_set_subpixel");
+    }
+    void RunBatch(const unsigned char *grayL, const unsigned char *grayR, int pairs, float *dispL, float *dispR, unsigned char *cls)
+    {
+        const size_t n = (size_t)pairs * row_ * col_;
+        DevBuf<unsigned char> l(n), r(n), c(n);
+        DevBuf<float> dl(n), dr(n);
+        l.upload(grayL); r.upload(grayR);
+        check(smt_pipeline_run_batch(h_, l.get(), r.get(), pairs, dl.get(), dr.get(), c.get(), nullptr), "smt_pipeline_run_batch");
+        check(smt_pipeline_status(h_), "smt_pipeline_status");
+        dl.download(dispL); dr.download(dispR); c.download(cls);
+    }
+private:
+    smt_pipeline *h_ = nullptr;
+    int row_, col_;
+};
 
 // ------------------------------------------------------------------ config 5: a batch over the node's GPUs
 // One host thread, one smt_adcensus handle per device (smt_adcensus_create_on); pair b goes to device
