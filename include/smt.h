@@ -256,7 +256,7 @@ int smt_host_free(void *p);
 int smt_adcensus_host_selftest_schedule(int pairs, int chunk);
 
 /* GetPtrLeft / GetPtrRight (AD-Census.h:50-72): borrowed device pointer, valid until
- * destroy. view = SMT_VIEW_LEFT or SMT_VIEW_RIGHT.  The first call on a handle ends the deferral of
+ * destroy, to the view's float32 [H][W][D] volume. view = SMT_VIEW_LEFT or SMT_VIEW_RIGHT.  The first call on a handle ends the deferral of
  * smt_adcensus_compute_batch's last pair for good; if that pair's volumes are pending it writes both with one
  * launch of the both-views cost kernel on the handle's stream and waits for it (with smt_adcensus_timing on,
  * that launch is one more entry of smt_adcensus_kernel_times, with ~0 for the tables).  Every later call only
@@ -422,6 +422,7 @@ int smt_crossarm_load_arm_maps(smt_crossarm *h, const int *left, const int *righ
  *          EXCLUSIVE upper bounds [-up, down) x [-L, R); a pixel whose rectangle is empty divides 0 by 0
  *          (:138) -- the result is NaN there and smt_crossarm_status returns SMT_ERR_REF_UB.
  * Sequential float adds in exactly that order, divided by the tap count.
+ * vol_in, vol_out float32 [H][W][D] of the handle, distinct; disp float32 [H][W].
  * If disp != NULL the WTA of the aggregated volume is fused (CrossArm.cpp:33-57).
  * Returns SMT_ERR_REF_UB from smt_crossarm_status when a rectangle leaves the plane
  * (possible with the right-arm stride bug on small / non-landscape images). */
@@ -537,7 +538,8 @@ int smt_scanline_set_subpixel(smt_scanline *h, const smt_subpixel_params *p);
 
 /* ScanlineOptimizer::ScanLine (:104-128): the four passes and ((left+right)+up)+down,
  * written to vol_out (`_ProcessedVolume`).  gray: float32 [H][W] guidance image
- * (`leftptr`, main.cpp:88).  If disp != NULL, ScanlineOptimizer::WTA (:40-64) is fused.
+ * (`leftptr`, main.cpp:88).  vol_in, vol_out float32 [H][W][D]; disp float32 [H][W].
+ * If disp != NULL, ScanlineOptimizer::WTA (:40-64) is fused.
  * vol_out must not alias vol_in. */
 int smt_scanline_run(smt_scanline *h, const float *vol_in, const float *gray, float *vol_out,
                      float *disp);
@@ -577,6 +579,8 @@ int smt_pipeline_set_subpixel(smt_pipeline *h, const smt_subpixel_params *p);
  *   dispL   float32 [pairs][H][W]: the scanline WTA map after the LR check (+inf = rejected)
  *   dispR   float32 [pairs][H][W]: WTA of the aggregated right volume (main.cpp:84)
  *   cls     uint8   [pairs][H][W] as smt_lrcheck;  counts int32 [pairs][2] (may be NULL)
+ * dispL, dispR and cls are all required, and pairs >= 1: SMT_ERR_ARG for a NULL handle, image or map and for
+ * pairs <= 0 (an empty batch is not a no-op here, unlike the flows below).
  * Asynchronous: the call enqueues and returns; part of the work runs on streams the handle owns (the right
  * view's aggregation beside the left view's scanline passes, see csrc/pipeline.hip), but everything a call
  * enqueued is ordered before whatever the caller enqueues next on the handle's stream, and after whatever the
@@ -631,7 +635,7 @@ int smt_cblsm_flow_set_stream(smt_cblsm_flow *h, void *stream);
  * costAggregationV5 pass of the left view (ComputeAD volume, left arms) and of the right view (ComputeADRight volume,
  * right arms); the second pass of the left view on the left arms and of the right view on the LEFT arms (:150); the
  * WTA of each second pass (ComputeDispOringin, :152-153).
- *   dispL, dispR   float32 [pairs][H][W], integer-valued
+ *   dispL, dispR   float32 [pairs][H][W], integer-valued; both required (SMT_ERR_ARG for a NULL map or image, pairs < 0)
  * The first pass never materialises the AD volume while max(sec_length, max_length) <= 127: its sums are then exact in
  * float and come from a summed-area table, bit-identical to the reference's loop (csrc/cblsm.hip); above that bound it
  * is smt_cblsm_ad + smt_crossarm_aggregate(order 1).  pairs == 0 is a no-op.  Asynchronous like
@@ -778,7 +782,8 @@ int smt_lrcheck_lists(const uint8_t *cls_host, int H, int W, int *occlusion_pair
  * the list was not replaced) return it.  SMT_ERR_REF_UB where the reference writes out of
  * bounds: a listed pair outside the buffer (nothing is modified), or more third-pass holes than
  * the mismatch list had entries (`fill_disps` is sized before the list is replaced, :177 vs
- * :186; passes 0 and 1 have been applied by then, as in the reference).  Synchronising. */
+ * :186; passes 0 and 1 have been applied by then, as in the reference).  A list pointer may be NULL when
+ * its count is 0 (the data() of an empty std::vector); n_occ / n_mis < 0 is SMT_ERR_ARG.  Synchronising. */
 int smt_fill_the_hole(float *disp, int row, int col, int dispRange, const int *occlusion_pairs,
                       int n_occ, const int *mismatch_pairs, int n_mis, int *third_pairs,
                       int *n_third, void *stream);
@@ -831,7 +836,7 @@ int smt_crossagg_aggregate(smt_crossagg *h, const uint8_t *img_left, const float
 /* Test hook: 2 = shared-tap passes (16 pixels per wave along the pass axis, default), 1 = one pixel per wave
  * (first formulation).  Identical bits. */
 int smt_crossagg_set_impl(smt_crossagg *h, int impl);
-/* get_cost_ptr (:125-133) / get_arms_ptr (:120-123): borrowed. arms: uint8 [H][W][4] =
+/* get_cost_ptr (:125-133) / get_arms_ptr (:120-123): borrowed. cost: float32 [H][W][D]; arms: uint8 [H][W][4] =
  * left,right,top,bottom (struct CrossArm, cross_aggregator.h:17-20). */
 int smt_crossagg_cost(smt_crossagg *h, float **cost);
 int smt_crossagg_arms(smt_crossagg *h, uint8_t **arms);
@@ -1128,7 +1133,8 @@ int smt_asw_masks(int winSize, double sigma_space, double sigma_color, double *s
 /* AdaptiveSupportWeight (ASW.h:329-378, SMT_VIEW_LEFT) / AdaptiveSupportWeightRight
  * (:382-431, SMT_VIEW_RIGHT): bilateralfiterWight (:210-257) per hypothesis + WinTakeAll
  * (:193-208).  Lp, Rp: uint8 [H+2w][W+2w] replicate-padded by w = winSize+1
- * (ASWeight.cpp:54-57); space/color: DEVICE float64 tables from smt_asw_masks; T: error
+ * (ASWeight.cpp:54-57); space/color: DEVICE float64 tables from smt_asw_masks, (2*winSize+3)^2 and 256 entries, all of
+ * which are read whatever the caller allocated; T: error
  * truncation.  disp float32 [H][W]; cost (optional) float32 [H][W][D]. */
 int smt_asw(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winSize,
             const double *space, const double *color, int T, int view, float *disp, float *cost,

@@ -10,7 +10,12 @@
 // Deviations (all forced by the missing OpenCV dependency, none changes results):
 //   - cv::Mat parameters become (const unsigned char* data, int channels).
 //   - Errors: the reference returns void and has UB on bad input; these methods throw
-//     std::runtime_error carrying smt_strerror().
+//     std::runtime_error carrying smt_strerror().  What the C entry cannot see is checked here, before any device work: a
+//     negative pair count, a padded image smaller than its border, ASW masks of another window size, an Image whose
+//     vector does not hold rows * cols * channels bytes, CrossAggregator::Aggregate without SetData.
+//   - The classes that own a handle are not copyable.
+// tests/test_cpp_mirror_cpu.py runs every function here against a contract stub of smt.h under AddressSanitizer and
+// holds this file to its case table: a new function needs a case there (or a stated reason).
 #pragma once
 #include <array>
 #include <cstdint>
@@ -25,6 +30,19 @@ namespace smt {
 inline void check(int rc, const char *what)
 {
     if (rc != SMT_OK) throw std::runtime_error(std::string(what) + ": " + smt_strerror(rc));
+}
+
+// elements of a batch of `pairs` maps of `per` elements; a negative count must not reach a size_t product
+inline size_t batch_elems_(size_t per, int pairs)
+{
+    if (pairs < 0) check(SMT_ERR_ARG, "pairs");
+    return per * (size_t)pairs;
+}
+// the unpadded size of an image padded by w on every side (the window matchers' rows / cols are the padded ones)
+inline void inner_size_(int rows, int cols, int w, int &H, int &W)
+{
+    H = rows - 2 * w; W = cols - 2 * w;
+    if (w < 1 || H <= 0 || W <= 0) check(SMT_ERR_ARG, "padded image smaller than its border");
 }
 
 // RAII device buffer
@@ -126,6 +144,8 @@ private:
 class CrossArmAggregation {
 public:
     CrossArmAggregation() = default;
+    CrossArmAggregation(const CrossArmAggregation &) = delete;            // one owner per handle
+    CrossArmAggregation &operator=(const CrossArmAggregation &) = delete;
     ~CrossArmAggregation() { if (h_) smt_crossarm_destroy(h_); }
     void Initialize(int row, int col, float * /*leftImage*/, float * /*rightImage*/, int tao, int dispRange)
     {
@@ -386,6 +406,8 @@ class CrossAggregator {
 public:
     CrossAggregator() = default;
     ~CrossAggregator() { if (h_) smt_crossagg_destroy(h_); }
+    CrossAggregator(const CrossAggregator &) = delete;                    // one owner per handle
+    CrossAggregator &operator=(const CrossAggregator &) = delete;
     bool Initialize(const int &width, const int &height, const int &min_disparity, const int &max_disparity)
     {
         w_ = width; hgt_ = height; D_ = max_disparity - min_disparity;
@@ -393,19 +415,29 @@ public:
         const int rc = smt_crossagg_create(width, height, D_, &h_);
         if (rc == SMT_ERR_ARG) return false;            // reference returns false, :28-31
         check(rc, "smt_crossagg_create");
+        // :34-35 clear + resize: zeroed arms; :52 resize: the cost buffer exists from here on (get_cost_ptr is non-null)
+        const size_t n = (size_t)w_ * hgt_;
+        host_arms_.assign(n, CrossArm{0, 0, 0, 0});
+        host_cost_.resize(n * D_);
+        if (have_params_) check(smt_crossagg_set_params(h_, L1_, L2_, t1_, t2_), "smt_crossagg_set_params");
         return true;
     }
     void SetData(const uint8_t *img_left, const uint8_t * /*img_right*/, const float *cost_init)
     {
         img_ = img_left; cost_ = cost_init;
     }
+    // The reference stores the four values in members that Initialize leaves alone (:67-74), so SetParams may come
+    // before Initialize and holds across a second one.  Never called: the library's defaults (adcensus_types.h:69-70),
+    // where the reference would run with the constructor's zeros.
     void SetParams(const int &L1, const int &L2, const int &t1, const int &t2)
     {
         if (h_) check(smt_crossagg_set_params(h_, L1, L2, t1, t2), "smt_crossagg_set_params");
+        L1_ = L1; L2_ = L2; t1_ = t1; t2_ = t2; have_params_ = true;
     }
     void Aggregate(const int &num_iters)
     {
         if (!h_) return;                                 // :91-93
+        if (!img_ || !cost_) check(SMT_ERR_ARG, "CrossAggregator::Aggregate before SetData");   // the reference reads through null
         const size_t n = (size_t)w_ * hgt_;
         DevBuf<uint8_t> img(n * 3);
         DevBuf<float> c(n * D_);
@@ -424,6 +456,8 @@ public:
 private:
     smt_crossagg *h_ = nullptr;
     int w_ = 0, hgt_ = 0, D_ = 0;
+    int L1_ = 0, L2_ = 0, t1_ = 0, t2_ = 0;
+    bool have_params_ = false;
     const uint8_t *img_ = nullptr;
     const float *cost_ = nullptr;
     std::vector<float> host_cost_;
@@ -439,7 +473,8 @@ private:
 inline void GetPointDepth(int *disparity, const unsigned char *leftimg, const unsigned char *rightimg, int rows,
                           int cols, int MaxDisparity, int winsize, bool left_view)
 {
-    const int w = winsize + 1, H = rows - 2 * w, W = cols - 2 * w;
+    int H, W;
+    inner_size_(rows, cols, winsize + 1, H, W);
     DevBuf<unsigned char> L((size_t)rows * cols), R((size_t)rows * cols);
     DevBuf<int> d((size_t)H * W);
     L.upload(leftimg); R.upload(rightimg);
@@ -456,7 +491,8 @@ inline void GetPointDepthRight(int *disparity, const unsigned char *l, const uns
 inline void GetPointDepthBoth(int *dispLeft, int *dispRight, const unsigned char *leftimg, const unsigned char *rightimg,
                               int rows, int cols, int MaxDisparity, int winsize)
 {
-    const int w = winsize + 1, H = rows - 2 * w, W = cols - 2 * w;
+    int H, W;
+    inner_size_(rows, cols, winsize + 1, H, W);
     DevBuf<unsigned char> L((size_t)rows * cols), R((size_t)rows * cols);
     DevBuf<int> dl((size_t)H * W), dr((size_t)H * W);
     L.upload(leftimg); R.upload(rightimg);
@@ -480,7 +516,7 @@ public:
     // grayL, grayR: uchar [pairs][rows][cols]; depthleft, depthright, lastdisp: int [pairs][rows][cols] (any may be null)
     void run(const unsigned char *grayL, const unsigned char *grayR, int pairs, int *depthleft, int *depthright, int *lastdisp)
     {
-        const size_t n = n_ * (size_t)pairs;
+        const size_t n = batch_elems_(n_, pairs);
         DevBuf<unsigned char> L(n), R(n), cls(n);
         DevBuf<int> dl(n), dr(n), last(n);
         L.upload(grayL); R.upload(grayR);
@@ -524,7 +560,7 @@ public:
     // leftImages, rigthImages: uchar [pairs][rows][cols]; disp: int [pairs][rows][cols]
     void run(const unsigned char *leftImages, const unsigned char *rigthImages, int pairs, int *disp)
     {
-        const size_t n = n_ * (size_t)pairs;
+        const size_t n = batch_elems_(n_, pairs);
         DevBuf<unsigned char> L(n), R(n);
         DevBuf<int> d(n);
         L.upload(leftImages); R.upload(rigthImages);
@@ -536,7 +572,7 @@ public:
     void runBoth(const unsigned char *leftImages, const unsigned char *rigthImages, int pairs, int *dispLeft, int *dispRight,
                  int *lastdisp, unsigned char *cls)
     {
-        const size_t n = n_ * (size_t)pairs;
+        const size_t n = batch_elems_(n_, pairs);
         DevBuf<unsigned char> L(n), R(n), c(n);
         DevBuf<int> dl(n), dr(n), last(n);
         L.upload(leftImages); R.upload(rigthImages);
@@ -598,7 +634,7 @@ public:
     void run(const unsigned char *in1, const unsigned char *in2, int pairs, unsigned char *depthLeft, unsigned char *depthRight,
              int *offLeft, int *offRight, int *lastdisp)
     {
-        const size_t n = n_ * (size_t)pairs;
+        const size_t n = batch_elems_(n_, pairs);
         DevBuf<unsigned char> L(n), R(n), dl(n), dr(n), c(n);
         DevBuf<int> ol(n), orr(n), last(n);
         L.upload(in1); R.upload(in2);
@@ -625,12 +661,20 @@ inline void getMasks(std::vector<double> &spaceMask, std::vector<double> &colorM
     check(smt_asw_masks(winSize, spaceSigma, colorSigma, spaceMask.data(), colorMask.data()), "smt_asw_masks");
 }
 
+// the masks smt_asw reads are (2 winSize + 3)^2 and 256 doubles whatever the vectors hold: shorter ones must not be uploaded
+inline void check_masks_(const std::vector<double> &space, const std::vector<double> &color, int winSize)
+{
+    const size_t side = 2 * (size_t)(winSize < 0 ? 0 : winSize) + 3;
+    if (winSize < 0 || space.size() != side * side || color.size() != 256) check(SMT_ERR_ARG, "ASW masks: getMasks(winSize) sizes expected");
+}
 // AdaptiveSupportWeight / AdaptiveSupportWeightRight (ASW.h:329-431); disp float [rows-2w][cols-2w], w = winSize+1
 inline void AdaptiveSupportWeight(float *disp, const unsigned char *leftGray, const unsigned char *rightGray, int rows,
                                   int cols, int winSize, int dispRange, const std::vector<double> &space,
                                   const std::vector<double> &color, int T, bool left_view = true)
 {
-    const int w = winSize + 1, H = rows - 2 * w, W = cols - 2 * w;
+    int H, W;
+    inner_size_(rows, cols, winSize + 1, H, W);
+    check_masks_(space, color, winSize);
     DevBuf<unsigned char> L((size_t)rows * cols), R((size_t)rows * cols);
     DevBuf<double> sp(space.size()), cm(color.size());
     DevBuf<float> d((size_t)H * W);
@@ -646,7 +690,9 @@ inline void AdaptiveSupportWeightBoth(float *dispL, float *dispR, unsigned char 
                                       const unsigned char *rightGray, int rows, int cols, int winSize, int dispRange,
                                       const std::vector<double> &space, const std::vector<double> &color, int T)
 {
-    const int w = winSize + 1, H = rows - 2 * w, W = cols - 2 * w;
+    int H, W;
+    inner_size_(rows, cols, winSize + 1, H, W);
+    check_masks_(space, color, winSize);
     DevBuf<unsigned char> L((size_t)rows * cols), R((size_t)rows * cols), last((size_t)H * W);
     DevBuf<double> sp(space.size()), cm(color.size());
     DevBuf<float> dl((size_t)H * W), dr((size_t)H * W);
@@ -732,6 +778,12 @@ struct Image {
     int rows = 0, cols = 0, channels = 0;
     std::vector<unsigned char> data;
 };
+// an Image whose vector does not hold rows * cols * channels bytes must not be uploaded as if it did
+inline void check_image_(const Image &im, const char *what)
+{
+    if (im.rows <= 0 || im.cols <= 0 || im.channels <= 0 || im.data.size() != (size_t)im.rows * im.cols * im.channels)
+        check(SMT_ERR_ARG, what);
+}
 inline Image imread(const std::string &path, int want_channels = 3)
 {
     Image im;
@@ -748,6 +800,7 @@ inline void imwrite(const std::string &path, const unsigned char *data, int rows
 inline Image cvtColorBGR2GRAY(const Image &bgr)
 {
     if (bgr.channels != 3) throw std::runtime_error("cvtColorBGR2GRAY: 3-channel image expected");
+    check_image_(bgr, "cvtColorBGR2GRAY");
     const size_t n = (size_t)bgr.rows * bgr.cols;
     DevBuf<unsigned char> in(n * 3), out(n);
     in.upload(bgr.data.data());
@@ -763,6 +816,7 @@ inline Image cvtColorBGR2GRAY(const Image &bgr)
 // `tao` is BY VALUE -- every call starts from it again, the drop to 6 past secLength is local to the call.
 inline void arm_length_(const Image &image, unsigned char tao, int *arm, int maxLength, int secLength, int dir)
 {
+    check_image_(image, "ArmLength");
     smt_crossarm_params p;
     smt_crossarm_cblsm_params(&p);
     p.tau = tao; p.max_length = maxLength; p.sec_length = secLength;
@@ -812,6 +866,9 @@ inline void compute_disp_(float *dispVolume, const Image &leftimg, const Image &
     if (leftimg.rows != _row_ + 2 * w || leftimg.cols != _col_ + 2 * w || leftimg.channels != ch ||
         rightimg.rows != leftimg.rows || rightimg.cols != leftimg.cols || rightimg.channels != ch)
         check(SMT_ERR_ARG, "ComputeDisp: images must be padded by winsize + 1");
+    check_image_(leftimg, "ComputeDisp");
+    check_image_(rightimg, "ComputeDisp");
+    if (form == SMT_CBLSM_COST_RIGHT && _col_ <= w) check(SMT_ERR_REF_UB, "ComputeDispRight");     // before any device work
     DevBuf<unsigned char> L(leftimg.data.size()), R(rightimg.data.size());
     DevBuf<float> vol((size_t)_row_ * _col_ * dispRange);
     L.upload(leftimg.data.data()); R.upload(rightimg.data.data());
@@ -846,7 +903,7 @@ public:
 private:
     void run_(const unsigned char *grayL, const unsigned char *grayR, int pairs, int winSize, float *dispLeft, float *dispRight)
     {
-        const size_t n = n_ * (size_t)pairs;
+        const size_t n = batch_elems_(n_, pairs);
         DevBuf<unsigned char> L(n), R(n);
         DevBuf<float> dl(n), dr(n);
         L.upload(grayL); R.upload(grayR);
@@ -929,7 +986,7 @@ inline void WTASubpixel(float *costVolume, float *disp, int dispRange, int row, 
 
 // ------------------------------------------------------------------ the batched main.cpp pipeline (smt_pipeline_*)
 // Host buffers in and out: grayL / grayR uint8 [pairs][row][col]; dispL (after the LR check), dispR float and cls uint8
-// [pairs][row][col].  setSubpixel(min_den): both maps refined (smt_pipeline_set_subpixel), 0 = integer maps, the default.
+// [pairs][row][col], any of the three may be null.  setSubpixel(min_den): both maps refined (smt_pipeline_set_subpixel), 0 = integer maps, the default.
 class Pipeline {
 public:
     Pipeline(int row, int col, int dispRange, const smt_pipeline_params *p = nullptr) : row_(row), col_(col)
@@ -947,13 +1004,15 @@ public:
     }
     void RunBatch(const unsigned char *grayL, const unsigned char *grayR, int pairs, float *dispL, float *dispR, unsigned char *cls)
     {
-        const size_t n = (size_t)pairs * row_ * col_;
+        const size_t n = batch_elems_((size_t)row_ * col_, pairs);
         DevBuf<unsigned char> l(n), r(n), c(n);
         DevBuf<float> dl(n), dr(n);
         l.upload(grayL); r.upload(grayR);
         check(smt_pipeline_run_batch(h_, l.get(), r.get(), pairs, dl.get(), dr.get(), c.get(), nullptr), "smt_pipeline_run_batch");
         check(smt_pipeline_status(h_), "smt_pipeline_status");
-        dl.download(dispL); dr.download(dispR); c.download(cls);
+        if (dispL) dl.download(dispL);                   // any output may be null, as in the sibling flows
+        if (dispR) dr.download(dispR);
+        if (cls) c.download(cls);
     }
 private:
     smt_pipeline *h_ = nullptr;
@@ -974,7 +1033,22 @@ inline int AD_Census_batch_all_devices(const float *L, const float *R, int pairs
     if (G > pairs) G = pairs;
     if (G <= 0) throw std::runtime_error("no device / empty batch");
     const size_t n = (size_t)row * col;
-    struct Dev { smt_adcensus *h = nullptr; void *stream = nullptr; float *L = nullptr, *R = nullptr, *dl = nullptr, *dr = nullptr; int start = 0, count = 0; };
+    struct Dev {
+        smt_adcensus *h = nullptr; void *stream = nullptr; float *L = nullptr, *R = nullptr, *dl = nullptr, *dr = nullptr; int start = 0, count = 0;
+        int id = -1;
+        void release()      // idempotent; also what a throw half-way through the loops below runs, on every device reached
+        {
+            if (id < 0) return;
+            smt_set_device(id);
+            if (h) smt_adcensus_status(h);              // drains the device's stream before its buffers go
+            smt_free(L); smt_free(R); smt_free(dl); smt_free(dr);
+            if (h) smt_adcensus_destroy(h);
+            if (stream) smt_stream_destroy(stream);
+            h = nullptr; stream = nullptr; L = R = dl = dr = nullptr; id = -1;
+        }
+        ~Dev() { release(); }
+    };
+    struct Home { ~Home() { smt_set_device(0); } } home;       // destroyed after `dev`: the caller's device 0 again
     std::vector<Dev> dev(G);
     const int q = pairs / G, r = pairs % G;
     for (int g = 0; g < G; g++) {
@@ -982,6 +1056,7 @@ inline int AD_Census_batch_all_devices(const float *L, const float *R, int pairs
         d.count = q + (g < r ? 1 : 0);
         d.start = g * q + (g < r ? g : r);
         check(smt_set_device(g), "smt_set_device");
+        d.id = g;
         check(smt_adcensus_create_on(g, row, col, dispRange, sigmaC, sigmaS, &d.h), "smt_adcensus_create_on");
         check(smt_stream_create(&d.stream), "smt_stream_create");
         check(smt_adcensus_set_stream(d.h, d.stream), "smt_adcensus_set_stream");
@@ -999,9 +1074,7 @@ inline int AD_Census_batch_all_devices(const float *L, const float *R, int pairs
         Dev &d = dev[g];
         check(smt_set_device(g), "smt_set_device");
         check(smt_adcensus_status(d.h), "smt_adcensus_status");        // synchronises the device's stream
-        smt_free(d.L); smt_free(d.R); smt_free(d.dl); smt_free(d.dr);
-        smt_adcensus_destroy(d.h);
-        smt_stream_destroy(d.stream);
+        d.release();
     }
     check(smt_set_device(0), "smt_set_device");
     return G;
