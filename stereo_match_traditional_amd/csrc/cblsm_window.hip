@@ -3,12 +3,12 @@
 //
 // Two formulations of the gray forms:
 //   1  k_win_tap   one thread per (pixel, d), the side x side tap loop (cwrule::entry); also the only form of V4;
-//   2  k_win_box   csrc/sad_both.hip's box recurrence with the view as a template parameter: lanes along d
-//                  (d = lane + 64 k), 8 or 4 columns per wave, the rows of both images staged in LDS (box_stage.h), a
-//                  running horizontal window sum per row and a running box sum per column in registers, so the work
-//                  per hypothesis does not grow with side.  The `cost = last` chains are applied at the store: LEFT
-//                  broadcasts lane x, RIGHT the lane W - 1 - w - x; the row-constant value of RIGHT's last w columns is a
-//                  running box sum of its own, kept by the waves that own such columns.
+//   2  k_win_box   the box recurrence of csrc/box_stage.h (box_steps, the engine k_ncc_box runs too) with the view as a
+//                  template parameter: lanes along d (d = lane + 64 k), 8 or 4 columns per wave, the rows of both images
+//                  staged in LDS, a running horizontal window sum per row and a running box sum per column in
+//                  registers, so the work per hypothesis does not grow with side.  The `cost = last` chains are applied
+//                  at the store: LEFT broadcasts lane x, RIGHT the lane W - 1 - w - x; the row-constant value of RIGHT's
+//                  last w columns is a running box sum of its own, kept by the waves that own such columns.
 // The kernel writes 4 bytes per hypothesis and reads two image rows per step, so its ceiling is the store rate; the
 // volume is produced in one pass (chaining a SAD cost volume afterwards would read and write [H][W][D] once more).
 #include "smt_common.h"
@@ -30,13 +30,6 @@ constexpr int BNT = 256;                 // four waves per workgroup
 template <int KT> constexpr int win_bs() { return KT == 1 ? 8 : 4; }
 template <int KT> constexpr int win_bsw() { return win_bs<KT>() * (BNT / 64); }   // columns per workgroup
 
-// Staged row geometry, as k_sad_box: one dword per BYTE offset (entry A = bytes A .. A + 3).  "own" is the image whose
-// window stays at the pixel's column (LEFT: the left image, RIGHT: the right image), "oth" the one indexed by d (LEFT:
-// the right image at x - d, RIGHT: the left image at x + d).  Own entries start at column x0 - 1; oth entries at
-// x0 - 64 KT (LEFT) or x0 - 1 (RIGHT): one entry of slack in front, for the masked tail dword of a 3-wide window.
-__host__ __device__ inline int win_lwe(int side, int bsw) { return (bsw + side + 3) & ~3; }
-__host__ __device__ inline int win_rwe(int side, int KT, int bsw) { return (64 * KT + bsw + side + 3) & ~3; }
-
 // The kernel's quotient: a / n for a = (float)S, 0 <= S < 2^24, and fn = (float)n, 9 <= n <= 32761, rn = v_rcp_f32(fn).
 // smt_common.h's wave_quotient argument without its range ballot: a is an integer below 2^24 and fn an integer below
 // 2^16, so every value is 0 or in [1, 2^24) and the three-instruction sequence rounds as the division does; S = 0 gives
@@ -55,10 +48,12 @@ __device__ __forceinline__ void win_store(float *p, float v)
     else *p = v;
 }
 
-// grid (strips of BSW columns, bands of `band` rows, pairs).  Step t of a band that starts at row i0 brings in padded row
-// i0 + t, takes out padded row i0 + t - side (once there is one) and, from t = side - 1 on, emits output row
-// i0 + t - side + 1.  The two rows of step t + 1 are fetched into registers before step t computes and written to the
-// other half of the LDS row buffer after it; one barrier per step.  VIEW 0: ComputeDispLeft, 1: ComputeDispRight.
+// grid (strips of BSW columns, bands of `band` rows, pairs).  The staged rows, the running sums and the step loop of a band
+// are box_steps (csrc/box_stage.h) with the v_sad_u8 tap.  "own" is the image whose window stays at the pixel's column
+// (LEFT: the left image, RIGHT: the right image), "oth" the one indexed by d (LEFT: the right image at x - d, RIGHT: the
+// left image at x + d).  Own entries start at column x0 - 1; oth entries at x0 - 64 KT (LEFT) or x0 - 1 (RIGHT).  What is
+// here is RIGHT's edge sum and the emit step: the chain, the quotient, the store.  VIEW 0: ComputeDispLeft, 1:
+// ComputeDispRight.
 template <int KT, int VIEW, bool NT>
 __global__ void __launch_bounds__(BNT, 2) k_win_box(const uint8_t *__restrict__ Lp0, const uint8_t *__restrict__ Rp0, size_t img_stride,
                                                  int H, int W, int D, int w, int band, float *__restrict__ vol0, size_t vol_stride)
@@ -66,7 +61,6 @@ __global__ void __launch_bounds__(BNT, 2) k_win_box(const uint8_t *__restrict__ 
     extern __shared__ __attribute__((aligned(16))) unsigned s_box[];
     constexpr int BS = win_bs<KT>(), BSW = win_bsw<KT>();
     const int side = 2 * w + 1, Wp = W + 2 * w;
-    const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x0 = blockIdx.x * BSW, i0 = blockIdx.y * band;
     const int i1 = i0 + band < H ? i0 + band : H;
@@ -74,103 +68,16 @@ __global__ void __launch_bounds__(BNT, 2) k_win_box(const uint8_t *__restrict__ 
     const uint8_t *own = VIEW == 0 ? Lp : Rp, *oth = VIEW == 0 ? Rp : Lp;
     float *vol = vol0 + (size_t)blockIdx.z * vol_stride;
     const int nk = (D + 63) >> 6;                              // live hypothesis slots (uniform)
-    const int LWE = win_lwe(side, BSW), RWE = win_rwe(side, KT, BSW), ROWE = LWE + RWE;
-    const int xAb = x0 - 1, xBb = VIEW == 0 ? x0 - 64 * KT : x0 - 1;
-    unsigned *s_rows = s_box;                                  // [2 halves][entering, leaving][LWE own + RWE oth entries]
-
-    // staging: one item = four consecutive entries (two unaligned dword loads, three v_alignbyte, one 16-byte store).
-    // Items of a step: entering row own, entering row oth, leaving row own, leaving row oth; at most 2 per thread.
-    const int nL4 = LWE >> 2, nR4 = RWE >> 2, nrow4 = nL4 + nR4;
-    unsigned slo[2], shi[2];
-    auto fetch = [&](int t) {
-        const int rE = i0 + t, rL = rE - side;
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const int e = threadIdx.x + q * BNT;
-            slo[q] = shi[q] = 0;
-            if (e < 2 * nrow4) {
-                const int which = e >= nrow4, f = e - which * nrow4;
-                const int r = which ? rL : rE;
-                if (!which || rL >= i0) {
-                    const bool second = f >= nL4;
-                    const int x = second ? xBb + 4 * (f - nL4) : xAb + 4 * f;
-                    box_load8((second ? oth : own) + (size_t)r * Wp, x, Wp, slo[q], shi[q]);
-                }
-            }
-        }
-    };
-    auto commit = [&](int half) {
-        typedef unsigned u4v __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const int e = threadIdx.x + q * BNT;
-            if (e < 2 * nrow4)
-                *reinterpret_cast<u4v *>(s_rows + (size_t)half * 2 * ROWE + 4 * e) =
-                    u4v{slo[q], __builtin_amdgcn_alignbyte(shi[q], slo[q], 1), __builtin_amdgcn_alignbyte(shi[q], slo[q], 2),
-                        __builtin_amdgcn_alignbyte(shi[q], slo[q], 3)};
-        }
-    };
-    fetch(0);
-    commit(0);
-    __syncthreads();
-
     const int xw = x0 + BS * wv;                               // this wave's first column
-    const bool live = xw < W;
-    const int nfull = side >> 2, rem = side & 3;
-    const unsigned tmask = rem ? (0xffffffffu << (8 * (4 - rem))) : 0u;
-    const int la = xw - xAb;                                   // own entry of column xw
-    int ra[KT];                                                // oth entry of column xw - d (LEFT) / xw + d (RIGHT)
-    unsigned C[BS][KT];
-#pragma unroll
-    for (int k = 0; k < KT; k++) {
-        ra[k] = VIEW == 0 ? xw - xBb - (lane + 64 * k) : xw - xBb + (lane + 64 * k);
-#pragma unroll
-        for (int j = 0; j < BS; j++) C[j][k] = 0;
-    }
-    // horizontal window sums of one staged row over the wave's BS columns, added to (SUB = false) or taken from C
-    auto row_pass = [&](const unsigned *Arow, const unsigned *Brow, auto sub) {
-        constexpr bool SUB = decltype(sub)::value;
-        unsigned run[KT];
-#pragma unroll
-        for (int k = 0; k < KT; k++) run[k] = 0;
-        for (int g = 0; g < nfull; g++) {
-            const unsigned a4 = Arow[la + 4 * g];
-#pragma unroll
-            for (int k = 0; k < KT; k++)
-                if (k < nk) run[k] = __builtin_amdgcn_sad_u8(a4, Brow[ra[k] + 4 * g], run[k]);
-        }
-        if (rem) {
-            // the last dword ends at the window's last byte; the bytes already counted are masked out of both operands
-            const unsigned a4 = Arow[la + side - 4] & tmask;
-#pragma unroll
-            for (int k = 0; k < KT; k++)
-                if (k < nk) run[k] = __builtin_amdgcn_sad_u8(a4, Brow[ra[k] + side - 4] & tmask, run[k]);
-        }
-        const uint8_t *Ab = reinterpret_cast<const uint8_t *>(Arow), *Bb = reinterpret_cast<const uint8_t *>(Brow);
-#pragma unroll
-        for (int j = 0; j < BS; j++) {
-            if (j > 0) {
-                const unsigned aN = Ab[4 * (la + j - 1 + side)], aO = Ab[4 * (la + j - 1)];
-#pragma unroll
-                for (int k = 0; k < KT; k++)
-                    if (k < nk) {
-                        const unsigned bN = Bb[4 * (ra[k] + j - 1 + side)], bO = Bb[4 * (ra[k] + j - 1)];
-                        run[k] = __builtin_amdgcn_sad_u8(aN, bN, run[k]) - __builtin_amdgcn_sad_u8(aO, bO, 0u);
-                    }
-            }
-#pragma unroll
-            for (int k = 0; k < KT; k++)
-                if (k < nk) C[j][k] = SUB ? C[j][k] - run[k] : C[j][k] + run[k];
-        }
-    };
 
     // RIGHT's last w columns hold hypothesis 0 of column xe = W - 1 - w (cwrule::right_src): a wave that owns such a
     // column keeps that box sum E too, one horizontal window sum of the entering and of the leaving row per step, the
     // side taps spread over the lanes and read from global memory (two rows the workgroup has just staged: cache hits).
     const int xe = W - 1 - w;
-    const bool edge = VIEW == 1 && live && xw + BS - 1 > xe;
+    const bool edge = VIEW == 1 && xw < W && xw + BS - 1 > xe;
     unsigned E = 0;
-    auto edge_row = [&](int r) {
+    auto edge_row = [&](int r) __attribute__((always_inline)) {
+        const int lane = threadIdx.x & 63;                     // not captured: see box_steps
         const uint8_t *a = Lp + (size_t)r * Wp + xe, *b = Rp + (size_t)r * Wp + xe;
         unsigned s = 0;
         for (int c = lane; c < side; c += 64) s += cwrule::absdiff_u8(a[c], b[c]);
@@ -178,54 +85,41 @@ __global__ void __launch_bounds__(BNT, 2) k_win_box(const uint8_t *__restrict__ 
         for (int off = 32; off >= 1; off >>= 1) s += (unsigned)__shfl_xor((int)s, off, WAVE);
         return s;
     };
+    auto edge_step = [&](int t, bool leaving) __attribute__((always_inline)) {
+        if (edge) {
+            E += edge_row(i0 + t);
+            if (leaving) E -= edge_row(i0 + t - side);
+        }
+    };
 
     const float fn = (float)(side * side), rn = __builtin_amdgcn_rcpf(fn);
-    const int nsteps = side - 1 + (i1 - i0);
-    for (int t = 0; t < nsteps; t++) {
-        const int half = t & 1;
-        const int io = i0 + t - side + 1;                      // output row of this step (>= i0: there is one)
-        const bool leaving = t >= side;
-        if (t + 1 < nsteps) fetch(t + 1);
-        if (live) {
-            const unsigned *rows = s_rows + (size_t)half * 2 * ROWE;
-            row_pass(rows, rows + LWE, std::false_type());
-            if (leaving) row_pass(rows + ROWE, rows + ROWE + LWE, std::true_type());
-            if (edge) {
-                E += edge_row(i0 + t);
-                if (leaving) E -= edge_row(i0 + t - side);
-            }
-            if (io >= i0) {
+    auto emit = [&](int, int io, int x, const unsigned (&Cj)[KT]) __attribute__((always_inline)) {
+        const int lane = threadIdx.x & 63;                     // not captured: see box_steps
+        unsigned cc[KT];
 #pragma unroll
-                for (int j = 0; j < BS; j++) {
-                    const int x = xw + j;
-                    if (x >= W) break;
-                    unsigned cc[KT];
+        for (int k = 0; k < KT; k++) cc[k] = Cj[k];
+        // the chain: entries past `lim` repeat the entry at lim (LEFT: lim = x, RIGHT: lim = xe - x)
+        const int lim = VIEW == 0 ? x : xe - x;
+        if (lim < 0) {
 #pragma unroll
-                    for (int k = 0; k < KT; k++) cc[k] = C[j][k];
-                    // the chain: entries past `lim` repeat the entry at lim (LEFT: lim = x, RIGHT: lim = xe - x)
-                    const int lim = VIEW == 0 ? x : xe - x;
-                    if (lim < 0) {
+            for (int k = 0; k < KT; k++) cc[k] = E;
+        } else if (lim < D - 1) {
+            unsigned bc = 0;
 #pragma unroll
-                        for (int k = 0; k < KT; k++) cc[k] = E;
-                    } else if (lim < D - 1) {
-                        unsigned bc = 0;
+            for (int k = 0; k < KT; k++)
+                if (k == (lim >> 6)) bc = (unsigned)__builtin_amdgcn_readlane((int)cc[k], lim & 63);
 #pragma unroll
-                        for (int k = 0; k < KT; k++)
-                            if (k == (lim >> 6)) bc = (unsigned)__builtin_amdgcn_readlane((int)cc[k], lim & 63);
-#pragma unroll
-                        for (int k = 0; k < KT; k++)
-                            if (lane + 64 * k > lim) cc[k] = bc;
-                    }
-                    float *dst = vol + ((size_t)io * W + x) * D;
-#pragma unroll
-                    for (int k = 0; k < KT; k++)
-                        if (k < nk && lane + 64 * k < D) win_store<NT>(dst + lane + 64 * k, win_quot((float)cc[k], fn, rn));
-                }
-            }
+            for (int k = 0; k < KT; k++)
+                if (lane + 64 * k > lim) cc[k] = bc;
         }
-        if (t + 1 < nsteps) commit(half ^ 1);
-        __syncthreads();
-    }
+        float *dst = vol + ((size_t)io * W + x) * D;
+#pragma unroll
+        for (int k = 0; k < KT; k++)
+            if (k < nk && lane + 64 * k < D) win_store<NT>(dst + lane + 64 * k, win_quot((float)cc[k], fn, rn));
+    };
+    const int xAb = x0 - box_tap_sad::LEAD, xBb = VIEW == 0 ? x0 - 64 * KT : xAb;
+    box_steps<KT, BS, BNT, box_tap_sad, VIEW == 0 ? -1 : 1>(s_box, own, oth, Wp, xAb, xBb, x0, i0, i1, W, side, nk, box_no_hook(),
+                                                            edge_step, emit);
 }
 
 // The direct formulation: one thread per (pixel, d), the rules of cblsm_window_rules.h and nothing else
@@ -277,9 +171,9 @@ int launch_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int pairs, 
 {
     constexpr int BSW = win_bsw<KT>();
     const int side = 2 * w + 1;
-    int band = g_win_band > 0 ? (g_win_band < H ? g_win_band : H) : box_band(H, W, side, BSW);
+    int band = box_band_rule(g_win_band, H, W, side, BSW);
     if ((H + band - 1) / band > 65535) band = (H + 65534) / 65535;
-    const size_t shm = (size_t)4 * (win_lwe(side, BSW) + win_rwe(side, KT, BSW)) * 4;   // <= 16 KiB
+    const size_t shm = (size_t)4 * (box_lwe(side, BSW) + box_rwe(side, KT, BSW)) * 4;   // <= 16 KiB
     const dim3 grid((W + BSW - 1) / BSW, (H + band - 1) / band, pairs);
     const bool nt = g_win_store == 0 ? win_default_nt() : g_win_store == 2;
     if (nt) hipLaunchKernelGGL((k_win_box<KT, VIEW, true>), grid, dim3(BNT), shm, st, Lp, Rp, is, H, W, D, w, band, vol, vs);
@@ -291,11 +185,7 @@ int launch_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int pairs, 
 template <int VIEW>
 int run_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int pairs, size_t is, int H, int W, int D, int w, float *vol, size_t vs)
 {
-    const int K = (D + 63) / 64;
-    if (K <= 1) return launch_box<1, VIEW>(st, Lp, Rp, pairs, is, H, W, D, w, vol, vs);
-    if (K <= 2) return launch_box<2, VIEW>(st, Lp, Rp, pairs, is, H, W, D, w, vol, vs);
-    if (K <= 4) return launch_box<4, VIEW>(st, Lp, Rp, pairs, is, H, W, D, w, vol, vs);
-    return launch_box<8, VIEW>(st, Lp, Rp, pairs, is, H, W, D, w, vol, vs);
+    return box_dispatch_kt(D, [&](auto kt) { return launch_box<decltype(kt)::value, VIEW>(st, Lp, Rp, pairs, is, H, W, D, w, vol, vs); });
 }
 
 // the argument rules shared by the device entry and the host twin; on SMT_OK the dense strides are filled in

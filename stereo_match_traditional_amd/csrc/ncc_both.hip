@@ -117,21 +117,6 @@ int left_view(int form, const uint8_t *L, const uint8_t *R, int pairs, int H, in
                                      : smt_ncc_box_enqueue(L, R, pairs, H, W, D, win, sumL, rootL, sumR, rootR, disp, cost, st, rkeys);
 }
 
-struct scratch_set {                                       // arena blocks of one call, freed in reverse order
-    hipStream_t st;
-    void *p[6];
-    int n = 0;
-    explicit scratch_set(hipStream_t s) : st(s) {}
-    void *get(size_t bytes)
-    {
-        void *q = nullptr;
-        if (n >= 6 || smt_scratch_alloc(&q, bytes, st) != hipSuccess) return nullptr;
-        p[n++] = q;
-        return q;
-    }
-    ~scratch_set() { while (n > 0) smt_scratch_free(p[--n], st); }
-};
-
 }  // namespace
 
 int smt_lrncc_enqueue(int form, const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int win, int *sumL,

@@ -19,24 +19,16 @@
 
 namespace {
 
-constexpr int NBT = 256;                 // four waves per workgroup
-constexpr int NBS = 16;                  // columns per wave: C[NBS][KT] running box sums in VGPRs
-constexpr int NBSW = NBS * (NBT / 64);   // columns per workgroup (the strip width)
+constexpr int BNT = 256;                 // four waves per workgroup
+constexpr int BS = 16;                   // columns per wave: C[BS][KT] running box sums in VGPRs
+constexpr int BSW = BS * (BNT / 64);     // columns per workgroup (the strip width)
 
-// Staged row geometry, shared by the kernel and its host restatement.  A row of either image sits in LDS expanded to one
-// dword per BYTE offset (entry A = bytes A .. A + 3, as k_sad_box stages its rows): the initial window sum of a row
-// reads aligned dwords for v_dot4 whatever the hypothesis, the sliding sum reads the low byte of an entry, and lanes with
-// consecutive d read consecutive dwords (one bank each; the left entry is one address for the wave, a broadcast).  Left
-// entries start at column x0, right entries at x0 - 64 KT.  Columns outside the image are clamped into the row by
-// box_load8, for the entering and the leaving row alike: a hypothesis that reads them (x - d < 0) keeps consistent
-// running sums and costs 255.0 whatever they hold.
-__host__ __device__ inline int nbox_lwe(int side) { return (NBSW + side + 3) & ~3; }
-__host__ __device__ inline int nbox_rwe(int side, int KT) { return (64 * KT + NBSW + side + 3) & ~3; }
-
-// grid (strips of NBSW window columns, bands of `band` window rows, pairs).  Step t of a band that starts at window row
-// i0 brings in image row i0 + t, takes out image row i0 + t - side (once there is one) and, from t = side - 1 on, emits
-// window row i0 + t - side + 1, i.e. image row i0 + t - side + 1 + win.  The two rows of step t + 1 are fetched into
-// registers before step t computes and written to the other half of the LDS row buffer after it; one barrier per step.
+// grid (strips of BSW window columns, bands of `band` window rows, pairs).  The staged rows, the running sums and the step
+// loop of a band are box_steps (csrc/box_stage.h) with the v_dot4 tap, over window rows and columns: step t brings in
+// image row i0 + t and, from t = side - 1 on, emits window row io = i0 + t - side + 1, i.e. image row io + win.  Left
+// entries start at column x0, right entries at x0 - 64 KT; a hypothesis that reads clamped columns (x - d < 0) keeps
+// consistent running sums and costs 255.0 whatever they hold.  What is here is the emit step: the cost, the ordered
+// WinTakeAll and PUB's keys.
 //
 // PUB (the both-view call, csrc/ncc_both.hip): every real, non-NaN cost of (x, d) is also offered to right pixel x - d as
 // a rank key (csrc/ncc_keys.h).  The workgroup's 64 columns times 64 KT hypotheses reach 64 KT + 64 right pixels of a
@@ -44,7 +36,7 @@ __host__ __device__ inline int nbox_rwe(int side, int KT) { return (64 * KT + NB
 // agent-scope maximum per touched pixel to rkeys ([pairs][H][W], zero before the launch) and clears the row -- behind
 // the step's own barrier, so no barrier is added.
 template <int KT, bool PUB>
-__global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R, int H, int W,
+__global__ void __launch_bounds__(BNT) k_ncc_box(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R, int H, int W,
                                                  int D, int win, int band, const int *__restrict__ sumL,
                                                  const double *__restrict__ rootL, const int *__restrict__ sumR,
                                                  const double *__restrict__ rootR, int32_t *__restrict__ disp,
@@ -58,52 +50,15 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
         if (cost_out) cost_out += po * D;
         if constexpr (PUB) rkeys += po;
     }
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int x0 = blockIdx.x * NBSW, i0 = blockIdx.y * band;
+    const int x0 = blockIdx.x * BSW, i0 = blockIdx.y * band;
     const int i1 = i0 + band < Hi ? i0 + band : Hi;
     const int nk = (D + 63) >> 6;                              // live hypothesis slots (uniform)
-    const int LWE = nbox_lwe(side), RWE = nbox_rwe(side, KT), ROWE = LWE + RWE;
-    const int xLb = x0, xRb = x0 - 64 * KT;
-    unsigned *s_rows = s_nbox;                                 // [2 halves][entering, leaving][LWE left + RWE right entries]
-
-    // staging: one item = four consecutive entries (two unaligned dword loads, three v_alignbyte, one 16-byte store).
-    // Items of a step: entering row left, entering row right, leaving row left, leaving row right; at most 2 per thread.
-    const int nL4 = LWE >> 2, nR4 = RWE >> 2, nrow4 = nL4 + nR4;
-    unsigned slo[2], shi[2];
-    auto fetch = [&](int t) {
-        const int rE = i0 + t, rL = rE - side;
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const int e = threadIdx.x + q * NBT;
-            slo[q] = shi[q] = 0;
-            if (e < 2 * nrow4) {
-                const int which = e >= nrow4, f = e - which * nrow4;
-                const int r = which ? rL : rE;
-                if (!which || rL >= i0) {
-                    const bool right = f >= nL4;
-                    const int x = right ? xRb + 4 * (f - nL4) : xLb + 4 * f;
-                    box_load8((right ? R : L) + (size_t)r * W, x, W, slo[q], shi[q]);
-                }
-            }
-        }
-    };
-    auto commit = [&](int half) {
-        typedef unsigned u4v __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const int e = threadIdx.x + q * NBT;
-            if (e < 2 * nrow4)
-                *reinterpret_cast<u4v *>(s_rows + (size_t)half * 2 * ROWE + 4 * e) =
-                    u4v{slo[q], __builtin_amdgcn_alignbyte(shi[q], slo[q], 1), __builtin_amdgcn_alignbyte(shi[q], slo[q], 2),
-                        __builtin_amdgcn_alignbyte(shi[q], slo[q], 3)};
-        }
-    };
+    const int ROWE = box_lwe(side, BSW) + box_rwe(side, KT, BSW);
     // PUB: [2][NKE] keys behind the staged rows; entry e of a row is right window column x0 - 64 KT + e
-    constexpr int NKE = 64 * KT + NBSW;
+    constexpr int NKE = 64 * KT + BSW;
     unsigned long long *s_keys = reinterpret_cast<unsigned long long *>(s_nbox + 4 * ROWE);
-    auto flush = [&](int half, int io) {                       // the keys of window row io go out, the row is cleared
-        for (int e = threadIdx.x; e < NKE; e += NBT) {
+    auto flush = [&](int half, int io) __attribute__((always_inline)) {   // the keys of window row io go out, the row is cleared
+        for (int e = threadIdx.x; e < NKE; e += BNT) {
             const unsigned long long v = s_keys[half * NKE + e];
             if (v) {
                 atomicMax(rkeys + (size_t)(io + win) * W + win + (x0 - 64 * KT + e), v);
@@ -112,148 +67,74 @@ __global__ void __launch_bounds__(NBT) k_ncc_box(const uint8_t *__restrict__ L, 
         }
     };
     if constexpr (PUB)
-        for (int e = threadIdx.x; e < 2 * NKE; e += NBT) s_keys[e] = 0ull;
-    fetch(0);
-    commit(0);
-    __syncthreads();
-
-    const int xw = x0 + NBS * wv;                              // this wave's first window column
-    const bool live = xw < Wi;
-    const int nfull = side >> 2, rem = side & 3;
-    const unsigned hmask = (1u << (8 * rem)) - 1u;             // the window's last rem columns: the low bytes of one more dword
-    const int la = xw - xLb;                                   // left entry of column xw
-    int ra[KT];                                                // right entry of column xw - d
-    unsigned C[NBS][KT];
-#pragma unroll
-    for (int k = 0; k < KT; k++) {
-        ra[k] = xw - xRb - (lane + 64 * k);
-#pragma unroll
-        for (int j = 0; j < NBS; j++) C[j][k] = 0;
-    }
-    // horizontal window sums of one staged row over the wave's NBS columns, added to (SUB = false) or taken from C
-    auto row_pass = [&](const unsigned *Lrow, const unsigned *Rrow, auto sub) {
-        constexpr bool SUB = decltype(sub)::value;
-        unsigned run[KT];
-#pragma unroll
-        for (int k = 0; k < KT; k++) run[k] = 0;
-        for (int g = 0; g < nfull; g++) {
-            const unsigned a4 = Lrow[la + 4 * g];
-#pragma unroll
-            for (int k = 0; k < KT; k++)
-                if (k < nk) run[k] = __builtin_amdgcn_udot4(a4, Rrow[ra[k] + 4 * g], run[k], false);
-        }
-        if (rem) {
-            const unsigned a4 = Lrow[la + 4 * nfull] & hmask;  // a zero byte on the left takes the right one out of the sum
-#pragma unroll
-            for (int k = 0; k < KT; k++)
-                if (k < nk) run[k] = __builtin_amdgcn_udot4(a4, Rrow[ra[k] + 4 * nfull], run[k], false);
-        }
-        const uint8_t *Lb = reinterpret_cast<const uint8_t *>(Lrow), *Rb = reinterpret_cast<const uint8_t *>(Rrow);
-#pragma unroll
-        for (int j = 0; j < NBS; j++) {
-            if (j > 0) {
-                const unsigned aN = Lb[4 * (la + j - 1 + side)], aO = Lb[4 * (la + j - 1)];
-#pragma unroll
-                for (int k = 0; k < KT; k++)
-                    if (k < nk) {
-                        const unsigned bN = Rb[4 * (ra[k] + j - 1 + side)], bO = Rb[4 * (ra[k] + j - 1)];
-                        // one byte per operand: two single products, through the intrinsic on purpose.  Written as plain
-                        // multiplies, the compiler (ROCm 7.2) folds the products of neighbouring columns into v_dot4 of
-                        // v_perm-packed bytes, and in the KT = 1 instantiation the packed operands take in a leaving pair
-                        // (aO, bO), whose product is then added instead of subtracted (tools/dot4_fold_probe.hip)
-                        run[k] = __builtin_amdgcn_udot4(aN, bN, run[k], false) - __builtin_amdgcn_udot4(aO, bO, 0u, false);
-                    }
-            }
-#pragma unroll
-            for (int k = 0; k < KT; k++)
-                if (k < nk) C[j][k] = SUB ? C[j][k] - run[k] : C[j][k] + run[k];
-        }
-    };
+        for (int e = threadIdx.x; e < 2 * NKE; e += BNT) s_keys[e] = 0ull;
 
     const double n = (double)(side * side);
-    const int nsteps = side - 1 + (i1 - i0);
-    for (int t = 0; t < nsteps; t++) {
-        const int half = t & 1;
-        const int io = i0 + t - side + 1;                      // window row of this step (>= i0: there is one)
-        const bool leaving = t >= side;
-        if (t + 1 < nsteps) fetch(t + 1);
+    auto pre = [&](int half, int io) __attribute__((always_inline)) {
         if constexpr (PUB)
-            if (io > i0) flush(half ^ 1, io - 1);              // what step t - 1 emitted
-        if (live) {
-            const unsigned *rows = s_rows + (size_t)half * 2 * ROWE;
-            row_pass(rows, rows + LWE, std::false_type());
-            if (leaving) row_pass(rows + ROWE, rows + ROWE + LWE, std::true_type());
-            if (io >= i0) {
+            if (io > i0) flush(half ^ 1, io - 1);              // what the step before emitted
+    };
+    auto emit = [&](int half, int io, int x, const unsigned (&Cj)[KT]) __attribute__((always_inline)) {
+        const int lane = threadIdx.x & 63;                     // not captured: see box_steps
+        const size_t p = (size_t)(io + win) * W + x + win;
+        const double sa = (double)sumL[p], rta = rootL[p];
+        double c[KT];
+        float v[KT];
+        bool poison = false;
 #pragma unroll
-                for (int j = 0; j < NBS; j++) {
-                    const int x = xw + j;
-                    if (x >= Wi) break;
-                    const size_t p = (size_t)(io + win) * W + x + win;
-                    const double sa = (double)sumL[p], rta = rootL[p];
-                    double c[KT];
-                    float v[KT];
-                    bool poison = false;
-#pragma unroll
-                    for (int k = 0; k < KT; k++) {
-                        const int d = lane + 64 * k;
-                        const bool act = k < nk && d < D;
-                        if (act && x - d >= 0) {
-                            const size_t q = p - d;
-                            c[k] = ncc_int_cost(n, C[j][k], sa, rta, sumR[q], rootR[q]);
-                        } else c[k] = 255.0;                   // `invalid` 0xff, NCC.h:88
-                        if (cost_out && act) cost_out[p * D + d] = c[k];
-                        if constexpr (PUB)
-                            if (act && x - d >= 0 && c[k] == c[k])
-                                atomicMax(s_keys + half * NKE + (x - d - (x0 - 64 * KT)), ncc_rank_key(c[k], d));
-                        if (k == 0) poison = __ballot(c[0] != c[0] && lane == 0) != 0;   // d = 0 is slot 0 of lane 0
-                        v[k] = ncc_wta_term(c[k], act);
-                    }
-                    // WinTakeAll in d order = (slot, lane): before (k, lane) = max(every lane of the slots < k, the
-                    // lanes below `lane` of slot k)
-                    float below = -INFINITY;
-                    unsigned key = 0;                          // 1 + the largest winning d of the lane (0: none)
-#pragma unroll
-                    for (int k = 0; k < KT; k++)
-                        if (k < nk) {
-                            const int d = lane + 64 * k;
-                            const float inc = wave_prefix_max_f32(v[k], lane);
-                            const float up = __shfl_up(inc, 1, WAVE);
-                            const float m = fmaxf(below, lane >= 1 ? up : -INFINITY);
-                            if (d < D && (double)m < c[k]) key = (unsigned)d + 1u;   // d grows with k
-                            below = fmaxf(below, __shfl(inc, 63, WAVE));
-                        }
-                    const int out = ncc_wta_last(key, poison);
-                    if (lane == 0) disp[p] = out;
-                }
-            }
+        for (int k = 0; k < KT; k++) {
+            const int d = lane + 64 * k;
+            const bool act = k < nk && d < D;
+            if (act && x - d >= 0) {
+                const size_t q = p - d;
+                c[k] = ncc_int_cost(n, Cj[k], sa, rta, sumR[q], rootR[q]);
+            } else c[k] = 255.0;                               // `invalid` 0xff, NCC.h:88
+            if (cost_out && act) cost_out[p * D + d] = c[k];
+            if constexpr (PUB)
+                if (act && x - d >= 0 && c[k] == c[k])
+                    atomicMax(s_keys + half * NKE + (x - d - (x0 - 64 * KT)), ncc_rank_key(c[k], d));
+            if (k == 0) poison = __ballot(c[0] != c[0] && lane == 0) != 0;   // d = 0 is slot 0 of lane 0
+            v[k] = ncc_wta_term(c[k], act);
         }
-        if (t + 1 < nsteps) commit(half ^ 1);
-        __syncthreads();
-    }
-    if constexpr (PUB) flush((nsteps - 1) & 1, i1 - 1);        // the last step's row (i1 > i0: it emitted)
+        // WinTakeAll in d order = (slot, lane): before (k, lane) = max(every lane of the slots < k, the lanes below `lane`
+        // of slot k)
+        float below = -INFINITY;
+        unsigned key = 0;                                      // 1 + the largest winning d of the lane (0: none)
+#pragma unroll
+        for (int k = 0; k < KT; k++)
+            if (k < nk) {
+                const int d = lane + 64 * k;
+                const float inc = wave_prefix_max_f32(v[k], lane);
+                const float up = __shfl_up(inc, 1, WAVE);
+                const float m = fmaxf(below, lane >= 1 ? up : -INFINITY);
+                if (d < D && (double)m < c[k]) key = (unsigned)d + 1u;   // d grows with k
+                below = fmaxf(below, __shfl(inc, 63, WAVE));
+            }
+        const int out = ncc_wta_last(key, poison);
+        if (lane == 0) disp[p] = out;
+    };
+    box_steps<KT, BS, BNT, box_tap_dot, -1>(s_nbox, L, R, W, x0 - box_tap_dot::LEAD, x0 - 64 * KT, x0, i0, i1, Wi, side, nk, pre,
+                                            box_no_hook(), emit);
+    // the last step's row (i1 > i0: it emitted), in the last step's half
+    if constexpr (PUB) flush((side - 2 + (i1 - i0)) & 1, i1 - 1);
 }
 
 int g_ncc_box_band = 0;        // test hook: window rows per band, 0 = box_band's choice
-
-int nbox_band(int Hi, int Wi, int side)
-{
-    return g_ncc_box_band > 0 ? (g_ncc_box_band < Hi ? g_ncc_box_band : Hi) : box_band(Hi, Wi, side, NBSW);
-}
 
 template <int KT>
 int launch_nbox(hipStream_t st, const uint8_t *L, const uint8_t *R, int pairs, int H, int W, int D, int win, const int *sumL,
                 const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost,
                 unsigned long long *rkeys)
 {
-    const int side = 2 * win + 1, Hi = H - 2 * win, Wi = W - 2 * win, band = nbox_band(Hi, Wi, side);
-    const size_t shm = (size_t)4 * (nbox_lwe(side) + nbox_rwe(side, KT)) * 4;   // <= 16 KiB; two staging items per thread suffice
-    static_assert(2 * (((NBSW + NCC_INT_MAX_SIDE + 3) & ~3) + ((64 * KT + NBSW + NCC_INT_MAX_SIDE + 3) & ~3)) / 4 <= 2 * NBT, "staging items");
-    const dim3 grid((Wi + NBSW - 1) / NBSW, (Hi + band - 1) / band, pairs);
+    const int side = 2 * win + 1, Hi = H - 2 * win, Wi = W - 2 * win, band = box_band_rule(g_ncc_box_band, Hi, Wi, side, BSW);
+    const size_t shm = (size_t)4 * (box_lwe(side, BSW) + box_rwe(side, KT, BSW)) * 4;   // <= 16 KiB; two staging items per thread suffice
+    static_assert(2 * (((BSW + NCC_INT_MAX_SIDE + 3) & ~3) + ((64 * KT + BSW + NCC_INT_MAX_SIDE + 3) & ~3)) / 4 <= 2 * BNT, "staging items");
+    const dim3 grid((Wi + BSW - 1) / BSW, (Hi + band - 1) / band, pairs);
     if (rkeys)                                                 // + the two key rows, at most 9 KiB
-        hipLaunchKernelGGL((k_ncc_box<KT, true>), grid, dim3(NBT), shm + (size_t)2 * (64 * KT + NBSW) * 8, st, L, R, H, W, D, win, band,
+        hipLaunchKernelGGL((k_ncc_box<KT, true>), grid, dim3(BNT), shm + (size_t)2 * (64 * KT + BSW) * 8, st, L, R, H, W, D, win, band,
                            sumL, rootL, sumR, rootR, disp, cost, rkeys);
     else
-        hipLaunchKernelGGL((k_ncc_box<KT, false>), grid, dim3(NBT), shm, st, L, R, H, W, D, win, band, sumL, rootL, sumR, rootR, disp,
+        hipLaunchKernelGGL((k_ncc_box<KT, false>), grid, dim3(BNT), shm, st, L, R, H, W, D, win, band, sumL, rootL, sumR, rootR, disp,
                            cost, rkeys);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
@@ -285,12 +166,9 @@ int smt_ncc_box_enqueue(const uint8_t *L, const uint8_t *R, int pairs, int H, in
                         const double *rootL, const int *sumR, const double *rootR, int32_t *disp, double *cost, hipStream_t st,
                         unsigned long long *rkeys)
 {
-    const int K = (D + 63) / 64;
-    int rc;
-    if (K <= 1) rc = launch_nbox<1>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
-    else if (K <= 2) rc = launch_nbox<2>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
-    else if (K <= 4) rc = launch_nbox<4>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
-    else rc = launch_nbox<8>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
+    const int rc = box_dispatch_kt(D, [&](auto kt) {
+        return launch_nbox<decltype(kt)::value>(st, L, R, pairs, H, W, D, winSize, sumL, rootL, sumR, rootR, disp, cost, rkeys);
+    });
     if (rc == SMT_OK) g_smt_ncc_last_form = SMT_NCC_FORM_BOX;
     return rc;
 }
@@ -311,78 +189,10 @@ SMT_API int smt_ncc_box_set_band(int band)
 }
 
 // ---- host-only check -----------------------------------------------------------------------------------------------
-namespace {
-
-unsigned host_dot4(unsigned a, unsigned b, unsigned acc)
-{
-    for (int q = 0; q < 4; q++) acc += ((a >> (8 * q)) & 255u) * ((b >> (8 * q)) & 255u);
-    return acc;
-}
-
-// k_ncc_box on the host, hypothesis by hypothesis: the same strips, bands, steps, staged entries (clamped columns
-// included), dword groups, sliding sums and entering and leaving rows, in uint32.  sab: [Hi][Wi][D].
-void nbox_host(const uint8_t *L, const uint8_t *R, int H, int W, int D, int win, int band, unsigned *sab)
-{
-    const int side = 2 * win + 1, Hi = H - 2 * win, Wi = W - 2 * win;
-    const int KT = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
-    const int LWE = nbox_lwe(side), RWE = nbox_rwe(side, KT);
-    const int nfull = side >> 2, rem = side & 3;
-    const unsigned hmask = (1u << (8 * rem)) - 1u;
-    std::vector<unsigned> eL(LWE), eR(RWE), lL(LWE), lR(RWE), C((size_t)NBS * 64 * KT);
-    auto stage = [&](std::vector<unsigned> &dst, const uint8_t *row, int xb) {
-        for (size_t e = 0; e < dst.size(); e++) {
-            unsigned v = 0;
-            for (int b = 0; b < 4; b++) {
-                int x = xb + (int)e + b;
-                x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
-                v |= (unsigned)row[x] << (8 * b);
-            }
-            dst[e] = v;
-        }
-    };
-    for (int i0 = 0; i0 < Hi; i0 += band) {
-        const int i1 = i0 + band < Hi ? i0 + band : Hi;
-        for (int x0 = 0; x0 < Wi; x0 += NBSW) {
-            const int xLb = x0, xRb = x0 - 64 * KT;
-            for (int xw = x0; xw < x0 + NBSW && xw < Wi; xw += NBS) {
-                std::fill(C.begin(), C.end(), 0u);
-                const int la = xw - xLb;
-                const int nsteps = side - 1 + (i1 - i0);
-                for (int t = 0; t < nsteps; t++) {
-                    const int rE = i0 + t, rL = rE - side, io = rE - side + 1;
-                    stage(eL, L + (size_t)rE * W, xLb);
-                    stage(eR, R + (size_t)rE * W, xRb);
-                    if (rL >= i0) { stage(lL, L + (size_t)rL * W, xLb); stage(lR, R + (size_t)rL * W, xRb); }
-                    for (int d = 0; d < D; d++) {
-                        const int ra = xw - xRb - d;
-                        for (int pass = 0; pass < (rL >= i0 ? 2 : 1); pass++) {
-                            const unsigned *Lrow = pass ? lL.data() : eL.data(), *Rrow = pass ? lR.data() : eR.data();
-                            unsigned run = 0;
-                            for (int g = 0; g < nfull; g++) run = host_dot4(Lrow[la + 4 * g], Rrow[ra + 4 * g], run);
-                            if (rem) run = host_dot4(Lrow[la + 4 * nfull] & hmask, Rrow[ra + 4 * nfull], run);
-                            for (int j = 0; j < NBS; j++) {
-                                if (j > 0)
-                                    run = run + (Lrow[la + j - 1 + side] & 255u) * (Rrow[ra + j - 1 + side] & 255u) -
-                                          (Lrow[la + j - 1] & 255u) * (Rrow[ra + j - 1] & 255u);
-                                unsigned &c = C[(size_t)j * 64 * KT + d];
-                                c = pass ? c - run : c + run;
-                            }
-                        }
-                    }
-                    if (io < i0) continue;
-                    for (int j = 0; j < NBS && xw + j < Wi; j++)
-                        for (int d = 0; d < D; d++)
-                            sab[((size_t)io * Wi + xw + j) * D + d] = C[(size_t)j * 64 * KT + d];
-                }
-            }
-        }
-    }
-}
-
-}  // namespace
+// box_host<Tap>, the restatement of the kernel's recurrence: csrc/box_stage.h
 
 // Host only (no GPU).  On four unpadded pairs of the given shape -- pseudo-random, 255 against 255 (the largest sums),
-// opposed checkerboards, a shifted copy -- the restated recurrence of k_ncc_box (nbox_host, under the band the launch
+// opposed checkerboards, a shifted copy -- the restated recurrence of k_ncc_box (box_host<box_tap_dot>, under the band the launch
 // would choose and under a band of 1 and of 3 rows) equals the direct double loop sum a b over the window for every
 // (i, x, d); columns left of the image are read clamped by both.  An empty interior has nothing to compare: SMT_OK.
 SMT_API int smt_ncc_selftest_box(int H, int W, int D, int winSize, unsigned seed)
@@ -417,10 +227,10 @@ SMT_API int smt_ncc_selftest_box(int H, int W, int D, int winSize, unsigned seed
                         }
                     want[((size_t)i * Wi + x) * D + d] = acc;
                 }
-        const int bands[3] = {box_band(Hi, Wi, side, NBSW), 1, 3};
+        const int bands[3] = {box_band(Hi, Wi, side, BSW), 1, 3};
         for (int b = 0; b < 3; b++) {
             std::fill(got.begin(), got.end(), 0xdeadbeefu);
-            nbox_host(L.data(), R.data(), H, W, D, win, bands[b] < Hi ? bands[b] : Hi, got.data());
+            box_host<box_tap_dot>(L.data(), R.data(), W, Hi, Wi, D, side, bands[b] < Hi ? bands[b] : Hi, got.data());
             if (got != want) return SMT_ERR_STATE;
         }
     }

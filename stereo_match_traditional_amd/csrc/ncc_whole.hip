@@ -235,21 +235,6 @@ __global__ void __launch_bounds__(NWT) k_nw_finish(const double *__restrict__ pc
     if (outs.off[vs]) outs.off[vs][pair * N + pix] = best_o;
 }
 
-struct nw_scratch {                                            // arena blocks of one call, freed in reverse order
-    hipStream_t st;
-    void *p[6];
-    int n = 0;
-    explicit nw_scratch(hipStream_t s) : st(s) {}
-    void *get(size_t bytes)
-    {
-        void *q = nullptr;
-        if (n >= 6 || smt_scratch_alloc(&q, bytes, st) != hipSuccess) return nullptr;
-        p[n++] = q;
-        return q;
-    }
-    ~nw_scratch() { while (n > 0) smt_scratch_free(p[--n], st); }
-};
-
 int nw_groups(long wgs, int O)
 {
     long G = g_nw_groups > 0 ? g_nw_groups : (NW_TARGET + wgs - 1) / wgs;
@@ -269,7 +254,7 @@ int nw_enqueue(int form, const uint8_t *L, const uint8_t *R, int pairs, int H, i
 {
     const int k = P.kernel_size, O = P.max_offset;
     const size_t N = (size_t)H * W, PN = (size_t)pairs * N;
-    nw_scratch S(st);
+    scratch_set S(st);
     const uint8_t *Ru = R;
     if (P.add_constant) {                                      // :127-130 on a copy: the caller's image stays as it is
         uint8_t *Rc = (uint8_t *)S.get(PN);
@@ -582,7 +567,7 @@ SMT_API int smt_whole_ncc_flow_run_batch(smt_whole_ncc_flow *h, const uint8_t *g
     hipStream_t st = h->stream;
     const int form = h->form ? h->form : nw_form_for(g_nw_impl, h->P.kernel_size);
     const bool check = lastdisp || cls;
-    nw_scratch S(st);
+    scratch_set S(st);
     int32_t *ol = offL, *orr = offR, *last1 = nullptr;
     uint8_t *cls1 = nullptr;
     if (check) {                                               // the cross-check reads both offset maps

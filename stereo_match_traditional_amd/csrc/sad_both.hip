@@ -30,20 +30,19 @@ constexpr int BSW = BS * (BNT / 64);     // columns per workgroup
 constexpr unsigned NOKEY = 0xffffffffu;
 constexpr int BOX_MAX_SIDE = 181;        // 255 * side^2 < 2^23: (cost << 9) | d fits 32 bits and never equals NOKEY
 
-// Staged row geometry, shared by the kernel and its host restatement.  A row of either image sits in LDS expanded to one
-// dword per BYTE offset (entry A = bytes A .. A + 3, as k_sad2 stages its rows): the initial window sum of a row reads
-// aligned dwords for v_sad_u8 whatever the hypothesis, the sliding sum reads the low byte of an entry, and lanes with
-// consecutive d touch consecutive dwords.  Left entries start at column x0 - 1, right entries at x0 - 64 KT (one entry of
-// slack each: the masked tail dword of a 3-wide window starts one byte before the window).
-__host__ __device__ inline int box_lwe(int side) { return (BSW + side + 3) & ~3; }
-__host__ __device__ inline int box_rwe(int side, int KT) { return (64 * KT + BSW + side + 3) & ~3; }
-
-// box_load8 (entries A .. A + 7 of an image row, columns clamped into the row): csrc/box_stage.h
-
 // grid (strips of BSW columns, bands of `band` rows).  Step t of a band that starts at row i0 brings in padded row
 // i0 + t, takes out padded row i0 + t - side (once there is one) and, from t = side - 1 on, emits output row
 // i0 + t - side + 1.  The two rows of step t + 1 are fetched into registers before step t computes and written to the
 // other half of the LDS row buffer after it; one barrier per step.  rkeys == nullptr: no right view.
+//
+// This is the skeleton that box_steps (csrc/box_stage.h) holds for k_ncc_box and k_win_box, written out: row geometry,
+// band rule, slot dispatch and host restatement are the shared ones, but staging, row_pass and the step loop stay here.
+// Run through box_steps with its emit step and key-row flush as closures, the KT = 2 instantiation took 231 VGPRs for
+// 171 and smt_sad_both was 1.7 % to 2.5 % slower at 1920x1080 D = 128, outside the parent's own spread
+// (profiles/box_engine_ab.json).  With its own step loop on staging and row_pass factored out of
+// box_steps as force-inlined functions taking references, the KT = 8 instantiation keeps C in scratch (560 private bytes
+// for 0, one loop left rolled) and KT = 4 takes 394 VGPRs for 275; timed in the same section.  A fix to the skeleton goes
+// into both places.
 template <int KT>
 __global__ void __launch_bounds__(BNT) k_sad_box(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
                                                  int D, int w, int band, int32_t *__restrict__ dispL,
@@ -56,7 +55,7 @@ __global__ void __launch_bounds__(BNT) k_sad_box(const uint8_t *__restrict__ Lp,
     const int x0 = blockIdx.x * BSW, i0 = blockIdx.y * band;
     const int i1 = i0 + band < H ? i0 + band : H;
     const int nk = (D + 63) >> 6;                              // live hypothesis slots (uniform)
-    const int LWE = box_lwe(side), RWE = box_rwe(side, KT), ROWE = LWE + RWE;
+    const int LWE = box_lwe(side, BSW), RWE = box_rwe(side, KT, BSW), ROWE = LWE + RWE;
     const int xLb = x0 - 1, xRb = x0 - 64 * KT;
     constexpr int NKEY = 64 * KT + BSW;
     unsigned *s_rows = s_box;                                  // [2 halves][entering, leaving][LWE left + RWE right entries]
@@ -261,15 +260,15 @@ __global__ void __launch_bounds__(256) k_sad_volume(const uint8_t *__restrict__ 
     costL[e] = (float)acc;
 }
 
-// Rows per band: box_band (csrc/box_stage.h).  g_sad_both_band overrides it.
+// Rows per band: box_band_rule (csrc/box_stage.h).
 int g_sad_both_band = 0;       // test hook: rows per band, 0 = box_band's choice
 
 template <int KT>
 int launch_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int32_t *dispL, float *costL,
                unsigned *rkeys)
 {
-    const int side = 2 * w + 1, band = g_sad_both_band > 0 ? (g_sad_both_band < H ? g_sad_both_band : H) : box_band(H, W, side, BSW);
-    const size_t shm = ((size_t)4 * (box_lwe(side) + box_rwe(side, KT)) + 2 * (64 * KT + BSW)) * 4;   // <= 24 KiB
+    const int side = 2 * w + 1, band = box_band_rule(g_sad_both_band, H, W, side, BSW);
+    const size_t shm = ((size_t)4 * (box_lwe(side, BSW) + box_rwe(side, KT, BSW)) + 2 * (64 * KT + BSW)) * 4;   // <= 24 KiB
     const dim3 grid((W + BSW - 1) / BSW, (H + band - 1) / band);
     hipLaunchKernelGGL(k_sad_box<KT>, grid, dim3(BNT), shm, st, Lp, Rp, H, W, D, w, band, dispL, costL, rkeys);
     SMT_LAUNCH_CHECK();
@@ -279,11 +278,7 @@ int launch_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int 
 int run_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int32_t *dispL, float *costL,
             unsigned *rkeys)
 {
-    const int K = (D + 63) / 64;
-    if (K <= 1) return launch_box<1>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
-    if (K <= 2) return launch_box<2>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
-    if (K <= 4) return launch_box<4>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
-    return launch_box<8>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys);
+    return box_dispatch_kt(D, [&](auto kt) { return launch_box<decltype(kt)::value>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys); });
 }
 
 // Which path serves (side, D) by default.  Measured on one MI355X (tools/sad_both_time.py, profiles/sad_both_time.json;
@@ -371,83 +366,12 @@ SMT_API int smt_sad_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int
 }
 
 // ---- host-only checks ----------------------------------------------------------------------------------------------
-namespace {
-
-// host_rng: csrc/box_stage.h
-
-unsigned host_sad_u8(unsigned a, unsigned b, unsigned acc)
-{
-    for (int q = 0; q < 4; q++) acc += (unsigned)abs((int)((a >> (8 * q)) & 255) - (int)((b >> (8 * q)) & 255));
-    return acc;
-}
-
-// k_sad_box on the host, hypothesis by hypothesis: the same strips, bands, steps, staged entries, masked dword groups,
-// sliding sums, entering and leaving rows and chain.  cost: [H][W][D].
-void box_host(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int band, unsigned *cost)
-{
-    const int side = 2 * w + 1, Wp = W + 2 * w;
-    const int KT = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
-    const int LWE = box_lwe(side), RWE = box_rwe(side, KT);
-    const int nfull = side >> 2, rem = side & 3;
-    const unsigned tmask = rem ? (0xffffffffu << (8 * (4 - rem))) : 0u;
-    std::vector<unsigned> eL(LWE), eR(RWE), lL(LWE), lR(RWE), C((size_t)BS * 64 * KT);
-    auto stage = [&](std::vector<unsigned> &dst, const uint8_t *row, int xb) {
-        for (size_t e = 0; e < dst.size(); e++) {
-            unsigned v = 0;
-            for (int b = 0; b < 4; b++) {
-                int x = xb + (int)e + b;
-                x = x < 0 ? 0 : (x > Wp - 1 ? Wp - 1 : x);
-                v |= (unsigned)row[x] << (8 * b);
-            }
-            dst[e] = v;
-        }
-    };
-    for (int i0 = 0; i0 < H; i0 += band) {
-        const int i1 = i0 + band < H ? i0 + band : H;
-        for (int x0 = 0; x0 < W; x0 += BSW) {
-            const int xLb = x0 - 1, xRb = x0 - 64 * KT;
-            for (int xw = x0; xw < x0 + BSW && xw < W; xw += BS) {
-                std::fill(C.begin(), C.end(), 0u);
-                const int la = xw - xLb;
-                const int nsteps = side - 1 + (i1 - i0);
-                for (int t = 0; t < nsteps; t++) {
-                    const int rE = i0 + t, rL = rE - side, io = rE - side + 1;
-                    stage(eL, Lp + (size_t)rE * Wp, xLb);
-                    stage(eR, Rp + (size_t)rE * Wp, xRb);
-                    if (rL >= i0) { stage(lL, Lp + (size_t)rL * Wp, xLb); stage(lR, Rp + (size_t)rL * Wp, xRb); }
-                    for (int d = 0; d < D; d++) {
-                        const int ra = xw - xRb - d;
-                        for (int pass = 0; pass < (rL >= i0 ? 2 : 1); pass++) {
-                            const unsigned *Lrow = pass ? lL.data() : eL.data(), *Rrow = pass ? lR.data() : eR.data();
-                            unsigned run = 0;
-                            for (int g = 0; g < nfull; g++) run = host_sad_u8(Lrow[la + 4 * g], Rrow[ra + 4 * g], run);
-                            if (rem) run = host_sad_u8(Lrow[la + side - 4] & tmask, Rrow[ra + side - 4] & tmask, run);
-                            for (int j = 0; j < BS; j++) {
-                                if (j > 0)
-                                    run = host_sad_u8(Lrow[la + j - 1 + side] & 255, Rrow[ra + j - 1 + side] & 255, run) -
-                                          host_sad_u8(Lrow[la + j - 1] & 255, Rrow[ra + j - 1] & 255, 0u);
-                                unsigned &c = C[(size_t)j * 64 * KT + d];
-                                c = pass ? c - run : c + run;
-                            }
-                        }
-                    }
-                    if (io < i0) continue;
-                    for (int j = 0; j < BS && xw + j < W; j++) {
-                        const int x = xw + j;
-                        for (int d = 0; d < D; d++)
-                            cost[((size_t)io * W + x) * D + d] = C[(size_t)j * 64 * KT + (d > x ? x : d)];
-                    }
-                }
-            }
-        }
-    }
-}
-
-}  // namespace
+// host_rng and box_host<Tap>, the restatement of the kernel's recurrence: csrc/box_stage.h
 
 // Host only (no GPU).  On four padded pairs of the given shape -- pseudo-random, constant 0 against constant 255,
-// opposed checkerboards, a shifted copy -- the restated recurrence of k_sad_box (box_host, under the band the launch
-// would choose and under a band of 1 and of 3 rows) equals the direct double loop over the window for every (i, x, d).
+// opposed checkerboards, a shifted copy -- the restated recurrence of k_sad_box (box_host<box_tap_sad> and the chain of the
+// kernel's emit step, under the band the launch would choose and under a band of 1 and of 3 rows) equals the direct double
+// loop over the window for every (i, x, d).
 SMT_API int smt_sad_selftest_box(int H, int W, int D, int winsize, unsigned seed)
 {
     if (H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0 || 2 * (winsize + 1) + 1 > BOX_MAX_SIDE ||
@@ -481,7 +405,9 @@ SMT_API int smt_sad_selftest_box(int H, int W, int D, int winsize, unsigned seed
         const int bands[3] = {box_band(H, W, side, BSW), 1, 3};
         for (int b = 0; b < 3; b++) {
             std::fill(got.begin(), got.end(), 0xdeadbeefu);
-            box_host(L.data(), R.data(), H, W, D, w, bands[b], got.data());
+            box_host<box_tap_sad>(L.data(), R.data(), Wp, H, W, D, side, bands[b], got.data());
+            for (size_t p = 0; p < (size_t)H * W; p++)                 // the chain: d > x repeats the sum at d = x
+                for (int d = (int)(p % W) + 1; d < D; d++) got[p * D + d] = got[p * D + p % W];
             if (got != want) return SMT_ERR_STATE;
         }
     }

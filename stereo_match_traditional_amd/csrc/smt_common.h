@@ -49,6 +49,20 @@ static inline int smt_current_device() { int d = -1; return hipGetDevice(&d) == 
 // set of the library.  Free with smt_scratch_free on the same stream.
 hipError_t smt_scratch_alloc(void **p, size_t bytes, hipStream_t st);
 void smt_scratch_free(void *p, hipStream_t st);
+struct scratch_set {                                       // arena blocks of one call, freed in reverse order
+    hipStream_t st;
+    void *p[6];
+    int n = 0;
+    explicit scratch_set(hipStream_t s) : st(s) {}
+    void *get(size_t bytes)
+    {
+        void *q = nullptr;
+        if (n >= 6 || smt_scratch_alloc(&q, bytes, st) != hipSuccess) return nullptr;
+        p[n++] = q;
+        return q;
+    }
+    ~scratch_set() { while (n > 0) smt_scratch_free(p[--n], st); }
+};
 
 // Batched RemoveSpeckles on caller-owned scratch (csrc/speckle.hip; smt_pipeline_run_batch_post owns one for a pair):
 // smt_speckle_scratch_bytes(pairs, W, H) bytes, arguments already checked.  Enqueues four launches on `st`.
