@@ -318,7 +318,21 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  *   int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
  * the same for the counts of an H x W x D pair (first: nothing to convert, last: no tables to build), and the items'
  * pixel arithmetic covers each key, each pixel of the columns W-2-D .. W-1 and each of the columns 0..2 exactly once,
- * and no column W-3-D < j' <= W-4 has an empty edge range.  SMT_OK, SMT_ERR_STATE, or SMT_ERR_ARG (also for W < D + 6). */
+ * and no column W-3-D < j' <= W-4 has an empty edge range.  SMT_OK, SMT_ERR_STATE, or SMT_ERR_ARG (also for W < D + 6).
+ * Tapered tail.  The chunks of a maps-only launch (shared or two-view) are cut into workgroups per XCD slice by one span
+ * rule (adcensus.hip, maps_span): the slice's last n1 workgroups take 1 chunk, the n2 before them max(1, K/2), all
+ * before those K (SMT_MAPS_CHUNKS), and the launch's auxiliary workgroups are placed in front of the first tapered one.
+ * Maps do not depend on it.  The counts come from the device (workgroups resident per slice, queried at create) and
+ * are 0 for a launch of at most one round of workgroups (DESIGN.md section 4 "Tapered tail").
+ *   SMT_MAPS_TAPER in the environment (read at every call): 0 is off, the plain rule and placement exactly; n2,n1 are
+ *   these counts per slice whatever the launch size (tests, sweeps).  The host-only selftests above walk what the
+ *   variable selects.
+ * Test hook, host only (no GPU), exported and declared in csrc/adcensus_internal.h:
+ *   int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);
+ * over the 8 slices of a launch of nb chunks: every chunk belongs to exactly one workgroup, none crosses its slice or
+ * has more than K chunks, the workgroup count is the rule's, tails that fit have the sizes above, and n2 = n1 = 0 is
+ * the plain rule [g K, g K + K).  SMT_OK, SMT_ERR_STATE, or SMT_ERR_ARG unless 1 <= nb <= 2^28, 1 <= K <= 64,
+ * n2, n1 >= 0. */
 
 /* Synchronises the stream and returns SMT_ERR_DOMAIN if any pixel seen since the previous
  * smt_adcensus_status call (or since create) was not an integer in 0..255 (then those pairs' volumes

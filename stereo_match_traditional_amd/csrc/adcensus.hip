@@ -456,16 +456,58 @@ static_assert(shared_ring_spill(3, true) <= SH_SPILL && shared_ring_spill(4, fal
 // SH_RUN from its start, each a run in every respect (shared_run_len: chunks of the run that starts at chunk bx with
 // `left` chunks of the workgroup to go).  The one flush of run [S, E] takes every column the run published to.
 constexpr int SH_RUN = 4;
-__host__ __device__ inline int shared_wg_chunks(int nbx, int H, int K, long b, int &i, int &bx)
+// Span rule of the maps-only launches (k_cost_maps_shared, k_cost_maps2p): how the `per` chunks of one XCD's slice are
+// cut into workgroups.  Group g = b >> 3 of slice b & 7 takes maps_span()'s chunks [first, first + n) of the slice.
+// The slice's last n1 groups take 1 chunk each, the n2 groups before them max(1, K / 2) each, every group before
+// those K (the last of them what is left): a TAPERED TAIL, so that the workgroups of the launch's last round end
+// closer together.  n2 = n1 = 0 is the plain rule, group g takes [g K, g K + K).  A slice too
+// short for the tails shrinks them (maps_span_tails: first n1, then n2), so the body never goes negative and no
+// group before maps_span_groups() is empty.  Workgroup-uniform, once per workgroup; the divisions are taken by the
+// tail groups and by shrunk tails only.
+__host__ __device__ inline long maps_span_tails(long per, int K, int &n2, int &n1)   // -> chunks of the body
 {
-    const long nb = (long)nbx * H, per = (nb + 7) >> 3, cl = (b >> 3) * K;
-    if (cl >= per) return 0;
+    const int K2 = K > 1 ? K >> 1 : 1;
+    if (n1 < 0) n1 = 0;
+    if (n2 < 0) n2 = 0;
+    if (n1 > per) n1 = (int)per;
+    const long rem = per - n1;
+    if ((long)n2 * K2 > rem) n2 = (int)(rem / K2);
+    return rem - (long)n2 * K2;
+}
+__host__ __device__ inline int maps_span(long per, int K, int n2, int n1, long g, long &first)
+{
+    const long body = maps_span_tails(per, K, n2, n1);
+    first = g * K;
+    if (first < body) return (int)(body - first < K ? body - first : K);
+    const int K2 = K > 1 ? K >> 1 : 1;
+    const long gt = g - (body + K - 1) / K;                          // group of the tails
+    if (gt < n2) { first = body + gt * K2; return K2; }
+    first = body + (long)n2 * K2 + (gt - n2);
+    return gt - n2 < n1 ? 1 : 0;
+}
+// groups of the body: the first tapered group, if any, is this one
+__host__ __device__ inline long maps_span_body(long per, int K, int n2, int n1)
+{
+    return (maps_span_tails(per, K, n2, n1) + K - 1) / K;
+}
+__host__ __device__ inline long maps_span_groups(long per, int K, int n2, int n1)
+{
+    const long nbody = maps_span_body(per, K, n2, n1);               // shrinks n2, n1 by value only: shrink again
+    (void)maps_span_tails(per, K, n2, n1);
+    return nbody + n2 + n1;
+}
+__host__ __device__ inline int shared_wg_chunks(int nbx, int H, int K, long b, int &i, int &bx, int n2 = 0, int n1 = 0)
+{
+    const long nb = (long)nbx * H, per = (nb + 7) >> 3;
+    long cl;
+    const int m = maps_span(per, K, n2, n1, b >> 3, cl);
+    if (m <= 0) return 0;
     const long c = (b & 7) * per + cl;
     if (c >= nb) return 0;
     i = (int)(c / nbx);
     bx = (int)(c - (long)i * nbx);
-    long n = per - cl < nb - c ? per - cl : nb - c;
-    return (int)(n < K ? n : K);
+    const long n = nb - c;
+    return (int)(n < m ? n : m);
 }
 __host__ __device__ inline int shared_run_len(int nbx, int bx, int left)
 {
@@ -779,13 +821,12 @@ __device__ __forceinline__ void cost_fast_body(int H, int W, int Drt, const Tabl
 // same box) than with chunks in dispatch order.  The grid is 1-D, padded to a multiple of 8.
 // chunk_decode is the general form: workgroup b takes the K consecutive chunks (b >> 3) * K + t, t = 0 .. K-1, of its
 // XCD's eighth (the maps-only kernel, which fills a 32 KB table once per workgroup); K = 1 is chunk_of_block.
-// maps_groups() is the number of workgroups that covers a launch.
-__host__ __device__ inline bool chunk_decode(int nbx, int H, int nviews, int K, long b, int t, int &view, int &i, int &bx)
+// maps_groups() is the number of workgroups that covers a launch.  With a tapered tail (n2, n1: maps_span) the
+// workgroup's chunks are the span's, still consecutive; chunk_at is the decode of one of them.
+__host__ __device__ inline bool chunk_at(int nbx, int H, int nviews, long b, long cl, int &view, int &i, int &bx)
 {
     const long nb = (long)nbx * H * nviews;
     const long per = (nb + 7) >> 3;
-    const long cl = (b >> 3) * K + t;
-    if (cl >= per) return false;
     const long c = (b & 7) * per + cl;
     if (c >= nb) return false;
     const long rows = (long)nbx * H;
@@ -795,10 +836,25 @@ __host__ __device__ inline bool chunk_decode(int nbx, int H, int nviews, int K, 
     bx = (int)(r - (long)i * nbx);
     return true;
 }
-__host__ __device__ inline int maps_groups(int nbx, int H, int nviews, int K)
+__host__ __device__ inline bool chunk_decode(int nbx, int H, int nviews, int K, long b, int t, int &view, int &i, int &bx,
+                                             int n2 = 0, int n1 = 0)
 {
     const long per = ((long)nbx * H * nviews + 7) >> 3;
-    return (int)(8 * ((per + K - 1) / K));
+    long first;
+    if (t >= maps_span(per, K, n2, n1, b >> 3, first)) return false;
+    return chunk_at(nbx, H, nviews, b, first + t, view, i, bx);
+}
+__host__ __device__ inline int maps_groups(int nbx, int H, int nviews, int K, int n2 = 0, int n1 = 0)
+{
+    const long per = ((long)nbx * H * nviews + 7) >> 3;
+    return (int)(8 * maps_span_groups(per, K, n2, n1));
+}
+// cost groups in front of the first tapered one (fused_grid's body), 0 without a taper
+__host__ __device__ inline int maps_body_groups(int nbx, int H, int nviews, int K, int n2, int n1)
+{
+    const long per = ((long)nbx * H * nviews + 7) >> 3;
+    (void)maps_span_tails(per, K, n2, n1);
+    return n2 + n1 > 0 ? (int)maps_span_body(per, K, n2, n1) : 0;
 }
 __device__ __forceinline__ bool chunk_of_block(int nbx, int H, int nviews, int &view, int &i, int &bx, long b = -1)
 {
@@ -854,11 +910,21 @@ __global__ void __launch_bounds__(NT) k_cost_fast2(int H, int W, int D, Tables T
 // fused_grid() is the host's side of the same arithmetic.  Measured against the two-stream form (tables of pair
 // n + 1 on an internal stream, two event edges per pair): DESIGN.md section 4.
 struct FusedGrid { int cgroups, pgroups, every, slots, groups; };
-__host__ __device__ inline FusedGrid fused_grid(int ncost, int nprep)
+// With a tapered tail (cbody > 0: the cost groups in front of the first tapered one, maps_body_groups) the table groups
+// are spread through the body alone, one after every cbody / pgroups cost groups and none in further slots: a table
+// tile lasts about as long as a 4-chunk cost workgroup and would undo the taper from inside the tail.  A body with
+// fewer groups than there are table groups keeps the placement below.
+__host__ __device__ inline FusedGrid fused_grid(int ncost, int nprep, int cbody = 0)
 {
     FusedGrid f;
     f.cgroups = ncost >> 3;                                  // ncost is a multiple of 8
     f.pgroups = (nprep + 7) >> 3;
+    if (cbody > 0 && f.pgroups > 0 && cbody >= f.pgroups && cbody < f.cgroups) {
+        f.every = cbody / f.pgroups;
+        f.slots = f.pgroups;
+        f.groups = f.cgroups + f.pgroups;
+        return f;
+    }
     f.every = f.cgroups / (f.pgroups > 0 ? f.pgroups : 1);
     if (f.every < 1) f.every = 1;
     f.slots = f.cgroups / f.every;                           // table groups inside the cost range (>= pgroups unless every == 1)
@@ -973,7 +1039,7 @@ template <int C, bool FULL, int MODE>
 __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables T, float *__restrict__ disp0,
                                                     float *__restrict__ disp1, int nbx, int K, int ncost, int nprep,
                                                     const float *__restrict__ nL, const float *__restrict__ nR,
-                                                    Tables Tn, int ptx)
+                                                    Tables Tn, int ptx, int n2, int n1, int cbody)
 {
     static_assert(PNT == NT, "");
     constexpr int TABN = MapsCfg<MODE>::TABN, NBUF = MapsCfg<MODE>::NBUF;
@@ -982,7 +1048,7 @@ __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables 
     uint16_t *s_tab = lds.tab;
     long b = blockIdx.x;
     if (nprep > 0) {
-        const FusedGrid f = fused_grid(ncost, nprep);
+        const FusedGrid f = fused_grid(ncost, nprep, cbody);
         int idx;
         const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
         b = idx * 8 + (int)(blockIdx.x & 7);
@@ -999,10 +1065,13 @@ __global__ void __launch_bounds__(NT) k_cost_maps2p(int H, int W, int D, Tables 
     } else {
         for (int e = tid; e < 320; e += NT) ((float *)s_tab)[e] = T.lut[e];
     }
+    // the workgroup's chunks: c0 .. c0 + m - 1 of its slice (maps_span; m < K in a tapered tail)
+    long c0;
+    const int m = maps_span((((long)nbx * H * 2) + 7) >> 3, K, n2, n1, b >> 3, c0);
     // the workgroup's next chunk at or after t whose map is requested (workgroup-uniform), K when there is none
     auto next = [&](int t, int &view, int &i, int &bx) {
-        for (; t < K; t++) {
-            if (!chunk_decode(nbx, H, 2, K, b, t, view, i, bx)) return K;
+        for (; t < m; t++) {
+            if (!chunk_at(nbx, H, 2, b, c0 + t, view, i, bx)) return K;
             if (view == 0 ? disp0 : disp1) return t;
         }
         return K;
@@ -1395,7 +1464,8 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
                                                          int nbx, int K, int pubhi, int ncost, int nprep,
                                                          const float *__restrict__ nL, const float *__restrict__ nR,
                                                          Tables Tn, int ptx, int nconv, int nedge,
-                                                         unsigned long long *__restrict__ ckeys, float *__restrict__ cdisp)
+                                                         unsigned long long *__restrict__ ckeys, float *__restrict__ cdisp,
+                                                         int n2, int n1, int cbody)
 {
     static_assert(PNT == NT && NT == 256, "");
     static_assert(2 * PSR * PSW * 4 <= PREP_LDS_U16 * 2 && 320 * 4 <= PREP_LDS_U16 * 2, "");
@@ -1403,7 +1473,7 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
     __shared__ unsigned long long ring[SH_RING_N];
     long b;
     {
-        const FusedGrid f = fused_grid(ncost, nprep + nconv + nedge);
+        const FusedGrid f = fused_grid(ncost, nprep + nconv + nedge, cbody);
         int idx;
         const bool table = fused_decode(f, (int)(blockIdx.x >> 3), idx);   // workgroup-uniform
         b = idx * 8 + (int)(blockIdx.x & 7);
@@ -1420,7 +1490,7 @@ __global__ void __launch_bounds__(NT, SMT_SHARED_MIN_WAVES) k_cost_maps_shared(i
     }
     const int tid = threadIdx.x;
     int i = 0, bx = 0;
-    int left = shared_wg_chunks(nbx, H, K, b, i, bx);                      // workgroup-uniform
+    int left = shared_wg_chunks(nbx, H, K, b, i, bx, n2, n1);              // workgroup-uniform
     if (left == 0) return;
     for (int e = tid; e < 320; e += NT) ((float *)lds.tab)[e] = T.lut[e];
     const int Dd = FULL ? 64 * C : D;
@@ -1552,6 +1622,10 @@ struct smt_adcensus {
     // smt_adcensus_set_quirks changes only edge_col, which the table kernels alone read) and plain_stores is fixed at
     // create.
     bool vol_lent, vol_pending;
+    // Workgroups that one slice's CUs (an eighth of the device) hold at a time, of the maps-only kernel this handle's D
+    // launches: [0] k_cost_maps_shared, [1] k_cost_maps2p float, [2] k_cost_maps2p rank.  From the occupancy query at
+    // create; 0 (unknown, or D > 256) leaves the tapered tail's default rule off (maps_taper).
+    int maps_resident[3];
 };
 
 SMT_API const char *smt_strerror(int s)
@@ -1795,6 +1869,36 @@ static void flush_conversion(smt_adcensus *h)
     h->conv_pending = false;
 }
 
+// maps_resident of the handle: CUs / 8 x the workgroups per CU the runtime reports for the instantiation that D selects
+// (launch_fast_as).  A query that fails leaves 0: the tapered tail's default rule stays off.
+template <int C, bool FULL>
+static void query_maps_resident(smt_adcensus *h, int cus)
+{
+    int n[3] = {0, 0, 0};
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[0], k_cost_maps_shared<C, FULL>, NT, 0) != hipSuccess) n[0] = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[1], k_cost_maps2p<C, FULL, MODE_MAPS_FLOAT>, NT, 0) != hipSuccess) n[1] = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[2], k_cost_maps2p<C, FULL, MODE_MAPS_RANK>, NT, 0) != hipSuccess) n[2] = 0;
+    for (int t = 0; t < 3; t++) h->maps_resident[t] = n[t] > 0 ? cus / 8 * n[t] : 0;
+}
+static void set_maps_resident(smt_adcensus *h)
+{
+    h->maps_resident[0] = h->maps_resident[1] = h->maps_resident[2] = 0;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 8) return;
+    switch ((h->D + 63) / 64 * 2 + (h->D % 64 == 0 ? 1 : 0)) {
+    case 3: query_maps_resident<1, true>(h, cus); break;
+    case 5: query_maps_resident<2, true>(h, cus); break;
+    case 7: query_maps_resident<3, true>(h, cus); break;
+    case 9: query_maps_resident<4, true>(h, cus); break;
+    case 2: query_maps_resident<1, false>(h, cus); break;
+    case 4: query_maps_resident<2, false>(h, cus); break;
+    case 6: query_maps_resident<3, false>(h, cus); break;
+    case 8: query_maps_resident<4, false>(h, cus); break;
+    default: break;
+    }
+    (void)hipGetLastError();
+}
+
 static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsigned flags, smt_adcensus **out)
 {
     if (!out || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || !(sigmaC > 0.0f) || !(sigmaS > 0.0f) ||
@@ -1856,6 +1960,7 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
         return SMT_ERR_HIP;
     }
     calibrate_store_mode(h, !(flags & SMT_ADCENSUS_NO_STORE_CALIBRATION));
+    set_maps_resident(h);
     *out = h;
     return SMT_OK;
 }
@@ -1952,6 +2057,31 @@ static int maps_chunks()
     return k >= 1 && k <= 64 ? k : 4;
 }
 
+// Tapered tail of a maps-only launch (maps_span): the counts n2, n1 per slice for a launch whose slices have `per`
+// chunks, from S = the workgroups of the launching kernel that one slice's CUs hold at a time (maps_resident, queried
+// at create; 0: unknown).  THE DEFAULT RULE: off when the slice has no more than S groups -- a launch of at most one
+// round has no last round to taper -- and otherwise n2 = S * TAPER_N2_HALVES / 2, n1 = S * TAPER_N1_HALVES / 2, the
+// sizing chosen by the sweep of DESIGN.md section 4 "Tapered tail": one resident set of 1-chunk workgroups and no
+// half-sized ones, the only sizing of the sweep that won at all three workloads (more 1-chunk workgroups, or any
+// half-sized ones, lose 4 % at 1080p x 192, where a 1-chunk workgroup flushes four ring columns per pixel).
+//   SMT_MAPS_TAPER in the environment (read at every call): `0` is off -- the plain rule and the plain placement of the
+//   auxiliary groups; `n2,n1` are these counts per slice whatever the launch size (tests, the sweep).
+// Returns the counts shrunk to the slice (maps_span_tails), so the kernels' span arithmetic takes no division for them.
+constexpr int TAPER_N2_HALVES = 0, TAPER_N1_HALVES = 2;
+static void maps_taper(int S, long per, int K, int &n2, int &n1)
+{
+    n2 = n1 = 0;
+    const char *env = getenv("SMT_MAPS_TAPER");
+    if (env && env[0]) {
+        int a = 0, b = 0;
+        if (sscanf(env, "%d,%d", &a, &b) == 2 && a >= 0 && b >= 0) { n2 = a; n1 = b; }
+    } else if (S > 0 && maps_span_groups(per, K, 0, 0) > S) {
+        n2 = (int)((long)S * TAPER_N2_HALVES / 2);
+        n1 = (int)((long)S * TAPER_N1_HALVES / 2);
+    }
+    (void)maps_span_tails(per, K, n2, n1);
+}
+
 // SMT_MAPS_SHARED=0 in the environment (read at every call) keeps the two-view k_cost_maps2p where the shared form
 // (k_cost_maps_shared) would run: same-process A/Bs and tests.
 static bool maps_shared()
@@ -2002,38 +2132,40 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
     if (views == SMT_VIEW_BOTH && maps) {
         // pair of a batch whose volumes nobody can read: maps only, the next pair's table workgroups (if any) fused in
         const int K = maps_chunks();
-        const int ncost = maps_groups(nbx, h->H, 2, K);
         int nprep = 0, ptx = 1;
-        unsigned grid = (unsigned)ncost;
-        if (nL) {
-            nprep = prep_items(h->H, h->W, ptx);
-            grid = 8u * (unsigned)fused_grid(ncost, nprep).groups;
-        }
+        if (nL) nprep = prep_items(h->H, h->W, ptx);
         const Tables &Tn = h->TS[(h->n_pairs + 1) & 1];
         const char *env = getenv("SMT_MAPS_KERNEL");
+        int n2, n1;
         if (pair_takes_shared(h, views, dL, dR, maps)) {
             // One launch on the caller's stream: the left-view runs, this pair's edge items, the next pair's table tiles
             // and the previous shared pair's conversion.  This pair's own conversion stays pending.
             const int km = (int)(h->n_pairs & 1);
             if (h->conv_pending && h->conv_map == km) flush_conversion(h);   // cannot happen: shared pairs in a row alternate
             const bool carried = h->conv_pending;
-            const int ncs = maps_groups(nbx, h->H, 1, K), Dd = FULL ? 64 * C : h->D;
+            maps_taper(h->maps_resident[0], ((long)nbx * h->H + 7) >> 3, K, n2, n1);
+            const int ncs = maps_groups(nbx, h->H, 1, K, n2, n1), Dd = FULL ? 64 * C : h->D;
+            const int cbody = maps_body_groups(nbx, h->H, 1, K, n2, n1);
             const int nconv = carried ? shared_conv_items(h->H, h->W) : 0, nedge = shared_edge_items(h->H, h->W, Dd);
-            const unsigned gs = 8u * (unsigned)fused_grid(ncs, nprep + nconv + nedge).groups;
+            const unsigned gs = 8u * (unsigned)fused_grid(ncs, nprep + nconv + nedge, cbody).groups;
             hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
                                h->skeys[km], nbx, K, shared_pub_hi(h->W), ncs, nprep, nL, nR, Tn, ptx, nconv, nedge,
-                               carried ? h->skeys[h->conv_map] : nullptr, carried ? h->conv_dR : nullptr);
+                               carried ? h->skeys[h->conv_map] : nullptr, carried ? h->conv_dR : nullptr, n2, n1, cbody);
             if (SMT_SHARED_KNOCKOUT != 2) { h->conv_pending = true; h->conv_map = km; h->conv_dR = dR; }
             else h->conv_pending = false;
             if (shared_finish_apart()) flush_conversion(h);
             return;
         }
-        if (env && env[0] == 'r')
+        const bool rank = env && env[0] == 'r';
+        maps_taper(h->maps_resident[rank ? 2 : 1], ((long)nbx * h->H * 2 + 7) >> 3, K, n2, n1);
+        const int ncost = maps_groups(nbx, h->H, 2, K, n2, n1), cbody = maps_body_groups(nbx, h->H, 2, K, n2, n1);
+        const unsigned grid = nL ? 8u * (unsigned)fused_grid(ncost, nprep, cbody).groups : (unsigned)ncost;
+        if (rank)
             hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_RANK>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
-                               h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx);
+                               h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx, n2, n1, cbody);
         else
             hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_FLOAT>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
-                               h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx);
+                               h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx, n2, n1, cbody);
         return;
     }
     if (views == SMT_VIEW_BOTH && nL) {
@@ -2377,21 +2509,25 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
     int rc = (keys && val && nw) ? SMT_OK : SMT_ERR_ALLOC;
     for (size_t p = 0; rc == SMT_OK && p < N; p++) keys[p] = SH_NOKEY;
     if (rc == SMT_OK && idhi >= 3) {
-        const int nleft = maps_groups(nbx, H, 1, K);
+        // the taper the launch would take (maps_taper: SMT_MAPS_TAPER's forced counts; no device here, so the default
+        // rule is off)
+        int n2, n1;
+        maps_taper(0, ((long)nbx * H + 7) >> 3, K, n2, n1);
+        const int nleft = maps_groups(nbx, H, 1, K, n2, n1);
         unsigned long long ring[SH_RING_N];
         int owner[SH_RING_N];                                             // right column that holds a slot in this run
         for (long b = 0; b < nleft && rc == SMT_OK; b++) {
             for (int e = 0; e < SH_RING_N; e++) ring[e] = SH_NOKEY;
             int view, i, bx, ni, nbxn;
-            int left = shared_wg_chunks(nbx, H, K, b, i, bx);
+            int left = shared_wg_chunks(nbx, H, K, b, i, bx, n2, n1);
             for (int t = 0; t < K; t++)                                   // the chunks are chunk_decode's
-                if (chunk_decode(nbx, H, 1, K, b, t, view, ni, nbxn) != (t < left)) rc = SMT_ERR_STATE;
+                if (chunk_decode(nbx, H, 1, K, b, t, view, ni, nbxn, n2, n1) != (t < left)) rc = SMT_ERR_STATE;
             // sub-runs of SH_RUN: the publishes of the whole run, then its one flush
             for (int t = 0; left > 0 && rc == SMT_OK;) {
                 const int n = shared_run_len(nbx, bx, left);
                 if (n < 1 || n > SH_RUN) { rc = SMT_ERR_STATE; break; }
                 for (int u = 0; u < n; u++)
-                    if (!chunk_decode(nbx, H, 1, K, b, t + u, view, ni, nbxn) || ni != i || nbxn != bx + u) rc = SMT_ERR_STATE;
+                    if (!chunk_decode(nbx, H, 1, K, b, t + u, view, ni, nbxn, n2, n1) || ni != i || nbxn != bx + u) rc = SMT_ERR_STATE;
                 const int S = 64 * bx, E = S + 64 * n - 1;
                 for (int e = 0; e < SH_RING_N; e++) owner[e] = -1;
                 for (int j = S; j <= E && j < W; j++)
@@ -2523,15 +2659,20 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
 // Host-side check of a shared launch's auxiliary list (fused_grid / fused_decode over ncost cost workgroups and
 // nprep + nconv + nedge auxiliary items, shared_aux_decode): every cost workgroup and every table, conversion and edge
 // item is decoded exactly once.  Needs no GPU.
-SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv)
+// With a tapered tail (cbody > 0: the cost groups of the body) and a body that takes the auxiliary groups, none of them
+// follows cost group cbody, the first tapered one; cbody = 0 must give the plain placement.
+static int shared_aux_grid_check(int ncost, int nprep, int nedge, int nconv, int cbody)
 {
-    if (ncost <= 0 || (ncost & 7) || nprep < 0 || nedge < 0 || nconv < 0) return SMT_ERR_ARG;
+    if (ncost <= 0 || (ncost & 7) || nprep < 0 || nedge < 0 || nconv < 0 || cbody < 0) return SMT_ERR_ARG;
     const int naux = nprep + nconv + nedge;
-    const FusedGrid f = fused_grid(ncost, naux);
+    const FusedGrid f = fused_grid(ncost, naux, cbody), f0 = fused_grid(ncost, naux);
     if (8L * f.groups < (long)ncost + naux) return SMT_ERR_STATE;
+    if (cbody == 0 && (f.every != f0.every || f.slots != f0.slots || f.groups != f0.groups)) return SMT_ERR_STATE;
+    const bool in_body = cbody > 0 && cbody < f.cgroups && f.pgroups > 0 && cbody >= f.pgroups;
     unsigned char *cost = new (std::nothrow) unsigned char[(size_t)ncost]();
     unsigned char *aux = new (std::nothrow) unsigned char[(size_t)naux + 1]();
     int rc = (cost && aux) ? SMT_OK : SMT_ERR_ALLOC;
+    bool tapered = false;                                                 // a tapered cost group has been dispatched
     for (long blk = 0; blk < 8L * f.groups && rc == SMT_OK; blk++) {
         int idx = -1;
         const bool table = fused_decode(f, (int)(blk >> 3), idx);
@@ -2539,8 +2680,10 @@ SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedg
         const long b = (long)idx * 8 + (blk & 7);
         if (!table) {
             if (b >= ncost || cost[b]++) rc = SMT_ERR_STATE;
+            if (in_body && idx >= cbody) tapered = true;
             continue;
         }
+        if (in_body && tapered) rc = SMT_ERR_STATE;
         int item = -1;
         const int kind = shared_aux_decode((int)b, nprep, nconv, nedge, item);
         if (kind == AUX_NONE) { if (b < naux) rc = SMT_ERR_STATE; continue; }
@@ -2552,6 +2695,10 @@ SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedg
     for (int a = 0; a < naux && rc == SMT_OK; a++) if (aux[a] != 1) rc = SMT_ERR_STATE;
     delete[] cost; delete[] aux;
     return rc;
+}
+SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv)
+{
+    return shared_aux_grid_check(ncost, nprep, nedge, nconv, 0);
 }
 
 // Host-side check of the shared launch of an H x W x D pair with K chunks per cost workgroup, through the functions the
@@ -2565,9 +2712,11 @@ SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int fir
     const int idhi = shared_id_hi(W, D), nbx = (W + FTJ - 1) / FTJ;
     if (idhi < 3) return SMT_ERR_ARG;                                     // the two-view kernel serves this shape
     int ptx;
-    const int ncost = maps_groups(nbx, H, 1, K), nprep = last ? 0 : prep_items(H, W, ptx);
+    int n2, n1;                                                           // the launch's taper (maps_taper), no device
+    maps_taper(0, ((long)nbx * H + 7) >> 3, K, n2, n1);
+    const int ncost = maps_groups(nbx, H, 1, K, n2, n1), nprep = last ? 0 : prep_items(H, W, ptx);
     const int nconv = first ? 0 : shared_conv_items(H, W), nedge = shared_edge_items(H, W, D);
-    int rc = smt_adcensus_selftest_shared_aux_grid(ncost, nprep, nedge, nconv);
+    int rc = shared_aux_grid_check(ncost, nprep, nedge, nconv, maps_body_groups(nbx, H, 1, K, n2, n1));
     if (rc != SMT_OK) return rc;
     const long N = (long)H * W;
     unsigned char *seen = new (std::nothrow) unsigned char[(size_t)N]();
@@ -2604,6 +2753,52 @@ SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int fir
             if (c > idhi && c <= W - 4 && (lo > hi || lo < 1 || c + lo != W - 3)) rc = SMT_ERR_STATE;
             if (edge && (lo < 0 || hi > D - 1 || lo > hi)) rc = SMT_ERR_STATE;
         }
+    delete[] seen;
+    return rc;
+}
+
+// Host-side check of the span rule (maps_span, maps_span_groups) over the 8 slices of a launch of nb chunks with K
+// chunks per workgroup and tails n2, n1: every chunk 0 .. nb-1 belongs to exactly one group, no group crosses its slice
+// or has more than K chunks, no group before the last of a slice is empty, the group count is the companion's, and
+// with n1 = n2 = 0 every group is the plain rule's [g K, g K + K).  With tails that fit the slice, the slice's last n1
+// groups have 1 chunk and the n2 before them max(1, K / 2).  Needs no GPU.
+SMT_API int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1)
+{
+    if (nb <= 0 || nb > (1L << 28) || K < 1 || K > 64 || n2 < 0 || n1 < 0) return SMT_ERR_ARG;
+    const long per = (nb + 7) >> 3, ng = maps_span_groups(per, K, n2, n1);
+    unsigned char *seen = new (std::nothrow) unsigned char[(size_t)nb]();
+    if (!seen) return SMT_ERR_ALLOC;
+    int rc = SMT_OK, e2 = n2, e1 = n1;
+    const long body = maps_span_tails(per, K, e2, e1);
+    const int K2 = K > 1 ? K >> 1 : 1;
+    if (body < 0 || e2 > n2 || e1 > n1 || body + (long)e2 * K2 + e1 != per || ng != (body + K - 1) / K + e2 + e1) rc = SMT_ERR_STATE;
+    for (int x = 0; x < 8 && rc == SMT_OK; x++) {
+        long expect = 0;                                                  // groups are consecutive in the slice
+        for (long g = 0; g < ng + 2 && rc == SMT_OK; g++) {
+            long first = -1;
+            const int m = maps_span(per, K, n2, n1, g, first);
+            if (g >= ng) { if (m != 0) rc = SMT_ERR_STATE; continue; }
+            if (m < 1 || m > K || first != expect || first + m > per) { rc = SMT_ERR_STATE; break; }
+            if (g >= ng - e1 ? m != 1 : g >= ng - e1 - e2 ? m != K2 : (m != K && g != ng - e1 - e2 - 1)) rc = SMT_ERR_STATE;
+            if (n1 == 0 && n2 == 0) {
+                const long cl = g * K, lim = per - cl < K ? per - cl : K;      // the plain rule
+                if (first != cl || m != lim) rc = SMT_ERR_STATE;
+            }
+            expect = first + m;
+            for (long c = x * per + first; c < x * per + first + m; c++)
+                if (c < nb && seen[c]++) rc = SMT_ERR_STATE;
+        }
+        if (expect != per) rc = SMT_ERR_STATE;
+    }
+    for (long c = 0; c < nb && rc == SMT_OK; c++) if (seen[c] != 1) rc = SMT_ERR_STATE;
+    // the launch's own decode agrees with the span: shared_wg_chunks over a one-chunk-per-row image
+    for (long b = 0; b < 8 * ng && rc == SMT_OK && nb <= (1L << 20); b++) {
+        long first;
+        int i = -1, bx = -1;
+        const int m = maps_span(per, K, n2, n1, b >> 3, first), got = shared_wg_chunks(1, (int)nb, K, b, i, bx, n2, n1);
+        const long c = (b & 7) * per + first, want = c >= nb ? 0 : (nb - c < m ? nb - c : m);
+        if (got != want || (got > 0 && (i != c || bx != 0))) rc = SMT_ERR_STATE;
+    }
     delete[] seen;
     return rc;
 }

@@ -20,3 +20,5 @@ SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsign
 // Host-only selftests of the shared form's auxiliary work items (documented in include/smt.h).
 SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
 SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
+// Host-only selftest of the maps-only launches' span rule with a tapered tail (documented in include/smt.h).
+SMT_API int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);

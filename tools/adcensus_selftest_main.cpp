@@ -5,6 +5,7 @@
 //         tools/adcensus_selftest_main.cpp -fsanitize=address,undefined -o adcensus_selftest && ./adcensus_selftest
 // Exit status 0 iff every selftest returned SMT_OK on every shape (and the sanitizers stayed silent).
 #include <cstdio>
+#include <cstdlib>
 
 extern "C" {
 int smt_adcensus_selftest_fused_grid(int ncost, int nprep);
@@ -12,6 +13,7 @@ int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep);
 int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
 int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
 int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
+int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);
 }
 
 int main()
@@ -38,6 +40,25 @@ int main()
                 if (smt_adcensus_selftest_shared_aux(s[0], s[1], s[2], K, fl & 1, fl >> 1) != 0) { printf("shared_aux %d %d %d K=%d %d\n", s[0], s[1], s[2], K, fl); bad++; }
             if (smt_adcensus_selftest_maps_grid((s[1] + 63) / 64, s[0], K, 5) != 0) { printf("maps_grid %d %d K=%d\n", s[0], s[1], K); bad++; }
         }
+    // the span rule of the tapered tail, tails longer than the slice included
+    static const long nbs[] = {1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 80, 2000, 2047, 32400};
+    static const int spanKs[] = {1, 2, 3, 4, 5, 8, 64};
+    static const int tails[][2] = {{0, 0}, {0, 1}, {1, 0}, {1, 2}, {3, 3}, {7, 50}, {1000, 1000}};
+    for (long nb : nbs)
+        for (int K : spanKs)
+            for (const auto &t : tails)
+                if (smt_adcensus_selftest_spans(nb, K, t[0], t[1]) != 0) { printf("spans %ld K=%d %d,%d\n", nb, K, t[0], t[1]); bad++; }
+    // the shared form's walk and its auxiliary placement under forced tapers (SMT_MAPS_TAPER is read at every call)
+    static const char *forced[] = {"0", "0,2", "1,2", "3,1", "7,50"};
+    for (const char *f : forced) {
+        setenv("SMT_MAPS_TAPER", f, 1);
+        for (const auto &s : shapes)
+            for (int K : Ks) {
+                if (smt_adcensus_selftest_shared_keys(s[0], s[1], s[2], K, 3u) != 0) { printf("shared_keys %d %d %d K=%d taper %s\n", s[0], s[1], s[2], K, f); bad++; }
+                if (s[1] - 3 - s[2] >= 3 && smt_adcensus_selftest_shared_aux(s[0], s[1], s[2], K, 0, 0) != 0) { printf("shared_aux %d %d %d K=%d taper %s\n", s[0], s[1], s[2], K, f); bad++; }
+            }
+    }
+    unsetenv("SMT_MAPS_TAPER");
     printf("%s: %d failures\n", bad ? "FAILED" : "ok", bad);
     return bad ? 1 : 0;
 }
