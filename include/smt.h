@@ -213,7 +213,40 @@ int smt_adcensus_compute(smt_adcensus *h, const float *L, const float *R, int vi
  * are double-buffered inside the handle: with both views and D <= 256 the table workgroups of pair
  * b+1 are spread through the grid of pair b's cost launch (one launch per pair, one stream); single
  * views and D > 256 build them on an internal stream beside pair b's cost kernel.  SMT_OVERLAP =
- * 0 / 1 / 2 in the environment forces in-order / internal-stream / fused (read at every call). */
+ * 0 / 1 / 2 / 3 in the environment forces in-order / internal-stream / fused / chained (read at every call).
+ * Chained (3, the default wherever the fused schedule would apply): the fused schedule on NC chains.  Pair b belongs to chain b % NC; a chain is the
+ * fused schedule with a stride of NC on two table sets and two key maps of its own (its first pair's tables by a
+ * stand-alone table kernel, pair b's launch carrying the tables of pair b + NC and the conversion of pair b - NC).
+ * Chain 0 runs on the caller's stream, chain c > 0 on an internal non-blocking stream that waits for an event the
+ * caller's stream records behind chain 0's table kernel, and the caller's stream waits for one event per internal
+ * chain behind its last launch before the call returns: events only, the call stays asynchronous, and nothing of it is
+ * pending or un-joined when it returns.  Launches of consecutive pairs then share the device, so one fills the other's
+ * ramp and drain.  A call takes it where it would take the fused schedule, with pairs >= 2 and not under
+ * SMT_BATCH_VOLUMES=all (every pair would store the same two volumes); else it keeps the fused one.  The maps are the
+ * same bit for bit.  A last pair that writes its volumes does so on its chain's stream.  All chains' state is allocated
+ * at create: 2 table sets and 2 key maps per chain, 84 H W + 128 H bytes for the sets and 16 H W for the maps, 207 MB
+ * per chain at 1920 x 1080 (415 MB for the two extra chains) beside 3.2 GB of volumes at D = 192.
+ *   SMT_CHAINS=<1..3> (read at every call; default 2; 3 is the maximum, a process has 4 hardware queues and the
+ *   caller's stream is one).  SMT_CHAIN_FORK=start forks the internal streams from the start of the call instead
+ *   (measurement).  SMT_CHAIN_ORDER=pairs|ab|ba (tests) keeps every chain's state indexing and changes the order on
+ *   the device: every chain on the caller's stream in pair order / chain c + 1 behind the whole of chain c / chain 0
+ *   behind the whole of the internal chains.  SMT_CHAIN_TAPER=all|last|none (measurement; default none): which
+ *   launches of a chained call keep the tapered tail's default rule -- beside another chain's launch a launch has no
+ *   drain of its own to recover ("Tapered tail" below; SMT_MAPS_TAPER still forces counts).
+ *   With smt_adcensus_timing a chained pair's events are recorded on its chain's stream: kernel_ms of such a pair spans
+ *   a launch that shares the device with its neighbour's, and the stand-alone table kernel of a chain's first pair is
+ *   not inside its table interval.
+ * Test hook, host only (no GPU), exported and declared in csrc/adcensus_internal.h:
+ *   int smt_adcensus_selftest_chains(int pairs, int chains, long c0, long c1, long c2, int order, unsigned flags);
+ * writes the plan of such a call down (the function the call itself runs) for chains whose pair counters stand at c0,
+ * c1, c2 (earlier calls leave any parity), order 0 (default) / 1 pairs / 2 ab / 3 ba, flags 1 shared form | 2 the last
+ * pair writes volumes | 4 fork at the start | 8 SMT_SHARED_FINISH=apart, and computes happens-before over its launches
+ * from stream order and the event edges.  SMT_OK iff every event is recorded before it is waited on, every table set a
+ * launch reads was built for its pair by a launch before it and is built by no other unless before that builder or
+ * behind the reader, every key map is merged, converted exactly once into the merging pair's map and only then merged
+ * again, by launches in a total order, every pair is launched once and its right map is complete before the call's end
+ * on the caller's stream, and every operation lies between the call's start and its end there.  SMT_ERR_STATE
+ * otherwise; SMT_ERR_ARG unless 1 <= pairs <= 512, 1 <= chains <= 3, counters >= 0, order 0..3, flags < 16. */
 int smt_adcensus_compute_batch(smt_adcensus *h, const float *L, const float *R, int pairs,
                                int views, float *dispL, float *dispR);
 

@@ -29,6 +29,7 @@
 #include <string.h>
 #include <algorithm>
 #include <new>
+#include <vector>
 #include <type_traits>
 
 namespace {
@@ -1584,17 +1585,42 @@ __global__ void __launch_bounds__(NT) k_wta(const float *__restrict__ vol, int N
 
 thread_local int g_smt_last_hip = 0;
 
+// Chains of the chained batch schedule (chain_plan).  Three at the most: a process has four hardware queues here and
+// the caller's stream is one of them.
+constexpr int SMT_MAX_CHAINS = 3;
+constexpr int SMT_CHAINS_DEFAULT = 2;
+// The chained schedule is the default of smt_adcensus_compute_batch wherever the fused one would be (batch_schedule).
+constexpr bool SMT_CHAINED_DEFAULT = true;
+struct ChainState {
+    long n_pairs;        // pairs issued on this chain ([0]: and by every schedule that is not chained)
+    bool conv_pending;
+    int conv_map;        // index into skeys[]
+    float *conv_dR;
+};
+// Table set and key map that chain c's pair number n (the chain's own counter) uses: TS[] / skeys[] index.
+static inline int chain_slot(int c, long n) { return 2 * c + (int)(n & 1); }
+
 struct smt_adcensus {
     int device;          // HIP device the handle lives on
     int H, W, D;
     float sigmaC, sigmaS;
     hipStream_t stream;
     float *vol[2];
-    Tables T;            // table set used by the pair being issued (= TS[n_pairs & 1])
-    Tables TS[2];        // two sets: the tables of pair n+1 are built while pair n's cost kernel runs
-    hipStream_t prep_stream;                 // internal, non-blocking
+    Tables T;            // table set used by the pair being issued (= TS[chain_slot(cur, its chain's n_pairs)])
+    // Two sets per chain (chain c owns 2c and 2c+1): the tables of a chain's next pair are built while its pair runs.
+    // Chain 0 is the state of every schedule but the chained one (smt_adcensus_compute, schedules 0 .. 2, host-fed flow).
+    Tables TS[2 * SMT_MAX_CHAINS];
+    hipStream_t prep_stream;                 // internal, non-blocking: schedule 1's table stream and chain 1's stream
+    hipStream_t chain2_stream;               // internal, non-blocking: chain 2's stream
     hipEvent_t in_ready, prep_done[2], cost_done[2];
-    long n_pairs;        // pairs issued on this handle
+    hipEvent_t fork_ev, join_ev[SMT_MAX_CHAINS];   // the chained schedule's edges per call (chain_plan); join_ev[0] unused
+    ChainState chain[SMT_MAX_CHAINS];
+    // The chain whose state the pair being issued uses, and the internal stream each chain runs on in the call being
+    // issued (0: the caller's stream).  All 0 outside adcensus_batch_chained.
+    int cur, chain_on[SMT_MAX_CHAINS];
+    // The pair being issued runs beside another chain's launch, which fills its drain: the tapered tail's default rule
+    // is off for it (maps_taper, chain_taper).  False outside adcensus_batch_chained.
+    bool beside;
     hipEvent_t *ev;      // SMT_TIMING_SLOTS * 4, lazily created
     bool timing;
     bool force_generic;  // test hook: route D%64==0 through the generic kernel too
@@ -1606,14 +1632,12 @@ struct smt_adcensus {
     float store_mode_ms[2];   // calibration: kernel ms with streaming / plain stores (0: not calibrated)
     int place_tries;     // candidate volume pairs tried by place_volumes
     float place_ms;      // store-only time of the pair that was kept (0: no search)
-    // Two [H][W] key maps of the shared maps-only form; pair n merges into map n_pairs & 1.  Both are all SH_NOKEY after
-    // create and whenever no conversion is pending.  conv_pending: the shared pair issued last has its partial keys in
-    // skeys[conv_map], still to be converted into its right map conv_dR -- by the next pair's shared launch, or by
-    // flush_conversion().  Never true when an entry point returns (the caller may free its maps).
-    unsigned long long *skeys[2];
-    bool conv_pending;
-    int conv_map;
-    float *conv_dR;
+    // Two [H][W] key maps of the shared maps-only form per chain; a chain's pair n merges into map chain_slot(c, n).
+    // All are SH_NOKEY after create and whenever no conversion is pending.  chain[c].conv_pending: the shared pair the
+    // chain issued last has its partial keys in skeys[conv_map], still to be converted into its right map conv_dR -- by
+    // the chain's next shared launch, or by flush_conversion().  Never true when an entry point returns (the caller may
+    // free its maps).
+    unsigned long long *skeys[2 * SMT_MAX_CHAINS];
     // Deferred volumes of a batch's last pair (smt_adcensus_compute_batch, smt_adcensus_volume).  vol_lent: a caller
     // has been given a volume pointer, so every batch from then on writes its last pair's volumes itself.
     // vol_pending: the last pair took the maps-only path and its volumes are still to be written, by the both-views
@@ -1858,15 +1882,24 @@ static bool build_rank(const float *lut, uint16_t *rank)
     return true;
 }
 
-// The pending conversion of the shared form, if any, as a launch of its own on the handle's stream.  Every path that
-// is not the next pair's shared launch calls this before it does anything else on the stream.
-static void flush_conversion(smt_adcensus *h)
+// The stream chain c runs on in the call being issued: the caller's, or the internal one the chained schedule gave it.
+static hipStream_t chain_stream(const smt_adcensus *h, int c)
 {
-    if (!h->conv_pending) return;
+    return h->chain_on[c] == 0 ? h->stream : h->chain_on[c] == 1 ? h->prep_stream : h->chain2_stream;
+}
+// The stream of the pair being issued.
+static hipStream_t run_stream(const smt_adcensus *h) { return chain_stream(h, h->cur); }
+
+// The pending conversion of chain c's shared form, if any, as a launch of its own on the chain's stream.  Every path
+// that is not the chain's next shared launch calls this before it does anything else on that stream.
+static void flush_conversion(smt_adcensus *h, int c)
+{
+    ChainState &ch = h->chain[c];
+    if (!ch.conv_pending) return;
     const long N = (long)h->H * h->W;
-    hipLaunchKernelGGL(k_shared_convert, dim3((unsigned)shared_conv_items(h->H, h->W)), dim3(NT), 0, h->stream,
-                       h->skeys[h->conv_map], h->conv_dR, N);
-    h->conv_pending = false;
+    hipLaunchKernelGGL(k_shared_convert, dim3((unsigned)shared_conv_items(h->H, h->W)), dim3(NT), 0, chain_stream(h, c),
+                       h->skeys[ch.conv_map], ch.conv_dR, N);
+    ch.conv_pending = false;
 }
 
 // maps_resident of the handle: CUs / 8 x the workgroups per CU the runtime reports for the instantiation that D selects
@@ -1909,7 +1942,6 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
     h->device = smt_current_device();
     h->H = H; h->W = W; h->D = D; h->sigmaC = sigmaC; h->sigmaS = sigmaS;
     h->stream = nullptr; h->timing = false; h->force_generic = false; h->ev = nullptr; h->n_timed = 0; h->n_seen = 0; h->timing_stride = 1; h->ev_merged = nullptr;
-    h->n_pairs = 0;
     const size_t N = (size_t)H * W, V = N * D;
     const int WX = W + 4;
     int rc = place_volumes(h, !(flags & SMT_ADCENSUS_NO_PLACEMENT_SEARCH));
@@ -1917,7 +1949,7 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
     alloc((void **)&h->TS[0].lut, 320 * 4);
     alloc((void **)&h->TS[0].rank, RANK_N * 2);
     alloc((void **)&h->TS[0].flag, 4);
-    for (int t = 0; t < 2; t++) {
+    for (int t = 0; t < 2 * SMT_MAX_CHAINS; t++) {
         h->TS[t].WX = WX;
         h->TS[t].stamp = nullptr;
         h->TS[t].lut = h->TS[0].lut;                     // shared
@@ -1930,14 +1962,21 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
         }
         alloc((void **)&h->TS[t].mask, N * 8);
     }
-    for (int t = 0; t < 2; t++) alloc((void **)&h->skeys[t], N * 8);
+    for (int t = 0; t < 2 * SMT_MAX_CHAINS; t++) alloc((void **)&h->skeys[t], N * 8);
     h->T = h->TS[0];
     if (rc != SMT_OK) { smt_adcensus_destroy(h); return rc; }
     if (hipStreamCreateWithFlags(&h->prep_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->in_ready, hipEventDisableTiming) != hipSuccess) {
+        hipStreamCreateWithFlags(&h->chain2_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&h->in_ready, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming) != hipSuccess) {
         smt_adcensus_destroy(h);
         return SMT_ERR_HIP;
     }
+    for (int c = 1; c < SMT_MAX_CHAINS; c++)
+        if (hipEventCreateWithFlags(&h->join_ev[c], hipEventDisableTiming) != hipSuccess) {
+            smt_adcensus_destroy(h);
+            return SMT_ERR_HIP;
+        }
     for (int t = 0; t < 2; t++)
         if (hipEventCreateWithFlags(&h->prep_done[t], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&h->cost_done[t], hipEventDisableTiming) != hipSuccess) {
@@ -1954,11 +1993,12 @@ static int adcensus_create(int H, int W, int D, float sigmaC, float sigmaS, unsi
     // GetPtrLeft/Right before the first Compute* reads zeros
     if (!rank_ok || hipMemcpy(h->TS[0].lut, lut, sizeof(lut), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(h->vol[0], 0, V * 4) != hipSuccess || hipMemset(h->vol[1], 0, V * 4) != hipSuccess ||
-        hipMemset(h->TS[0].flag, 0, 4) != hipSuccess || hipMemset(h->skeys[0], 0xFF, N * 8) != hipSuccess ||
-        hipMemset(h->skeys[1], 0xFF, N * 8) != hipSuccess) {
+        hipMemset(h->TS[0].flag, 0, 4) != hipSuccess) {
         smt_adcensus_destroy(h);
         return SMT_ERR_HIP;
     }
+    for (int t = 0; t < 2 * SMT_MAX_CHAINS; t++)
+        if (hipMemset(h->skeys[t], 0xFF, N * 8) != hipSuccess) { smt_adcensus_destroy(h); return SMT_ERR_HIP; }
     calibrate_store_mode(h, !(flags & SMT_ADCENSUS_NO_STORE_CALIBRATION));
     set_maps_resident(h);
     *out = h;
@@ -1992,22 +2032,27 @@ SMT_API int smt_adcensus_destroy(smt_adcensus *h)
 {
     if (!h) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
-    if (h->conv_pending) { flush_conversion(h); (void)hipStreamSynchronize(h->stream); }
+    for (int c = 0; c < SMT_MAX_CHAINS; c++)                 // never pending here; chain_on is all 0: the handle's stream
+        if (h->chain[c].conv_pending) { flush_conversion(h, c); (void)hipStreamSynchronize(h->stream); }
     if (h->prep_stream) { (void)hipStreamSynchronize(h->prep_stream); (void)hipStreamDestroy(h->prep_stream); }
+    if (h->chain2_stream) { (void)hipStreamSynchronize(h->chain2_stream); (void)hipStreamDestroy(h->chain2_stream); }
     if (h->in_ready) (void)hipEventDestroy(h->in_ready);
+    if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
+    for (int c = 1; c < SMT_MAX_CHAINS; c++)
+        if (h->join_ev[c]) (void)hipEventDestroy(h->join_ev[c]);
     for (int t = 0; t < 2; t++) {
         if (h->prep_done[t]) (void)hipEventDestroy(h->prep_done[t]);
         if (h->cost_done[t]) (void)hipEventDestroy(h->cost_done[t]);
     }
     (void)hipFree(h->vol[0]); (void)hipFree(h->vol[1]);
-    for (int t = 0; t < 2; t++) {
+    for (int t = 0; t < 2 * SMT_MAX_CHAINS; t++) {
         for (int v = 0; v < 2; v++) {
             (void)hipFree(h->TS[t].cenA[v]); (void)hipFree(h->TS[t].cenX[v]); (void)hipFree(h->TS[t].u8[v]);
         }
         (void)hipFree(h->TS[t].mask);
     }
     (void)hipFree(h->TS[0].lut); (void)hipFree(h->TS[0].rank); (void)hipFree(h->TS[0].flag);
-    (void)hipFree(h->skeys[0]); (void)hipFree(h->skeys[1]);
+    for (int t = 0; t < 2 * SMT_MAX_CHAINS; t++) (void)hipFree(h->skeys[t]);
     if (h->ev) {
         for (int k = 0; k < SMT_TIMING_SLOTS * 4; k++) (void)hipEventDestroy(h->ev[k]);
         delete[] h->ev_merged;
@@ -2031,7 +2076,8 @@ SMT_API int smt_adcensus_set_quirks(smt_adcensus *h, unsigned quirks)
     // every launch takes its Tables (this pair's and, for the table workgroups riding in a cost launch, the next
     // pair's) by value from these at issue time; no call leaves tables built for the next one
     const int col = (quirks & SMT_QUIRK_FIX_CENSUS_RIGHT_EDGE) ? h->W - 1 : 0;
-    h->T.edge_col = h->TS[0].edge_col = h->TS[1].edge_col = col;
+    h->T.edge_col = col;
+    for (int t = 0; t < 2 * SMT_MAX_CHAINS; t++) h->TS[t].edge_col = col;
     return SMT_OK;
 }
 
@@ -2043,7 +2089,7 @@ static void launch_cost(smt_adcensus *h, int view0, int nviews, float *d0, float
     const int NX = TJ + D;
     size_t shm = (size_t)NX * 8 + TJ * 16 + 320 * 4 + NX + TJ;
     shm = (shm + 15) & ~(size_t)15;
-    hipLaunchKernelGGL((k_cost<C, FULL>), grid, dim3(NT), shm, h->stream, h->H, h->W, D, h->T,
+    hipLaunchKernelGGL((k_cost<C, FULL>), grid, dim3(NT), shm, run_stream(h), h->H, h->W, D, h->T,
                        view0, h->vol[0], h->vol[1], d0, d1);
 }
 
@@ -2129,42 +2175,44 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
 {
     const int nbx = (h->W + FTJ - 1) / FTJ;
     auto blocks = [&](int nviews) { return dim3((unsigned)(((long)nbx * h->H * nviews + 7) / 8 * 8)); };
+    ChainState &ch = h->chain[h->cur];
+    const hipStream_t st = run_stream(h);
     if (views == SMT_VIEW_BOTH && maps) {
         // pair of a batch whose volumes nobody can read: maps only, the next pair's table workgroups (if any) fused in
         const int K = maps_chunks();
         int nprep = 0, ptx = 1;
         if (nL) nprep = prep_items(h->H, h->W, ptx);
-        const Tables &Tn = h->TS[(h->n_pairs + 1) & 1];
+        const Tables &Tn = h->TS[chain_slot(h->cur, ch.n_pairs + 1)];
         const char *env = getenv("SMT_MAPS_KERNEL");
         int n2, n1;
         if (pair_takes_shared(h, views, dL, dR, maps)) {
-            // One launch on the caller's stream: the left-view runs, this pair's edge items, the next pair's table tiles
-            // and the previous shared pair's conversion.  This pair's own conversion stays pending.
-            const int km = (int)(h->n_pairs & 1);
-            if (h->conv_pending && h->conv_map == km) flush_conversion(h);   // cannot happen: shared pairs in a row alternate
-            const bool carried = h->conv_pending;
-            maps_taper(h->maps_resident[0], ((long)nbx * h->H + 7) >> 3, K, n2, n1);
+            // One launch on the chain's stream: the left-view runs, this pair's edge items, the table tiles of the
+            // chain's next pair and the conversion of its previous shared pair.  This pair's own conversion stays pending.
+            const int km = chain_slot(h->cur, ch.n_pairs);
+            if (ch.conv_pending && ch.conv_map == km) flush_conversion(h, h->cur);   // cannot happen: shared pairs in a row alternate
+            const bool carried = ch.conv_pending;
+            maps_taper(h->beside ? 0 : h->maps_resident[0], ((long)nbx * h->H + 7) >> 3, K, n2, n1);
             const int ncs = maps_groups(nbx, h->H, 1, K, n2, n1), Dd = FULL ? 64 * C : h->D;
             const int cbody = maps_body_groups(nbx, h->H, 1, K, n2, n1);
             const int nconv = carried ? shared_conv_items(h->H, h->W) : 0, nedge = shared_edge_items(h->H, h->W, Dd);
             const unsigned gs = 8u * (unsigned)fused_grid(ncs, nprep + nconv + nedge, cbody).groups;
-            hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, dL, dR,
+            hipLaunchKernelGGL((k_cost_maps_shared<C, FULL>), dim3(gs), dim3(NT), 0, st, h->H, h->W, h->D, h->T, dL, dR,
                                h->skeys[km], nbx, K, shared_pub_hi(h->W), ncs, nprep, nL, nR, Tn, ptx, nconv, nedge,
-                               carried ? h->skeys[h->conv_map] : nullptr, carried ? h->conv_dR : nullptr, n2, n1, cbody);
-            if (SMT_SHARED_KNOCKOUT != 2) { h->conv_pending = true; h->conv_map = km; h->conv_dR = dR; }
-            else h->conv_pending = false;
-            if (shared_finish_apart()) flush_conversion(h);
+                               carried ? h->skeys[ch.conv_map] : nullptr, carried ? ch.conv_dR : nullptr, n2, n1, cbody);
+            if (SMT_SHARED_KNOCKOUT != 2) { ch.conv_pending = true; ch.conv_map = km; ch.conv_dR = dR; }
+            else ch.conv_pending = false;
+            if (shared_finish_apart()) flush_conversion(h, h->cur);
             return;
         }
         const bool rank = env && env[0] == 'r';
-        maps_taper(h->maps_resident[rank ? 2 : 1], ((long)nbx * h->H * 2 + 7) >> 3, K, n2, n1);
+        maps_taper(h->beside ? 0 : h->maps_resident[rank ? 2 : 1], ((long)nbx * h->H * 2 + 7) >> 3, K, n2, n1);
         const int ncost = maps_groups(nbx, h->H, 2, K, n2, n1), cbody = maps_body_groups(nbx, h->H, 2, K, n2, n1);
         const unsigned grid = nL ? 8u * (unsigned)fused_grid(ncost, nprep, cbody).groups : (unsigned)ncost;
         if (rank)
-            hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_RANK>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
+            hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_RANK>), dim3(grid), dim3(NT), 0, st, h->H, h->W,
                                h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx, n2, n1, cbody);
         else
-            hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_FLOAT>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W,
+            hipLaunchKernelGGL((k_cost_maps2p<C, FULL, MODE_MAPS_FLOAT>), dim3(grid), dim3(NT), 0, st, h->H, h->W,
                                h->D, h->T, dL, dR, nbx, K, ncost, nprep, nL, nR, Tn, ptx, n2, n1, cbody);
         return;
     }
@@ -2175,29 +2223,29 @@ static void launch_fast(smt_adcensus *h, int views, float *dL, float *dR, const 
         const int eb = (h->H + PNT / 16 - 1) / (PNT / 16);
         const int nprep = ptx * (pty + (eb + ptx - 1) / ptx);
         const unsigned grid = 8u * (unsigned)fused_grid(ncost, nprep).groups;
-        const Tables &Tn = h->TS[(h->n_pairs + 1) & 1];
+        const Tables &Tn = h->TS[chain_slot(h->cur, ch.n_pairs + 1)];
         if (h->plain_stores)
-            hipLaunchKernelGGL((k_cost_fast2p<C, FULL, false>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T,
+            hipLaunchKernelGGL((k_cost_fast2p<C, FULL, false>), dim3(grid), dim3(NT), 0, st, h->H, h->W, h->D, h->T,
                                h->vol[0], h->vol[1], dL, dR, nbx, ncost, nprep, nL, nR, Tn, ptx);
         else
-            hipLaunchKernelGGL((k_cost_fast2p<C, FULL, true>), dim3(grid), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T,
+            hipLaunchKernelGGL((k_cost_fast2p<C, FULL, true>), dim3(grid), dim3(NT), 0, st, h->H, h->W, h->D, h->T,
                                h->vol[0], h->vol[1], dL, dR, nbx, ncost, nprep, nL, nR, Tn, ptx);
         return;
     }
     if (views == SMT_VIEW_BOTH) {
         if (h->plain_stores)
-            hipLaunchKernelGGL((k_cost_fast2<C, FULL, false>), blocks(2), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, h->vol[0],
+            hipLaunchKernelGGL((k_cost_fast2<C, FULL, false>), blocks(2), dim3(NT), 0, st, h->H, h->W, h->D, h->T, h->vol[0],
                                h->vol[1], dL, dR, nbx);
         else
-            hipLaunchKernelGGL((k_cost_fast2<C, FULL, true>), blocks(2), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T, h->vol[0],
+            hipLaunchKernelGGL((k_cost_fast2<C, FULL, true>), blocks(2), dim3(NT), 0, st, h->H, h->W, h->D, h->T, h->vol[0],
                                h->vol[1], dL, dR, nbx);
         return;
     }
     if (views & SMT_VIEW_LEFT)
-        hipLaunchKernelGGL((k_cost_fast<C, 0, FULL>), blocks(1), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T,
+        hipLaunchKernelGGL((k_cost_fast<C, 0, FULL>), blocks(1), dim3(NT), 0, st, h->H, h->W, h->D, h->T,
                            h->vol[0], dL, nbx);
     if (views & SMT_VIEW_RIGHT)
-        hipLaunchKernelGGL((k_cost_fast<C, 1, FULL>), blocks(1), dim3(NT), 0, h->stream, h->H, h->W, h->D, h->T,
+        hipLaunchKernelGGL((k_cost_fast<C, 1, FULL>), blocks(1), dim3(NT), 0, st, h->H, h->W, h->D, h->T,
                            h->vol[1], dR, nbx);
 }
 
@@ -2218,7 +2266,8 @@ static bool launch_fast_as(int C, bool full, smt_adcensus *h, int views, float *
     return true;
 }
 
-// One pair into table set (n & 1).  Three schedules for the pairs of a batch:
+// One pair into its chain's table set chain_slot(cur, n).  Three schedules for the pairs of a batch on chain 0, and the
+// chained one (chain_plan below), which issues every pair as a `prepped` pair of the fused schedule on its chain:
 //   fused (default, both views through the register-window kernel): the table workgroups of pair n + 1 ride in the
 //     grid of pair n's cost kernel (k_cost_fast2p) -- one stream, one launch per pair, no events; `prepped` says this
 //     pair's tables were built that way, `nL / nR` are the next pair's images (null for the last pair of a batch);
@@ -2236,36 +2285,42 @@ static bool fast_both_views(const smt_adcensus *h, int views)
     return views == SMT_VIEW_BOTH && !h->force_generic && (h->D + 63) / 64 <= 4;
 }
 
+// The stand-alone table kernel of one pair: tile workgroups + the workgroups of the 13 border columns (16 rows each)
+// in one launch.
+static void launch_prep(const smt_adcensus *h, hipStream_t st, const float *L, const float *R, const Tables &T)
+{
+    const int tx = (h->W + PTW - 1) / PTW, ty = (h->H + PTH - 1) / PTH;
+    const int eb = (h->H + PNT / 16 - 1) / (PNT / 16);
+    hipLaunchKernelGGL(k_prep, dim3(tx, ty + (eb + tx - 1) / tx), dim3(PNT), 0, st, L, R, h->H, h->W, T);
+}
+
 // maps: the pair's volumes are not written (a batch pair before the last; fast_both_views only).
 static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int views, float *dL,
                          float *dR, bool overlap, bool prepped = false, const float *nL = nullptr,
                          const float *nR = nullptr, bool maps = false)
 {
-    const int H = h->H, W = h->W, D = h->D;
-    const int set = (int)(h->n_pairs & 1);
+    const int D = h->D;
+    ChainState &ch = h->chain[h->cur];
+    const int set = chain_slot(h->cur, ch.n_pairs);
+    const hipStream_t st = run_stream(h);                    // the caller's stream unless a chain runs on an internal one
     h->T = h->TS[set];
     h->vol_pending = false;                                  // never observable: dropped with the tables they would come from
-    if (!pair_takes_shared(h, views, dL, dR, maps)) flush_conversion(h);
+    if (!pair_takes_shared(h, views, dL, dR, maps)) flush_conversion(h, h->cur);
     const bool timed = h->timing && (h->n_seen++ % h->timing_stride) == 0;
     const long slot = h->n_timed % SMT_TIMING_SLOTS;
     hipEvent_t *ev = timed ? h->ev + 4 * slot : nullptr;
     // overlap == false: everything in order on the caller's stream (single pairs, first pair of a batch)
-    hipStream_t ps = overlap ? h->prep_stream : h->stream;
-    if (overlap && h->n_pairs >= 2) SMT_HIP(hipStreamWaitEvent(ps, h->cost_done[set], 0));
+    hipStream_t ps = overlap ? h->prep_stream : st;          // overlap: chain 0 only, set is 0 or 1
+    if (overlap && ch.n_pairs >= 2) SMT_HIP(hipStreamWaitEvent(ps, h->cost_done[set], 0));
     if (timed) (void)hipEventRecord(ev[0], ps);
-    if (!prepped) {
-        // tile workgroups + the workgroups of the 13 border columns (16 rows each) in one launch
-        const int tx = (W + PTW - 1) / PTW, ty = (H + PTH - 1) / PTH;
-        const int eb = (H + PNT / 16 - 1) / (PNT / 16);
-        hipLaunchKernelGGL(k_prep, dim3(tx, ty + (eb + tx - 1) / tx), dim3(PNT), 0, ps, L, R, H, W, h->T);
-    }
+    if (!prepped) launch_prep(h, ps, L, R, h->T);
     if (timed) (void)hipEventRecord(ev[1], ps);
     if (overlap) {
         SMT_HIP(hipEventRecord(h->prep_done[set], ps));
-        SMT_HIP(hipStreamWaitEvent(h->stream, h->prep_done[set], 0));
+        SMT_HIP(hipStreamWaitEvent(st, h->prep_done[set], 0));
     }
     // one stream: the event after the table kernels is also the cost kernel's start
-    if (timed) { h->ev_merged[slot] = !overlap; if (overlap) (void)hipEventRecord(ev[2], h->stream); }
+    if (timed) { h->ev_merged[slot] = !overlap; if (overlap) (void)hipEventRecord(ev[2], st); }
     const int view0 = (views & SMT_VIEW_LEFT) ? 0 : 1;
     const int nviews = (views == SMT_VIEW_BOTH) ? 2 : 1;
     const int C = (D + 63) / 64;
@@ -2284,10 +2339,11 @@ static int adcensus_pair(smt_adcensus *h, const float *L, const float *R, int vi
         default: launch_cost<8, false>(h, view0, nviews, dL, dR); break;
         }
     } else if (!launch_fast_as(C, full, h, views, dL, dR, nL, nR, maps)) return SMT_ERR_ARG;
-    if (timed) { (void)hipEventRecord(ev[3], h->stream); h->n_timed++; }
-    // the two-stream schedule waits on this before it reuses the table set; the fused one is ordered by its stream
-    if (!prepped && !nL) SMT_HIP(hipEventRecord(h->cost_done[set], h->stream));
-    h->n_pairs++;
+    if (timed) { (void)hipEventRecord(ev[3], st); h->n_timed++; }
+    // the two-stream schedule waits on this before it reuses the table set; the fused one is ordered by its stream and
+    // a chain > 0 by the call's join
+    if (!prepped && !nL && h->cur == 0) SMT_HIP(hipEventRecord(h->cost_done[set], st));
+    ch.n_pairs++;
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -2300,14 +2356,217 @@ SMT_API int smt_adcensus_compute(smt_adcensus *h, const float *L, const float *R
     return adcensus_pair(h, L, R, views, dispL, dispR, false);
 }
 
-// schedule of the pairs b >= 1 of a batch: 0 in order, 1 two streams, 2 fused launches (adcensus_pair)
+// schedule of the pairs b >= 1 of a batch: 0 in order, 1 two streams, 2 fused launches (adcensus_pair), 3 fused
+// launches in chains (chain_plan); smt_adcensus_compute_batch keeps 2 where 3 does not apply
 static int batch_schedule(const smt_adcensus *h, int views)
 {
-    const char *env = getenv("SMT_OVERLAP");             // tuning hook: 0 / 1 / 2 forces the choice
-    int want = 2;
-    if (env && env[0] >= '0' && env[0] <= '2' && env[1] == 0) want = env[0] - '0';
-    if (want == 2 && !fast_both_views(h, views)) want = 1;
+    const char *env = getenv("SMT_OVERLAP");             // tuning hook: 0 / 1 / 2 / 3 forces the choice
+    int want = SMT_CHAINED_DEFAULT ? 3 : 2;
+    if (env && env[0] >= '0' && env[0] <= '3' && env[1] == 0) want = env[0] - '0';
+    if (want >= 2 && !fast_both_views(h, views)) want = 1;
     return want;
+}
+
+// ---- The chained schedule (3): pair b of a call belongs to chain b % NC; inside a chain everything is the fused
+// schedule with a stride of NC, on the chain's own two table sets and two key maps; chain 0 runs on the caller's
+// stream, chain c > 0 on internal stream c, forked from and joined into the caller's stream by events.  chain_plan
+// writes the call down as a list of operations in issue order; adcensus_batch_chained issues that list and
+// smt_adcensus_selftest_chains proves its order.  DESIGN.md section 4 "Chained launches".
+enum { CH_PREP, CH_PAIR, CH_CONVERT, CH_RECORD, CH_WAIT };
+constexpr int SMT_CHAIN_TAPER_DEFAULT = 0;               // CHAIN_TAPER_NONE
+enum { CHAIN_ORDER_BESIDE = 0, CHAIN_ORDER_PAIRS, CHAIN_ORDER_AB, CHAIN_ORDER_BA };
+enum { CHAIN_SHARED = 1, CHAIN_LAST_VOLUMES = 2, CHAIN_FORK_START = 4, CHAIN_FINISH_APART = 8, CHAIN_FLAGS = 15 };
+struct ChainOp {
+    int kind;
+    int stream;            // 0: the caller's stream, c: the internal stream of chain c
+    int chain;
+    int pair;              // CH_PREP: the pair whose tables it builds; CH_PAIR: the pair; CH_CONVERT: -1
+    int ts_read;           // CH_PAIR: TS[] index the launch reads; else -1
+    int ts_built;          // CH_PREP, CH_PAIR: TS[] index the launch builds, for pair `built_for`; -1: none
+    int built_for;
+    int key_merged;        // CH_PAIR in the shared form: skeys[] index the launch merges into; else -1
+    int key_conv;          // CH_PAIR, CH_CONVERT: skeys[] index converted, into the right map of pair `conv_pair`; -1: none
+    int conv_pair;
+    int ev;                // CH_RECORD, CH_WAIT: 0 the fork event, c the join event of chain c
+};
+
+// n pairs on nc chains whose pair counters stand at count0[] (only their parity matters).  flags: CHAIN_SHARED the
+// maps-only pairs take the shared form; CHAIN_LAST_VOLUMES the last pair writes its volumes (never shared, converts
+// nothing of its own); CHAIN_FORK_START fork from the call's first event instead of behind chain 0's k_prep;
+// CHAIN_FINISH_APART every shared pair is converted right behind its launch (SMT_SHARED_FINISH=apart).  order: the
+// SMT_CHAIN_ORDER forms; each keeps the state indexing and changes only streams and edges.
+static int chain_plan(int n, int nc, const long *count0, int order, unsigned flags, std::vector<ChainOp> &ops)
+{
+    ops.clear();
+    if (n < 1 || nc < 1 || nc > SMT_MAX_CHAINS || !count0 || order < CHAIN_ORDER_BESIDE || order > CHAIN_ORDER_BA ||
+        (flags & ~(unsigned)CHAIN_FLAGS))
+        return SMT_ERR_ARG;
+    long cnt[SMT_MAX_CHAINS];
+    int pend_key[SMT_MAX_CHAINS], pend_pair[SMT_MAX_CHAINS];
+    for (int c = 0; c < SMT_MAX_CHAINS; c++) {
+        if (count0[c] < 0) return SMT_ERR_ARG;
+        cnt[c] = count0[c]; pend_key[c] = pend_pair[c] = -1;
+    }
+    if (nc > n) nc = n;                                      // a chain without pairs issues nothing
+    auto on = [&](int c) { return order == CHAIN_ORDER_PAIRS ? 0 : c; };
+    auto blank = [&](int kind, int c) { return ChainOp{kind, on(c), c, -1, -1, -1, -1, -1, -1, -1, -1}; };
+    auto event = [&](int kind, int stream, int ev) {
+        if (order == CHAIN_ORDER_PAIRS || nc < 2) return;    // one stream: no edges
+        ChainOp o = blank(kind, stream); o.stream = stream; o.ev = ev; ops.push_back(o);
+    };
+    auto prep = [&](int c) {
+        ChainOp o = blank(CH_PREP, c); o.pair = o.built_for = c; o.ts_built = chain_slot(c, cnt[c]); ops.push_back(o);
+    };
+    auto convert = [&](int c) {
+        if (pend_key[c] < 0) return;
+        ChainOp o = blank(CH_CONVERT, c); o.key_conv = pend_key[c]; o.conv_pair = pend_pair[c]; ops.push_back(o);
+        pend_key[c] = pend_pair[c] = -1;
+    };
+    auto pair = [&](int b) {
+        const int c = b % nc;
+        const bool shared = (flags & CHAIN_SHARED) && !(b + 1 == n && (flags & CHAIN_LAST_VOLUMES));
+        if (!shared) convert(c);
+        ChainOp o = blank(CH_PAIR, c);
+        o.pair = b; o.ts_read = chain_slot(c, cnt[c]);
+        if (b + nc < n) { o.ts_built = chain_slot(c, cnt[c] + 1); o.built_for = b + nc; }
+        if (shared) {
+            o.key_merged = chain_slot(c, cnt[c]); o.key_conv = pend_key[c]; o.conv_pair = pend_pair[c];
+            pend_key[c] = o.key_merged; pend_pair[c] = b;
+        }
+        ops.push_back(o);
+        cnt[c]++;
+        if (flags & CHAIN_FINISH_APART) convert(c);
+    };
+    auto whole_chain = [&](int c) { prep(c); for (int b = c; b < n; b += nc) pair(b); convert(c); };
+    switch (order) {
+    case CHAIN_ORDER_BESIDE: case CHAIN_ORDER_PAIRS:
+        if (flags & CHAIN_FORK_START) event(CH_RECORD, 0, 0);
+        prep(0);
+        if (!(flags & CHAIN_FORK_START)) event(CH_RECORD, 0, 0);
+        for (int c = 1; c < nc; c++) { event(CH_WAIT, c, 0); prep(c); }
+        for (int b = 0; b < n; b++) pair(b);
+        for (int c = 0; c < nc; c++) convert(c);
+        for (int c = 1; c < nc; c++) event(CH_RECORD, c, c);
+        for (int c = 1; c < nc; c++) event(CH_WAIT, 0, c);
+        break;
+    case CHAIN_ORDER_AB:                                     // chain c + 1 behind the whole of chain c
+        whole_chain(0);
+        event(CH_RECORD, 0, 0);
+        for (int c = 1; c < nc; c++) { event(CH_WAIT, c, c - 1); whole_chain(c); event(CH_RECORD, c, c); }
+        for (int c = 1; c < nc; c++) event(CH_WAIT, 0, c);
+        break;
+    default:                                                 // CHAIN_ORDER_BA: chain 0 behind the whole of the others
+        event(CH_RECORD, 0, 0);
+        for (int c = 1; c < nc; c++) { event(CH_WAIT, c, 0); whole_chain(c); event(CH_RECORD, c, c); }
+        for (int c = 1; c < nc; c++) event(CH_WAIT, 0, c);
+        whole_chain(0);
+        break;
+    }
+    return SMT_OK;
+}
+
+// Chains of a chained call: SMT_CHAINS=<1..3> in the environment (read at every call), 2 otherwise.
+static int chain_count()
+{
+    const char *env = getenv("SMT_CHAINS");
+    return env && env[0] >= '1' && env[0] <= '0' + SMT_MAX_CHAINS && env[1] == 0 ? env[0] - '0' : SMT_CHAINS_DEFAULT;
+}
+// SMT_CHAIN_ORDER=pairs|ab|ba in the environment (read at every call): test hook, the orders of chain_plan.
+static int chain_order()
+{
+    const char *env = getenv("SMT_CHAIN_ORDER");
+    if (!env) return CHAIN_ORDER_BESIDE;
+    return strcmp(env, "pairs") == 0 ? CHAIN_ORDER_PAIRS : strcmp(env, "ab") == 0 ? CHAIN_ORDER_AB :
+           strcmp(env, "ba") == 0 ? CHAIN_ORDER_BA : CHAIN_ORDER_BESIDE;
+}
+
+// Which launches of a chained call keep the tapered tail's default rule: SMT_CHAIN_TAPER=all|last|none in the
+// environment (read at every call; measurement).  The taper recovers the drain of a launch that runs alone; beside
+// another chain's launch there is no such drain and its 1-chunk workgroups only cost.
+enum { CHAIN_TAPER_NONE, CHAIN_TAPER_LAST, CHAIN_TAPER_ALL };
+static int chain_taper()
+{
+    const char *env = getenv("SMT_CHAIN_TAPER");
+    if (!env) return SMT_CHAIN_TAPER_DEFAULT;
+    return strcmp(env, "all") == 0 ? CHAIN_TAPER_ALL : strcmp(env, "last") == 0 ? CHAIN_TAPER_LAST :
+           strcmp(env, "none") == 0 ? CHAIN_TAPER_NONE : SMT_CHAIN_TAPER_DEFAULT;
+}
+
+// Schedule 3 of adcensus_batch_pairs: issues chain_plan's list.  Events only, no host synchronisation.  Whatever
+// happens, every chain's pending conversion is issued and every internal stream that was given work is joined into the
+// caller's stream before this returns, ahead of anything else the caller's stream gets.
+static int adcensus_batch_chained(smt_adcensus *h, const float *L, const float *R, int n, int views, float *dispL,
+                                  float *dispR, bool last_volumes)
+{
+    const size_t N = (size_t)h->H * h->W;
+    const char *fenv = getenv("SMT_CHAIN_FORK");
+    unsigned flags = 0;
+    if (pair_takes_shared(h, views, dispL, dispR, true)) flags |= CHAIN_SHARED;
+    if (last_volumes) flags |= CHAIN_LAST_VOLUMES;
+    if (fenv && strcmp(fenv, "start") == 0) flags |= CHAIN_FORK_START;
+    if (shared_finish_apart()) flags |= CHAIN_FINISH_APART;
+    long count0[SMT_MAX_CHAINS];
+    for (int c = 0; c < SMT_MAX_CHAINS; c++) count0[c] = h->chain[c].n_pairs;
+    std::vector<ChainOp> ops;
+    const int nc = chain_count(), order = chain_order(), taper = chain_taper();
+    int rc = chain_plan(n, nc, count0, order, flags, ops);
+    if (rc != SMT_OK) return rc;
+    const bool concurrent = order == CHAIN_ORDER_BESIDE && std::min(nc, n) >= 2;
+    auto internal = [&](int s) { return s == 1 ? h->prep_stream : h->chain2_stream; };
+    auto stream = [&](int s) { return s == 0 ? h->stream : internal(s); };
+    bool open[SMT_MAX_CHAINS] = {false, false, false};       // internal stream s has work that no join event covers yet
+    int last_set = 0;
+    auto issue = [&](const ChainOp &o) -> int {
+        if (o.stream > 0 && o.kind != CH_RECORD) open[o.stream] = true;
+        h->cur = o.chain;
+        h->chain_on[o.chain] = o.kind == CH_RECORD || o.kind == CH_WAIT ? h->chain_on[o.chain] : o.stream;
+        switch (o.kind) {
+        case CH_PREP:
+            launch_prep(h, stream(o.stream), L + o.pair * N, R + o.pair * N, h->TS[o.ts_built]);
+            return SMT_OK;
+        case CH_PAIR: {
+            const int b = o.pair;
+            if (chain_slot(o.chain, h->chain[o.chain].n_pairs) != o.ts_read) return SMT_ERR_STATE;   // plan and state disagree
+            if (b + 1 == n) last_set = o.ts_read;
+            h->beside = concurrent && (taper == CHAIN_TAPER_NONE || (taper == CHAIN_TAPER_LAST && b + 1 < n));
+            return adcensus_pair(h, L + b * N, R + b * N, views, dispL ? dispL + b * N : nullptr,
+                                 dispR ? dispR + b * N : nullptr, false, true,
+                                 o.ts_built >= 0 ? L + o.built_for * N : nullptr,
+                                 o.ts_built >= 0 ? R + o.built_for * N : nullptr, !(b + 1 == n && last_volumes));
+        }
+        case CH_CONVERT:
+            flush_conversion(h, o.chain);
+            return SMT_OK;
+        case CH_RECORD:
+            SMT_HIP(hipEventRecord(o.ev ? h->join_ev[o.ev] : h->fork_ev, stream(o.stream)));
+            if (o.stream > 0) open[o.stream] = false;
+            return SMT_OK;
+        default:
+            SMT_HIP(hipStreamWaitEvent(stream(o.stream), o.ev ? h->join_ev[o.ev] : h->fork_ev, 0));
+            return SMT_OK;
+        }
+    };
+    for (size_t k = 0; k < ops.size() && rc == SMT_OK; k++) rc = issue(ops[k]);
+    if (rc != SMT_OK) {
+        // an error path: what the plan had not issued yet of conversions and joins.  Waiting on a join event a second
+        // time is harmless; an event recorded again is waited on again.
+        for (int c = 0; c < SMT_MAX_CHAINS; c++) flush_conversion(h, c);
+        for (int s = 1; s < SMT_MAX_CHAINS; s++) {
+            bool used = open[s];
+            for (int c = 0; c < SMT_MAX_CHAINS; c++) used = used || h->chain_on[c] == s;
+            if (!used) continue;
+            (void)hipEventRecord(h->join_ev[s], internal(s));
+            (void)hipStreamWaitEvent(h->stream, h->join_ev[s], 0);
+        }
+    } else {
+        h->T = h->TS[last_set];                              // the deferred volumes come from the last pair's tables
+    }
+    h->cur = 0;
+    h->beside = false;
+    for (int c = 0; c < SMT_MAX_CHAINS; c++) h->chain_on[c] = 0;
+    if (rc != SMT_OK) return rc;
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
 }
 
 // The per-pair loop of a batch (adcensus_internal.h).  Pair b >= 1 follows `sched`; pair 0 is in order, with its tables
@@ -2320,6 +2579,11 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
 {
     const size_t N = (size_t)h->H * h->W;
     maps_ok = maps_ok && fast_both_views(h, views);
+    if (sched == 3) {
+        if (maps_ok && n >= 2 && !prepped && !nL && !nR)
+            return adcensus_batch_chained(h, L, R, n, views, dispL, dispR, last_volumes);
+        sched = 2;                                           // every pair stores the handle's two volumes, or a host-fed chunk
+    }
     for (int b = 0; b < n; b++) {
         const bool last = b + 1 == n;
         const float *bl = sched == 2 ? (last ? nL : L + (b + 1) * N) : nullptr;
@@ -2327,10 +2591,10 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
         int rc = adcensus_pair(h, L + b * N, R + b * N, views, dispL ? dispL + b * N : nullptr,
                                dispR ? dispR + b * N : nullptr, sched == 1 && b > 0, b > 0 ? sched == 2 : prepped,
                                bl, br, maps_ok && (!last || !last_volumes));
-        if (rc != SMT_OK) { flush_conversion(h); return rc; }
+        if (rc != SMT_OK) { flush_conversion(h, 0); return rc; }
     }
     // the last shared pair has no next launch; the caller may read or free its maps behind this call
-    flush_conversion(h);
+    flush_conversion(h, 0);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -2343,7 +2607,7 @@ bool adcensus_fused_both_views(const smt_adcensus *h) { return fast_both_views(h
 // what it would have.  With timing on, the launch is recorded like a pair whose tables were already built.
 static int materialise_volumes(smt_adcensus *h)
 {
-    flush_conversion(h);
+    flush_conversion(h, 0);                                  // never pending here: no entry point leaves one
     if (!h->vol_pending) return SMT_OK;
     const long slot = h->n_timed % SMT_TIMING_SLOTS;
     hipEvent_t *ev = h->timing ? h->ev + 4 * slot : nullptr;
@@ -2806,6 +3070,90 @@ SMT_API int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1)
 // Host-side check of the rank table (build_rank) against the float sums it stands for: for sigmaC, sigmaS > 0, every
 // sum lut[ad] + lut[256 + hd] is finite and >= +0, ranks are dense from 0, and for any two entries rank order equals
 // float order (equal ranks exactly when the bit patterns are equal).  Needs no GPU.
+// Host-side proof of the chained schedule's order (include/smt.h): chain_plan's list for `pairs` pairs on `chains`
+// chains whose counters stand at c0, c1, c2, under `order` and `flags`, with happens-before computed over its
+// operations -- program order per stream plus every record -> wait edge, between a start and an end on the caller's
+// stream.  Needs no GPU.
+SMT_API int smt_adcensus_selftest_chains(int pairs, int chains, long c0, long c1, long c2, int order, unsigned flags)
+{
+    if (pairs < 1 || pairs > 512) return SMT_ERR_ARG;
+    const long count0[SMT_MAX_CHAINS] = {c0, c1, c2};
+    std::vector<ChainOp> ops;
+    const int prc = chain_plan(pairs, chains, count0, order, flags, ops);
+    if (prc != SMT_OK) return prc;
+    const int nc = std::min(chains, pairs);
+    // node 0: the call's start on the caller's stream; node m + 1: its end there
+    const int m = (int)ops.size(), M = m + 2;
+    auto stream_of = [&](int k) { return k == 0 || k == M - 1 ? 0 : ops[k - 1].stream; };
+    std::vector<std::vector<unsigned char>> before(M, std::vector<unsigned char>(M, 0));   // before[i][j]: j happens before i
+    int last_on[SMT_MAX_CHAINS] = {-1, -1, -1}, recorded[SMT_MAX_CHAINS] = {-1, -1, -1};
+    auto edge = [&](int from, int to) {
+        for (int j = 0; j < M; j++) before[to][j] |= before[from][j];
+        before[to][from] = 1;
+    };
+    for (int k = 0; k < M; k++) {
+        const int s = stream_of(k);
+        if (s < 0 || s >= SMT_MAX_CHAINS) return SMT_ERR_STATE;
+        if (last_on[s] >= 0) edge(last_on[s], k);
+        last_on[s] = k;
+        if (k == 0 || k == M - 1) continue;
+        const ChainOp &o = ops[k - 1];
+        if (o.kind == CH_RECORD) recorded[o.ev] = k;
+        if (o.kind == CH_WAIT) {
+            if (recorded[o.ev] < 0) return SMT_ERR_STATE;    // an event is recorded before anything waits on it
+            edge(recorded[o.ev], k);
+        }
+    }
+    auto hb = [&](int a, int b) { return before[b][a] != 0; };
+    // nothing starts ahead of the call (the fork) and nothing is left un-joined
+    for (int k = 1; k < M - 1; k++)
+        if (!hb(0, k) || !hb(k, M - 1)) return SMT_ERR_STATE;
+    std::vector<int> launches(pairs, 0), converted(pairs, 0);
+    for (int k = 1; k < M - 1; k++) {
+        const ChainOp &o = ops[k - 1];
+        if (o.kind == CH_PAIR) {
+            if (o.pair < 0 || o.pair >= pairs || o.chain != o.pair % nc) return SMT_ERR_STATE;
+            if (o.stream != (order == CHAIN_ORDER_PAIRS ? 0 : o.chain)) return SMT_ERR_STATE;
+            launches[o.pair]++;
+            // the set it reads was built for this pair by a launch before it, and whatever else builds that set does so
+            // before that builder or behind this reader
+            int builder = -1;
+            for (int j = 1; j < M - 1; j++)
+                if (ops[j - 1].ts_built == o.ts_read && ops[j - 1].built_for == o.pair && hb(j, k)) builder = builder < 0 ? j : -2;
+            if (builder < 0) return SMT_ERR_STATE;
+            for (int j = 1; j < M - 1; j++)
+                if (j != builder && ops[j - 1].ts_built == o.ts_read && !hb(j, builder) && !hb(k, j)) return SMT_ERR_STATE;
+            if (o.key_merged >= 0 && o.key_merged == o.key_conv) return SMT_ERR_STATE;
+        }
+        if (o.key_conv >= 0) {
+            if (o.conv_pair < 0 || o.conv_pair >= pairs) return SMT_ERR_STATE;
+            converted[o.conv_pair]++;
+        }
+    }
+    const bool any_shared = (flags & CHAIN_SHARED) != 0;
+    for (int b = 0; b < pairs; b++) {
+        const bool shared = any_shared && !(b + 1 == pairs && (flags & CHAIN_LAST_VOLUMES));
+        if (launches[b] != 1 || converted[b] != (shared ? 1 : 0)) return SMT_ERR_STATE;
+    }
+    // every key map: merged, converted into the merging pair's map, merged again ..., by operations in a total order
+    for (int key = 0; key < 2 * SMT_MAX_CHAINS; key++) {
+        int prev = -1, merged_by = -1;                       // the last operation on the key; the pair whose keys it holds
+        for (int k = 1; k < M - 1; k++) {
+            const ChainOp &o = ops[k - 1];
+            if (o.key_conv == key) {
+                if (merged_by < 0 || o.conv_pair != merged_by || !hb(prev, k)) return SMT_ERR_STATE;
+                prev = k; merged_by = -1;
+            }
+            if (o.key_merged == key) {
+                if (merged_by >= 0 || (prev >= 0 && !hb(prev, k))) return SMT_ERR_STATE;
+                prev = k; merged_by = o.pair;
+            }
+        }
+        if (merged_by >= 0) return SMT_ERR_STATE;            // a conversion left pending
+    }
+    return SMT_OK;
+}
+
 SMT_API int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS)
 {
     if (!(sigmaC > 0.0f) || !(sigmaS > 0.0f)) return SMT_ERR_ARG;
@@ -2913,7 +3261,7 @@ struct DiagResources {
 
 static int smt_adcensus_diag_impl(smt_adcensus *h, int reps, float *sclk_mhz, float *cost_ms, float *store_only_ms, DiagResources &res)
 {
-    if (h->n_pairs == 0) return SMT_ERR_STATE;               // needs the tables of a computed pair
+    if (h->chain[0].n_pairs == 0) return SMT_ERR_STATE;      // needs the tables of a computed pair
     const int D = h->D, C = D / 64;
     if (D % 64 != 0 || C < 1 || C > 4) return SMT_ERR_ARG;
     const int nbx = (h->W + FTJ - 1) / FTJ;

@@ -5,7 +5,8 @@
 
 // The per-pair loop of smt_adcensus_compute_batch over pairs [0, n) of L / R ([n][H][W] each, maps likewise) on the
 // handle's stream.  sched: how pairs b >= 1 get their tables -- 0 in order, 1 on the internal stream, 2 built inside
-// the previous pair's launch (needs adcensus_fused_both_views and views == SMT_VIEW_BOTH).  prepped: pair 0's tables
+// the previous pair's launch (needs adcensus_fused_both_views and views == SMT_VIEW_BOTH), 3 as 2 in chains on internal
+// streams joined before the return (include/smt.h; as 2 where n < 2, maps_ok is clear, prepped is set or nL / nR given).  prepped: pair 0's tables
 // were built by the previous call's last launch (sched 2 with nL / nR).  nL, nR: with sched 2, the images of the pair
 // after the last one, whose tables the last pair's launch builds (nullptr: none).  maps_ok: pairs may skip their
 // volume stores (maps-only kernel); last_volumes: the last pair writes its volumes all the same.  The caller has
@@ -22,3 +23,5 @@ SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedg
 SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
 // Host-only selftest of the maps-only launches' span rule with a tapered tail (documented in include/smt.h).
 SMT_API int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);
+// Host-only selftest of the chained batch schedule's order (documented in include/smt.h).
+SMT_API int smt_adcensus_selftest_chains(int pairs, int chains, long c0, long c1, long c2, int order, unsigned flags);

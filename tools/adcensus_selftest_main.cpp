@@ -14,6 +14,7 @@ int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed)
 int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
 int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
 int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);
+int smt_adcensus_selftest_chains(int pairs, int chains, long c0, long c1, long c2, int order, unsigned flags);
 }
 
 int main()
@@ -59,6 +60,18 @@ int main()
             }
     }
     unsetenv("SMT_MAPS_TAPER");
+    // the chained schedule's order: every order and flag set, every parity of the chains' counters
+    for (int pairs = 1; pairs <= 12; pairs++)
+        for (int chains = 1; chains <= 3; chains++)
+            for (int order = 0; order < 4; order++)
+                for (unsigned flags = 0; flags < 16; flags++)
+                    for (int par = 0; par < 8; par++)
+                        if (smt_adcensus_selftest_chains(pairs, chains, par & 1, 2 + ((par >> 1) & 1), 5 - (par >> 2), order, flags) != 0) {
+                            printf("chains %d %d order %d flags %u parity %d\n", pairs, chains, order, flags, par); bad++;
+                        }
+    if (smt_adcensus_selftest_chains(0, 2, 0, 0, 0, 0, 0) != -1 || smt_adcensus_selftest_chains(4, 4, 0, 0, 0, 0, 0) != -1 ||
+        smt_adcensus_selftest_chains(4, 2, 0, -1, 0, 0, 0) != -1 || smt_adcensus_selftest_chains(4, 2, 0, 0, 0, 4, 0) != -1 ||
+        smt_adcensus_selftest_chains(4, 2, 0, 0, 0, 0, 16) != -1) { printf("chains: bad arguments accepted\n"); bad++; }
     printf("%s: %d failures\n", bad ? "FAILED" : "ok", bad);
     return bad ? 1 : 0;
 }
