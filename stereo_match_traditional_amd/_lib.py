@@ -211,6 +211,18 @@ def _declare_subpixel(l):
         getattr(l, name).argtypes = [vp, pp]
 
 
+def _declare_sad_subpixel(l):
+    """The signatures of include/smt_sad_subpixel.h; an older build loaded through SMT_HIP_LIB is left as it is."""
+    if not hasattr(l, "smt_sad_subpixel"):
+        return
+    vp, i = C.c_void_p, C.c_int
+    pp = C.POINTER(SubpixelParams)
+    l.smt_sad_subpixel.argtypes = [vp, vp, i, i, i, i, i, pp, vp, vp, vp]
+    l.smt_sad_both_subpixel.argtypes = [vp, vp, i, i, i, i, pp, vp, vp, vp, vp, vp, vp]
+    l.smt_sad_subpixel_host.argtypes = [vp, vp, i, i, i, i, pp, vp, vp, vp, vp]
+    l.smt_sad_flow_run_batch_subpixel.argtypes = [vp, vp, vp, i, pp, vp, vp, vp, vp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -225,6 +237,7 @@ def lib():
         _declare_cblsm_window(_lib)
         _declare_ncc_whole(_lib)
         _declare_subpixel(_lib)
+        _declare_sad_subpixel(_lib)
     return _lib
 
 

@@ -18,7 +18,7 @@ from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
 from ._lib import NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT  # noqa: F401
 from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
-__all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "wta_subpixel", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
+__all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "wta_subpixel", "GetPointDepthSubpixel", "GetPointDepthBothSubpixel", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
            "ScanlineOptimizer", "LeftRightConsistency", "LeftAndRightConsistency", "CrossAggregator", "GetPointDepthLeft",
            "GetPointDepthRight", "sad_CrossCheckDiaparity", "NCC_algorithem", "ncc_set_impl", "sad_set_impl", "asw_masks",
            "AdaptiveSupportWeight", "sad_batch", "ncc_batch", "asw_batch", "asw_set_impl", "asw_CrossCheckDiaparity", "cvtColor_BGR2GRAY", "copyMakeBorder_replicate",
@@ -851,6 +851,43 @@ def GetPointDepthBoth(leftimg, rightimg, MaxDisparity, winsize, want_cost=False)
     check(lib().smt_sad_both(_ptr(leftimg), _ptr(rightimg), H, W, MaxDisparity, winsize, _ptr(dl), _ptr(dr), _ptr(cl),
                              current_stream_ptr()), "smt_sad_both")
     return (dl, dr, cl) if want_cost else (dl, dr)
+
+
+@_on_tensor_device
+def GetPointDepthSubpixel(leftimg, rightimg, MaxDisparity, winsize, view=VIEW_LEFT, min_den=1.0, want_winner=False):
+    """smt_sad_subpixel: one SAD view with the parabola of Sad.h:76-81 kept (include/smt_sad_subpixel.h).  uint8 images
+    replicate-padded by winsize+1 -> disp float32 [H][W], or (disp, winner) with want_winner (int32: smt_sad's map).
+    min_den None = the library's default."""
+    w = winsize + 1
+    Hp, Wp = leftimg.shape
+    H, W = Hp - 2 * w, Wp - 2 * w
+    _dev(leftimg, torch.uint8, (Hp, Wp), "leftimg")
+    _dev(rightimg, torch.uint8, (Hp, Wp), "rightimg")
+    disp = torch.empty((H, W), dtype=torch.float32, device=leftimg.device)
+    win = torch.empty((H, W), dtype=torch.int32, device=leftimg.device) if want_winner else None
+    check(lib().smt_sad_subpixel(_ptr(leftimg), _ptr(rightimg), H, W, MaxDisparity, winsize, view, _subpixel_arg(min_den),
+                                 _ptr(disp), _ptr(win), current_stream_ptr()), "smt_sad_subpixel")
+    return (disp, win) if want_winner else disp
+
+
+@_on_tensor_device
+def GetPointDepthBothSubpixel(leftimg, rightimg, MaxDisparity, winsize, min_den=1.0, want_winner=False, want_cost=False):
+    """smt_sad_both_subpixel: both sub-pixel SAD maps from one evaluation of the hypotheses, behind GetPointDepthBoth's
+    hooks.  -> (dispL, dispR) float32, then (winL, winR) int32 with want_winner, then costL with want_cost."""
+    w = winsize + 1
+    Hp, Wp = leftimg.shape
+    H, W = Hp - 2 * w, Wp - 2 * w
+    _dev(leftimg, torch.uint8, (Hp, Wp), "leftimg")
+    _dev(rightimg, torch.uint8, (Hp, Wp), "rightimg")
+    dl = torch.empty((H, W), dtype=torch.float32, device=leftimg.device)
+    dr = torch.empty_like(dl)
+    wl = torch.empty((H, W), dtype=torch.int32, device=leftimg.device) if want_winner else None
+    wr = torch.empty_like(wl) if want_winner else None
+    cl = torch.empty((H, W, MaxDisparity), dtype=torch.float32, device=leftimg.device) if want_cost else None
+    check(lib().smt_sad_both_subpixel(_ptr(leftimg), _ptr(rightimg), H, W, MaxDisparity, winsize, _subpixel_arg(min_den),
+                                      _ptr(dl), _ptr(dr), _ptr(wl), _ptr(wr), _ptr(cl), current_stream_ptr()),
+          "smt_sad_both_subpixel")
+    return (dl, dr) + ((wl, wr) if want_winner else ()) + ((cl,) if want_cost else ())
 
 
 def sad_both_set_impl(impl):
@@ -1872,6 +1909,26 @@ class SADFlow:
         check(lib().smt_sad_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_sad_flow_set_stream")
         check(lib().smt_sad_flow_run_batch(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(last), _ptr(cls)),
               "smt_sad_flow_run_batch")
+        return dl, dr, last, cls
+
+    def run_subpixel(self, grayL, grayR, min_den=1.0):
+        """run() with the parabola of Sad.h:76-81 kept (smt_sad_flow_run_batch_subpixel) -> (dispL, dispR, lastdisp, cls):
+        float32, float32, float32, uint8.  The cross-check is decided on the integer winners, so cls is run()'s; lastdisp
+        is dispL where accepted and +inf where rejected."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"SAD handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        last = torch.empty_like(dl)
+        cls = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        check(lib().smt_sad_flow_set_stream(self._h, current_stream_ptr(self.device)), "smt_sad_flow_set_stream")
+        check(lib().smt_sad_flow_run_batch_subpixel(self._h, _ptr(grayL), _ptr(grayR), P, _subpixel_arg(min_den), _ptr(dl),
+                                                    _ptr(dr), _ptr(last), _ptr(cls)), "smt_sad_flow_run_batch_subpixel")
         return dl, dr, last, cls
 
     def close(self):

@@ -17,7 +17,7 @@ def _stale():
         return True
     t = os.path.getmtime(OUT)
     deps = glob.glob(os.path.join(CSRC, "*")) + glob.glob(os.path.join(HERE, "host", "*")) + \
-        [os.path.join(HERE, "..", "include", "smt.h")]
+        glob.glob(os.path.join(HERE, "..", "include", "*.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -43,10 +43,16 @@ constexpr int BOX_MAX_SIDE = 181;        // 255 * side^2 < 2^23: (cost << 9) | d
 // box_steps as force-inlined functions taking references, the KT = 8 instantiation keeps C in scratch (560 private bytes
 // for 0, one loop left rolled) and KT = 4 takes 394 VGPRs for 275; timed in the same section.  A fix to the skeleton goes
 // into both places.
-template <int KT>
+//
+// SPX (smt_sad_both_subpixel): the left view's float map subL from the chained row of the emit
+// step (sad_wave_subpixel), dispL the optional integer winner.  SPX = false is the integer kernel: subL and min_den are
+// dead kernel arguments there.  (As a force-inlined body under two kernels of the old signatures, the KT = 2 integer
+// instantiation took 230 VGPRs for 171: the sensitivity described above.)
+template <int KT, bool SPX>
 __global__ void __launch_bounds__(BNT) k_sad_box(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
                                                  int D, int w, int band, int32_t *__restrict__ dispL,
-                                                 float *__restrict__ costL, unsigned *__restrict__ rkeys)
+                                                 float *__restrict__ costL, unsigned *__restrict__ rkeys,
+                                                 float *__restrict__ subL, float min_den)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned s_box[];
     const int side = 2 * w + 1, Wp = W + 2 * w;
@@ -181,7 +187,7 @@ __global__ void __launch_bounds__(BNT) k_sad_box(const uint8_t *__restrict__ Lp,
                     for (int k = 0; k < KT; k++) sad[k] = (k < nk && lane + 64 * k < D) ? (float)cc[k] : 0.0f;   // sadvalue :15-20
                     const int out = sad_optimal<KT>(sad, D, lane);
                     const size_t pix = (size_t)io * W + x;
-                    if (lane == 0) dispL[pix] = out;
+                    sad_store<SPX>(pix, lane, out, SPX ? sad_wave_subpixel<KT>(sad, out, D, min_den) : 0.0f, dispL, subL);
                     if (costL) {
 #pragma unroll
                         for (int k = 0; k < KT; k++)
@@ -209,6 +215,69 @@ __global__ void __launch_bounds__(BNT) k_sad_box(const uint8_t *__restrict__ Lp,
                 }
             }
         }
+    }
+}
+
+// The right view's sub-pixel map from the finished key map.  The keys hold the winner w = key & 511 and its cost
+// cm = key >> 9 only; the neighbours are other pixels' costs, costR(x', w +- 1) = costL(x' + w +- 1, w +- 1), which no
+// lane of the box kernel holds when the key is final.  So they are recomputed: the two window sums of the right window at
+// x' against the left windows at x' + w - 1 and x' + w + 1, with v_sad_u8 over full dwords plus the masked last dword of
+// a row as sad_pixel (csrc/window.hip) takes them (bytes for the 3 x 3 window).  G lanes share a pixel (G a power of two
+// from 4 to 64, chosen by the host from the window's dword count; 64 / G pixels per wave), each takes every G-th dword of
+// the window, and the sums meet in an xor butterfly inside the group.  2 side^2 byte taps per pixel whatever D is.
+// w + 1 > dmax = min(D - 1, W - 1 - x') is the copied tail (Sad.h:167-171): row[w + 1] == row[w] == cm.  A winner at
+// either end of the range has no parabola; the last row and column are 0 (:157, :160).
+__global__ void __launch_bounds__(256) k_sad_refine_right(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp,
+                                                          const unsigned *__restrict__ rkeys, int H, int W, int D, int w, int G,
+                                                          float min_den, float *__restrict__ dispR)
+{
+    const int side = 2 * w + 1, Wp = W + 2 * w;
+    const int ppb = 256 / G, sub = threadIdx.x & (G - 1);
+    const size_t p = (size_t)blockIdx.x * ppb + threadIdx.x / G;
+    const bool inside = p < (size_t)H * W;
+    const int x = inside ? (int)(p % W) : 0, i = inside ? (int)(p / W) : 0;
+    const bool real = inside && i < H - 1 && x < W - 1;
+    const unsigned key = real ? rkeys[p] : 0u;
+    const int wd = (int)(key & 511u);
+    const int dmax = D - 1 < W - 1 - x ? D - 1 : W - 1 - x;
+    const bool para = real && sad_spx_has_parabola(wd, D);
+    const bool two = para && wd + 1 <= dmax;
+    unsigned s1 = 0, s2 = 0;
+    if (para) {
+        const uint8_t *a = Rp + (size_t)i * Wp + x, *b1 = Lp + (size_t)i * Wp + x + wd - 1;
+        const uint8_t *b2 = two ? b1 + 2 : b1;                             // never read past the row: w + 1 <= dmax
+        if (side >= 4) {
+            const int nfull = side >> 2, rem = side & 3, ndw = nfull + (rem ? 1 : 0);
+            const unsigned tmask = rem ? (0xffffffffu << (8 * (4 - rem))) : 0u;
+            for (int t = sub; t < side * ndw; t += G) {
+                const int r = t / ndw, g = t - r * ndw;
+                const int c0 = (g < nfull) ? 4 * g : side - 4;
+                const unsigned m = (g < nfull) ? 0xffffffffu : tmask;
+                const size_t o = (size_t)r * Wp + c0;
+                unsigned a4, v1, v2;
+                __builtin_memcpy(&a4, a + o, 4);
+                __builtin_memcpy(&v1, b1 + o, 4);
+                __builtin_memcpy(&v2, b2 + o, 4);
+                a4 &= m;
+                s1 = __builtin_amdgcn_sad_u8(a4, v1 & m, s1);
+                s2 = __builtin_amdgcn_sad_u8(a4, v2 & m, s2);
+            }
+        } else {
+            for (int t = sub; t < side * side; t += G) {
+                const int r = t / side, c = t - r * side;
+                const size_t o = (size_t)r * Wp + c;
+                s1 += (unsigned)abs((int)a[o] - (int)b1[o]);
+                s2 += (unsigned)abs((int)a[o] - (int)b2[o]);
+            }
+        }
+    }
+    for (int off = G >> 1; off >= 1; off >>= 1) {                          // every lane of the wave takes part
+        s1 += (unsigned)__shfl_xor((int)s1, off, 64);
+        s2 += (unsigned)__shfl_xor((int)s2, off, 64);
+    }
+    if (inside && sub == 0) {
+        const float cm = (float)(key >> 9);
+        dispR[p] = real ? sad_spx_value(wd, D, (float)s1, cm, two ? (float)s2 : cm, min_den) : 0.0f;
     }
 }
 
@@ -243,6 +312,37 @@ __global__ void __launch_bounds__(256) k_sad_diag(const float *__restrict__ cost
     if (lane == 0) dispR[p] = (int32_t)(key & 511u);
 }
 
+// k_sad_diag with the parabola: the neighbours of the winner are two more elements of the diagonal, read from the volume
+// (the formulation independent of k_sad_refine_right's recomputation).  winR optional.
+__global__ void __launch_bounds__(256) k_sad_diag_sub(const float *__restrict__ costL, int H, int W, int D, float min_den,
+                                                      float *__restrict__ dispR, int32_t *__restrict__ winR)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t p = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= (size_t)H * W) return;
+    const int x = (int)(p % W), i = (int)(p / W);
+    if (i >= H - 1 || x >= W - 1) {
+        sad_store<true>(p, lane, 0, 0.0f, winR, dispR);
+        return;
+    }
+    const int dmax = D - 1 < W - 1 - x ? D - 1 : W - 1 - x;
+    unsigned key = NOKEY;
+    for (int d = lane; d <= dmax; d += 64) {
+        const unsigned k = ((unsigned)costL[(p + d) * D + d] << 9) | (unsigned)d;
+        key = k < key ? k : key;
+    }
+    key = wave_min_u32(key);
+    const int wd = (int)(key & 511u);
+    const float cm = (float)(key >> 9);
+    float f = (float)wd;
+    if (sad_spx_has_parabola(wd, D)) {                                     // wave-uniform
+        const float c1 = costL[(p + wd - 1) * D + wd - 1];
+        const float c2 = wd + 1 <= dmax ? costL[(p + wd + 1) * D + wd + 1] : cm;   // the copied tail (Sad.h:167-171)
+        f = spx_refine(wd, D, c1, cm, c2, min_den);
+    }
+    sad_store<true>(p, lane, wd, f, winR, dispR);
+}
+
 // The left view's sad vector, tap by tap, for windows beyond the box kernel: one thread per (pixel, d)
 __global__ void __launch_bounds__(256) k_sad_volume(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
                                                     int D, int w, float *__restrict__ costL)
@@ -270,7 +370,7 @@ int launch_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int 
     const int side = 2 * w + 1, band = box_band_rule(g_sad_both_band, H, W, side, BSW);
     const size_t shm = ((size_t)4 * (box_lwe(side, BSW) + box_rwe(side, KT, BSW)) + 2 * (64 * KT + BSW)) * 4;   // <= 24 KiB
     const dim3 grid((W + BSW - 1) / BSW, (H + band - 1) / band);
-    hipLaunchKernelGGL(k_sad_box<KT>, grid, dim3(BNT), shm, st, Lp, Rp, H, W, D, w, band, dispL, costL, rkeys);
+    hipLaunchKernelGGL((k_sad_box<KT, false>), grid, dim3(BNT), shm, st, Lp, Rp, H, W, D, w, band, dispL, costL, rkeys, (float *)nullptr, 0.0f);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }
@@ -279,6 +379,48 @@ int run_box(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, 
             unsigned *rkeys)
 {
     return box_dispatch_kt(D, [&](auto kt) { return launch_box<decltype(kt)::value>(st, Lp, Rp, H, W, D, w, dispL, costL, rkeys); });
+}
+
+template <int KT>
+int launch_box_sub(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int32_t *winL, float *costL,
+                   unsigned *rkeys, float *subL, float min_den)
+{
+    const int side = 2 * w + 1, band = box_band_rule(g_sad_both_band, H, W, side, BSW);
+    const size_t shm = ((size_t)4 * (box_lwe(side, BSW) + box_rwe(side, KT, BSW)) + 2 * (64 * KT + BSW)) * 4;   // as launch_box
+    const dim3 grid((W + BSW - 1) / BSW, (H + band - 1) / band);
+    hipLaunchKernelGGL((k_sad_box<KT, true>), grid, dim3(BNT), shm, st, Lp, Rp, H, W, D, w, band, winL, costL, rkeys, subL, min_den);
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+int run_box_sub(hipStream_t st, const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int w, int32_t *winL, float *costL,
+                unsigned *rkeys, float *subL, float min_den)
+{
+    return box_dispatch_kt(D, [&](auto kt) {
+        return launch_box_sub<decltype(kt)::value>(st, Lp, Rp, H, W, D, w, winL, costL, rkeys, subL, min_den);
+    });
+}
+
+// lanes that share a right pixel in k_sad_refine_right: the power of two from 4 to 64 nearest above the window's dword
+// count (9 x 9: 27 dwords, 32 lanes, two pixels per wave; 45 x 45 and beyond: the whole wave)
+int refine_group(int side)
+{
+    const int items = side >= 4 ? side * ((side + 3) >> 2) : side * side;
+    int g = 4;
+    while (g < 64 && g < items) g <<= 1;
+    return g;
+}
+
+// Which box form serves smt_sad_both_subpixel by default (dispatch 0, impl 2): true = the left volume in the scratch arena
+// and k_sad_diag_sub, false = rank keys and k_sad_refine_right.  The refinement kernel's work grows with side^2, the
+// volume's with D.  Measured on one MI355X (tools/sad_subpixel_time.py, profiles/sad_subpixel_time.json, medians; keys +
+// refine over volume + diagonal): 0.88 at 450x375 D=60 9x9, 0.67 at 1920x1080 D=128 9x9, 1.38 at 45x45, 3.11 at 450x375
+// D=60 181x181.  Per pixel that is about 0.23 + 0.00041 side^2 ns for the refinement against 0.15 + 0.0036 D ns for the
+// volume's store and gather; the rule below is where the two lines cross, exact at the four measured points and
+// extrapolated everywhere else (D > 128 is not timed).  Volumes beyond 2 GiB stay with the keys.
+bool sad_sub_use_volume(int side, int D, size_t N)
+{
+    return (long long)side * side > 9LL * D - 200 && N * (size_t)D * 4 <= ((size_t)2 << 30);
 }
 
 // Which path serves (side, D) by default.  Measured on one MI355X (tools/sad_both_time.py, profiles/sad_both_time.json;
@@ -358,6 +500,65 @@ SMT_API int smt_sad_both(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int
     if (!vol && smt_scratch_alloc((void **)&vol, N * D * 4, st) != hipSuccess) return SMT_ERR_ALLOC;
     int rc = run_box(st, Lp, Rp, H, W, D, w, dispL, vol, nullptr);
     if (rc == SMT_OK) hipLaunchKernelGGL(k_sad_diag, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const float *)vol, H, W, D, dispR);
+    if (!costL) smt_scratch_free(vol, st);
+    if (rc != SMT_OK) return rc;
+    SMT_LAUNCH_CHECK();
+    g_sad_both_last = SMT_SAD_FORM_BOX_VOLUME;
+    return SMT_OK;
+}
+
+// smt_sad_both with the parabola kept (include/smt_sad_subpixel.h): the same three forms behind
+// the same hooks.  Box + keys: the left view inside k_sad_box_sub, the right view by k_sad_refine_right behind the
+// finished keys.  Box + volume: k_sad_diag_sub reads the neighbours from the volume.  Composed: smt_sad_subpixel per view.
+SMT_API int smt_sad_both_subpixel(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winsize,
+                                  const smt_subpixel_params *params, float *dispL, float *dispR, int32_t *winL, int32_t *winR,
+                                  float *costL, void *stream)
+{
+    if (!Lp || !Rp || !dispL || !dispR || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0)
+        return SMT_ERR_ARG;
+    const float md = params ? params->min_den : 1.0f;
+    if (!spx_min_den_ok(md)) return SMT_ERR_ARG;
+    hipStream_t st = smt_stream(stream);
+    const size_t N = (size_t)H * W;
+    const int w = winsize + 1;
+    const long long side = 2LL * w + 1;
+    const bool covered = side <= BOX_MAX_SIDE;
+    const bool box = covered && (g_sad_both_dispatch == 1 || (g_sad_both_dispatch == 0 && sad_both_use_box((int)side, D)));
+    if (!box) {
+        int rc = smt_sad_subpixel(Lp, Rp, H, W, D, winsize, SMT_VIEW_LEFT, params, dispL, winL, stream);
+        if (rc == SMT_OK) rc = smt_sad_subpixel(Lp, Rp, H, W, D, winsize, SMT_VIEW_RIGHT, params, dispR, winR, stream);
+        if (rc != SMT_OK) return rc;
+        if (costL) {
+            hipLaunchKernelGGL(k_sad_volume, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, st, Lp, Rp, H, W, D, w, costL);
+            SMT_LAUNCH_CHECK();
+        }
+        g_sad_both_last = SMT_SAD_FORM_COMPOSED;
+        return SMT_OK;
+    }
+    // the hooks are obeyed to the letter when the box form is forced (dispatch 1); by default the measured rule chooses
+    const bool keys = g_sad_both_impl == 2 && (g_sad_both_dispatch == 1 || !sad_sub_use_volume((int)side, D, N));
+    if (keys) {
+        unsigned *rkeys = nullptr;
+        if (smt_scratch_alloc((void **)&rkeys, N * 4, st) != hipSuccess) return SMT_ERR_ALLOC;
+        int rc = hipMemsetAsync(rkeys, 0xFF, N * 4, st) == hipSuccess ? SMT_OK : SMT_ERR_HIP;
+        if (rc == SMT_OK) rc = run_box_sub(st, Lp, Rp, H, W, D, w, winL, costL, rkeys, dispL, md);
+        if (rc == SMT_OK) {
+            if (winR) hipLaunchKernelGGL(k_sad_rkeys_finish, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rkeys, H, W, winR);
+            const int G = refine_group((int)side), ppb = 256 / G;
+            hipLaunchKernelGGL(k_sad_refine_right, dim3((unsigned)((N + ppb - 1) / ppb)), dim3(256), 0, st, Lp, Rp, rkeys, H, W, D, w,
+                               G, md, dispR);
+        }
+        smt_scratch_free(rkeys, st);
+        if (rc != SMT_OK) return rc;
+        SMT_LAUNCH_CHECK();
+        g_sad_both_last = SMT_SAD_FORM_BOX_KEYS;
+        return SMT_OK;
+    }
+    float *vol = costL;
+    if (!vol && smt_scratch_alloc((void **)&vol, N * D * 4, st) != hipSuccess) return SMT_ERR_ALLOC;
+    int rc = run_box_sub(st, Lp, Rp, H, W, D, w, winL, vol, nullptr, dispL, md);
+    if (rc == SMT_OK)
+        hipLaunchKernelGGL(k_sad_diag_sub, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const float *)vol, H, W, D, md, dispR, winR);
     if (!costL) smt_scratch_free(vol, st);
     if (rc != SMT_OK) return rc;
     SMT_LAUNCH_CHECK();
@@ -461,6 +662,7 @@ struct smt_sad_flow {
     uint8_t *padL, *padR;       // [H + 2 w][W + 2 w]
     int32_t *mapL, *mapR, *last;   // maps of the current pair where the caller passes no buffer
     uint8_t *cls;
+    float *subL, *subR;            // float maps of smt_sad_flow_run_batch_subpixel, allocated by its first call
 };
 
 SMT_API void smt_sad_default_params(smt_sad_params *p)
@@ -476,6 +678,7 @@ SMT_API int smt_sad_flow_destroy(smt_sad_flow *h)
     (void)hipDeviceSynchronize();
     (void)hipFree(h->padL); (void)hipFree(h->padR);
     (void)hipFree(h->mapL); (void)hipFree(h->mapR); (void)hipFree(h->last); (void)hipFree(h->cls);
+    (void)hipFree(h->subL); (void)hipFree(h->subR);
     delete h;
     return SMT_OK;
 }
@@ -531,6 +734,58 @@ SMT_API int smt_sad_flow_run_batch(smt_sad_flow *h, const uint8_t *grayL, const 
         if (rc == SMT_OK && (lastdisp || cls))
             rc = smt_sad_crosscheck(dl, dr, H, W, lastdisp ? lastdisp + b * N : h->last, cls ? cls + b * N : h->cls, st);   // :68
         if (rc != SMT_OK) return rc;
+    }
+    return SMT_OK;
+}
+
+// lastdisp of the sub-pixel flow: CrossCheckDiaparity's decision (cls, made on the integer winners) applied to the float
+// map -- dispL where accepted, Invalid_Float (Sad.h:13) where rejected
+namespace {
+__global__ void __launch_bounds__(256) k_sad_last_sub(const uint8_t *__restrict__ cls, const float *__restrict__ subL, int n,
+                                                      float *__restrict__ last)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < n) last[p] = cls[p] ? INFINITY : subL[p];
+}
+}  // namespace
+
+SMT_API int smt_sad_flow_run_batch_subpixel(smt_sad_flow *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                            const smt_subpixel_params *params, float *dispL, float *dispR, float *lastdisp,
+                                            uint8_t *cls)
+{
+    if (!h || pairs < 0) return SMT_ERR_ARG;
+    if (params && !spx_min_den_ok(params->min_den)) return SMT_ERR_ARG;
+    if (pairs == 0) return SMT_OK;
+    if (!grayL || !grayR) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    const int H = h->H, W = h->W, w = h->P.winsize + 1;
+    const size_t N = (size_t)H * W;
+    if (!h->subL) {                                            // the first sub-pixel call of the handle
+        int rc = smt_malloc((void **)&h->subL, N * 4);
+        if (rc == SMT_OK) rc = smt_malloc((void **)&h->subR, N * 4);
+        if (rc != SMT_OK) {
+            (void)hipFree(h->subL); (void)hipFree(h->subR);
+            h->subL = h->subR = nullptr;
+            return rc;
+        }
+    }
+    void *st = (void *)h->stream;
+    const bool check = lastdisp || cls;
+    for (int b = 0; b < pairs; b++) {
+        float *dl = dispL ? dispL + b * N : h->subL, *dr = dispR ? dispR + b * N : h->subR;
+        uint8_t *c = cls ? cls + b * N : h->cls;
+        int rc = smt_pad_replicate(grayL + b * N, H, W, w, h->padL, st);                              // SADmain.cpp:47
+        if (rc == SMT_OK) rc = smt_pad_replicate(grayR + b * N, H, W, w, h->padR, st);                // :48
+        if (rc == SMT_OK)
+            rc = smt_sad_both_subpixel(h->padL, h->padR, H, W, h->D, h->P.winsize, params, dl, dr, check ? h->mapL : nullptr,
+                                       check ? h->mapR : nullptr, nullptr, st);                       // :66-67
+        if (rc == SMT_OK && check) rc = smt_sad_crosscheck(h->mapL, h->mapR, H, W, h->last, c, st);   // :68, on the winners
+        if (rc != SMT_OK) return rc;
+        if (lastdisp) {
+            hipLaunchKernelGGL(k_sad_last_sub, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, (const uint8_t *)c,
+                               (const float *)dl, (int)N, lastdisp + b * N);
+            SMT_LAUNCH_CHECK();
+        }
     }
     return SMT_OK;
 }

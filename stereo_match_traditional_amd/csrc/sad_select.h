@@ -1,6 +1,8 @@
 // The SAD selection rules shared by the tap-loop kernels (csrc/window.hip) and the box-sum kernel (csrc/sad_both.hip).
 #pragma once
 #include "smt_common.h"
+#include "sad_subpixel_rule.h"
+#include "../../include/smt_sad_subpixel.h"
 
 // wave minimum of non-negative floats (SAD sums, 65535, +inf): for v >= +0 the bit patterns order like
 // the values, so this is the DPP integer reduction (no LDS-crossbar shuffles)
@@ -35,4 +37,39 @@ __device__ int sad_optimal(const float (&sad)[KS], int D, int lane)
     if ((double)(sec - minv) <= 0.01) return 0;                           // :66
     if (best == 0.0f || best == (float)(D - 1)) return 0;                 // :71
     return (int)best;                                                     // :84
+}
+
+// The sub-pixel value of the wave-distributed row for the wave-uniform integer r its selection rule returned
+// (sad_subpixel_rule.h; either view: the right view's row holds its copied tail).  The neighbours sit in lane d & 63,
+// slot d >> 6: every slot of that lane is read with v_readlane and an unrolled scalar select on the wave-uniform slot
+// picks one, as wave_wta_subpixel does (sad[d >> 6] would move the row to LDS).  Returned wave-uniform.
+template <int KS>
+__device__ __forceinline__ float sad_wave_subpixel(const float (&sad)[KS], int r, int D, float min_den)
+{
+    r = __builtin_amdgcn_readfirstlane(r);
+    if (!sad_spx_has_parabola(r, D)) return (float)r;
+    auto at = [&](int d) {
+        const int l = d & 63, s = d >> 6;
+        int x = __builtin_amdgcn_readlane(__float_as_int(sad[0]), l);
+#pragma unroll
+        for (int k = 1; k < KS; k++) {
+            const int xk = __builtin_amdgcn_readlane(__float_as_int(sad[k]), l);
+            x = (s == k) ? xk : x;
+        }
+        return __int_as_float(x);
+    };
+    return spx_refine(r, D, at(r - 1), at(r), at(r + 1), min_den);
+}
+
+// one pixel's results: the integer map alone (SUB = false: the code of before), or the float map and, when asked for, the
+// integer winner
+template <bool SUB>
+__device__ __forceinline__ void sad_store(size_t p, int lane, int out, float f, int32_t *__restrict__ disp, float *__restrict__ sub)
+{
+    if (SUB) {
+        if (lane == 0) {
+            sub[p] = f;
+            if (disp) disp[p] = out;
+        }
+    } else if (lane == 0) disp[p] = out;
 }

@@ -27,9 +27,12 @@ constexpr int KMAX = 4;        // D <= 256
 
 // grid: one wave per ORIGINAL pixel (io, jo); Lp/Rp padded by w = winsize+1.  KS hypothesis slots per lane: KMAX in
 // k_sad (D <= 256), 8 in k_sad8 (D <= SMT_MAX_DISPARITY); the slots past ceil(D / 64) are skipped at run time.
-template <int KS>
+// SUB (smt_sad_subpixel): the float map sub from the row the wave holds (sad_wave_subpixel), disp
+// the optional integer winner; SUB = false is the integer kernel, with sub and min_den dead arguments of the inlined body.
+template <int KS, bool SUB>
 __device__ __forceinline__ void sad_pixel(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
-                                          int D, int w, int view, int32_t *__restrict__ disp)
+                                          int D, int w, int view, int32_t *__restrict__ disp, float *__restrict__ sub,
+                                          float min_den)
 {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -38,7 +41,7 @@ __device__ __forceinline__ void sad_pixel(const uint8_t *__restrict__ Lp, const 
     const int io = p / W, jo = p - io * W;
     const int Wp = W + 2 * w, side = 2 * w + 1;
     if (view == 1 && (io >= H - 1 || jo >= W - 1)) {                      // never written (:157,:160)
-        if (lane == 0) disp[p] = 0;
+        sad_store<SUB>(p, lane, 0, 0.0f, disp, sub);
         return;
     }
     const int dmax = (view == 0) ? jo : (W - 1 - jo);                     // last in-range disparity
@@ -100,19 +103,33 @@ __device__ __forceinline__ void sad_pixel(const uint8_t *__restrict__ Lp, const 
         int cand = (lm == m) ? ld : 0x7fffffff;
         out = (int)wave_min_u32((unsigned)cand);
     }
-    if (lane == 0) disp[p] = out;
+    sad_store<SUB>(p, lane, out, SUB ? sad_wave_subpixel<KS>(sad, out, D, min_den) : 0.0f, disp, sub);
 }
 
 __global__ void __launch_bounds__(NT) k_sad(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                             int W, int D, int w, int view, int32_t *__restrict__ disp)
 {
-    sad_pixel<KMAX>(Lp, Rp, H, W, D, w, view, disp);
+    sad_pixel<KMAX, false>(Lp, Rp, H, W, D, w, view, disp, nullptr, 0.0f);
 }
 
 __global__ void __launch_bounds__(NT) k_sad8(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H,
                                              int W, int D, int w, int view, int32_t *__restrict__ disp)
 {
-    sad_pixel<8>(Lp, Rp, H, W, D, w, view, disp);
+    sad_pixel<8, false>(Lp, Rp, H, W, D, w, view, disp, nullptr, 0.0f);
+}
+
+__global__ void __launch_bounds__(NT) k_sad_sub(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
+                                                int D, int w, int view, int32_t *__restrict__ winner,
+                                                float *__restrict__ sub, float min_den)
+{
+    sad_pixel<KMAX, true>(Lp, Rp, H, W, D, w, view, winner, sub, min_den);
+}
+
+__global__ void __launch_bounds__(NT) k_sad8_sub(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
+                                                 int D, int w, int view, int32_t *__restrict__ winner,
+                                                 float *__restrict__ sub, float min_den)
+{
+    sad_pixel<8, true>(Lp, Rp, H, W, D, w, view, winner, sub, min_den);
 }
 
 // Second formulation (default for windows of side >= 4): k_sad above is bound by its own global-load latency (one
@@ -128,9 +145,12 @@ __global__ void __launch_bounds__(NT) k_sad8(const uint8_t *__restrict__ Lp, con
 // Sums, masks and the selection rules are those of k_sad; the two are compared bit for bit in the tests.
 constexpr int STP = 32;                                   // pixels per workgroup (8 per wave)
 
-template <int K>
+// SUB as in sad_pixel; sub and min_den are dead kernel arguments of the integer instantiations.  (As a force-inlined body
+// under two kernels of the old signatures, the K = 5 integer instantiation took 51 VGPRs for 41.)
+template <int K, bool SUB>
 __global__ void __launch_bounds__(NT) k_sad2(const uint8_t *__restrict__ Lp, const uint8_t *__restrict__ Rp, int H, int W,
-                                             int D, int w, int view, int32_t *__restrict__ disp, int ALW, int OLW)
+                                             int D, int w, int view, int32_t *__restrict__ disp, int ALW, int OLW,
+                                             float *__restrict__ sub, float min_den)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned s_sad[];
     const int side = 2 * w + 1, Wp = W + 2 * w;
@@ -183,7 +203,7 @@ __global__ void __launch_bounds__(NT) k_sad2(const uint8_t *__restrict__ Lp, con
         if (jo >= W) break;
         const int pix = io * W + jo;
         if (view == 1 && (io >= H - 1 || jo >= W - 1)) {                  // never written (:157,:160)
-            if (lane == 0) disp[pix] = 0;
+            sad_store<SUB>(pix, lane, 0, 0.0f, disp, sub);
             continue;
         }
         const int dmax = (view == 0) ? jo : (W - 1 - jo);                 // last in-range disparity
@@ -232,7 +252,7 @@ __global__ void __launch_bounds__(NT) k_sad2(const uint8_t *__restrict__ Lp, con
             int cand = (lm == mn) ? ld : 0x7fffffff;
             out = (int)wave_min_u32((unsigned)cand);
         }
-        if (lane == 0) disp[pix] = out;
+        sad_store<SUB>(pix, lane, out, SUB ? sad_wave_subpixel<KS>(sad, out, D, min_den) : 0.0f, disp, sub);
     }
 }
 
@@ -1217,10 +1237,10 @@ SMT_API int smt_sad(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
     if (g_sad_impl == 2 && side >= 4 && K <= KMAX && shm <= 64 * 1024) {
         const dim3 grid((W + STP - 1) / STP, H);
         switch (K) {
-        case 1: hipLaunchKernelGGL(k_sad2<1>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); break;
-        case 2: hipLaunchKernelGGL(k_sad2<2>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); break;
-        case 3: hipLaunchKernelGGL(k_sad2<3>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); break;
-        default: hipLaunchKernelGGL(k_sad2<4>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); break;
+        case 1: hipLaunchKernelGGL((k_sad2<1, false>), grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW, (float *)nullptr, 0.0f); break;
+        case 2: hipLaunchKernelGGL((k_sad2<2, false>), grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW, (float *)nullptr, 0.0f); break;
+        case 3: hipLaunchKernelGGL((k_sad2<3, false>), grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW, (float *)nullptr, 0.0f); break;
+        default: hipLaunchKernelGGL((k_sad2<4, false>), grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW, (float *)nullptr, 0.0f); break;
         }
         SMT_LAUNCH_CHECK();
         return SMT_OK;
@@ -1231,8 +1251,8 @@ SMT_API int smt_sad(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
         const dim3 grid((W + STP - 1) / STP, H);
 #define SMT_SAD2W(KK)                                                                                        \
     do {                                                                                                     \
-        SMT_HIP(hipFuncSetAttribute((const void *)k_sad2<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
-        hipLaunchKernelGGL(k_sad2<KK>, grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW); \
+        SMT_HIP(hipFuncSetAttribute((const void *)k_sad2<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+        hipLaunchKernelGGL((k_sad2<KK, false>), grid, dim3(NT), shm, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp, ALW, OLW, (float *)nullptr, 0.0f); \
     } while (0)
         switch (K) {
         case 5: SMT_SAD2W(5); break;
@@ -1246,6 +1266,43 @@ SMT_API int smt_sad(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, i
     }
     if (K > KMAX) hipLaunchKernelGGL(k_sad8, dim3((N + 3) / 4), dim3(NT), 0, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp);
     else hipLaunchKernelGGL(k_sad, dim3((N + 3) / 4), dim3(NT), 0, smt_stream(stream), Lp, Rp, H, W, D, w, v, disp);
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+// smt_sad with the parabola of Sad.h:76-81 kept (include/smt_sad_subpixel.h): smt_sad's dispatch
+// over the SUB instantiations of the same kernel bodies, so both formulations behind smt_sad_set_impl serve it
+SMT_API int smt_sad_subpixel(const uint8_t *Lp, const uint8_t *Rp, int H, int W, int D, int winsize, int view,
+                             const smt_subpixel_params *params, float *disp, int32_t *winner, void *stream)
+{
+    if (!Lp || !Rp || !disp || H <= 0 || W <= 0 || D <= 0 || D > SMT_MAX_DISPARITY || winsize < 0 ||
+        (view != SMT_VIEW_LEFT && view != SMT_VIEW_RIGHT))
+        return SMT_ERR_ARG;
+    const float md = params ? params->min_den : 1.0f;
+    if (!spx_min_den_ok(md)) return SMT_ERR_ARG;
+    const int N = H * W;
+    const int w = winsize + 1, side = 2 * w + 1, K = (D + 63) / 64, v = view == SMT_VIEW_LEFT ? 0 : 1;
+    auto copy_words = [](int bytes) { int n = (bytes + 3) / 4 + 1; return n + ((8 - n % 32) % 32 + 32) % 32; };   // as smt_sad
+    const int ALW = copy_words(STP + side - 1), OLW = copy_words(STP + side - 1 + 64 * K - 1);
+    const size_t shm = (size_t)side * 4 * (ALW + OLW) * 4;
+    hipStream_t st = smt_stream(stream);
+    if (g_sad_impl == 2 && side >= 4 && shm <= (K <= KMAX ? 64 : 160) * 1024) {
+        const dim3 grid((W + STP - 1) / STP, H);
+#define SMT_SAD2S(KK)                                                                                        \
+    case KK:                                                                                                 \
+        if (KK > KMAX) SMT_HIP(hipFuncSetAttribute((const void *)k_sad2<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+        hipLaunchKernelGGL((k_sad2<KK, true>), grid, dim3(NT), shm, st, Lp, Rp, H, W, D, w, v, winner, ALW, OLW, disp, md); \
+        break
+        switch (K) {
+            SMT_SAD2S(1); SMT_SAD2S(2); SMT_SAD2S(3); SMT_SAD2S(4); SMT_SAD2S(5); SMT_SAD2S(6); SMT_SAD2S(7);
+        default: SMT_SAD2S(8);
+        }
+#undef SMT_SAD2S
+        SMT_LAUNCH_CHECK();
+        return SMT_OK;
+    }
+    if (K > KMAX) hipLaunchKernelGGL(k_sad8_sub, dim3((N + 3) / 4), dim3(NT), 0, st, Lp, Rp, H, W, D, w, v, winner, disp, md);
+    else hipLaunchKernelGGL(k_sad_sub, dim3((N + 3) / 4), dim3(NT), 0, st, Lp, Rp, H, W, D, w, v, winner, disp, md);
     SMT_LAUNCH_CHECK();
     return SMT_OK;
 }

@@ -8,10 +8,14 @@
 // buffers in and out, everything computed by libsmt_hip.so through smt_host.hpp.  Prints FNV-1a hashes for the tests.
 //   usage: sad_main H W D seed [winsize]          synthetic pair, MaxDisparity D
 //          sad_main left.png right.png [D] [winsize]
+//   --subpixel anywhere on the line, or --subpixel min_den as its last two words: the maps keep the parabola OptimalDisparity computes and drops
+//   (Sad.h:76-81) through smt::SadSubpixelFlow; float maps under the same three names, lastdisp +inf where rejected, and
+//   the class map.  Without the flag the output is the integer flow's.
 #include <cctype>
 #include <cstdio>
 #include <cstdlib>
-#include "smt_host.hpp"
+#include <cstring>
+#include "smt_sad_subpixel.hpp"
 
 static uint64_t fnv(const void *p, size_t n)
 {
@@ -45,6 +49,20 @@ int main(int argc, char **argv)
 {
     try {
         using namespace smt;
+        bool subpixel = false;
+        float min_den = 1.0f;                                                   // Sad.h:80
+        for (int a = 1; a < argc; a++)
+            if (!strcmp(argv[a], "--subpixel")) {
+                subpixel = true;
+                int take = 1;
+                if (a + 1 < argc && (isdigit((unsigned char)argv[a + 1][0]) || argv[a + 1][0] == '.') && a + 2 == argc) {
+                    min_den = (float)atof(argv[a + 1]);                         // a value only as the line's last word
+                    take = 2;
+                }
+                for (int b = a; b + take <= argc; b++) argv[b] = argv[b + take];   // argv[argc] is the null pointer
+                argc -= take;
+                break;
+            }
         Image leftimg, rightimg;
         int MaxDisparity = 60;                                                  // SADmain.cpp:33
         int winsize = 3;                                                        // :34
@@ -64,6 +82,16 @@ int main(int argc, char **argv)
         }
         const int row = leftimg.rows, col = leftimg.cols;                      // :43-44
         const size_t n = (size_t)row * col;
+        if (subpixel) {
+            std::vector<float> depthleft(n), depthright(n), lastdisp(n);
+            std::vector<unsigned char> cls(n);
+            SadSubpixelFlow flow(row, col, MaxDisparity, winsize, min_den);
+            flow.run(leftimg.data.data(), rightimg.data.data(), 1, depthleft.data(), depthright.data(), lastdisp.data(), cls.data());
+            printf("depthleft %016llx\ndepthright %016llx\nlastdisp %016llx\ncls %016llx\n", (unsigned long long)fnv(depthleft.data(), n * 4),
+                   (unsigned long long)fnv(depthright.data(), n * 4), (unsigned long long)fnv(lastdisp.data(), n * 4),
+                   (unsigned long long)fnv(cls.data(), n));
+            return 0;
+        }
         std::vector<int> depthleft(n), depthright(n), lastdisp(n);              // :57-59
         SadFlow flow(row, col, MaxDisparity, winsize);
         flow.run(leftimg.data.data(), rightimg.data.data(), 1, depthleft.data(), depthright.data(), lastdisp.data());   // :47-48, :66-68

@@ -227,6 +227,20 @@ def sad_batch(L8, R8, D, **params):
     return dl, dr
 
 
+def sad_subpixel_batch(L8, R8, D, min_den=1.0, **params):
+    """sad_batch with the parabola of Sad.h:76-81 kept (smt_sad_flow_run_batch_subpixel) -> (left maps, right maps),
+    float32.  Keywords as api.SADFlow."""
+    from .api import SADFlow
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    flow = SADFlow(H, W, D, L8.device, **params)
+    dl, dr, _, _ = flow.run_subpixel(L8.contiguous(), R8.contiguous(), min_den)
+    flow.close()
+    return dl, dr
+
+
 def ncc_batch(L8, R8, D, **params):
     """`compute` for run_sharded on NCC_main.cpp's flow (smt_ncc_flow_run_batch) for a [count, H, W] uint8 shard on this
     rank's GPU -> (left maps, left maps again: NCC has no right view and run_sharded gathers two map sets), int32.
