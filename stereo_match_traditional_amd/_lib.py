@@ -223,6 +223,17 @@ def _declare_sad_subpixel(l):
     l.smt_sad_flow_run_batch_subpixel.argtypes = [vp, vp, vp, i, pp, vp, vp, vp, vp]
 
 
+def _declare_scan_views(l):
+    """The signatures of include/smt_scan_views.h; an older build loaded through SMT_HIP_LIB is left as it is."""
+    if not hasattr(l, "smt_scanline_run_pair"):
+        return
+    vp = C.c_void_p
+    l.smt_scanline_run_pair.argtypes = [vp] * 9
+    l.smt_scanline_run_map.argtypes = [vp] * 4
+    l.smt_pipeline_set_scan_views.argtypes = [vp, C.c_int]
+    l.smt_pipeline_scan_right_volume.argtypes = [vp, C.POINTER(vp)]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -238,6 +249,7 @@ def lib():
         _declare_ncc_whole(_lib)
         _declare_subpixel(_lib)
         _declare_sad_subpixel(_lib)
+        _declare_scan_views(_lib)
     return _lib
 
 

@@ -629,6 +629,48 @@ class ScanlineOptimizer:
         self._processed = out
         return out
 
+    def ScanLinePair(self, costL, ImageL, costR, ImageR, out=None, disp=None, maps_only=False):
+        """ScanLine on two volumes of the handle's shape in the same launches (smt_scanline_run_pair): per view exactly
+        what ScanLine gives.  out = (outL, outR) and disp = (dispL, dispR), entries may be None.  maps_only: True, or a
+        pair of flags per view -- that view stores no volume (its `out` entry must be None) and needs its disp map.
+        Without maps_only a missing `out` entry is allocated.  Returns (outL, outR, dispL, dispR), None for what a view
+        does not produce."""
+        shp = (self.row, self.col, self.dispRange)
+        mo = (bool(maps_only),) * 2 if isinstance(maps_only, (bool, int)) else tuple(bool(m) for m in maps_only)
+        out = list(out) if out is not None else [None, None]
+        disp = list(disp) if disp is not None else [None, None]
+        for v, (cost, img) in enumerate(((costL, ImageL), (costR, ImageR))):
+            _dev(cost, torch.float32, shp, "cost" + "LR"[v])
+            _dev(img, torch.float32, (self.row, self.col), "Image" + "LR"[v])
+            if mo[v]:
+                if out[v] is not None:
+                    raise ValueError("a maps-only view takes no `out` volume")
+                if disp[v] is None:
+                    disp[v] = torch.empty((self.row, self.col), dtype=torch.float32, device=cost.device)
+            elif out[v] is None:
+                out[v] = torch.empty(shp, dtype=torch.float32, device=cost.device)
+            if out[v] is not None:
+                _dev(out[v], torch.float32, shp, "out" + "LR"[v])
+            if disp[v] is not None:
+                _dev(disp[v], torch.float32, (self.row, self.col), "disp" + "LR"[v])
+        check(lib().smt_scanline_set_stream(self._h, current_stream_ptr(self.device)), "smt_scanline_set_stream")
+        check(lib().smt_scanline_run_pair(self._h, _ptr(costL), _ptr(ImageL), _ptr(out[0]), _ptr(disp[0]),
+                                          _ptr(costR), _ptr(ImageR), _ptr(out[1]), _ptr(disp[1])), "smt_scanline_run_pair")
+        if out[0] is not None:
+            self._processed = out[0]
+        return out[0], out[1], disp[0], disp[1]
+
+    def ScanLineMap(self, costVolume, Image, disp=None):
+        """ScanLine + WTA with no volume returned (smt_scanline_run_map): the last pass stores the map only."""
+        _dev(costVolume, torch.float32, (self.row, self.col, self.dispRange), "costVolume")
+        _dev(Image, torch.float32, (self.row, self.col), "Image")
+        if disp is None:
+            disp = torch.empty((self.row, self.col), dtype=torch.float32, device=costVolume.device)
+        _dev(disp, torch.float32, (self.row, self.col), "disp")
+        check(lib().smt_scanline_set_stream(self._h, current_stream_ptr(self.device)), "smt_scanline_set_stream")
+        check(lib().smt_scanline_run_map(self._h, _ptr(costVolume), _ptr(Image), _ptr(disp)), "smt_scanline_run_map")
+        return disp
+
     def ScanPass(self, costVolume, Image, which):
         """One path volume: 'left' (ScanLineLeftRight isLeft=true, :130-192), 'right', 'up'
         (ScanLineUpDown isUp=true, :194-253), 'down'."""
@@ -1471,10 +1513,10 @@ def scratch_info(device=None):
 class Pipeline:
     """main.cpp:46-92 (scanline and LR check enabled) for batches of gray pairs; the sharding unit of config 3."""
 
-    def __init__(self, row, col, dispRange, device=None, quirks=0, subpixel=None, **params):
+    def __init__(self, row, col, dispRange, device=None, quirks=0, subpixel=None, scan_views=VIEW_LEFT, **params):
         """params: the fields of smt_pipeline_params.  quirks: QUIRK_FIX_* for every stage, 0 = the reference's
         results; QUIRK_FIX_RIGHT_ARM_STRIDE also admits row > col.  subpixel: min_den of set_subpixel, None = integer
-        maps."""
+        maps.  scan_views: VIEW_LEFT = main.cpp's flow, VIEW_BOTH = set_scan_views."""
         self.row, self.col, self.dispRange = int(row), int(col), int(dispRange)
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         p = _lib.PipelineParams()
@@ -1491,10 +1533,24 @@ class Pipeline:
             self.set_quirks(quirks)
         if subpixel is not None:
             self.set_subpixel(subpixel)
+        if scan_views != VIEW_LEFT:
+            self.set_scan_views(scan_views)
 
     def set_quirks(self, quirks):
         """QUIRK_FIX_* from the next run on (between runs)."""
         check(lib().smt_pipeline_set_quirks(self._h, C.c_uint(quirks)), "smt_pipeline_set_quirks")
+
+    def set_scan_views(self, views):
+        """From the next run on (between runs): VIEW_BOTH scanline-optimises the aggregated right volume too (guided by
+        the float right image), so dispR is the WTA of that sum and the LR check compares two optimised maps; VIEW_LEFT
+        = main.cpp's flow, the default."""
+        check(lib().smt_pipeline_set_scan_views(self._h, int(views)), "smt_pipeline_set_scan_views")
+
+    def scan_right_volume(self):
+        """The right view's scanline sum of the last pair of the last VIEW_BOTH run (borrowed, [row][col][dispRange])."""
+        p = C.c_void_p()
+        check(lib().smt_pipeline_scan_right_volume(self._h, C.byref(p)), "smt_pipeline_scan_right_volume")
+        return _view_of(p.value, (self.row, self.col, self.dispRange), torch.float32, self.device)
 
     def set_subpixel(self, min_den=None):
         """From the next run on (between runs), dispL and dispR carry the parabola's fraction (wta_subpixel's rule with

@@ -31,6 +31,8 @@
 // forest and counts, an error word) is the handle's, allocated by the first _post call; tails follow each other on M,
 // so one set serves every pair.
 #include "smt_common.h"
+#include "../../include/smt_scan_views.h"
+#include <initializer_list>
 #include <limits.h>
 #include <new>
 #include <stdlib.h>
@@ -51,6 +53,14 @@ struct smt_pipeline {
     float *agg[2], *sovol;   // aggregated left / right, scanline sum
     void *tail;              // speckle scratch of one pair (smt_speckle_scratch_bytes), first _post call
     int *tail_err;           // nonzero when a speckle kernel hit a loop cap; read and cleared by smt_pipeline_status
+    // smt_pipeline_set_scan_views(SMT_VIEW_BOTH), all allocated by the first BOTH run (see "Both views" below)
+    int scan_views;          // SMT_VIEW_LEFT (the default) or SMT_VIEW_BOTH
+    unsigned quirks;         // what smt_pipeline_set_quirks / _set_subpixel were given, for soR
+    float sub_min_den;
+    smt_scanline *soR;       // schedules 1, 2: the right view's scanline handle, on S
+    float *sovolR;           // the right view's scanline sum (the last pair's)
+    bool sovolR_valid;
+    hipEvent_t ev_aggR, ev_scanR[2];
 };
 
 // main.cpp:93-94 on one pair, or nothing (post == NULL: smt_pipeline_run_batch)
@@ -90,6 +100,10 @@ SMT_API int smt_pipeline_destroy(smt_pipeline *h)
     if (h->caL) smt_crossarm_destroy(h->caL);
     if (h->caR) smt_crossarm_destroy(h->caR);
     if (h->so) smt_scanline_destroy(h->so);
+    if (h->soR) smt_scanline_destroy(h->soR);
+    (void)hipFree(h->sovolR);
+    for (hipEvent_t e : {h->ev_aggR, h->ev_scanR[0], h->ev_scanR[1]})
+        if (e) (void)hipEventDestroy(e);
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
     if (h->ev_left) (void)hipEventDestroy(h->ev_left);
     if (h->side) (void)hipStreamDestroy(h->side);
@@ -106,6 +120,7 @@ static int pipeline_apply_streams(smt_pipeline *h)
     int rc = smt_crossarm_set_stream(h->caL, m);
     if (rc == SMT_OK) rc = smt_scanline_set_stream(h->so, m);
     if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_stream(h->caR, (void *)h->side);
+    if (rc == SMT_OK && h->soR) rc = smt_scanline_set_stream(h->soR, (void *)h->side);
     for (int k = 0; k < 2 && rc == SMT_OK; k++)
         if (h->adc[k]) rc = smt_adcensus_set_stream(h->adc[k], h->sched == 2 ? (void *)h->front : m);
     return rc;
@@ -118,6 +133,7 @@ SMT_API int smt_pipeline_create(int H, int W, int D, const smt_pipeline_params *
     if (!h) return SMT_ERR_ALLOC;
     h->device = smt_current_device();
     h->H = H; h->W = W; h->D = D;
+    h->scan_views = SMT_VIEW_LEFT;
     if (p) h->P = *p; else smt_pipeline_default_params(&h->P);
     {
         const char *e = getenv("SMT_PIPE_SCHEDULE");
@@ -176,8 +192,10 @@ SMT_API int smt_pipeline_set_quirks(smt_pipeline *h, unsigned quirks)
     int rc = smt_crossarm_set_quirks_internal(h->caL, quirks);
     if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_quirks_internal(h->caR, quirks);
     if (rc == SMT_OK) rc = smt_scanline_set_quirks(h->so, quirks);
+    if (rc == SMT_OK && h->soR) rc = smt_scanline_set_quirks(h->soR, quirks);
     for (int k = 0; k < 2 && rc == SMT_OK; k++)
         if (h->adc[k]) rc = smt_adcensus_set_quirks(h->adc[k], quirks);
+    if (rc == SMT_OK) h->quirks = quirks;
     return rc;
 }
 
@@ -190,6 +208,8 @@ SMT_API int smt_pipeline_set_subpixel(smt_pipeline *h, const smt_subpixel_params
     int rc = smt_scanline_set_subpixel(h->so, p);
     if (rc == SMT_OK) rc = smt_crossarm_set_subpixel(h->caL, p);
     if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_subpixel(h->caR, p);
+    if (rc == SMT_OK && h->soR) rc = smt_scanline_set_subpixel(h->soR, p);
+    if (rc == SMT_OK) h->sub_min_den = p ? p->min_den : 0.0f;
     return rc;
 }
 
@@ -263,9 +283,211 @@ static int pipeline_run_simple(smt_pipeline *h, const uint8_t *grayL, const uint
     return SMT_OK;
 }
 
+// ---- Both views (smt_pipeline_set_scan_views(SMT_VIEW_BOTH), include/smt_scan_views.h) -------------------------------
+// dispR is the WTA of ScanLine(aggregated right volume, float right image); the right view's aggregation writes no map.
+// The functions above are the LEFT flow and stay as they are; these are their BOTH twins.  A scanline pass is HBM and
+// latency bound and belongs beside an aggregation (vector-issue bound, see the header of this file), so under schedules
+// 1 and 2 the right view's scan goes on S behind the right view's aggregation, on a scanline handle of its own (soR),
+// and runs beside the next pair's front end and left aggregation on M; M's LR check of pair b - 1 moves behind the
+// scanline of pair b, which gives S that whole scan on top of the aggregation to finish.  Pairs before the last run
+// the maps-only last pass (smt_scanline_run_map); the last pair stores its sum in sovolR (smt_pipeline_scan_right_volume).
+// Edges on top of the LEFT flow's:
+//   S: scan(right, b) --ev_scanR / ev_right[s]--> M: LR check of pair b     (not only aggregate(right, b))
+//   schedule 1: S: aggregate(right, b) --ev_aggR--> M: AD-Census of pair b + 1; the one AD-Census set does not wait for
+//               the scan.  The float right image does: it guides scan(right, b), so pairs alternate between Rf[0] and
+//               Rf[1], and Rf[s] is rewritten by pair b + 2 on M behind the LR check of pair b.  S issues the arms of
+//               pair b + 1 (which M's left aggregation waits for) BEFORE scan(right, b), else the scan would sit in
+//               front of them and the aggregation beside it could not start.
+//   schedule 2: ev_right[s] is recorded behind scan(right, b), so F's wait for set s covers Rf[s] too
+//   agg[1]: aggregate(right, b) follows scan(right, b - 1) on S in every schedule
+//   M: scan(left, b) --ev_scan[s]--> S: scan(right, b)     two scans side by side share HBM and gain nothing; measured,
+//               DESIGN.md section 5.18, where the whole flow's figures are: under schedules 1 and 2 it is still dearer per
+//               pair than a scan appended to the caller's stream
+// Schedule 0: one smt_scanline_run_pair per pair on the caller's stream, both views in the same three launches.
+static int pipeline_both_prepare(smt_pipeline *h)
+{
+    int rc = SMT_OK;
+    if (!h->sovolR) rc = smt_malloc((void **)&h->sovolR, (size_t)h->H * h->W * h->D * 4);
+    for (hipEvent_t *e : {&h->ev_aggR, &h->ev_scanR[0], &h->ev_scanR[1]})
+        if (rc == SMT_OK && !*e && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) rc = SMT_ERR_HIP;
+    if (rc == SMT_OK && h->sched >= 1 && !h->soR) {
+        rc = smt_scanline_create(h->H, h->W, h->D, h->P.p1, h->P.p2, &h->soR);
+        if (rc == SMT_OK) rc = smt_scanline_set_stream(h->soR, (void *)h->side);
+        if (rc == SMT_OK) rc = smt_scanline_set_quirks(h->soR, h->quirks);
+        smt_subpixel_params sp{h->sub_min_den};
+        if (rc == SMT_OK) rc = smt_scanline_set_subpixel(h->soR, h->sub_min_den > 0.0f ? &sp : nullptr);
+    }
+    if (rc == SMT_OK && h->sched == 1 && !h->Rf[1]) rc = smt_malloc((void **)&h->Rf[1], (size_t)h->H * h->W * 4);
+    return rc;
+}
+
+// S: the right view's scan of the pair whose float right image is Rf[s], into dr
+static int pipeline_scan_right(smt_pipeline *h, int s, bool store, float *dr, hipEvent_t done)
+{
+    // not before M has finished the left view's scan of the same pair: two scans side by side share HBM and gain
+    // nothing, so this one starts when M turns to the next pair's front end and left aggregation
+    if (hipStreamWaitEvent(h->side, h->ev_scan[s], 0) != hipSuccess) return SMT_ERR_HIP;
+    int rc = store ? smt_scanline_run(h->soR, h->agg[1], h->Rf[s], h->sovolR, dr)
+                   : smt_scanline_run_map(h->soR, h->agg[1], h->Rf[s], dr);
+    PIPE_HIP(hipEventRecord(done, h->side));
+    return rc;
+}
+
+static int pipeline_run_simple_both(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
+                                    float *dispR, uint8_t *cls, int *counts, const pipe_tail &tail)
+{
+    const int H = h->H, W = h->W;
+    const size_t N = (size_t)H * W;
+    void *st = (void *)h->stream;
+    const bool two = h->sched == 1;
+    int rc = SMT_OK;
+    if (two) {
+        PIPE_HIP(hipEventRecord(h->ev_in, h->stream));
+        PIPE_HIP(hipStreamWaitEvent(h->side, h->ev_in, 0));
+    }
+    for (int b = 0; b < pairs && rc == SMT_OK; b++) {
+        const int s = two ? (b & 1) : 0;
+        const uint8_t *L8 = grayL + b * N, *R8 = grayR + b * N;
+        float *dl = dispL + b * N, *dr = dispR + b * N;
+        if (two) {
+            rc = smt_crossarm_set_stream(h->caL, (void *)h->side);
+            if (rc == SMT_OK) rc = smt_crossarm_arms(h->caL, L8, 1);                   // :67-72
+            PIPE_HIP(hipEventRecord(h->ev_front[0], h->side));
+            const int rc2 = smt_crossarm_set_stream(h->caL, st);
+            if (rc == SMT_OK) rc = rc2;
+            if (rc == SMT_OK) rc = smt_crossarm_arms(h->caR, R8, 1);                   // :77-81
+            if (rc == SMT_OK && b >= 1)                                                 // beside this pair's AD-Census and left aggregation
+                rc = pipeline_scan_right(h, s ^ 1, false, dr - N, h->ev_scanR[s ^ 1]);
+        }
+        if (rc == SMT_OK) rc = smt_u8_to_f32(L8, H, W, h->Lf[0], st);                   // main.cpp:46-55
+        if (rc == SMT_OK) rc = smt_u8_to_f32(R8, H, W, h->Rf[s], st);
+        if (two && b >= 1) PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_aggR, 0));    // aggregate(right, b - 1) read the volumes
+        if (rc == SMT_OK) rc = smt_adcensus_compute(h->adc[0], h->Lf[0], h->Rf[s], SMT_VIEW_BOTH, nullptr, nullptr);   // :57-61
+        float *vol[2] = {nullptr, nullptr};
+        if (rc == SMT_OK) rc = smt_adcensus_volume(h->adc[0], SMT_VIEW_LEFT, &vol[0]);
+        if (rc == SMT_OK) rc = smt_adcensus_volume(h->adc[0], SMT_VIEW_RIGHT, &vol[1]);
+        if (two) PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_front[0], 0));
+        else if (rc == SMT_OK) rc = smt_crossarm_arms(h->caL, L8, 1);                  // :67-72
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, vol[0], h->agg[0], 0, nullptr);  // :73
+        if (two) {
+            PIPE_HIP(hipEventRecord(h->ev_left, h->stream));
+            PIPE_HIP(hipStreamWaitEvent(h->side, h->ev_left, 0));
+            if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caR, vol[1], h->agg[1], 0, nullptr);   // :82-83, beside the scanline
+            PIPE_HIP(hipEventRecord(h->ev_aggR, h->side));
+            if (rc == SMT_OK) rc = smt_scanline_run(h->so, h->agg[0], h->Lf[0], h->sovol, dl);     // :86-89
+            PIPE_HIP(hipEventRecord(h->ev_scan[s], h->stream));
+            if (b >= 1) {                                                                           // :92 of pair b - 1
+                PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_scanR[s ^ 1], 0));
+                if (rc == SMT_OK)
+                    rc = smt_lrcheck(dl - N, dr - N, H, W, h->P.gate, cls + (b - 1) * N, counts ? counts + 2 * (b - 1) : nullptr, st);
+                if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, b - 1);
+            }
+        } else {
+            if (rc == SMT_OK) rc = smt_crossarm_arms(h->caL, R8, 1);                   // :77-81
+            if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, vol[1], h->agg[1], 0, nullptr);   // :82-83
+            if (rc == SMT_OK)                                                           // :86-89 on both views
+                rc = smt_scanline_run_pair(h->so, h->agg[0], h->Lf[0], h->sovol, dl, h->agg[1], h->Rf[0],
+                                           b == pairs - 1 ? h->sovolR : nullptr, dr);
+            if (rc == SMT_OK) rc = smt_lrcheck(dl, dr, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);   // :92
+            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl, b);                       // :93-94
+        }
+    }
+    if (two && rc == SMT_OK) {
+        const int b = pairs - 1, s = b & 1;
+        rc = pipeline_scan_right(h, s, true, dispR + b * N, h->ev_scanR[s]);
+        PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_scanR[s], 0));
+        if (rc == SMT_OK)
+            rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, b);
+    }
+    if (rc != SMT_OK) { (void)hipStreamSynchronize(h->side); return rc; }
+    h->last_set = 0;
+    return SMT_OK;
+}
+
+static int pipeline_run_both(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
+                             float *dispR, uint8_t *cls, int *counts, const pipe_tail &tail)
+{
+    int rc = pipeline_both_prepare(h);
+    if (rc != SMT_OK) return rc;
+    h->sovolR_valid = false;
+    if (h->sched != 2) {
+        rc = pipeline_run_simple_both(h, grayL, grayR, pairs, dispL, dispR, cls, counts, tail);
+        h->sovolR_valid = rc == SMT_OK;
+        return rc;
+    }
+    const int H = h->H, W = h->W;
+    const size_t N = (size_t)H * W;
+    hipStream_t M = h->stream, S = h->side, F = h->front;
+    PIPE_HIP(hipEventRecord(h->ev_in, M));
+    PIPE_HIP(hipStreamWaitEvent(F, h->ev_in, 0));
+    for (int b = 0; b < pairs && rc == SMT_OK; b++) {
+        const int s = b & 1;
+        const uint8_t *L8 = grayL + b * N, *R8 = grayR + b * N;
+        float *dl = dispL + b * N, *dr = dispR + b * N;
+        // F: front end of pair b into set s
+        if (b >= 2) {
+            PIPE_HIP(hipStreamWaitEvent(F, h->ev_scan[s], 0));     // scanline(left, b-2) read Lf[s]; aggregate(left, b-2) read the volumes
+            PIPE_HIP(hipStreamWaitEvent(F, h->ev_right[s], 0));    // scan(right, b-2) read Rf[s]; aggregate(right, b-2) read the volumes
+        }
+        if (rc == SMT_OK) rc = smt_u8_to_f32(L8, H, W, h->Lf[s], (void *)F);                   // main.cpp:46-55
+        if (rc == SMT_OK) rc = smt_u8_to_f32(R8, H, W, h->Rf[s], (void *)F);
+        if (rc == SMT_OK) rc = smt_adcensus_compute(h->adc[s], h->Lf[s], h->Rf[s], SMT_VIEW_BOTH, nullptr, nullptr);   // :57-61
+        PIPE_HIP(hipEventRecord(h->ev_front[s], F));
+        float *vol[2] = {nullptr, nullptr};
+        if (rc == SMT_OK) rc = smt_adcensus_volume(h->adc[s], SMT_VIEW_LEFT, &vol[0]);
+        if (rc == SMT_OK) rc = smt_adcensus_volume(h->adc[s], SMT_VIEW_RIGHT, &vol[1]);
+        // M: left view
+        PIPE_HIP(hipStreamWaitEvent(M, h->ev_front[s], 0));
+        if (rc == SMT_OK) rc = smt_crossarm_arms(h->caL, L8, 1);                               // :67-72
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caL, vol[0], h->agg[0], 0, nullptr);  // :73
+        PIPE_HIP(hipEventRecord(h->ev_left, M));
+        if (rc == SMT_OK) rc = smt_scanline_run(h->so, h->agg[0], h->Lf[s], h->sovol, dl);     // :86-89
+        PIPE_HIP(hipEventRecord(h->ev_scan[s], M));
+        if (b >= 1) {                                                                           // :92 of pair b - 1
+            PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s ^ 1], 0));
+            if (rc == SMT_OK)
+                rc = smt_lrcheck(dl - N, dr - N, H, W, h->P.gate, cls + (b - 1) * N, counts ? counts + 2 * (b - 1) : nullptr, (void *)M);
+            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, b - 1);                     // :93-94 of pair b - 1
+        }
+        // S: right view: aggregation beside the left view's scanline, scan beside the next pair's left aggregation
+        PIPE_HIP(hipStreamWaitEvent(S, h->ev_left, 0));
+        if (rc == SMT_OK) rc = smt_crossarm_arms(h->caR, R8, 1);                               // :77-81
+        if (rc == SMT_OK) rc = smt_crossarm_aggregate(h->caR, vol[1], h->agg[1], 0, nullptr);  // :82-83
+        if (rc == SMT_OK) rc = pipeline_scan_right(h, s, b == pairs - 1, dr, h->ev_right[s]);
+    }
+    if (rc == SMT_OK) {
+        const int b = pairs - 1, s = b & 1;
+        PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s], 0));
+        if (rc == SMT_OK)
+            rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, (void *)M);
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, b);
+        h->last_set = s;
+    }
+    if (rc != SMT_OK) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(F); }
+    h->sovolR_valid = rc == SMT_OK;
+    return rc;
+}
+
+SMT_API int smt_pipeline_set_scan_views(smt_pipeline *h, int views)
+{
+    if (!h || (views != SMT_VIEW_LEFT && views != SMT_VIEW_BOTH)) return SMT_ERR_ARG;
+    h->scan_views = views;
+    return SMT_OK;
+}
+
+SMT_API int smt_pipeline_scan_right_volume(smt_pipeline *h, float **sum)
+{
+    if (!h || !sum) return SMT_ERR_ARG;
+    if (!h->sovolR_valid) return SMT_ERR_STATE;
+    *sum = h->sovolR;
+    return SMT_OK;
+}
+
 static int pipeline_run(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs, float *dispL,
                         float *dispR, uint8_t *cls, int *counts, const pipe_tail &tail)
 {
+    if (h->scan_views == SMT_VIEW_BOTH) return pipeline_run_both(h, grayL, grayR, pairs, dispL, dispR, cls, counts, tail);
     if (h->sched != 2) return pipeline_run_simple(h, grayL, grayR, pairs, dispL, dispR, cls, counts, tail);
     const int H = h->H, W = h->W;
     const size_t N = (size_t)H * W;

@@ -21,6 +21,7 @@
 // ScanlineOptimizer::WTA (:40-64).  Same association order, 44 bytes of HBM traffic per
 // hypothesis in total (8 + 8 + 16 + 12).
 #include "smt_common.h"
+#include "../../include/smt_scan_views.h"
 #include <new>
 
 namespace {
@@ -124,17 +125,20 @@ __device__ __forceinline__ void st_row(float *p, int dl, int D, const float (&sr
 // PASS: 0 left->right, 1 right->left, 2 top->bottom, 3 bottom->top
 // MODE: 0 out = path ; 1 out = out + path ; 2 out = out + path and fused WTA of the sum ;
 //       3 out = (out + add2) + path ; 4 = 2 with the winner refined by the sub-pixel rule (smt_scanline_set_subpixel;
-//       the last pass only)
+//       the last pass only) ; 5 = 2 and 6 = 4 without the store of the sum (maps only, the last pass only: `out` is
+//       read through the prefetch ring and never written, 8 bytes per hypothesis instead of 12)
 // FIXV (PASS >= 2 only): the vertical pass is the horizontal recurrence along a column instead of the reference's
 template <int C, int PASS, int MODE, bool FULL, bool FIXV = false>
 __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int line)
 {
     static_assert(!FIXV || PASS >= 2, "FIXV is a property of the vertical passes");
+    static_assert(MODE < 5 || PASS == 3, "the maps-only modes belong to the last pass");
     constexpr int PF = (PASS < 2) ? PF_H : PF_V;
     constexpr bool ACC = (MODE >= 1);
     constexpr bool ACC2 = (MODE == 3);
-    constexpr bool WTA = (MODE == 2 || MODE == 4);
-    constexpr bool SUB = (MODE == 4);
+    constexpr bool WTA = (MODE == 2 || MODE == 4 || MODE == 5 || MODE == 6);
+    constexpr bool SUB = (MODE == 4 || MODE == 6);
+    constexpr bool STORE = (MODE < 5);
     const int lane = threadIdx.x & 63;
     constexpr bool HORIZ = (PASS < 2);
     const int H = a.H, W = a.W, D = a.D;
@@ -188,7 +192,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
 #pragma unroll
             for (int k = 0; k < C; k++) res[k] = last[k];
         }
-        st_row<C, FULL>(op + start * D, dl, D, res);
+        if (STORE) st_row<C, FULL>(op + start * D, dl, D, res);
         if (WTA) wta_store(res, start);
     }
     // minLastPath = min(cost, minLastPath) over the padded vector, in order (:162-166); pads are 65535.
@@ -251,7 +255,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, float *out, int lin
         _Pragma("unroll") for (int k = 0; k < C; k++)                                           \
             res[k] = ACC2 ? (obuf[ACC ? u : 0][k] + qbuf[ACC2 ? u : 0][k]) + cur[k]             \
                           : (ACC ? obuf[ACC ? u : 0][k] + cur[k] : cur[k]);                     \
-        st_row<C, FULL>(op + pix * D, dl, D, res);                                              \
+        if (STORE) st_row<C, FULL>(op + pix * D, dl, D, res);                                   \
         if (WTA) wta_store(res, pix);                                                           \
         minLast = wave_min_f32_dpp(cm);                                                         \
         _Pragma("unroll") for (int k = 0; k < C; k++) last[k] = (FULL || dl + k < D) ? cur[k] : PAD; \
@@ -303,6 +307,52 @@ __global__ void __launch_bounds__(NTLR) k_scan_lr(ScanArgs a)
     else scan_body<C, 1, 0, FULL>(a, a.out_b, line);
 }
 
+// The view axis (smt_scanline_run_pair, include/smt_scan_views.h): the same bodies over two volumes of one shape in one
+// grid, so that the scanlines of both views are resident together -- at H = 375 the left / right launch has 750 waves
+// for 1 024 SIMDs, with a second view 1 500.  One ScanArgs per view; the view index is a workgroup id, so the choice is
+// made on kernel arguments with scalar selects before the body starts, and every body is allocated the vector registers
+// of its single-view kernel (DESIGN.md section 5.18 has the table; indexing p.v[view] instead moved a few allocations).
+struct ScanArgs2 { ScanArgs v[2]; };
+__device__ __forceinline__ ScanArgs scan_view(const ScanArgs2 &p, unsigned view)
+{
+    ScanArgs a = p.v[0];                                   // H, W, D, p1, p2 and min_den are the same for both views
+    if (view) {
+        const ScanArgs &b = p.v[1];
+        a.cost = b.cost; a.gray = b.gray; a.out = b.out; a.add2 = b.add2; a.out_b = b.out_b; a.disp = b.disp;
+    }
+    return a;
+}
+
+template <int C, int PASS, int MODE, bool FULL, bool FIXV = false>
+__global__ void __launch_bounds__(scan_nt<PASS>()) k_scan_v(ScanArgs2 p)
+{
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const ScanArgs a = scan_view(p, blockIdx.y);
+    scan_body<C, PASS, MODE, FULL, FIXV>(a, a.out, blockIdx.x * (scan_nt<PASS>() / 64) + wv);
+}
+
+// the last pass with view 0 storing its sum (MA = 2 or 4) and view 1 maps-only (MB = 5 or 6): the launcher orders the
+// views that way
+template <int C, int MA, int MB, bool FULL, bool FIXV>
+__global__ void __launch_bounds__(NTS) k_scan_v_mixed(ScanArgs2 p)
+{
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int line = blockIdx.x * (NTS / 64) + wv;
+    if (blockIdx.y == 0) scan_body<C, 3, MA, FULL, FIXV>(p.v[0], p.v[0].out, line);
+    else scan_body<C, 3, MB, FULL, FIXV>(p.v[1], p.v[1].out, line);
+}
+
+// blockIdx.y picks the pass as in k_scan_lr, blockIdx.z the view
+template <int C, bool FULL>
+__global__ void __launch_bounds__(NTLR) k_scan_lr_v(ScanArgs2 p)
+{
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int line = blockIdx.x * (NTLR / 64) + wv;
+    const ScanArgs a = scan_view(p, blockIdx.z);
+    if (blockIdx.y == 0) scan_body<C, 0, 0, FULL>(a, a.out, line);
+    else scan_body<C, 1, 0, FULL>(a, a.out_b, line);
+}
+
 }  // namespace
 
 struct smt_scanline {
@@ -312,6 +362,8 @@ struct smt_scanline {
     float *scratch;      // one [H][W][D] volume: the right path until the up pass consumes it
     bool fix_vertical;   // SMT_QUIRK_FIX_SCAN_VERTICAL
     float sub_min_den;   // smt_scanline_set_subpixel: > 0 = the fused WTA of smt_scanline_run is refined; 0 = off
+    float *scratch_b;    // smt_scanline_run_pair: the second view's right path
+    float *sum[2];       // per view: (left + right) + up of a view that runs the maps-only last pass (vout == NULL)
 };
 
 SMT_API int smt_scanline_create(int H, int W, int D, int p1, int p2, smt_scanline **out)
@@ -336,6 +388,9 @@ SMT_API int smt_scanline_destroy(smt_scanline *h)
     if (!h) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
     if (h->scratch) (void)hipFree(h->scratch);
+    if (h->scratch_b) (void)hipFree(h->scratch_b);
+    for (float *p : h->sum)
+        if (p) (void)hipFree(p);
     delete h;
     return SMT_OK;
 }
@@ -368,6 +423,14 @@ static void launch_scan_sub(smt_scanline *h, const ScanArgs &a)
     if (h->fix_vertical) hipLaunchKernelGGL((k_scan<C, 3, 4, FULL, true>), grid, dim3(NTS), 0, h->stream, a);
     else hipLaunchKernelGGL((k_scan<C, 3, 4, FULL>), grid, dim3(NTS), 0, h->stream, a);
 }
+// and so do the maps-only MODEs 5 and 6
+template <int C, int MODE, bool FULL>
+static void launch_scan_map(smt_scanline *h, const ScanArgs &a)
+{
+    dim3 grid((h->W + NTS / 64 - 1) / (NTS / 64));
+    if (h->fix_vertical) hipLaunchKernelGGL((k_scan<C, 3, MODE, FULL, true>), grid, dim3(NTS), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_scan<C, 3, MODE, FULL>), grid, dim3(NTS), 0, h->stream, a);
+}
 
 template <int C, int MODE, bool FULL>
 static void launch_scan2(smt_scanline *h, int pass, const ScanArgs &a)
@@ -399,12 +462,16 @@ static void launch_scan(smt_scanline *h, int pass, const ScanArgs &a, int mode)
         else if (mode == 1) launch_scan2<CF, 1, true>(h, pass, a);
         else if (mode == 2) launch_scan2<CF, 2, true>(h, pass, a);
         else if (mode == 4) launch_scan_sub<CF, true>(h, a);
+        else if (mode == 5) launch_scan_map<CF, 5, true>(h, a);
+        else if (mode == 6) launch_scan_map<CF, 6, true>(h, a);
         else launch_scan2<CF, 3, true>(h, pass, a);
     } else {
         if (mode == 0) launch_scan2<C, 0, false>(h, pass, a);
         else if (mode == 1) launch_scan2<C, 1, false>(h, pass, a);
         else if (mode == 2) launch_scan2<C, 2, false>(h, pass, a);
         else if (mode == 4) launch_scan_sub<C, false>(h, a);
+        else if (mode == 5) launch_scan_map<C, 5, false>(h, a);
+        else if (mode == 6) launch_scan_map<C, 6, false>(h, a);
         else launch_scan2<C, 3, false>(h, pass, a);
     }
 }
@@ -433,6 +500,23 @@ static int scan_pass(smt_scanline *h, const ScanArgs &a, int pass, int mode)
     return SMT_OK;
 }
 
+// left -> a.out and right -> a.out_b in one launch
+static int scan_lr(smt_scanline *h, const ScanArgs &a)
+{
+    switch ((h->D + 63) / 64) {
+    case 1: launch_lr<1>(h, a); break;
+    case 2: launch_lr<2>(h, a); break;
+    case 3: launch_lr<3>(h, a); break;
+    case 4: launch_lr<4>(h, a); break;
+    case 5: launch_lr<5>(h, a); break;
+    case 6: launch_lr<6>(h, a); break;
+    case 7: launch_lr<7>(h, a); break;
+    default: launch_lr<8>(h, a); break;
+    }
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
 SMT_API int smt_scanline_pass(smt_scanline *h, const float *vin, const float *gray, int pass, float *vout)
 {
     if (!h || !vin || !gray || !vout || vin == vout || pass < 0 || pass > 3) return SMT_ERR_ARG;
@@ -450,20 +534,141 @@ SMT_API int smt_scanline_run(smt_scanline *h, const float *vin, const float *gra
         if (rc != SMT_OK) return rc;
     }
     ScanArgs a{vin, gray, vout, h->scratch, h->scratch, nullptr, h->H, h->W, h->D, (float)h->p1, (float)h->p2};
-    switch ((h->D + 63) / 64) {                                            // left -> vout, right -> scratch
-    case 1: launch_lr<1>(h, a); break;
-    case 2: launch_lr<2>(h, a); break;
-    case 3: launch_lr<3>(h, a); break;
-    case 4: launch_lr<4>(h, a); break;
-    case 5: launch_lr<5>(h, a); break;
-    case 6: launch_lr<6>(h, a); break;
-    case 7: launch_lr<7>(h, a); break;
-    default: launch_lr<8>(h, a); break;
-    }
-    SMT_LAUNCH_CHECK();
-    int rc = scan_pass(h, a, 2, 3);                                        // vout = (left + right) + up
+    int rc = scan_lr(h, a);                                                // left -> vout, right -> scratch
+    if (rc == SMT_OK) rc = scan_pass(h, a, 2, 3);                          // vout = (left + right) + up
     if (rc != SMT_OK) return rc;
     a.disp = disp;
     a.min_den = h->sub_min_den;
     return scan_pass(h, a, 3, disp ? (h->sub_min_den > 0.0f ? 4 : 2) : 1);  // vout = (..) + down [+ WTA, refined or not]
+}
+
+// ---- include/smt_scan_views.h ----------------------------------------------------------------------------------
+
+static int scan_volume(smt_scanline *h, float **p)
+{
+    return *p ? SMT_OK : smt_malloc((void **)p, (size_t)h->H * h->W * h->D * 4);
+}
+
+// One view, maps only: the sum before the last pass lives in the handle's scratch and the last pass stores no volume.
+SMT_API int smt_scanline_run_map(smt_scanline *h, const float *vin, const float *gray, float *disp)
+{
+    if (!h || !vin || !gray || !disp) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    int rc = scan_volume(h, &h->scratch);
+    if (rc == SMT_OK) rc = scan_volume(h, &h->sum[0]);
+    if (rc != SMT_OK) return rc;
+    ScanArgs a{vin, gray, h->sum[0], h->scratch, h->scratch, nullptr, h->H, h->W, h->D, (float)h->p1, (float)h->p2};
+    rc = scan_lr(h, a);
+    if (rc == SMT_OK) rc = scan_pass(h, a, 2, 3);
+    if (rc != SMT_OK) return rc;
+    a.disp = disp;
+    a.min_den = h->sub_min_den;
+    return scan_pass(h, a, 3, h->sub_min_den > 0.0f ? 6 : 5);
+}
+
+// stage 0: left / right, 1: up (MODE 3), 2: the last pass with the views' modes ma, mb (equal, or stored + maps-only)
+template <int C, bool FULL, bool FIXV>
+static void launch_pair_last(smt_scanline *h, const ScanArgs2 &p, int ma, int mb)
+{
+    dim3 grid((h->W + NTS / 64 - 1) / (NTS / 64), 2), block(NTS);
+    if (ma == 2 && mb == 2) hipLaunchKernelGGL((k_scan_v<C, 3, 2, FULL, FIXV>), grid, block, 0, h->stream, p);
+    else if (ma == 4 && mb == 4) hipLaunchKernelGGL((k_scan_v<C, 3, 4, FULL, FIXV>), grid, block, 0, h->stream, p);
+    else if (ma == 5 && mb == 5) hipLaunchKernelGGL((k_scan_v<C, 3, 5, FULL, FIXV>), grid, block, 0, h->stream, p);
+    else if (ma == 6 && mb == 6) hipLaunchKernelGGL((k_scan_v<C, 3, 6, FULL, FIXV>), grid, block, 0, h->stream, p);
+    else if (ma == 2) hipLaunchKernelGGL((k_scan_v_mixed<C, 2, 5, FULL, FIXV>), grid, block, 0, h->stream, p);
+    else hipLaunchKernelGGL((k_scan_v_mixed<C, 4, 6, FULL, FIXV>), grid, block, 0, h->stream, p);
+}
+
+template <int C, bool FULL>
+static void launch_pair2(smt_scanline *h, const ScanArgs2 &p, int stage, int ma, int mb)
+{
+    if (stage == 0) {
+        dim3 grid((h->H + NTLR / 64 - 1) / (NTLR / 64), 2, 2);
+        hipLaunchKernelGGL((k_scan_lr_v<C, FULL>), grid, dim3(NTLR), 0, h->stream, p);
+    } else if (stage == 1) {
+        dim3 grid((h->W + NTS / 64 - 1) / (NTS / 64), 2);
+        if (h->fix_vertical) hipLaunchKernelGGL((k_scan_v<C, 2, 3, FULL, true>), grid, dim3(NTS), 0, h->stream, p);
+        else hipLaunchKernelGGL((k_scan_v<C, 2, 3, FULL>), grid, dim3(NTS), 0, h->stream, p);
+    } else if (h->fix_vertical) launch_pair_last<C, FULL, true>(h, p, ma, mb);
+    else launch_pair_last<C, FULL, false>(h, p, ma, mb);
+}
+
+template <int C>
+static void launch_pair(smt_scanline *h, const ScanArgs2 &p, int stage, int ma, int mb)
+{
+    if (C <= 4 && h->D == 64 * C) launch_pair2<(C <= 4 ? C : 1), true>(h, p, stage, ma, mb);
+    else launch_pair2<C, false>(h, p, stage, ma, mb);
+}
+
+static int scan_pair_stage(smt_scanline *h, const ScanArgs2 &p, int stage, int ma = 0, int mb = 0)
+{
+    switch ((h->D + 63) / 64) {
+    case 1: launch_pair<1>(h, p, stage, ma, mb); break;
+    case 2: launch_pair<2>(h, p, stage, ma, mb); break;
+    case 3: launch_pair<3>(h, p, stage, ma, mb); break;
+    case 4: launch_pair<4>(h, p, stage, ma, mb); break;
+    case 5: launch_pair<5>(h, p, stage, ma, mb); break;
+    case 6: launch_pair<6>(h, p, stage, ma, mb); break;
+    case 7: launch_pair<7>(h, p, stage, ma, mb); break;
+    default: launch_pair<8>(h, p, stage, ma, mb); break;
+    }
+    SMT_LAUNCH_CHECK();
+    return SMT_OK;
+}
+
+// When the view axis pays.  Every scanline of a launch is resident at once, so a second view in the grid is nearly free
+// while one view leaves SIMDs without a wave, and costs where it does not: tools/scan_views_time.py on the MI355X (256 CUs,
+// 1 024 SIMDs), run_pair with the axis against two smt_scanline_run calls, median of 21: 450x375 D=64 0.355 against 0.640 ms
+// and 1242x375 D=256 2.149 against 2.277 (the left / right launch of one view has 2 H = 750 waves); 1920x1080 D=192 6.563
+// against 6.380 (2 160 waves; profiles/scan_views_axis_everywhere.json, the run before this rule).  So the axis is used
+// while the left / right launch of ONE view has at most one wave per SIMD, and beyond that smt_scanline_run_pair issues
+// the single-view launches, view after view: the same results.
+constexpr int SCAN_AXIS_MAX_WAVES = 1024;
+
+SMT_API int smt_scanline_run_pair(smt_scanline *h, const float *vinL, const float *grayL, float *voutL, float *dispL,
+                                  const float *vinR, const float *grayR, float *voutR, float *dispR)
+{
+    if (!h || !vinL || !grayL || !vinR || !grayR || (!voutL && !dispL) || (!voutR && !dispR)) return SMT_ERR_ARG;
+    if ((voutL && (voutL == vinL || voutL == vinR || voutL == voutR)) || (voutR && (voutR == vinL || voutR == vinR)) ||
+        (dispL && dispL == dispR))
+        return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    const float *vin[2] = {vinL, vinR}, *gray[2] = {grayL, grayR};
+    float *vout[2] = {voutL, voutR}, *disp[2] = {dispL, dispR};
+    float **path[2] = {&h->scratch, &h->scratch_b};
+    ScanArgs2 p;
+    int mode[2];
+    for (int v = 0; v < 2; v++) {
+        int rc = scan_volume(h, path[v]);
+        if (rc == SMT_OK && !vout[v]) rc = scan_volume(h, &h->sum[v]);
+        if (rc != SMT_OK) return rc;
+        p.v[v] = ScanArgs{vin[v], gray[v], vout[v] ? vout[v] : h->sum[v], *path[v], *path[v], nullptr, h->H, h->W, h->D,
+                          (float)h->p1, (float)h->p2};
+        const bool sub = h->sub_min_den > 0.0f;
+        mode[v] = !disp[v] ? 1 : vout[v] ? (sub ? 4 : 2) : (sub ? 6 : 5);
+    }
+    if (2 * h->H > SCAN_AXIS_MAX_WAVES) {                                  // one view fills the device: the single-view launches
+        for (int v = 0; v < 2; v++) {
+            int rc = scan_lr(h, p.v[v]);
+            if (rc == SMT_OK) rc = scan_pass(h, p.v[v], 2, 3);
+            if (rc != SMT_OK) return rc;
+            p.v[v].disp = disp[v]; p.v[v].min_den = h->sub_min_den;
+            rc = scan_pass(h, p.v[v], 3, mode[v]);
+            if (rc != SMT_OK) return rc;
+        }
+        return SMT_OK;
+    }
+    int rc = scan_pair_stage(h, p, 0);                                     // left -> sum, right -> path, both views
+    if (rc == SMT_OK) rc = scan_pair_stage(h, p, 1);                       // sum = (left + right) + up
+    if (rc != SMT_OK) return rc;
+    for (int v = 0; v < 2; v++) { p.v[v].disp = disp[v]; p.v[v].min_den = h->sub_min_den; }
+    if (mode[0] == 1 || mode[1] == 1) {                                    // a view without a map: the last pass per view
+        rc = scan_pass(h, p.v[0], 3, mode[0]);
+        return rc == SMT_OK ? scan_pass(h, p.v[1], 3, mode[1]) : rc;
+    }
+    if (mode[0] > mode[1]) {                                               // stored + maps-only: the stored view first
+        const ScanArgs t = p.v[0]; p.v[0] = p.v[1]; p.v[1] = t;
+        const int m = mode[0]; mode[0] = mode[1]; mode[1] = m;
+    }
+    return scan_pair_stage(h, p, 2, mode[0], mode[1]);
 }

@@ -8,6 +8,10 @@
 //          --subpixel [min_den] anywhere: the maps of the aggregation and of the scanline optimiser carry the parabola's
 //                                                      fraction (smt_wta_subpixel; min_den defaults to Sad.h:80's 1).  A
 //                                                      number right behind it is min_den: without one, put it last
+//          --scan-both anywhere: the scanline optimiser runs on the aggregated right volume too (guided by the float
+//                                                      right image), both views in the same launches
+//                                                      (smt_scanline_run_pair, maps only), and the LR check compares
+//                                                      the two optimised maps; prints so_wta_right as well
 //          adcensus_main --images left.png right.png D [disparity_out.png]     (imread -> cvtColor -> pipeline
 //                                                     -> imwrite, the file path of main.cpp:16-20, :115-117)
 //          adcensus_main --batch pairs H W D             (config 5 on every visible GPU, one handle per device)
@@ -19,6 +23,7 @@
 #include <cstring>
 #define SMT_HOST_WITH_RCCL
 #include "smt_host.hpp"
+#include "smt_scan_views.hpp"
 
 static double g_hash_ms = 0;   // time spent hashing products, excluded from the pipeline figure
 static uint64_t fnv(const void *p, size_t n)
@@ -100,6 +105,13 @@ int main(int argc, char **argv)
             for (int m = k; m + take < argc; m++) argv[m] = argv[m + take];
             argc -= take; k--;
         }
+    bool scan_both = false;
+    for (int k = 1; k < argc; k++)
+        if (!strcmp(argv[k], "--scan-both")) {
+            scan_both = true;
+            for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
+            argc--; k--;
+        }
     int row = argc > 1 ? atoi(argv[1]) : 72, col = argc > 2 ? atoi(argv[2]) : 160;
     int dispRange = argc > 3 ? atoi(argv[3]) : 64;
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 3;
@@ -154,6 +166,16 @@ int main(int argc, char **argv)
         printf("agg_left %016llx\nagg_right %016llx\n", (unsigned long long)fnv(aggL.data(), V * 4),
                (unsigned long long)fnv(aggR.data(), V * 4));
 
+        if (scan_both) {                                  // :86-89 on both views, in the same launches
+            smt::ScanlinePairOptimizer ScanlineOpt;
+            ScanlineOpt.setQuirks(quirks);
+            ScanlineOpt.setSubpixel(subpixel);
+            ScanlineOpt.Initialize(row, col, dispRange, p1, p2);
+            ScanlineOpt.ScanLinePair(aggL.data(), leftptr.data(), aggR.data(), rightptr.data(), nullptr, leftDisp.data(),
+                                     nullptr, rightDisp.data());
+            printf("so_wta_left %016llx\nso_wta_right %016llx\n", (unsigned long long)fnv(leftDisp.data(), n * 4),
+                   (unsigned long long)fnv(rightDisp.data(), n * 4));
+        } else {
         smt::ScanlineOptimizer ScanlineOpt;               // main.cpp:86-89 (enabled)
         ScanlineOpt.setQuirks(quirks);
         ScanlineOpt.setSubpixel(subpixel);
@@ -161,6 +183,7 @@ int main(int argc, char **argv)
         ScanlineOpt.ScanLine(aggL.data(), leftptr.data());
         ScanlineOpt.WTA(leftDisp.data());
         printf("so_wta_left %016llx\n", (unsigned long long)fnv(leftDisp.data(), n * 4));
+        }
 
         std::vector<std::pair<int, int>> occlusions, mismatches;
         smt::LeftRightConsistency(col, row, gate, leftDisp.data(), rightDisp.data(), occlusions, mismatches);   // main.cpp:92

@@ -73,17 +73,18 @@ def adcensus_batch(L, R, D, sigmaC=10.0, sigmaS=30.0):
     return dl, dr
 
 
-def pipeline_batch(L8, R8, D, quirks=0, subpixel=None, **params):
+def pipeline_batch(L8, R8, D, quirks=0, subpixel=None, scan_views=1, **params):
     """`compute` for run_sharded on configs[2]: the whole main.cpp pipeline (smt_pipeline_run_batch) for a
     [count, H, W] uint8 shard on this rank's GPU -> (LR-checked left maps, right maps).  quirks: QUIRK_FIX_* as
     api.Pipeline (0 = the reference's results).  subpixel: min_den of api.Pipeline.set_subpixel (both maps carry the
-    parabola's fraction), None = integer maps."""
+    parabola's fraction), None = integer maps.  scan_views: VIEW_LEFT (1) = main.cpp's flow, VIEW_BOTH (3) = the right
+    map comes from the scanline-optimised right volume too (api.Pipeline.set_scan_views)."""
     from .api import Pipeline
     c, H, W = L8.shape
     if c == 0:
         z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
         return z, z.clone()
-    pipe = Pipeline(H, W, D, L8.device, quirks=quirks, subpixel=subpixel, **params)
+    pipe = Pipeline(H, W, D, L8.device, quirks=quirks, subpixel=subpixel, scan_views=scan_views, **params)
     dl, dr, _, _ = pipe.run(L8.contiguous(), R8.contiguous())
     pipe.status()
     pipe.close()
