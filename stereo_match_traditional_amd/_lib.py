@@ -234,6 +234,22 @@ def _declare_scan_views(l):
     l.smt_pipeline_scan_right_volume.argtypes = [vp, C.POINTER(vp)]
 
 
+BILATERAL_NORM_RECIPROCAL, BILATERAL_NORM_DIVIDE = 0, 1      # SMT_BILATERAL_NORM_* (include/smt_bilateral.h)
+BILATERAL_FORM_DIRECT, BILATERAL_FORM_STAGED = 1, 2          # smt_bilateral_set_impl / smt_bilateral_last_form
+
+
+def _declare_bilateral(l):
+    """The signatures of include/smt_bilateral.h; an older build loaded through SMT_HIP_LIB is left as it is."""
+    if not hasattr(l, "smt_bilateral_filter_batch"):
+        return
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    l.smt_bilateral_masks.argtypes = [i, i, d, d, vp, vp]
+    l.smt_bilateral_filter_batch.argtypes = [vp, i, i, i, i, i, i, vp, vp, i, vp, vp, vp]
+    l.smt_bilateral_filter_host.argtypes = [vp, i, i, i, i, i, i, vp, vp, i, vp, vp]
+    l.smt_bilateral_set_impl.argtypes = [i]
+    l.smt_bilateral_last_form.argtypes = []
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -250,6 +266,7 @@ def lib():
         _declare_subpixel(_lib)
         _declare_sad_subpixel(_lib)
         _declare_scan_views(_lib)
+        _declare_bilateral(_lib)
     return _lib
 
 

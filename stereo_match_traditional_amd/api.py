@@ -16,6 +16,7 @@ from ._lib import NCC_FORM_LOOP, NCC_FORM_DOT4, NCC_FORM_BOX  # noqa: F401
 from ._lib import LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS  # noqa: F401
 from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
 from ._lib import NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT  # noqa: F401
+from ._lib import BILATERAL_NORM_RECIPROCAL, BILATERAL_NORM_DIVIDE, BILATERAL_FORM_DIRECT, BILATERAL_FORM_STAGED  # noqa: F401
 from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "wta_subpixel", "GetPointDepthSubpixel", "GetPointDepthBothSubpixel", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
@@ -31,7 +32,9 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "cblsm_window_set_store", "cblsm_window_last_form", "CBLSM_WINDOW_FORM_TAP", "CBLSM_WINDOW_FORM_BOX",
            "ncc", "bgr_to_grey", "ncc_whole_set_impl", "ncc_whole_last_form", "ncc_whole_set_groups", "ncc_whole_last_groups", "NCCWholeFlow", "NCC_WHOLE_FORM_LOOP",
            "NCC_WHOLE_FORM_INT",
-           "ASW_FIX_FILL_ROW_END", "MinMaxNormalizeU8", "FilterSpecklesU8", "MedianBlurU8", "FillImageNew", "ASWTail"]
+           "ASW_FIX_FILL_ROW_END", "MinMaxNormalizeU8", "FilterSpecklesU8", "MedianBlurU8", "FillImageNew", "ASWTail",
+           "bilateralfiter", "bilateral_masks", "bilateral_set_impl", "bilateral_last_form", "BILATERAL_NORM_RECIPROCAL",
+           "BILATERAL_NORM_DIVIDE", "BILATERAL_FORM_DIRECT", "BILATERAL_FORM_STAGED"]
 
 
 def current_stream_ptr(device=None):
@@ -1100,6 +1103,72 @@ def asw_masks(winSize, spaceSigma, colorSigma, device):
     check(lib().smt_asw_masks(winSize, C.c_double(spaceSigma), C.c_double(colorSigma),
                               sp.ctypes.data_as(C.c_void_p), cm.ctypes.data_as(C.c_void_p)), "smt_asw_masks")
     return torch.from_numpy(sp).to(device), torch.from_numpy(cm).to(device)
+
+
+def bilateral_masks(wsize, spaceSigma, colorSigma, device):
+    """getGausssianMask (BiliteralFilter.h:12-31) + getColorMask (:36-43), host float64 -> device tensors.  wsize:
+    (height, width) or one side; the space table is [height][width]."""
+    import numpy as np
+    h, w = (int(wsize), int(wsize)) if isinstance(wsize, int) else (int(wsize[0]), int(wsize[1]))
+    if not (1 <= h <= 64 and 1 <= w <= 64):
+        raise ValueError(f"wsize {wsize}: sides of 1..64 expected")
+    sp = np.empty((h, w), np.float64)
+    cm = np.empty(256, np.float64)
+    check(lib().smt_bilateral_masks(h, w, C.c_double(spaceSigma), C.c_double(colorSigma),
+                                    sp.ctypes.data_as(C.c_void_p), cm.ctypes.data_as(C.c_void_p)), "smt_bilateral_masks")
+    return torch.from_numpy(sp).to(device), torch.from_numpy(cm).to(device)
+
+
+_bilateral_tables = {}          # (h, w, spaceSigma, colorSigma, device) -> (space, color) on that device
+
+
+def bilateral_set_impl(impl):
+    """0 = the measured default, BILATERAL_FORM_DIRECT = one thread per pixel from global memory, BILATERAL_FORM_STAGED =
+    the LDS-staged tile kernel (test hook)."""
+    check(lib().smt_bilateral_set_impl(int(impl)), "smt_bilateral_set_impl")
+
+
+def bilateral_last_form():
+    """Which kernel the last bilateralfiter call launched: BILATERAL_FORM_DIRECT or BILATERAL_FORM_STAGED (0: none yet)."""
+    return int(lib().smt_bilateral_last_form())
+
+
+@_on_tensor_device
+def bilateralfiter(src, wsize=(23, 23), spaceSigma=10, colorSigma=30, norm=BILATERAL_NORM_RECIPROCAL, return_acc=False,
+                   tables=None):
+    """BiliteralFilter.h:49-142 (smt_bilateral_filter_batch): the bilateral filter of uint8 images [H,W], [H,W,3], or
+    with a leading images axis [n,H,W] (gray; a three-dimensional tensor whose last extent is 3 is one colour image, so
+    a gray stack 3 pixels wide goes in as [n,H,3,1]), [n,H,W,1] or [n,H,W,3]; every channel on its own, replicate padding.
+    wsize: (height, width) or one side, 1..64 (an even side acts as the odd side below it).  norm:
+    BILATERAL_NORM_RECIPROCAL (the weights times 1 / their sum, what OpenCV 3.1's Mat / double evaluates) or
+    BILATERAL_NORM_DIVIDE.  tables: (space, color) device float64 tensors instead of the cached ones of
+    bilateral_masks.  -> the filtered images, shaped like src; with return_acc also the unclamped float64 sums."""
+    h, w = (int(wsize), int(wsize)) if isinstance(wsize, int) else (int(wsize[0]), int(wsize[1]))
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise TypeError("src must be a contiguous uint8 torch tensor on the GPU")
+    if src.dim() == 2:
+        n, (H, W), ch = 1, src.shape, 1
+    elif src.dim() == 3 and src.shape[2] == 3:
+        n, (H, W), ch = 1, src.shape[:2], 3
+    elif src.dim() == 3:
+        (n, H, W), ch = src.shape, 1
+    elif src.dim() == 4 and src.shape[3] in (1, 3):
+        n, H, W, ch = src.shape
+    else:
+        raise ValueError(f"src has shape {tuple(src.shape)}: [H,W], [H,W,3], [n,H,W], [n,H,W,1] or [n,H,W,3] expected")
+    if tables is None:
+        key = (h, w, float(spaceSigma), float(colorSigma), src.device)
+        if key not in _bilateral_tables:
+            _bilateral_tables[key] = bilateral_masks((h, w), spaceSigma, colorSigma, src.device)
+        tables = _bilateral_tables[key]
+    space, color = tables
+    _dev(space, torch.float64, (h, w), "space")
+    _dev(color, torch.float64, (256,), "color")
+    dst = torch.empty_like(src)
+    acc = torch.empty(src.shape, dtype=torch.float64, device=src.device) if return_acc else None
+    check(lib().smt_bilateral_filter_batch(_ptr(src), int(n), int(H), int(W), int(ch), h, w, _ptr(space), _ptr(color), int(norm),
+                                           _ptr(dst), _ptr(acc), current_stream_ptr()), "smt_bilateral_filter_batch")
+    return (dst, acc) if return_acc else dst
 
 
 @_on_tensor_device

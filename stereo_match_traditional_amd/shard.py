@@ -286,3 +286,18 @@ def ncc_whole_batch(L8, R8, D=None, **params):
     _, _, ol, orr, _, _ = flow.run(L8.contiguous(), R8.contiguous(), want=("offL", "offR"))
     flow.close()
     return ol, orr
+
+
+def bilateral_batch(L8, R8, D=None, **params):
+    """`compute` for run_sharded on the bilateral image filter of BiliteralFilter.h:49-142 (smt_bilateral_filter_batch)
+    for a [count, H, W] uint8 shard of gray pairs on this rank's GPU -> (filtered left images, filtered right images),
+    uint8, both images of every pair in one call.  D is not used (an image-domain stage has no disparity range).
+    Keywords as api.bilateralfiter (wsize, spaceSigma, colorSigma, norm).  Colour stacks are not sharded: run_sharded
+    gathers [n, H, W] maps; filter [n, H, W, 3] stacks with api.bilateralfiter on the rank that holds them."""
+    from .api import bilateralfiter
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.uint8, device=L8.device)
+        return z, z.clone()
+    out = bilateralfiter(torch.cat([L8, R8], dim=0).contiguous().unsqueeze(-1), **params).squeeze(-1)
+    return out[:c], out[c:]
