@@ -250,6 +250,37 @@ def _declare_bilateral(l):
     l.smt_bilateral_last_form.argtypes = []
 
 
+REFINE_ARM_CLAMPED = 1                                       # SMT_REFINE_ARM_CLAMPED (include/smt_refine.h)
+REFINE_STATE_INTERPOLATED, REFINE_STATE_OUTLIER = 254, 255   # SMT_REFINE_STATE_*
+REFINE_FORM_DIRECT, REFINE_FORM_WAVE = 1, 2                  # smt_refine_set_impl / smt_refine_last_form
+
+
+class RefineParams(C.Structure):
+    """smt_refine_params: irv_ts, irv_th (adcensus_types.h:58-59, 72), the iteration count and the ray length."""
+    _fields_ = [("irv_ts", C.c_int), ("irv_th", C.c_float), ("irv_iters", C.c_int), ("search", C.c_int)]
+
+
+def _declare_refine(l):
+    """The signatures of include/smt_refine.h; an older build loaded through SMT_HIP_LIB is left as it is."""
+    if not hasattr(l, "smt_refine_batch"):
+        return
+    vp, i, z = C.c_void_p, C.c_int, C.c_size_t
+    l.smt_refine_default_params.argtypes = [vp]
+    l.smt_refine_default_params.restype = None
+    vote = [vp, i, z, vp, vp, vp, vp, z, i, i, i, vp, vp, z, vp]
+    interp = [vp, i, z, vp, z, vp, z, i, i, i, vp, vp, z, vp]
+    both = [vp, i, z, vp, vp, vp, vp, z, vp, z, vp, z, i, i, i, vp, vp, z, vp]
+    l.smt_region_vote_batch.argtypes = vote + [vp]
+    l.smt_interpolate_outliers_batch.argtypes = interp + [vp]
+    l.smt_refine_batch.argtypes = both + [vp]
+    l.smt_region_vote_batch_host.argtypes = vote
+    l.smt_interpolate_outliers_batch_host.argtypes = interp
+    l.smt_refine_batch_host.argtypes = both
+    l.smt_refine_set_impl.argtypes = [i]
+    l.smt_refine_last_form.argtypes = []
+    l.smt_pipeline_run_batch_refined.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -267,6 +298,7 @@ def lib():
         _declare_sad_subpixel(_lib)
         _declare_scan_views(_lib)
         _declare_bilateral(_lib)
+        _declare_refine(_lib)
     return _lib
 
 

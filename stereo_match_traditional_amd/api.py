@@ -17,6 +17,7 @@ from ._lib import LRNCC_FORM_COMPOSED, LRNCC_FORM_KEYS  # noqa: F401
 from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
 from ._lib import NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT  # noqa: F401
 from ._lib import BILATERAL_NORM_RECIPROCAL, BILATERAL_NORM_DIVIDE, BILATERAL_FORM_DIRECT, BILATERAL_FORM_STAGED  # noqa: F401
+from ._lib import REFINE_ARM_CLAMPED, REFINE_STATE_INTERPOLATED, REFINE_STATE_OUTLIER, REFINE_FORM_DIRECT, REFINE_FORM_WAVE  # noqa: F401
 from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "wta_subpixel", "GetPointDepthSubpixel", "GetPointDepthBothSubpixel", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
@@ -34,7 +35,10 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "NCC_WHOLE_FORM_INT",
            "ASW_FIX_FILL_ROW_END", "MinMaxNormalizeU8", "FilterSpecklesU8", "MedianBlurU8", "FillImageNew", "ASWTail",
            "bilateralfiter", "bilateral_masks", "bilateral_set_impl", "bilateral_last_form", "BILATERAL_NORM_RECIPROCAL",
-           "BILATERAL_NORM_DIVIDE", "BILATERAL_FORM_DIRECT", "BILATERAL_FORM_STAGED"]
+           "BILATERAL_NORM_DIVIDE", "BILATERAL_FORM_DIRECT", "BILATERAL_FORM_STAGED",
+           "RegionVote", "InterpolateOutliers", "Refine", "refine_params", "refine_set_impl", "refine_last_form",
+           "REFINE_ARM_CLAMPED", "REFINE_STATE_INTERPOLATED", "REFINE_STATE_OUTLIER", "REFINE_FORM_DIRECT",
+           "REFINE_FORM_WAVE"]
 
 
 def current_stream_ptr(device=None):
@@ -1356,6 +1360,100 @@ def RemoveSpecklesBatch(maps, diff_insame, min_speckle_aera, invalid_val):
     return maps
 
 
+# ---- region voting and outlier interpolation (include/smt_refine.h; parity unpinned: no reference code) ----------------
+def refine_params(option=None, **overrides):
+    """smt_refine_params: the defaults (irv_ts 20, irv_th 0.4, irv_iters 5, search 0), irv_ts and irv_th taken from an
+    ADCensusOption when one is given (adcensus_types.h:58-59), then the keywords."""
+    p = _lib.RefineParams()
+    lib().smt_refine_default_params(C.byref(p))
+    if option is not None:
+        p.irv_ts, p.irv_th = int(option.irv_ts), float(option.irv_th)
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def refine_set_impl(impl):
+    """0 = the default, REFINE_FORM_DIRECT = one thread per pixel, REFINE_FORM_WAVE = one wave per outlier: the voting
+    formulation, identical bits (test hook)."""
+    check(lib().smt_refine_set_impl(int(impl)), "smt_refine_set_impl")
+
+
+def refine_last_form():
+    """Which voting kernel the last call launched: REFINE_FORM_DIRECT or REFINE_FORM_WAVE (0: none yet)."""
+    return int(lib().smt_refine_last_form())
+
+
+def _plane_batch(t, dtype, P, H, W, name):
+    """[P][H][W] (or [H][W] when P == 1) planes on the GPU, each dense -> (tensor, stride between planes in elements)."""
+    t3 = t[None] if isinstance(t, torch.Tensor) and t.dim() == 2 else t
+    if not isinstance(t3, torch.Tensor) or not t3.is_cuda or t3.dtype != dtype or t3.dim() != 3:
+        raise TypeError(f"{name} must be a {dtype} [pairs][H][W] tensor on the GPU")
+    if tuple(t3.shape) != (P, H, W):
+        raise ValueError(f"{name} has shape {tuple(t3.shape)}, expected {(P, H, W)}")
+    if t3.stride(2) != 1 or (H > 1 and t3.stride(1) != W) or (P > 1 and t3.stride(0) < H * W):
+        raise TypeError(f"{name}: every plane must be dense and the planes must not overlap (strides {t3.stride()})")
+    return t3, (t3.stride(0) if P > 1 else H * W)
+
+
+def _refine_call(maps, arms, cls, gray, D, params, want_state, kw):
+    m3 = maps[None] if isinstance(maps, torch.Tensor) and maps.dim() == 2 else maps
+    P, H, W, stride = _map_batch(m3, "maps")
+    p = params if params is not None else refine_params(**kw)
+    if params is not None and kw:
+        raise TypeError("give params or keywords, not both")
+    state = torch.empty((P, H, W), dtype=torch.uint8, device=maps.device) if want_state else None
+    status = torch.zeros((P, 4), dtype=torch.int32, device=maps.device)
+    z, st = C.c_size_t, current_stream_ptr()
+    a = c = g = None
+    if arms is not None:
+        a = [_plane_batch(x, torch.int32, P, H, W, "arms[%d]" % k) for k, x in enumerate(arms)]
+        if len(a) != 4 or len({s for _, s in a}) != 1:
+            raise ValueError("arms: four int32 [pairs][H][W] tensors (left, right, top, bottom) with one stride")
+    if cls is not None:
+        c, g = _plane_batch(cls, torch.uint8, P, H, W, "cls"), _plane_batch(gray, torch.uint8, P, H, W, "gray")
+    single = maps.dim() == 2                             # one map in: state and status come back without the pairs axis
+    if P == 0:
+        return maps, state, status
+    tail = (H, W, int(D), C.byref(p), _ptr(state), z(0), _ptr(status), st)
+    if a is not None and c is not None:
+        check(lib().smt_refine_batch(_ptr(m3), P, z(stride), *[_ptr(x) for x, _ in a], z(a[0][1]), _ptr(c[0]), z(c[1]),
+                                     _ptr(g[0]), z(g[1]), *tail), "smt_refine_batch")
+    elif a is not None:
+        check(lib().smt_region_vote_batch(_ptr(m3), P, z(stride), *[_ptr(x) for x, _ in a], z(a[0][1]), *tail),
+              "smt_region_vote_batch")
+    else:
+        check(lib().smt_interpolate_outliers_batch(_ptr(m3), P, z(stride), _ptr(c[0]), z(c[1]), _ptr(g[0]), z(g[1]), *tail),
+              "smt_interpolate_outliers_batch")
+    return (maps, state[0] if want_state else None, status[0]) if single else (maps, state, status)
+
+
+@_on_tensor_device
+def RegionVote(maps, arms, dispRange, params=None, want_state=False, **kw):
+    """Iterative region voting (smt_region_vote_batch) on float32 [pairs][H][W] (or [H][W]) maps, in place,
+    asynchronous on the current stream.  arms: (left, right, top, bottom) int32 tensors of the maps' shape, as
+    CrossArmAggregation's arm maps.  params: refine_params(...), or its keywords (irv_ts, irv_th, irv_iters).
+    -> (maps, state uint8 or None, status int32 [pairs][4] = {outliers on entry, voted, 0, flags}); for one [H][W] map
+    state is [H][W] and status [4]."""
+    return _refine_call(maps, arms, None, None, dispRange, params, want_state, kw)
+
+
+@_on_tensor_device
+def InterpolateOutliers(maps, cls, gray, dispRange, params=None, want_state=False, **kw):
+    """Outlier interpolation along 16 rays (smt_interpolate_outliers_batch), in place, asynchronous.  cls: uint8 as
+    LeftRightConsistency writes it (1 = occlusion: the smallest candidate; otherwise the candidate nearest in gray);
+    gray: the uint8 left images.  Keyword: search.  -> (maps, state or None, status)."""
+    return _refine_call(maps, None, cls, gray, dispRange, params, want_state, kw)
+
+
+@_on_tensor_device
+def Refine(maps, arms, cls, gray, dispRange, params=None, want_state=False, **kw):
+    """RegionVote, then InterpolateOutliers (smt_refine_batch) -> (maps, state or None, status)."""
+    return _refine_call(maps, arms, cls, gray, dispRange, params, want_state, kw)
+
+
 @_on_tensor_device
 def MedianFilterInPlace(maps, wnd_size):
     """MedianFilter(d, d, ...) (PostProcessing.h:314-344 with in == out, as CBLSM.cpp:162 calls it): the raster-order
@@ -1670,6 +1768,38 @@ class Pipeline:
         check(lib().smt_pipeline_run_batch_post(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
                                                 _ptr(counts), C.byref(q), _ptr(last)), "smt_pipeline_run_batch_post")
         return dl, dr, cls, counts, last
+
+    def run_refined(self, grayL, grayR, refine=None, **post):
+        """run_post() with region voting and outlier interpolation between RemoveSpeckles and MedianFilter
+        (smt_pipeline_run_batch_refined; the arms are recomputed from every pair's left image) -> (dispL after the LR
+        check, RemoveSpeckles and the refinement, dispR, cls, counts, lastDisp = MedianFilter of dispL, state uint8
+        [pairs][row][col], status int32 [pairs][4]).  refine: refine_params(...), None = the defaults; keywords as
+        run_post."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"pipeline handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        q = _lib.PostParams()
+        lib().smt_post_default_params(C.byref(q))
+        for k, v in post.items():
+            if not hasattr(q, k):
+                raise AttributeError(k)
+            setattr(q, k, v)
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        last = torch.empty_like(dl)
+        cls = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        state = torch.empty_like(cls)
+        counts = torch.zeros((P, 2), dtype=torch.int32, device=grayL.device)
+        status = torch.zeros((P, 4), dtype=torch.int32, device=grayL.device)
+        check(lib().smt_pipeline_set_stream(self._h, current_stream_ptr(self.device)), "smt_pipeline_set_stream")
+        check(lib().smt_pipeline_run_batch_refined(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
+                                                   _ptr(counts), C.byref(q), C.byref(refine) if refine is not None else None,
+                                                   _ptr(last), _ptr(state), _ptr(status)), "smt_pipeline_run_batch_refined")
+        return dl, dr, cls, counts, last, state, status
 
     def volumes(self):
         ps = [C.c_void_p() for _ in range(5)]

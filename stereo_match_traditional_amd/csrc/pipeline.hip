@@ -30,8 +30,12 @@
 // sit in front of the right view's aggregation that the next LR check waits for.  Its scratch (one pair's speckle
 // forest and counts, an error word) is the handle's, allocated by the first _post call; tails follow each other on M,
 // so one set serves every pair.
+// smt_pipeline_run_batch_refined (include/smt_refine.h) puts region voting and outlier interpolation between :93 and
+// :94 of the same tail: the arms of the pair's left image, recomputed on M by a third crossarm handle (caT), then
+// smt_refine_batch on the pair's map.  The other two entry points launch what they launched.
 #include "smt_common.h"
 #include "../../include/smt_scan_views.h"
+#include "../../include/smt_refine.h"
 #include <initializer_list>
 #include <limits.h>
 #include <new>
@@ -61,12 +65,20 @@ struct smt_pipeline {
     float *sovolR;           // the right view's scanline sum (the last pair's)
     bool sovolR_valid;
     hipEvent_t ev_aggR, ev_scanR[2];
+    // smt_pipeline_run_batch_refined: the tail's own crossarm handle, on M, created by the first refined call.  A pair's
+    // tail cannot read caL's maps: under schedules 0 to 2 and SMT_VIEW_BOTH they hold another image's arms by then.
+    smt_crossarm *caT;
 };
 
 // main.cpp:93-94 on one pair, or nothing (post == NULL: smt_pipeline_run_batch)
 struct pipe_tail {
     const smt_post_params *post;
     float *last;             // lastDisp [pairs][H][W], may be NULL
+    // smt_pipeline_run_batch_refined: region voting and interpolation between :93 and :94, or nothing (refine == NULL)
+    const smt_refine_params *refine;
+    const uint8_t *grayL;    // the call's left images: the arms and the interpolation read pair b's
+    uint8_t *state;          // [pairs][H][W], may be NULL
+    int *status;             // [pairs][4], may be NULL
 };
 
 SMT_API void smt_pipeline_default_params(smt_pipeline_params *p)
@@ -99,6 +111,7 @@ SMT_API int smt_pipeline_destroy(smt_pipeline *h)
     }
     if (h->caL) smt_crossarm_destroy(h->caL);
     if (h->caR) smt_crossarm_destroy(h->caR);
+    if (h->caT) smt_crossarm_destroy(h->caT);
     if (h->so) smt_scanline_destroy(h->so);
     if (h->soR) smt_scanline_destroy(h->soR);
     (void)hipFree(h->sovolR);
@@ -120,6 +133,7 @@ static int pipeline_apply_streams(smt_pipeline *h)
     int rc = smt_crossarm_set_stream(h->caL, m);
     if (rc == SMT_OK) rc = smt_scanline_set_stream(h->so, m);
     if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_stream(h->caR, (void *)h->side);
+    if (rc == SMT_OK && h->caT) rc = smt_crossarm_set_stream(h->caT, m);
     if (rc == SMT_OK && h->soR) rc = smt_scanline_set_stream(h->soR, (void *)h->side);
     for (int k = 0; k < 2 && rc == SMT_OK; k++)
         if (h->adc[k]) rc = smt_adcensus_set_stream(h->adc[k], h->sched == 2 ? (void *)h->front : m);
@@ -191,6 +205,7 @@ SMT_API int smt_pipeline_set_quirks(smt_pipeline *h, unsigned quirks)
     // every stage takes the flags it knows; handles a schedule does not use do not exist
     int rc = smt_crossarm_set_quirks_internal(h->caL, quirks);
     if (rc == SMT_OK && h->caR) rc = smt_crossarm_set_quirks_internal(h->caR, quirks);
+    if (rc == SMT_OK && h->caT) rc = smt_crossarm_set_quirks_internal(h->caT, quirks);
     if (rc == SMT_OK) rc = smt_scanline_set_quirks(h->so, quirks);
     if (rc == SMT_OK && h->soR) rc = smt_scanline_set_quirks(h->soR, quirks);
     for (int k = 0; k < 2 && rc == SMT_OK; k++)
@@ -216,13 +231,25 @@ SMT_API int smt_pipeline_set_subpixel(smt_pipeline *h, const smt_subpixel_params
 #define PIPE_HIP(call) do { if (rc == SMT_OK && (call) != hipSuccess) rc = SMT_ERR_HIP; } while (0)
 
 // main.cpp:93-94 for pair b, on M after its LR check
-static int pipeline_tail(smt_pipeline *h, const pipe_tail &t, float *dl, int b)
+static int pipeline_tail(smt_pipeline *h, const pipe_tail &t, float *dl, const uint8_t *cls, int b)
 {
     if (!t.post) return SMT_OK;
     const int H = h->H, W = h->W;
     const smt_post_params &q = *t.post;
     int rc = smt_speckle_enqueue(dl, 1, 0, W, H, q.speckle_diff, q.speckle_min_area, q.speckle_invalid, h->tail,
                                  h->tail_err, h->stream);                                       // :93
+    if (rc == SMT_OK && t.refine) {
+        // the arms of this pair's left image (two launches), then voting and interpolation in place on dl
+        const size_t N = (size_t)H * W;
+        const uint8_t *L8 = t.grayL + b * N;
+        int *arm[4] = {nullptr, nullptr, nullptr, nullptr};
+        rc = smt_crossarm_arms(h->caT, L8, 1);
+        if (rc == SMT_OK) rc = smt_crossarm_arm_maps(h->caT, &arm[0], &arm[1], &arm[2], &arm[3]);
+        if (rc == SMT_OK)
+            rc = smt_refine_batch(dl, 1, 0, arm[0], arm[1], arm[2], arm[3], 0, cls, 0, L8, 0, H, W, h->D, t.refine,
+                                  t.state ? t.state + b * N : nullptr, 0, t.status ? t.status + 4 * b : nullptr,
+                                  (void *)h->stream);
+    }
     if (rc == SMT_OK && t.last) rc = smt_median_filter(dl, t.last + (size_t)b * H * W, W, H, q.median_wnd, (void *)h->stream);   // :94
     return rc;
 }
@@ -276,7 +303,7 @@ static int pipeline_run_simple(smt_pipeline *h, const uint8_t *grayL, const uint
         if (rc == SMT_OK) rc = smt_scanline_run(h->so, h->agg[0], h->Lf[0], h->sovol, dl);     // :86-89
         if (two) PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_right[0], 0));
         if (rc == SMT_OK) rc = smt_lrcheck(dl, dr, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);   // :92
-        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl, b);                                   // :93-94
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl, cls + b * N, b);                                   // :93-94
         if (rc != SMT_OK) { (void)hipStreamSynchronize(h->side); return rc; }
     }
     h->last_set = 0;
@@ -380,7 +407,7 @@ static int pipeline_run_simple_both(smt_pipeline *h, const uint8_t *grayL, const
                 PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_scanR[s ^ 1], 0));
                 if (rc == SMT_OK)
                     rc = smt_lrcheck(dl - N, dr - N, H, W, h->P.gate, cls + (b - 1) * N, counts ? counts + 2 * (b - 1) : nullptr, st);
-                if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, b - 1);
+                if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, cls + (b - 1) * N, b - 1);
             }
         } else {
             if (rc == SMT_OK) rc = smt_crossarm_arms(h->caL, R8, 1);                   // :77-81
@@ -389,7 +416,7 @@ static int pipeline_run_simple_both(smt_pipeline *h, const uint8_t *grayL, const
                 rc = smt_scanline_run_pair(h->so, h->agg[0], h->Lf[0], h->sovol, dl, h->agg[1], h->Rf[0],
                                            b == pairs - 1 ? h->sovolR : nullptr, dr);
             if (rc == SMT_OK) rc = smt_lrcheck(dl, dr, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);   // :92
-            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl, b);                       // :93-94
+            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl, cls + b * N, b);                       // :93-94
         }
     }
     if (two && rc == SMT_OK) {
@@ -398,7 +425,7 @@ static int pipeline_run_simple_both(smt_pipeline *h, const uint8_t *grayL, const
         PIPE_HIP(hipStreamWaitEvent(h->stream, h->ev_scanR[s], 0));
         if (rc == SMT_OK)
             rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, st);
-        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, b);
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, cls + b * N, b);
     }
     if (rc != SMT_OK) { (void)hipStreamSynchronize(h->side); return rc; }
     h->last_set = 0;
@@ -448,7 +475,7 @@ static int pipeline_run_both(smt_pipeline *h, const uint8_t *grayL, const uint8_
             PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s ^ 1], 0));
             if (rc == SMT_OK)
                 rc = smt_lrcheck(dl - N, dr - N, H, W, h->P.gate, cls + (b - 1) * N, counts ? counts + 2 * (b - 1) : nullptr, (void *)M);
-            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, b - 1);                     // :93-94 of pair b - 1
+            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, cls + (b - 1) * N, b - 1);                     // :93-94 of pair b - 1
         }
         // S: right view: aggregation beside the left view's scanline, scan beside the next pair's left aggregation
         PIPE_HIP(hipStreamWaitEvent(S, h->ev_left, 0));
@@ -461,7 +488,7 @@ static int pipeline_run_both(smt_pipeline *h, const uint8_t *grayL, const uint8_
         PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s], 0));
         if (rc == SMT_OK)
             rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, (void *)M);
-        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, b);
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, cls + b * N, b);
         h->last_set = s;
     }
     if (rc != SMT_OK) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(F); }
@@ -520,7 +547,7 @@ static int pipeline_run(smt_pipeline *h, const uint8_t *grayL, const uint8_t *gr
             PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s ^ 1], 0));
             if (rc == SMT_OK)
                 rc = smt_lrcheck(dl - N, dr - N, H, W, h->P.gate, cls + (b - 1) * N, counts ? counts + 2 * (b - 1) : nullptr, (void *)M);
-            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, b - 1);                     // :93-94 of pair b - 1
+            if (rc == SMT_OK) rc = pipeline_tail(h, tail, dl - N, cls + (b - 1) * N, b - 1);                     // :93-94 of pair b - 1
         }
         if (rc == SMT_OK) rc = smt_scanline_run(h->so, h->agg[0], h->Lf[s], h->sovol, dl);     // :86-89
         PIPE_HIP(hipEventRecord(h->ev_scan[s], M));
@@ -535,7 +562,7 @@ static int pipeline_run(smt_pipeline *h, const uint8_t *grayL, const uint8_t *gr
         PIPE_HIP(hipStreamWaitEvent(M, h->ev_right[s], 0));
         if (rc == SMT_OK)
             rc = smt_lrcheck(dispL + b * N, dispR + b * N, H, W, h->P.gate, cls + b * N, counts ? counts + 2 * b : nullptr, (void *)M);
-        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, b);
+        if (rc == SMT_OK) rc = pipeline_tail(h, tail, dispL + b * N, cls + b * N, b);
         h->last_set = s;
     }
     if (rc != SMT_OK) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(F); }
@@ -550,6 +577,17 @@ SMT_API int smt_pipeline_run_batch(smt_pipeline *h, const uint8_t *grayL, const 
     return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts, pipe_tail{nullptr, nullptr});
 }
 
+// the tail's scratch, allocated by the first call that has a tail
+static int pipeline_tail_prepare(smt_pipeline *h)
+{
+    if (h->tail) return SMT_OK;
+    int rc = smt_malloc(&h->tail, smt_speckle_scratch_bytes(1, h->W, h->H));
+    if (rc == SMT_OK) rc = smt_malloc((void **)&h->tail_err, 4);
+    if (rc == SMT_OK && hipMemsetAsync(h->tail_err, 0, 4, h->stream) != hipSuccess) rc = SMT_ERR_HIP;
+    if (rc != SMT_OK) { (void)hipFree(h->tail); (void)hipFree(h->tail_err); h->tail = nullptr; h->tail_err = nullptr; }
+    return rc;
+}
+
 SMT_API int smt_pipeline_run_batch_post(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
                                         float *dispL, float *dispR, uint8_t *cls, int *counts,
                                         const smt_post_params *post, float *lastDisp)
@@ -558,13 +596,35 @@ SMT_API int smt_pipeline_run_batch_post(smt_pipeline *h, const uint8_t *grayL, c
     if (post->median_wnd < 1 || post->median_wnd > 7 || lastDisp == dispL) return SMT_ERR_ARG;
     if ((long long)h->H * h->W >= (1ll << 31)) return SMT_ERR_ARG;
     smt_dev_guard dev_guard(h->device);
-    if (!h->tail) {
-        int rc = smt_malloc(&h->tail, smt_speckle_scratch_bytes(1, h->W, h->H));
-        if (rc == SMT_OK) rc = smt_malloc((void **)&h->tail_err, 4);
-        if (rc == SMT_OK && hipMemsetAsync(h->tail_err, 0, 4, h->stream) != hipSuccess) rc = SMT_ERR_HIP;
-        if (rc != SMT_OK) { (void)hipFree(h->tail); (void)hipFree(h->tail_err); h->tail = nullptr; h->tail_err = nullptr; return rc; }
-    }
+    const int rc = pipeline_tail_prepare(h);
+    if (rc != SMT_OK) return rc;
     return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts, pipe_tail{post, lastDisp});
+}
+
+SMT_API int smt_pipeline_run_batch_refined(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                           float *dispL, float *dispR, uint8_t *cls, int *counts,
+                                           const smt_post_params *post, const smt_refine_params *refine, float *lastDisp,
+                                           uint8_t *state, int *status)
+{
+    if (!h || !grayL || !grayR || pairs <= 0 || !dispL || !dispR || !cls || !post) return SMT_ERR_ARG;
+    if (post->median_wnd < 1 || post->median_wnd > 7 || lastDisp == dispL) return SMT_ERR_ARG;
+    if ((long long)h->H * h->W >= (1ll << 31)) return SMT_ERR_ARG;
+    smt_refine_params rp;
+    if (refine) rp = *refine; else smt_refine_default_params(&rp);
+    if (rp.irv_iters < 0 || rp.irv_iters > 16 || rp.search < 0) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    int rc = pipeline_tail_prepare(h);
+    if (rc == SMT_OK && !h->caT) {
+        smt_crossarm_params cp;
+        smt_crossarm_default_params(&cp);
+        cp.tau = h->P.tao;
+        rc = smt_crossarm_create(h->H, h->W, h->D, &cp, &h->caT);
+        if (rc == SMT_OK) rc = smt_crossarm_set_quirks_internal(h->caT, h->quirks);
+        if (rc == SMT_OK) rc = smt_crossarm_set_stream(h->caT, (void *)h->stream);
+        if (rc != SMT_OK && h->caT) { smt_crossarm_destroy(h->caT); h->caT = nullptr; }
+    }
+    if (rc != SMT_OK) return rc;
+    return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts, pipe_tail{post, lastDisp, &rp, grayL, state, status});
 }
 
 SMT_API int smt_pipeline_volumes(smt_pipeline *h, float **cost_left, float **cost_right, float **agg_left, float **agg_right,

@@ -12,6 +12,10 @@
 //                                                      right image), both views in the same launches
 //                                                      (smt_scanline_run_pair, maps only), and the LR check compares
 //                                                      the two optimised maps; prints so_wta_right as well
+//          --refine anywhere: behind the LR check, main.cpp:93 (RemoveSpeckles), then region voting and outlier
+//                                                      interpolation on the left image's arms (smt_refine_batch,
+//                                                      the defaults), then main.cpp:94 (MedianFilter); prints
+//                                                      refined_left, refine_status and median_left
 //          adcensus_main --images left.png right.png D [disparity_out.png]     (imread -> cvtColor -> pipeline
 //                                                     -> imwrite, the file path of main.cpp:16-20, :115-117)
 //          adcensus_main --batch pairs H W D             (config 5 on every visible GPU, one handle per device)
@@ -24,6 +28,8 @@
 #define SMT_HOST_WITH_RCCL
 #include "smt_host.hpp"
 #include "smt_scan_views.hpp"
+#include "smt_refine.hpp"
+#include <climits>
 
 static double g_hash_ms = 0;   // time spent hashing products, excluded from the pipeline figure
 static uint64_t fnv(const void *p, size_t n)
@@ -112,6 +118,13 @@ int main(int argc, char **argv)
             for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
             argc--; k--;
         }
+    bool refine = false;
+    for (int k = 1; k < argc; k++)
+        if (!strcmp(argv[k], "--refine")) {
+            refine = true;
+            for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
+            argc--; k--;
+        }
     int row = argc > 1 ? atoi(argv[1]) : 72, col = argc > 2 ? atoi(argv[2]) : 160;
     int dispRange = argc > 3 ? atoi(argv[3]) : 64;
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 3;
@@ -189,6 +202,22 @@ int main(int argc, char **argv)
         smt::LeftRightConsistency(col, row, gate, leftDisp.data(), rightDisp.data(), occlusions, mismatches);   // main.cpp:92
         printf("lr_left %016llx\nn_occlusion %zu\nn_mismatch %zu\n", (unsigned long long)fnv(leftDisp.data(), n * 4),
                occlusions.size(), mismatches.size());
+        if (refine) {
+            smt::RemoveSpeckles(leftDisp.data(), col, row, 1, 30, INT_MIN);                       // main.cpp:93
+            std::vector<int> arm(4 * n);
+            smt::ArmMaps(leftGray.data(), row, col, dispRange, tao, quirks, &arm[0], &arm[n], &arm[2 * n], &arm[3 * n]);
+            std::vector<unsigned char> cls(n);
+            smt::ClassMap(occlusions, mismatches, row, col, cls.data());
+            int status[4];
+            smt::RefineOutputs out;
+            out.status = status;
+            smt::Refine(leftDisp.data(), &arm[0], &arm[n], &arm[2 * n], &arm[3 * n], cls.data(), leftGray.data(), row, col, dispRange,
+                        smt::RefineDefaultParams(), out);
+            std::vector<float> lastDisp(n);
+            smt::MedianFilter(leftDisp.data(), lastDisp.data(), col, row, 3);                    // main.cpp:94
+            printf("refined_left %016llx\nrefine_status %d %d %d %d\nmedian_left %016llx\n", (unsigned long long)fnv(leftDisp.data(), n * 4),
+                   status[0], status[1], status[2], status[3], (unsigned long long)fnv(lastDisp.data(), n * 4));
+        }
         if (from_files && argc > 5) {
             // TransformToShow + normalize of main.cpp:98-110 reduced to its effect on a valid map: rejected
             // pixels (inf) black, disparities scaled to 0..255 by the range

@@ -91,6 +91,23 @@ def pipeline_batch(L8, R8, D, quirks=0, subpixel=None, scan_views=1, **params):
     return dl, dr
 
 
+def pipeline_refined_batch(L8, R8, D, quirks=0, subpixel=None, scan_views=1, refine=None, post=None, **params):
+    """`compute` for run_sharded on the pipeline with its whole tail and the refinement (smt_pipeline_run_batch_refined:
+    LR check, RemoveSpeckles, region voting and outlier interpolation, MedianFilter) for a [count, H, W] uint8 shard on
+    this rank's GPU -> (lastDisp, the refined left maps before the median).  refine: api.refine_params(...), None = the
+    defaults; post: a dict of run_post's keywords; the rest as pipeline_batch."""
+    from .api import Pipeline
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    pipe = Pipeline(H, W, D, L8.device, quirks=quirks, subpixel=subpixel, scan_views=scan_views, **params)
+    dl, _, _, _, last, _, _ = pipe.run_refined(L8.contiguous(), R8.contiguous(), refine=refine, **(post or {}))
+    pipe.status()
+    pipe.close()
+    return last, dl
+
+
 def cblsm_batch(L8, R8, D, **params):
     """`compute` for run_sharded on CBLSM.cpp's flow (smt_cblsm_flow_run_batch) for a [count, H, W] uint8 shard on this
     rank's GPU -> (left maps, right maps).  Keywords as api.CBLSMFlow."""
