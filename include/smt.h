@@ -236,7 +236,7 @@ int smt_adcensus_compute(smt_adcensus *h, const float *L, const float *R, int vi
  *   With smt_adcensus_timing a chained pair's events are recorded on its chain's stream: kernel_ms of such a pair spans
  *   a launch that shares the device with its neighbour's, and the stand-alone table kernel of a chain's first pair is
  *   not inside its table interval.
- * Test hook, host only (no GPU), exported and declared in csrc/adcensus_internal.h:
+ * Test hook, host only (no GPU), exported, defined in csrc/adcensus_selftest.hip:
  *   int smt_adcensus_selftest_chains(int pairs, int chains, long c0, long c1, long c2, int order, unsigned flags);
  * writes the plan of such a call down (the function the call itself runs) for chains whose pair counters stand at c0,
  * c1, c2 (earlier calls leave any parity), order 0 (default) / 1 pairs / 2 ab / 3 ba, flags 1 shared form | 2 the last
@@ -312,7 +312,7 @@ int smt_adcensus_selftest_maps_grid(int nbx, int H, int K, int nprep);
  * lut[ad] + lut[256+hd] it stands for (order preserved, equal ranks exactly when the bits are equal).  SMT_OK or
  * SMT_ERR_STATE; SMT_ERR_ARG unless both sigmas are > 0. */
 int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
-/* Shared maps-only form of smt_adcensus_compute_batch (adcensus.hip, k_cost_maps_shared).  For 3 <= j' and j' + d <= W-4
+/* Shared maps-only form of smt_adcensus_compute_batch (adcensus_kernels.h, k_cost_maps_shared).  For 3 <= j' and j' + d <= W-4
  * the right view's cost(i, j', d) is bit for bit the left view's cost(i, j' + d, d), so for the pairs of a batch that
  * write maps only (both maps requested, D <= 256, W >= D + 6) the right map of the columns 3 <= j' <= W-3-D is taken
  * from keys (cost bits << 32 | d) that the left pass publishes.  The columns j' > W-3-D get the keys of their
@@ -326,7 +326,7 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  *   W >= D + 6: same-process A/Bs and tests.  SMT_MAPS_KERNEL=rank selects the rank kernel as before.
  * In the left pass a workgroup stages a run of up to 4 consecutive 64-pixel chunks of one row once, every wave walks a
  * contiguous quarter of it in one pass and the run's columns are flushed once.
- * Test hook, host only (no GPU), exported by the library and declared in csrc/adcensus_internal.h:
+ * Test hook, host only (no GPU), exported by the library, defined in csrc/adcensus_selftest.hip:
  *   int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
  * walks the runs of K chunks per workgroup, the key ring, its flushes and the key-map merges of that form through the
  * kernel's own index functions over pseudo-random costs with many exact ties (seed % 3: 0 a palette with ties, 1 every
@@ -344,7 +344,7 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  * issued there: no conversion is pending when an entry point returns.
  *   SMT_SHARED_FINISH=apart in the environment (read at every call) converts every pair with that launch of its own
  *   right behind the pair's launch (two launches per pair): same-process A/Bs and tests.  Maps are the same.
- * Test hooks, host only (no GPU), exported and declared in csrc/adcensus_internal.h:
+ * Test hooks, host only (no GPU), exported, defined in csrc/adcensus_selftest.hip:
  *   int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
  * every cost workgroup (ncost > 0, a multiple of 8) and every table, edge and conversion item of such a launch is
  * decoded exactly once;
@@ -353,14 +353,14 @@ int smt_adcensus_selftest_cost_rank(float sigmaC, float sigmaS);
  * pixel arithmetic covers each key, each pixel of the columns W-2-D .. W-1 and each of the columns 0..2 exactly once,
  * and no column W-3-D < j' <= W-4 has an empty edge range.  SMT_OK, SMT_ERR_STATE, or SMT_ERR_ARG (also for W < D + 6).
  * Tapered tail.  The chunks of a maps-only launch (shared or two-view) are cut into workgroups per XCD slice by one span
- * rule (adcensus.hip, maps_span): the slice's last n1 workgroups take 1 chunk, the n2 before them max(1, K/2), all
+ * rule (adcensus_rules.h, maps_span): the slice's last n1 workgroups take 1 chunk, the n2 before them max(1, K/2), all
  * before those K (SMT_MAPS_CHUNKS), and the launch's auxiliary workgroups are placed in front of the first tapered one.
  * Maps do not depend on it.  The counts come from the device (workgroups resident per slice, queried at create) and
  * are 0 for a launch of at most one round of workgroups (DESIGN.md section 4 "Tapered tail").
  *   SMT_MAPS_TAPER in the environment (read at every call): 0 is off, the plain rule and placement exactly; n2,n1 are
  *   these counts per slice whatever the launch size (tests, sweeps).  The host-only selftests above walk what the
  *   variable selects.
- * Test hook, host only (no GPU), exported and declared in csrc/adcensus_internal.h:
+ * Test hook, host only (no GPU), exported, defined in csrc/adcensus_selftest.hip:
  *   int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);
  * over the 8 slices of a launch of nb chunks: every chunk belongs to exactly one workgroup, none crosses its slice or
  * has more than K chunks, the workgroup count is the rule's, tails that fit have the sizes above, and n2 = n1 = 0 is

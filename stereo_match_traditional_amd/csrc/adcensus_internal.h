@@ -16,12 +16,3 @@ int adcensus_batch_pairs(smt_adcensus *h, const float *L, const float *R, int n,
                          bool last_volumes);
 // Both views of this handle take the register-window kernels (D <= 256), so sched 2 and the maps-only kernel apply.
 bool adcensus_fused_both_views(const smt_adcensus *h);
-// Host-only selftest of the shared maps-only form's run / ring / flush / merge arithmetic (documented in include/smt.h).
-SMT_API int smt_adcensus_selftest_shared_keys(int H, int W, int D, int K, unsigned seed);
-// Host-only selftests of the shared form's auxiliary work items (documented in include/smt.h).
-SMT_API int smt_adcensus_selftest_shared_aux_grid(int ncost, int nprep, int nedge, int nconv);
-SMT_API int smt_adcensus_selftest_shared_aux(int H, int W, int D, int K, int first, int last);
-// Host-only selftest of the maps-only launches' span rule with a tapered tail (documented in include/smt.h).
-SMT_API int smt_adcensus_selftest_spans(long nb, int K, int n2, int n1);
-// Host-only selftest of the chained batch schedule's order (documented in include/smt.h).
-SMT_API int smt_adcensus_selftest_chains(int pairs, int chains, long c0, long c1, long c2, int order, unsigned flags);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/smt.h"
 #include "subpixel_rule.h"
 
@@ -114,8 +115,26 @@ int smt_lrncc_enqueue(int form, const uint8_t *L, const uint8_t *R, int pairs, i
 // effect from the next arms call.  SMT_ERR_ARG for an unknown bit.
 int smt_crossarm_set_quirks_internal(smt_crossarm *h, unsigned quirks);
 
+// A launcher's ladder over its kernel instantiations: run-time hypotheses per lane C -> f(std::integral_constant<int, C>)
+// for 1 <= C <= CMAX, true; false, and no call, for any other C.  What f instantiates is the whole kernel set.
+template <int CMAX, class F>
+static inline bool dispatch_c(int C, F &&f)
+{
+    if constexpr (CMAX > 0) {
+        if (C == CMAX) { f(std::integral_constant<int, CMAX>{}); return true; }
+        return dispatch_c<CMAX - 1>(C, f);
+    }
+    return false;
+}
+
 #ifdef __HIPCC__
 constexpr int WAVE = 64;
+
+template <int C> struct vecf { float v[C]; };          // C = 5..8 (D > 256): plain struct, the kernels there use the per-element paths
+template <> struct vecf<1> { float v[1]; };
+template <> struct __attribute__((aligned(8))) vecf<2> { float v[2]; };
+template <> struct vecf<3> { float v[3]; };
+template <> struct __attribute__((aligned(16))) vecf<4> { float v[4]; };
 
 // std::min / std::max semantics of the reference (returns the FIRST argument on ties and
 // for the +0/-0 pair), kept instead of fminf so that signs of zero cannot diverge.

@@ -1,4 +1,4 @@
-"""smt_adcensus_compute_batch with the maps-only kernel for pairs 0 .. n-2 (adcensus.hip, k_cost_maps2p): every map
+"""smt_adcensus_compute_batch with the maps-only kernel for pairs 0 .. n-2 (adcensus_kernels.h, k_cost_maps2p): every map
 against the oracle, the last pair's volumes bit for bit, the domain flag of a non-last pair, and the same maps with
 SMT_BATCH_VOLUMES=all -- under every batch schedule and for both / one / no map requested."""
 import ctypes as C

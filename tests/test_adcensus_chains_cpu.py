@@ -1,4 +1,4 @@
-"""The chained batch schedule of smt_adcensus_compute_batch (adcensus.hip, chain_plan) without a GPU.  The host selftest
+"""The chained batch schedule of smt_adcensus_compute_batch (adcensus_rules.h, chain_plan) without a GPU.  The host selftest
 writes down the plan that the call itself issues -- which chain, stream, table sets and key maps every launch uses, and
 the fork and join events -- and computes happens-before over it: every table set is built before it is read and not
 rebuilt under a reader, every key map is merged, converted once and merged again in a total order, every right map is

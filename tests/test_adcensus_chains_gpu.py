@@ -1,4 +1,4 @@
-"""The chained schedule of smt_adcensus_compute_batch (adcensus.hip, chain_plan): pair b of a call runs on chain b % NC,
+"""The chained schedule of smt_adcensus_compute_batch (adcensus_rules.h, chain_plan): pair b of a call runs on chain b % NC,
 every chain on two table sets and two key maps of its own, chain 0 on the caller's stream and the others on internal
 streams that are forked from it and joined into it by events.  Every map of every pair, NaN-prefilled, against the
 oracle's WTA, and every form bit-equal to every other: batches of several sizes on one handle (chain counters of every

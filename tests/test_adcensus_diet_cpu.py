@@ -1,4 +1,4 @@
-"""The index rules of the shared AD-Census launch (adcensus.hip, k_cost_maps_shared) without a GPU, over the shapes of
+"""The index rules of the shared AD-Census launch (adcensus_kernels.h, k_cost_maps_shared) without a GPU, over the shapes of
 test_adcensus_diet_gpu.py.  The D = 192 kernel computes a ring base once per group of 3 pixels of a wave's walk and
 reaches the group's slots at constant offsets (shared_ring_slot), up to 4 slots past the ring's end; the host model in
 smt_adcensus_selftest_shared_keys publishes by the same rule -- wave by wave, group by group -- and fails if two live

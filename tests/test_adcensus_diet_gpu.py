@@ -1,4 +1,4 @@
-"""The shared maps-only launch of smt_adcensus_compute_batch (adcensus.hip, k_cost_maps_shared) after its vector diet:
+"""The shared maps-only launch of smt_adcensus_compute_batch (adcensus_kernels.h, k_cost_maps_shared) after its vector diet:
 the D = 192 walk takes whole groups of 3 pixels without a per-pixel exit and computes the ring base once per group
 (shared_ring_slot), so a group reaches up to 4 slots past the ring's end.  Batches of 3 different pairs -- pair 0's
 tables from k_prep, pairs 1 and 2's from table workgroups that write the two table sets alternately -- with every map

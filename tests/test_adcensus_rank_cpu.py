@@ -1,4 +1,4 @@
-"""Host-side checks of the maps-only batch kernel (adcensus.hip, no GPU): the rank table that replaces the float costs
+"""Host-side checks of the maps-only batch kernel (adcensus_kernels.h, adcensus_rules.h; no GPU): the rank table that replaces the float costs
 in its WTA, and the workgroup arithmetic of its launch (K chunks per workgroup, table workgroups fused in)."""
 import ctypes
 

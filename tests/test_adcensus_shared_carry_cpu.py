@@ -1,4 +1,4 @@
-"""The auxiliary work items of a shared AD-Census launch (adcensus.hip, k_cost_maps_shared) without a GPU: the edge
+"""The auxiliary work items of a shared AD-Census launch (adcensus_kernels.h, k_cost_maps_shared) without a GPU: the edge
 items of the launch's own pair, the conversion items of the pair before it and the table tiles of the pair after it ride
 in the fused grid's table class.  The host selftests run the kernel's own index functions: every cost workgroup and every
 item decoded exactly once (smt_adcensus_selftest_shared_aux_grid), the items' pixel arithmetic covering its column set

@@ -1,5 +1,5 @@
 """The shared maps-only form of smt_adcensus_compute_batch with a pair finished inside its neighbours' launches
-(adcensus.hip, k_cost_maps_shared): the edge items of a pair ride in its own launch, the conversion of its partial keys
+(adcensus_kernels.h, k_cost_maps_shared): the edge items of a pair ride in its own launch, the conversion of its partial keys
 in the next pair's, and only the last shared pair of a call is converted by a launch of its own (k_shared_convert).
 Every map of every pair, NaN-prefilled, against the oracle's WTA: several batches on one handle (key-map parity across
 calls, the lone pair, a carried pair beside a stand-alone one), the other forms between shared calls, no write behind a

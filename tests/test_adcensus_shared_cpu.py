@@ -1,4 +1,4 @@
-"""The shared maps-only form of the AD-Census batch (adcensus.hip, k_cost_maps_shared) without a GPU: the host walk of
+"""The shared maps-only form of the AD-Census batch (adcensus_kernels.h, k_cost_maps_shared) without a GPU: the host walk of
 its run / ring / flush / merge arithmetic (smt_adcensus_selftest_shared_keys), and the identity it rests on, checked on
 the oracle's volumes: for 3 <= j' and j' + d <= W-4 the right view's cost(i, j', d) has the bits of the left view's
 cost(i, j' + d, d), so the right WTA map of the columns 3 <= j' <= W-3-D is the first minimum along a diagonal of the

@@ -1,4 +1,4 @@
-"""The shared maps-only form with the edges finished apart (adcensus.hip, k_cost_maps_shared + k_shared_finish) without
+"""The shared maps-only form with the edges finished apart (adcensus_kernels.h, k_cost_maps_shared + k_shared_finish) without
 a GPU.  Every left hypothesis (j, d) with j <= W-4 and j - d >= 3 publishes to right column j - d; a right column
 j' > W-3-D lacks only its edge hypotheses W-3 <= j' + d <= W+3, because the right view's cost is constant in d from
 W+3-j' on (the staging clamps the census index to W+3 and the value index to W-1); the columns 0..2 share nothing.

@@ -1,4 +1,4 @@
-"""The shared maps-only form of smt_adcensus_compute_batch with the edges finished apart (adcensus.hip,
+"""The shared maps-only form of smt_adcensus_compute_batch with the edges finished apart (adcensus_kernels.h,
 k_cost_maps_shared + k_shared_finish): the left pass publishes every shareable cost, the finishing launch evaluates the
 edge hypotheses W-3 <= j' + d <= W+3 of the columns j' > W-3-D and every hypothesis of the columns 0..2 and merges them
 with the column's key.  Every map of every pair, NaN-prefilled, against the oracle's WTA and against the same call under

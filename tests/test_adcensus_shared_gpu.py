@@ -1,4 +1,4 @@
-"""The shared maps-only form of smt_adcensus_compute_batch (adcensus.hip, k_cost_maps_shared + k_shared_finish): the right
+"""The shared maps-only form of smt_adcensus_compute_batch (adcensus_kernels.h, k_cost_maps_shared + k_shared_finish): the right
 map of the columns 3 <= j' <= W-3-D comes from the keys the left pass publishes, the other columns from the VIEW 1 body.
 Every map of every pair against the oracle's WTA and against the same call under SMT_MAPS_SHARED=0 (the two-view
 kernel), under every batch schedule and run length; ties at run edges; the census edge fix; one / no map requested and

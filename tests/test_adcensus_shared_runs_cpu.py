@@ -1,4 +1,4 @@
-"""The shared maps-only form with runs walked in one pass (adcensus.hip, k_cost_maps_shared) without a GPU: the host walk
+"""The shared maps-only form with runs walked in one pass (adcensus_kernels.h, k_cost_maps_shared) without a GPU: the host walk
 of the form's rules (smt_adcensus_selftest_shared_keys) over the shapes and chunk counts of
 test_adcensus_shared_runs_gpu.py.  A workgroup's consecutive chunks of one row form a run, cut into sub-runs of SH_RUN = 4
 chunks; a run is published as a whole and flushed once.  Every right pixel must be written exactly once with its first

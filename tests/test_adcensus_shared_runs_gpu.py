@@ -1,4 +1,4 @@
-"""The shared maps-only form of smt_adcensus_compute_batch with runs walked in one pass (adcensus.hip, k_cost_maps_shared):
+"""The shared maps-only form of smt_adcensus_compute_batch with runs walked in one pass (adcensus_kernels.h, k_cost_maps_shared):
 a workgroup stages a run of up to SH_RUN = 4 consecutive chunks of one row once, every wave walks a contiguous quarter of
 it, and the run's columns are flushed once.  Every map of every pair, NaN-prefilled, against the oracle's WTA and against
 the same call under SMT_MAPS_SHARED=0 (the two-view kernel), and a second identical call (the key map was left reset),

@@ -1,4 +1,4 @@
-"""Tapered tail of the maps-only launches (adcensus.hip: maps_span, maps_span_groups) without a GPU.  The library's own
+"""Tapered tail of the maps-only launches (adcensus_rules.h: maps_span, maps_span_groups) without a GPU.  The library's own
 check of the span rule (smt_adcensus_selftest_spans: every chunk in exactly one group, no group across its slice or
 longer than K, the group count the companion's, n2 = n1 = 0 the plain rule) over short launches, launches around the
 size of a few rounds of workgroups and the headline's 32 400 chunks, with tails from none to longer than the slice; then

@@ -1,4 +1,4 @@
-"""Tapered tail of the maps-only launches of smt_adcensus_compute_batch (adcensus.hip: maps_span, fused_grid's body
+"""Tapered tail of the maps-only launches of smt_adcensus_compute_batch (adcensus_rules.h: maps_span, fused_grid's body
 placement): the slice's last n1 workgroups take 1 chunk, the n2 before them max(1, K/2), and the auxiliary workgroups
 (table tiles, conversion and edge items) go in front of the first tapered one.  Maps must not depend on it: every map of a
 3-pair batch on one reused handle -- so that the table tiles and the carried conversion pass through the new placement --

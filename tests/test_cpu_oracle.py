@@ -83,7 +83,7 @@ def test_lib_exports_every_declared_symbol():
 
 def test_fused_launch_grid_is_a_bijection():
     """smt_adcensus_compute_batch puts the table workgroups of pair n+1 into the grid of pair n's cost launch in groups
-    of 8 (adcensus.hip: fused_grid / fused_decode).  The library's own host-side check of that arithmetic, over the
+    of 8 (adcensus_rules.h: fused_grid / fused_decode).  The library's own host-side check of that arithmetic, over the
     benchmark shapes, tiny grids and random sizes: every cost group and every table group exactly once."""
     from stereo_match_traditional_amd import build
     lib = ctypes.CDLL(build.build())

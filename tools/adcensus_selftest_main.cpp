@@ -1,8 +1,8 @@
-// Stand-alone driver of the host-only selftests of csrc/adcensus.hip, for sanitizer builds of the host code (no GPU, no
-// Python):
-//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//         -Xarch_host -fno-sanitize-recover=undefined stereo_match_traditional_amd/csrc/adcensus.hip \
-//         tools/adcensus_selftest_main.cpp -fsanitize=address,undefined -o adcensus_selftest && ./adcensus_selftest
+// Stand-alone driver of the host-only selftests of csrc/adcensus_selftest.hip, for sanitizer builds of the host code (no
+// GPU, no HIP, no Python); tests/test_adcensus_rules_cpu.py builds and runs it:
+//   g++ -O1 -g -std=c++17 -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all
+//       -x c++ stereo_match_traditional_amd/csrc/adcensus_selftest.hip tools/adcensus_selftest_main.cpp
+//       -o adcensus_selftest && ./adcensus_selftest
 // Exit status 0 iff every selftest returned SMT_OK on every shape (and the sanitizers stayed silent).
 #include <cstdio>
 #include <cstdlib>
