@@ -281,6 +281,25 @@ def _declare_refine(l):
     l.smt_pipeline_run_batch_refined.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
 
 
+FILLHOLES_UB_NAN = 1                                         # SMT_FILLHOLES_UB_NAN (include/smt_fill_holes.h)
+FILLHOLES_MAX_DIM = 8192                                     # SMT_FILLHOLES_MAX_DIM
+
+
+def _declare_fill_holes(l):
+    """The signatures of include/smt_fill_holes.h; an older build loaded through SMT_HIP_LIB is left as it is."""
+    if not hasattr(l, "smt_fill_holes_batch"):
+        return
+    vp, i, z, f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
+    l.smt_fill_holes_batch.argtypes = [vp, vp, i, z, z, i, i, f, vp, vp]
+    l.smt_fill_holes_batch_host.argtypes = [vp, vp, i, z, z, i, i, f, vp]
+    l.smt_fill_holes_constants.argtypes = [vp]
+    l.smt_fill_holes_constants.restype = None
+    l.smt_fill_holes_probe.argtypes = [i, i, i, i, C.POINTER(i), C.POINTER(i)]
+    l.smt_fill_holes_walk.argtypes = [i, i, i, i, i, vp, vp, i]
+    l.smt_fill_holes_host_passes.argtypes = [vp, vp, i, i, f, i]
+    l.smt_pipeline_run_batch_filled.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, f, vp, vp]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -299,6 +318,7 @@ def lib():
         _declare_scan_views(_lib)
         _declare_bilateral(_lib)
         _declare_refine(_lib)
+        _declare_fill_holes(_lib)
     return _lib
 
 

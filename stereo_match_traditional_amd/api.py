@@ -18,6 +18,7 @@ from ._lib import ASW_FIX_FILL_ROW_END  # noqa: F401
 from ._lib import NCC_WHOLE_FORM_LOOP, NCC_WHOLE_FORM_INT  # noqa: F401
 from ._lib import BILATERAL_NORM_RECIPROCAL, BILATERAL_NORM_DIVIDE, BILATERAL_FORM_DIRECT, BILATERAL_FORM_STAGED  # noqa: F401
 from ._lib import REFINE_ARM_CLAMPED, REFINE_STATE_INTERPOLATED, REFINE_STATE_OUTLIER, REFINE_FORM_DIRECT, REFINE_FORM_WAVE  # noqa: F401
+from ._lib import FILLHOLES_UB_NAN, FILLHOLES_MAX_DIM  # noqa: F401
 from ._lib import CBLSM_COST_LEFT, CBLSM_COST_RIGHT, CBLSM_COST_V4, CBLSM_WINDOW_FORM_TAP, CBLSM_WINDOW_FORM_BOX  # noqa: F401
 
 __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN_VERTICAL", "QUIRK_FIX_CENSUS_RIGHT_EDGE", "QUIRK_FIX_ALL", "MedianFilterInPlace", "median_inplace_set_impl", "CBLSMTail", "FillTheHole", "FillTheHoleBatch", "chooseArmLengthLeft", "chooseArmLengthRight", "chooseArmLengthUp", "chooseArmLengthDown", "costAggregationNew", "costAggregationV4", "AD_Census", "wta", "wta_subpixel", "GetPointDepthSubpixel", "GetPointDepthBothSubpixel", "current_stream_ptr", "CrossArmAggregation", "cblsm_ComputeAD",
@@ -38,7 +39,7 @@ __all__ = ["QUIRK_FIX_RIGHT_ARM_STRIDE", "QUIRK_FIX_STICKY_TAU", "QUIRK_FIX_SCAN
            "BILATERAL_NORM_DIVIDE", "BILATERAL_FORM_DIRECT", "BILATERAL_FORM_STAGED",
            "RegionVote", "InterpolateOutliers", "Refine", "refine_params", "refine_set_impl", "refine_last_form",
            "REFINE_ARM_CLAMPED", "REFINE_STATE_INTERPOLATED", "REFINE_STATE_OUTLIER", "REFINE_FORM_DIRECT",
-           "REFINE_FORM_WAVE"]
+           "REFINE_FORM_WAVE", "FillHolesInDispMap", "FILLHOLES_UB_NAN", "FILLHOLES_MAX_DIM"]
 
 
 def current_stream_ptr(device=None):
@@ -794,6 +795,33 @@ def FillTheHoleBatch(maps, cls, dispRange, check=False):
                 raise _lib.SmtError(_lib.SMT_ERR_REF_UB, "smt_fill_the_hole_batch: pair %d, %s" % (
                     b, "list entry outside the buffer" if f & SMT_FILL_UB_LIST else "more holes than mismatches"))
     return status
+
+
+@_on_tensor_device
+def FillHolesInDispMap(maps, cls, invalid=float("inf"), check=False):
+    """FillHolesInDispMap (SAD/Sad.h:317-400) on every map of [pairs][row][col] (or one [row][col]) float32, in place,
+    with the occlusion and mismatch lists taken from cls (uint8, same shape, as smt_lrcheck writes it: 1 and 2): the
+    filler for the +inf holes LeftRightConsistency leaves, which FillTheHole[Batch] (holes of 65535) does not see.
+    invalid: the hole value.  Asynchronous (one launch on the current stream, nothing waits).  Returns the [pairs, 4]
+    int32 status tensor {n_occ, n_mis, n_third, flags} ([4] for one map); a map that holds a NaN is not modified and
+    flagged FILLHOLES_UB_NAN.  check=True synchronises and raises SmtError(SMT_ERR_REF_UB) naming the first flagged
+    map."""
+    single = isinstance(maps, torch.Tensor) and maps.dim() == 2
+    m3 = maps[None] if single else maps
+    P, row, col, stride = _map_batch(m3, "maps")
+    c3, cstride = _plane_batch(cls, torch.uint8, P, row, col, "cls")
+    if c3.device != m3.device:
+        raise TypeError("cls must be on the maps' GPU")
+    status = torch.empty((P, 4), dtype=torch.int32, device=m3.device)
+    if P == 0:
+        return status
+    _lib.check(lib().smt_fill_holes_batch(_ptr(m3), _ptr(c3), P, C.c_size_t(stride), C.c_size_t(cstride), row, col,
+                                          C.c_float(invalid), _ptr(status), current_stream_ptr()), "smt_fill_holes_batch")
+    if check:
+        for b, f in enumerate(status[:, 3].cpu().tolist()):
+            if f:
+                raise _lib.SmtError(_lib.SMT_ERR_REF_UB, "smt_fill_holes_batch: map %d holds a NaN" % b)
+    return status[0] if single else status
 
 
 # ======================================================================================
@@ -1800,6 +1828,30 @@ class Pipeline:
                                                    _ptr(counts), C.byref(q), C.byref(refine) if refine is not None else None,
                                                    _ptr(last), _ptr(state), _ptr(status)), "smt_pipeline_run_batch_refined")
         return dl, dr, cls, counts, last, state, status
+
+    def run_filled(self, grayL, grayR, median_wnd=3, invalid=float("inf")):
+        """run() plus, per pair behind the LR check, Sad.h's FillHolesInDispMap on dispL with the pair's cls and the
+        MedianFilter (smt_pipeline_run_batch_filled; no RemoveSpeckles stage) -> (dispL after the LR check and the
+        filler, dispR, cls, counts, lastDisp = MedianFilter of dispL, status int32 [pairs][4] = {n_occ, n_mis, n_third,
+        flags})."""
+        if grayL.dim() == 2:
+            grayL, grayR = grayL[None], grayR[None]
+        P = grayL.shape[0]
+        if _dev_index(grayL.device) != _dev_index(self.device) or grayR.device != grayL.device:
+            raise ValueError(f"pipeline handle lives on {self.device}, images on {grayL.device} / {grayR.device}")
+        _dev(grayL, torch.uint8, (P, self.row, self.col), "grayL")
+        _dev(grayR, torch.uint8, (P, self.row, self.col), "grayR")
+        dl = torch.empty((P, self.row, self.col), dtype=torch.float32, device=grayL.device)
+        dr = torch.empty_like(dl)
+        last = torch.empty_like(dl)
+        cls = torch.empty((P, self.row, self.col), dtype=torch.uint8, device=grayL.device)
+        counts = torch.zeros((P, 2), dtype=torch.int32, device=grayL.device)
+        status = torch.zeros((P, 4), dtype=torch.int32, device=grayL.device)
+        check(lib().smt_pipeline_set_stream(self._h, current_stream_ptr(self.device)), "smt_pipeline_set_stream")
+        check(lib().smt_pipeline_run_batch_filled(self._h, _ptr(grayL), _ptr(grayR), P, _ptr(dl), _ptr(dr), _ptr(cls),
+                                                  _ptr(counts), int(median_wnd), C.c_float(invalid), _ptr(last),
+                                                  _ptr(status)), "smt_pipeline_run_batch_filled")
+        return dl, dr, cls, counts, last, status
 
     def volumes(self):
         ps = [C.c_void_p() for _ in range(5)]

@@ -33,9 +33,12 @@
 // smt_pipeline_run_batch_refined (include/smt_refine.h) puts region voting and outlier interpolation between :93 and
 // :94 of the same tail: the arms of the pair's left image, recomputed on M by a third crossarm handle (caT), then
 // smt_refine_batch on the pair's map.  The other two entry points launch what they launched.
+// smt_pipeline_run_batch_filled (include/smt_fill_holes.h) has another tail at the same place: Sad.h's FillHolesInDispMap
+// on the pair's map with the pair's class map (one launch), then the median.  It needs none of the tail's scratch.
 #include "smt_common.h"
 #include "../../include/smt_scan_views.h"
 #include "../../include/smt_refine.h"
+#include "../../include/smt_fill_holes.h"
 #include <initializer_list>
 #include <limits.h>
 #include <new>
@@ -79,6 +82,9 @@ struct pipe_tail {
     const uint8_t *grayL;    // the call's left images: the arms and the interpolation read pair b's
     uint8_t *state;          // [pairs][H][W], may be NULL
     int *status;             // [pairs][4], may be NULL
+    // smt_pipeline_run_batch_filled: FillHolesInDispMap and the median instead of :93-94 (post == NULL), or nothing (0)
+    int fill_wnd;            // the median's window, 1..7
+    float fill_invalid;
 };
 
 SMT_API void smt_pipeline_default_params(smt_pipeline_params *p)
@@ -233,8 +239,14 @@ SMT_API int smt_pipeline_set_subpixel(smt_pipeline *h, const smt_subpixel_params
 // main.cpp:93-94 for pair b, on M after its LR check
 static int pipeline_tail(smt_pipeline *h, const pipe_tail &t, float *dl, const uint8_t *cls, int b)
 {
-    if (!t.post) return SMT_OK;
     const int H = h->H, W = h->W;
+    if (t.fill_wnd) {
+        int rc = smt_fill_holes_batch(dl, cls, 1, 0, 0, H, W, t.fill_invalid, t.status ? t.status + 4 * b : nullptr,
+                                      (void *)h->stream);
+        if (rc == SMT_OK && t.last) rc = smt_median_filter(dl, t.last + (size_t)b * H * W, W, H, t.fill_wnd, (void *)h->stream);
+        return rc;
+    }
+    if (!t.post) return SMT_OK;
     const smt_post_params &q = *t.post;
     int rc = smt_speckle_enqueue(dl, 1, 0, W, H, q.speckle_diff, q.speckle_min_area, q.speckle_invalid, h->tail,
                                  h->tail_err, h->stream);                                       // :93
@@ -625,6 +637,18 @@ SMT_API int smt_pipeline_run_batch_refined(smt_pipeline *h, const uint8_t *grayL
     }
     if (rc != SMT_OK) return rc;
     return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts, pipe_tail{post, lastDisp, &rp, grayL, state, status});
+}
+
+SMT_API int smt_pipeline_run_batch_filled(smt_pipeline *h, const uint8_t *grayL, const uint8_t *grayR, int pairs,
+                                          float *dispL, float *dispR, uint8_t *cls, int *counts, int median_wnd,
+                                          float invalid, float *lastDisp, int *status)
+{
+    if (!h || !grayL || !grayR || pairs <= 0 || !dispL || !dispR || !cls) return SMT_ERR_ARG;
+    if (median_wnd < 1 || median_wnd > 7 || lastDisp == dispL || invalid != invalid) return SMT_ERR_ARG;
+    if (h->H > SMT_FILLHOLES_MAX_DIM || h->W > SMT_FILLHOLES_MAX_DIM) return SMT_ERR_ARG;
+    smt_dev_guard dev_guard(h->device);
+    return pipeline_run(h, grayL, grayR, pairs, dispL, dispR, cls, counts,
+                        pipe_tail{nullptr, lastDisp, nullptr, nullptr, nullptr, status, median_wnd, invalid});
 }
 
 SMT_API int smt_pipeline_volumes(smt_pipeline *h, float **cost_left, float **cost_right, float **agg_left, float **agg_right,

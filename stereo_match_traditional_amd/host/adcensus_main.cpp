@@ -16,6 +16,12 @@
 //                                                      interpolation on the left image's arms (smt_refine_batch,
 //                                                      the defaults), then main.cpp:94 (MedianFilter); prints
 //                                                      refined_left, refine_status and median_left
+//          --fill-holes anywhere: behind the LR check, SAD/Sad.h's FillHolesInDispMap on the left map with the LR
+//                                                      check's two lists (smt::FillHolesInDispMap on the reference's
+//                                                      signature, invalid = +inf), checked bit for bit against the
+//                                                      host twin, then main.cpp:94 (MedianFilter); prints filled_left,
+//                                                      fill_holes_status, fill_holes_host_twin and median_left.  Not
+//                                                      together with --refine
 //          adcensus_main --images left.png right.png D [disparity_out.png]     (imread -> cvtColor -> pipeline
 //                                                     -> imwrite, the file path of main.cpp:16-20, :115-117)
 //          adcensus_main --batch pairs H W D             (config 5 on every visible GPU, one handle per device)
@@ -29,6 +35,7 @@
 #include "smt_host.hpp"
 #include "smt_scan_views.hpp"
 #include "smt_refine.hpp"
+#include "smt_fill_holes.hpp"
 #include <climits>
 
 static double g_hash_ms = 0;   // time spent hashing products, excluded from the pipeline figure
@@ -125,6 +132,17 @@ int main(int argc, char **argv)
             for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
             argc--; k--;
         }
+    bool fill_holes = false;
+    for (int k = 1; k < argc; k++)
+        if (!strcmp(argv[k], "--fill-holes")) {
+            fill_holes = true;
+            for (int m = k; m + 1 < argc; m++) argv[m] = argv[m + 1];
+            argc--; k--;
+        }
+    if (refine && fill_holes) {
+        fprintf(stderr, "error: --refine and --fill-holes are two tails of the same map; give one\n");
+        return 1;
+    }
     int row = argc > 1 ? atoi(argv[1]) : 72, col = argc > 2 ? atoi(argv[2]) : 160;
     int dispRange = argc > 3 ? atoi(argv[3]) : 64;
     const uint32_t seed = argc > 4 ? (uint32_t)atoi(argv[4]) : 3;
@@ -217,6 +235,23 @@ int main(int argc, char **argv)
             smt::MedianFilter(leftDisp.data(), lastDisp.data(), col, row, 3);                    // main.cpp:94
             printf("refined_left %016llx\nrefine_status %d %d %d %d\nmedian_left %016llx\n", (unsigned long long)fnv(leftDisp.data(), n * 4),
                    status[0], status[1], status[2], status[3], (unsigned long long)fnv(lastDisp.data(), n * 4));
+        }
+        if (fill_holes) {
+            const float invalid = std::numeric_limits<float>::infinity();
+            std::vector<float> twin(leftDisp);                                  // the host twin on the same map and lists
+            std::vector<unsigned char> cls(n);
+            smt::ClassMap(occlusions, mismatches, row, col, cls.data());
+            int status[4], twin_status[4];
+            smt::check(smt_fill_holes_batch_host(twin.data(), cls.data(), 1, 0, 0, row, col, invalid, twin_status),
+                       "smt_fill_holes_batch_host");
+            smt::FillHolesInDispMap(col, row, leftDisp.data(), occlusions, mismatches, invalid, status);   // SADmain.cpp:79
+            const bool equal = !memcmp(twin.data(), leftDisp.data(), n * 4) && !memcmp(status, twin_status, sizeof(status));
+            std::vector<float> lastDisp(n);
+            smt::MedianFilter(leftDisp.data(), lastDisp.data(), col, row, 3);                    // main.cpp:94
+            printf("filled_left %016llx\nfill_holes_status %d %d %d %d\nfill_holes_host_twin %s\nmedian_left %016llx\n",
+                   (unsigned long long)fnv(leftDisp.data(), n * 4), status[0], status[1], status[2], status[3],
+                   equal ? "equal" : "DIFFERS", (unsigned long long)fnv(lastDisp.data(), n * 4));
+            if (!equal) throw std::runtime_error("the device map differs from the host twin's");
         }
         if (from_files && argc > 5) {
             // TransformToShow + normalize of main.cpp:98-110 reduced to its effect on a valid map: rejected

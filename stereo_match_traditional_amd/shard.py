@@ -108,6 +108,22 @@ def pipeline_refined_batch(L8, R8, D, quirks=0, subpixel=None, scan_views=1, ref
     return last, dl
 
 
+def pipeline_filled_batch(L8, R8, D, quirks=0, subpixel=None, scan_views=1, median_wnd=3, invalid=float("inf"), **params):
+    """`compute` for run_sharded on the pipeline with Sad.h's FillHolesInDispMap and the median behind the LR check
+    (smt_pipeline_run_batch_filled) for a [count, H, W] uint8 shard on this rank's GPU -> (lastDisp, the filled left
+    maps before the median).  The rest as pipeline_batch."""
+    from .api import Pipeline
+    c, H, W = L8.shape
+    if c == 0:
+        z = torch.empty((0, H, W), dtype=torch.float32, device=L8.device)
+        return z, z.clone()
+    pipe = Pipeline(H, W, D, L8.device, quirks=quirks, subpixel=subpixel, scan_views=scan_views, **params)
+    dl, _, _, _, last, _ = pipe.run_filled(L8.contiguous(), R8.contiguous(), median_wnd=median_wnd, invalid=invalid)
+    pipe.status()
+    pipe.close()
+    return last, dl
+
+
 def cblsm_batch(L8, R8, D, **params):
     """`compute` for run_sharded on CBLSM.cpp's flow (smt_cblsm_flow_run_batch) for a [count, H, W] uint8 shard on this
     rank's GPU -> (left maps, right maps).  Keywords as api.CBLSMFlow."""
